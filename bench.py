@@ -8,7 +8,12 @@ frame to 3840x2160.  One *step* = one pass over the per-GPU batch of units.
 Metric: Mpixels/s, input + output pixels of every kernel counted once each
 (26.9568 Mpix per unit).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (the hipEvent bracket of the timed launches, `roofline`,
+comes from inside the timed region and costs no run of its own).  `--full` adds everything else listed below: the oracle check
+of the timed outputs, the sustained leg, the informational legs, the copy ceilings, the host-fed leg, the rocprofv3 --pmc
+traffic passes and the CPU baseline.  `--dump-outputs DIR` writes what the last timed step computed (see dump_outputs).
 
 N > 1: one rank per GPU over RCCL; frames are sharded contiguously across ranks (weak
 scaling, no data-path collective; the only collective is the one-off broadcast of the
@@ -22,7 +27,7 @@ strip) is walked by two waves of k_lanczos3_x2 side by side -- one up-scaling fr
 storing the in-between rows and up-scaling them -- so all three outputs of a unit (the in-between frame and both 4K frames) come
 from one kernel; `--schedule three-stage` is the blend / upscale / upscale sequence of rounds 1-2 (same bytes out).
 
-Rank 0 prints ONE JSON line.  Inside it:
+Rank 0 prints ONE JSON line.  Inside it (all but the first with --full only):
   roofline       the dominant launch (the unit kernel + its two edge-column passes), hipEvent pairs on the launch stream
                  inside the timed region, algorithmic bytes of SURVEY.md section 8(d) against the 8 TB/s HBM peak; next to it
                  `upscale_kernel_alone`: k_lanczos3_x2 by itself on the same frames (41 472 000 B per frame);
@@ -119,6 +124,13 @@ def parse_args(argv=None):
                          "(the LUT broadcast, the barriers, the gathers): how a one-GPU box rehearses the RCCL calls of the 8-GPU run")
     ap.add_argument("--force-device", type=int, default=-1,
                     help="rehearsal only: put every rank on this GPU (with --backend gloo on a 1-GPU box)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the oracle check of the timed outputs, the sustained leg, the informational legs, "
+                         "the copy ceilings, the host-fed leg, the rocprofv3 --pmc passes and the CPU baseline (the --no-* and "
+                         "*-seconds options above shape these legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32; rank 0's shard; "
+                         "a fixed seeded sample of each output, at most 64 MB in all)")
     return ap.parse_args(argv)
 
 
@@ -334,6 +346,52 @@ def check_timed_outputs(frames, mid_t, up_real, up_mid, picks, w, h, first_frame
             if mx > 1 or frac >= 1e-3:
                 summary["ok"] = 0.0
     return report, summary
+
+
+DUMP_SEED = 0x5EED
+DUMP_MAX_ELEMENTS = 1 << 22  # per array: three outputs x 4 Mi float32 = 48 MiB, inside the 64 MB of --dump-outputs
+
+
+def dump_positions(name, n, max_elements=DUMP_MAX_ELEMENTS):
+    """The sorted flat positions dump_outputs writes of an array `name` of `n` elements (int64, every one < n), or None when
+    the array is written whole."""
+    import zlib
+
+    import numpy as np
+
+    if n <= max_elements:
+        return None
+    rng = np.random.default_rng([DUMP_SEED, zlib.crc32(name.encode())])
+    return np.sort(rng.integers(0, n, size=max_elements, dtype=np.int64))
+
+
+def dump_outputs(out_dir, arrays, max_elements=DUMP_MAX_ELEMENTS):
+    """Write each (name, tensor) of `arrays` as out_dir/<name>.npy in float32, outside any timed region.  A tensor of at most
+    `max_elements` elements is written whole (flattened); a larger one as the elements at the `max_elements` flat positions of
+    dump_positions (drawn with numpy's default_rng([DUMP_SEED, crc32(name)]) and sorted): they depend on the name and the
+    tensor's size alone, so two runs with the same arguments write the same positions.  The sample is gathered on the device
+    and fetched through nus_download.  Returns {name: (elements of the tensor, elements written)}."""
+    import numpy as np
+    import torch
+
+    from nu_scaler_amd.transfer import to_device, to_numpy as fetch
+
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, t in arrays:
+        if not t.is_contiguous():
+            raise ValueError(f"dump_outputs: {name} is not contiguous")
+        flat = t.view(-1)
+        n = flat.numel()
+        pos = dump_positions(name, n, max_elements)
+        if pos is None:
+            vals = fetch(flat)
+        else:
+            idx = to_device(pos, t.device) if t.is_cuda else torch.from_numpy(pos)
+            vals = fetch(flat.index_select(0, idx))
+        np.save(os.path.join(out_dir, name + ".npy"), vals.astype(np.float32))
+        written[name] = (n, int(vals.size))
+    return written
 
 
 def gather_rows(row, world, dist=None, torch=None, comm_dev=None):
@@ -828,23 +886,30 @@ def worker(args):
     launches, kernel_ms = pipe.upscaler.profile_collect() if profile else (0, 0.0)
     pipe.upscaler.set_profiling(False)
 
+    # What the last timed step computed (rank 0's shard), before any leg of --full overwrites the buffers.
+    if args.dump_outputs and rank == 0:
+        outputs = ([] if args.fused else [("mid", mid)]) + [("up_real", up_real), ("up_mid", up_mid)]
+        for name, (n, k) in dump_outputs(args.dump_outputs, outputs).items():
+            print(f"bench.py: {args.dump_outputs}/{name}.npy: {k} of {n} elements", file=sys.stderr)
+
+    full = args.full
     # The buffers the timed steps wrote, against the oracle -- on EVERY rank, each on frames of ITS shard regenerated on the
     # host, before any other leg overwrites them.  Nobody raises before the summaries have been gathered.
-    checkable = not args.no_check and args.pattern == "gradient" and args.lanczos_mode == "fma"
+    checkable = full and not args.no_check and args.pattern == "gradient" and args.lanczos_mode == "fma"
     check_report, check = None, {"ok": None, "input_ok": None, "mid_exact": None, "max_abs_diff": None, "frac_differing": None,
                                  "frames": None}
     if checkable:
         picks = sorted({0, count // 2 - 1 if count > 2 else 0, count - 1}) if world == 1 else sorted({0, count - 1})
         check_report, check = check_timed_outputs(frames, None if args.fused else mid, up_real, up_mid, picks, w, h,
                                                   first_frame=start, threads=my_cpus)
-    else:
+    elif full:
         # cheap sanity check: the outputs are fully written (alpha of the opaque stream stays 255)
         assert args.pattern != "gradient" or (int(up_real[0, ..., 3].min()) == 255 and int(up_mid[count - 1, ..., 3].min()) == 255)
 
     # What the very same step sustains for seconds, on every rank at the same time (never `value`): ms per step over the last
     # 3 s, hipEvent brackets of the upscale launches in that tail, the rank's own GPU's clocks and power sampled meanwhile.
     sustained = None
-    if args.sustained_seconds > 0:
+    if full and args.sustained_seconds > 0:
         barrier()
         sustained = sustained_leg(torch, do_step, pipe.upscaler, args.sustained_seconds, bdf=bdf, device_index=device_index)
         barrier()
@@ -872,7 +937,7 @@ def worker(args):
     check_failed = checkable and any(r["check_ok"] != 1.0 for r in rows)
 
     solo = rank == 0 and world == 1
-    extras = solo and not args.no_extras and not args.fused and not args.overlap
+    extras = full and solo and not args.no_extras and not args.fused and not args.overlap
 
     def timed_leg(step_fn, n, with_profile=True):
         """(ms per step, bracketed launches, their summed ms) of n steps after 2 warm-ups; informational legs only."""
@@ -904,11 +969,11 @@ def worker(args):
     # The denominators of THIS box, on every rank (a few milliseconds of plain kernels over the output buffers, which the
     # check is done with): copy ceilings and the f32 FMA rate -- boxes of one pool differ by 7-15 % on one binary.
     calib = None
-    if not args.no_extras and profile:
+    if full and not args.no_extras and profile:
         calib = box_calibration(nsc, torch, dev, stream, up_mid, up_real)
     crow = {k: (calib or {}).get(k) for k in ("hipMemcpyDtoDAsync_GBps", "stream_copy_float4_GBps", "write_only_GBps",
                                               "read_only_GBps", "one_read_four_writes_GBps", "valu_fma_f32_TFLOPs")}
-    crows = gather(crow)
+    crows = gather(crow) if full else None
 
     # Informational: the on-box ceiling for an upscale's very bytes AND access pattern -- k_nearest_x2 reads the same 1080p
     # frames and writes the same 4K frames with no arithmetic.
@@ -981,7 +1046,7 @@ def worker(args):
     # Mode (ii): every rank feeds its own GPU from host memory at the same time (any N; never `value`).  After the other host
     # legs: the same place in the process's life as config.host_path's batch figure
     host_fed = None
-    if args.host_fed_seconds > 0 and not args.no_extras:
+    if full and args.host_fed_seconds > 0 and not args.no_extras:
         rate = sh.run_host_fed(args.host_fed_seconds)  # (the product's: nu_scaler_amd.stream.ShardedStream.run_host_fed)
         hrows = gather({"rate": rate, "numa_node": place.get("numa_node"), "bound": 1.0 if place.get("bound") else 0.0})
         rates = [r["rate"] for r in hrows]
@@ -1140,6 +1205,7 @@ def worker(args):
                 "timed_output_check": None if check_report is None else {
                     "tolerance": per_rank_check["tolerance"], "rank": 0, "frames": check_report},
                 "timed_region_s": round(elapsed, 3),
+                "full": full,
                 "sustained": sustained,
                 ("three_stage_variant" if unit_schedule else "unit_variant"): None if other_schedule_leg is None else dict(
                     leg(other_schedule_leg[0]),
@@ -1181,7 +1247,7 @@ def worker(args):
             },
             "roofline": roofline,
         }
-        if world == 1 and roofline is not None and not args.no_pmc:
+        if full and world == 1 and roofline is not None and not args.no_pmc:
             traffic, detail = measure_traffic(count, unit_schedule)
             roofline["traffic"] = traffic
             roofline["traffic_detail"] = detail
@@ -1201,7 +1267,7 @@ def worker(args):
                                               "k_nearest_x2_GBps") if cc.get(k)},
                     "what": "the bytes the bracket's kernels really move through HBM (`traffic`, PMC) / the bracket's time: the "
                             "HBM-throughput reading of the same launch, next to `frac` (algorithmic bytes, SURVEY.md 8d)"}
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, pipe.unit_pixels)
         stdout_line.emit(json.dumps(out))
     if world > 1:
@@ -1216,6 +1282,8 @@ def main():
     args = parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(main_launcher(args))  # parent of the ranks: subprocess only, never the GPU
     worker(args)

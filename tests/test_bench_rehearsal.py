@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 
 def test_two_rank_rehearsal_reports_every_rank(nsc):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--force-device", "0", "--units", "8",
-           "--steps", "3", "--warmup", "1", "--sustained-seconds", "1", "--host-fed-seconds", "0.5"]
+           "--steps", "3", "--warmup", "1", "--sustained-seconds", "1", "--host-fed-seconds", "0.5", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]

@@ -11,9 +11,9 @@ if [ $part != b ]; then rm -rf $out; fi
 mkdir -p $out
 cd $root
 if [ $part != b ]; then
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_driver_command.log 2>&1 && grep "^{" $out/bench_driver_command.log | tail -1 > $out/bench_driver_command_steps20.json
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/bench_driver_command.log 2>&1 && grep "^{" $out/bench_driver_command.log | tail -1 > $out/bench_driver_command_steps20.json
 echo "driver command done: $(cut -c1-200 $out/bench_driver_command_steps20.json)"
-python3 bench.py > $out/bench_n1.log 2>&1 && grep "^{" $out/bench_n1.log | tail -1 > $out/bench_n1.json
+python3 bench.py --full > $out/bench_n1.log 2>&1 && grep "^{" $out/bench_n1.log | tail -1 > $out/bench_n1.json
 echo "bench done: $(cut -c1-160 $out/bench_n1.json)"
 (cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench_prof -o b -- python3 $root/bench.py --no-pmc --no-cpu-baseline --no-extras --no-check --sustained-seconds 0 --steps 450 --warmup 30 > $out/bench_prof.log 2>&1)
 grep "^{" $out/bench_prof.log | tail -1 > $out/bench_under_rocprof.json
@@ -59,9 +59,9 @@ for r in sorted(rows, key=lambda r: int(r["Start_Timestamp"])):
     print(f"{name}  queue {r.get('Queue_Id', '?'):>3s}  start {s_:10.1f}  end {e_:10.1f}  duration {e_ - s_:8.1f} us")
 PY
 rm -rf $out/edge_prof
-python3 bench.py --gpus 2 --backend gloo --force-device 0 --steps 30 --warmup 3 --units 100 --sustained-seconds 2 > $out/bench_n2_gloo.log 2>&1; grep "^{" $out/bench_n2_gloo.log | tail -1 > $out/bench_rehearsal_n2_gloo_one_gpu.json
+python3 bench.py --gpus 2 --backend gloo --force-device 0 --steps 30 --warmup 3 --units 100 --sustained-seconds 2 --full > $out/bench_n2_gloo.log 2>&1; grep "^{" $out/bench_n2_gloo.log | tail -1 > $out/bench_rehearsal_n2_gloo_one_gpu.json
 echo "rehearsal done: $(cut -c1-120 $out/bench_rehearsal_n2_gloo_one_gpu.json)"
-timeout -k 10 400 python3 bench.py --gpus 4 --backend gloo --force-device 0 --steps 20 --warmup 3 --units 60 --sustained-seconds 2 --host-fed-seconds 1 > $out/bench_n4_gloo.log 2>&1; grep "^{" $out/bench_n4_gloo.log | tail -1 > $out/bench_rehearsal_n4_gloo_one_gpu.json
+timeout -k 10 400 python3 bench.py --gpus 4 --backend gloo --force-device 0 --steps 20 --warmup 3 --units 60 --sustained-seconds 2 --host-fed-seconds 1 --full > $out/bench_n4_gloo.log 2>&1; grep "^{" $out/bench_n4_gloo.log | tail -1 > $out/bench_rehearsal_n4_gloo_one_gpu.json
 echo "4-rank rehearsal done: $(cut -c1-120 $out/bench_rehearsal_n4_gloo_one_gpu.json)"
 fi
 rm -rf $out/bench_prof $out/bench3_prof $root/gpurun_out/flowsprof $root/gpurun_out/flowprof
