@@ -204,7 +204,8 @@ int nus_upscaler_set_lanczos_mode(nus_upscaler *h, int mode);
 int nus_upscaler_set_option(nus_upscaler *h, const char *key, int64_t value);
 /* What the library decided (diagnostics; not in the reference): "pq_p" / "pq_q" (the factor P / Q of the small-rational-factor
  * resize kernel, 0 when another kernel runs), "pq_narrow_active" (1: that kernel sums the 4 non-zero taps of a support-2 filter,
- * option "pq_narrow" 0 turns it off: same bytes either way), "rows_per_wave".  Unknown key: NUS_ERR_INVALID_ARGUMENT. */
+ * option "pq_narrow" 0 turns it off: same bytes either way), "rows_per_wave", "win_outputs_per_lane" (4 or 2: output columns per
+ * lane of the register-window any-scale resize kernel, 0 when another kernel runs).  Unknown key: NUS_ERR_INVALID_ARGUMENT. */
 int nus_upscaler_get_option(nus_upscaler *h, const char *key, int64_t *value);
 /* Channel order of the input frames.  Captured frames arrive as BGRA and the reference swizzles them
  * on the CPU before upscaling (nu_scaler_core/src/lib.rs:251-270); with NUS_FORMAT_BGRA8 the kernels

@@ -194,6 +194,7 @@ int HipUpscaler::get_option(const char *key, int64_t *value)
     else if (!strcmp(key, "pq_q")) *value = pq ? pq_q_ : 0;
     else if (!strcmp(key, "pq_narrow_active")) *value = pq && pq_narrow_ && pq_narrow_allowed_ ? 1 : 0;
     else if (!strcmp(key, "rows_per_wave")) *value = rows_per_wave_;
+    else if (!strcmp(key, "win_outputs_per_lane")) *value = initialized_ && variant_ == Variant::ResizeWin ? win_outputs_per_lane_ : 0;
     else return fail(kInvalidArgument, fmt("unknown option '%s'", key));
     return kOk;
 }

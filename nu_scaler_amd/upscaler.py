@@ -246,7 +246,8 @@ class PyWgpuUpscaler:
         self._check(self._lib.nus_upscaler_set_option(self._h, key.encode(), int(value)))
 
     def get_option(self, key: str) -> int:
-        """What the library decided ("pq_p", "pq_q", "pq_narrow_active", "rows_per_wave": nus_upscaler_get_option)."""
+        """What the library decided ("pq_p", "pq_q", "pq_narrow_active", "rows_per_wave", "win_outputs_per_lane":
+        nus_upscaler_get_option)."""
         import ctypes
 
         v = ctypes.c_int64(0)

@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+from _resample64 import check_fma  # the FMA-mode contract: float64 resample, round to nearest, ties either way
 from conftest import GOLDEN, guarded
 from nu_scaler_amd.transfer import to_device as put, to_numpy as fetch  # host <-> HBM through nus_upload / nus_download, never
 # torch's pageable copies (docs/d2h_fault_analysis.md)
@@ -155,6 +156,7 @@ def test_lanczos_general(nsc, oracle_mod, dims):
     want = oracle_mod.lanczos3(img, ow, oh)
     out, _ = _up(nsc, "lanczos3", img, ow, oh)
     assert _maxdiff(out, want) <= 1
+    check_fma(oracle_mod, out, img, ow, oh, 0, ("lanczos3", dims))
     out_e, _ = _up(nsc, "lanczos3", img, ow, oh, lanczos_mode="exact")
     assert np.array_equal(out_e, want)
 
@@ -176,6 +178,7 @@ def test_bicubic_and_triangle_resize(nsc, oracle_mod, alg, filt, dims):
     assert u.kernel_variant == ("lanczos3_x2_regwin" if x2 else "lanczos3_r32_regwin" if r32 else "lanczos3_r43_regwin" if r43 else
                                 ("resize_regwin_lds" if upscale_by4 else ("resize_down_stream" if oh < h else "resize_rows_lds")))
     assert _maxdiff(out, want) <= 1
+    check_fma(oracle_mod, out, img, ow, oh, filt, (alg, dims, u.kernel_variant))
     out_e, _ = _up(nsc, alg, img, ow, oh, lanczos_mode="exact")
     assert np.array_equal(out_e, want)
     assert u.name == {"bicubic": "HipBicubicUpscaler", "triangle": "HipTriangleUpscaler"}[alg]
@@ -222,13 +225,17 @@ def test_reference_interp_fixture(nsc, oracle_mod, golden):
 
 
 def test_committed_oracle_vectors(nsc):
+    import oracle as oracle_mod
+
     v = np.load(os.path.join(GOLDEN, "oracle_vectors.npz"))
     noise = v["noise_48x27"]
     for name, (ow, oh) in {"x2": (96, 54), "x1p5": (72, 41), "down": (20, 11)}.items():
         assert np.array_equal(_up(nsc, "nearest", noise, ow, oh)[0], v[f"nearest_{name}"])
         assert np.array_equal(_up(nsc, "bilinear", noise, ow, oh)[0], v[f"bilinear_{name}"])
         assert np.array_equal(_up(nsc, "bilinear", noise, ow, oh, bilinear_variant="wgsl")[0], v[f"bilinear_wgsl_{name}"])
-        assert _maxdiff(_up(nsc, "lanczos3", noise, ow, oh)[0], v[f"lanczos3_{name}"]) <= 1
+        got_f = _up(nsc, "lanczos3", noise, ow, oh)[0]
+        assert _maxdiff(got_f, v[f"lanczos3_{name}"]) <= 1
+        check_fma(oracle_mod, got_f, noise, ow, oh, 0, ("lanczos3", name))
     it = nsc.WgpuFrameInterpolator()
     a, b, flow = v["warp_a"], v["warp_b"], v["warp_flow"]
     h, w = a.shape[:2]
@@ -247,7 +254,9 @@ def test_committed_oracle_vectors(nsc):
                                     ("lanczos3", v["noise_32x12"], (40, 15), "lanczos3_x5o4"), ("lanczos3", v["noise_32x12"], (80, 30), "lanczos3_x5o2")):
         got_e, ue = _up(nsc, alg, src, ow, oh, lanczos_mode="exact")
         assert np.array_equal(got_e, v[key]), key
-        assert _maxdiff(_up(nsc, alg, src, ow, oh)[0], v[key]) <= 1, key
+        got_f = _up(nsc, alg, src, ow, oh)[0]
+        assert _maxdiff(got_f, v[key]) <= 1, key
+        check_fma(oracle_mod, got_f, src, ow, oh, {"lanczos3": 0, "bicubic": 1, "triangle": 2}[alg], key)
         if key in ("lanczos3_x6o5", "catmullrom_x7o5", "lanczos3_x5o3", "triangle_x5o3", "lanczos3_x5o4", "lanczos3_x5o2"):
             assert ue.kernel_variant == "lanczos3_pq_regwin", (key, ue.kernel_variant)
     u = nsc.PyWgpuUpscaler("quality", "fsr1")
@@ -776,6 +785,10 @@ def test_fused_blend_upscale_equals_two_stage(nsc, oracle_mod, alg, t):
             for i in range(n):
                 m = oracle_mod.warp_blend(frames_np[i], frames_np[i + 1], None, t)
                 assert np.array_equal(fetch(fused[i]), oracle_mod.resize(m, 2 * w, 2 * h, filt)), (alg, t, i)
+        if mode == "fma":
+            for i in range(n):
+                m = oracle_mod.warp_blend(frames_np[i], frames_np[i + 1], None, t)
+                check_fma(oracle_mod, fetch(fused[i]), m, 2 * w, 2 * h, filt, (alg, t, i, u.kernel_variant))
     ub = nsc.PyWgpuUpscaler("quality", "bilinear")
     ub.initialize(w, h, 2 * w, 2 * h)
     with pytest.raises(RuntimeError, match="only the exact-x2 resize kernels"):
@@ -939,6 +952,8 @@ def test_random_shape_sweep(nsc, oracle_mod, alg):
             assert np.array_equal(got, want), (alg, (w, h), (ow, oh), u.kernel_variant)
             got_f, _ = _up(nsc, alg, img, ow, oh)
             assert _maxdiff(got_f, want) <= 1, (alg, (w, h), (ow, oh))
+            check_fma(oracle_mod, got_f, img, ow, oh, {"lanczos3": 0, "bicubic": 1, "triangle": 2}[alg],
+                      (alg, (w, h), (ow, oh), u.kernel_variant))
         else:
             got, u = _up(nsc, alg, img, ow, oh)
             assert np.array_equal(got, want), (alg, (w, h), (ow, oh), u.kernel_variant)
@@ -963,6 +978,7 @@ def test_lanczos_x2_opaque_and_mixed_alpha_rows(nsc, oracle_mod, alg):
         got, u = _up(nsc, alg, img, 2 * w, 2 * h)
         assert u.kernel_variant == "lanczos3_x2_regwin"
         assert _maxdiff(got, want) <= 1, name
+        check_fma(oracle_mod, got, img, 2 * w, 2 * h, filt, (alg, name))
         opaque_out = want[..., 3] == 255  # wherever the CPU says 255, so must the GPU (constant or 4-channel path)
         if name == "opaque":
             assert opaque_out.all() and (got[..., 3] == 255).all()
@@ -1054,6 +1070,7 @@ def test_resize_register_window_variant(nsc, oracle_mod, alg, filt, dims):
     ref_f, ur = _up(nsc, alg, img, ow, oh, options=dict(gen, force_rows=1))
     assert ur.kernel_variant == "resize_rows_lds"
     assert np.array_equal(got_f, ref_f) and _maxdiff(got_f, want) <= 1
+    check_fma(oracle_mod, got_f, img, ow, oh, filt, (alg, dims, u.kernel_variant, gen))
 
 
 @pytest.mark.parametrize("alg,filt", [("lanczos3", 0), ("bicubic", 1), ("triangle", 2)])
@@ -1076,6 +1093,7 @@ def test_resize_integer_factor_register_window(nsc, oracle_mod, alg, filt, facto
     # FMA mode packs with round-to-nearest-even; Triangle's dyadic weights put many sums on exact .5 ties,
     # where that differs from f32::round by one count
     assert _maxdiff(got_f, want) <= 1 and (got_f != want).mean() < (3e-2 if alg == "triangle" else 1e-3)
+    check_fma(oracle_mod, got_f, img, ow, oh, filt, (alg, factor, size, uf.kernel_variant))  # (Triangle: ties)
     # the general kernels agree (same weights, same operation order)
     ref_e, ug = _up(nsc, alg, img, ow, oh, lanczos_mode="exact", options={"force_general": 1})
     assert ug.kernel_variant in ("resize_regwin_lds", "resize_rows_lds") and np.array_equal(ref_e, want)
@@ -1107,6 +1125,7 @@ def test_resize_factor_three_halves_register_window(nsc, oracle_mod, alg, filt, 
     assert uf.kernel_variant == "lanczos3_r32_regwin"
     # FMA mode packs with round-to-nearest-even; Triangle's weights put many sums on exact .5 ties (see the x3 / x4 test)
     assert _maxdiff(got_f, want) <= 1 and (got_f != want).mean() < (5e-2 if alg == "triangle" else 1e-3)
+    check_fma(oracle_mod, got_f, img, ow, oh, filt, (alg, (w, h), (ow, oh), uf.kernel_variant))  # (Triangle: ties)
     ref_f, ug = _up(nsc, alg, img, ow, oh, options={"force_general": 1})
     assert ug.kernel_variant in ("resize_regwin_lds", "resize_rows_lds") and np.array_equal(got_f, ref_f)
     for th in (2, 6, 24, 37):
@@ -1141,6 +1160,7 @@ def test_resize_factor_four_thirds_register_window(nsc, oracle_mod, alg, filt, s
     got_f, uf = _up(nsc, alg, img, ow, oh)
     assert uf.kernel_variant == "lanczos3_r43_regwin"
     assert _maxdiff(got_f, want) <= 1 and (got_f != want).mean() < (5e-2 if alg == "triangle" else 1e-3)
+    check_fma(oracle_mod, got_f, img, ow, oh, filt, (alg, (w, h), (ow, oh), uf.kernel_variant))  # (Triangle: ties)
     ref_f, ug = _up(nsc, alg, img, ow, oh, options={"force_general": 1})
     assert ug.kernel_variant in ("resize_regwin_lds", "resize_rows_lds") and np.array_equal(got_f, ref_f)
     for th in (3, 7, 24, 40):
@@ -1189,6 +1209,7 @@ def test_resize_small_rational_factor_register_window(nsc, oracle_mod, alg, filt
     got_f, uf = _up(nsc, alg, img, ow, oh)
     assert uf.kernel_variant == kernel
     assert _maxdiff(got_f, want) <= 1 and (got_f != want).mean() < (5e-2 if alg == "triangle" else 1e-3)
+    check_fma(oracle_mod, got_f, img, ow, oh, filt, (alg, (w, h), (ow, oh), uf.kernel_variant))  # (Triangle: ties)
     ref_f, ug = _up(nsc, alg, img, ow, oh, options={"force_general": 1})
     assert ug.kernel_variant in ("resize_regwin_lds", "resize_rows_lds") and np.array_equal(got_f, ref_f)
     if kernel == "lanczos3_pq_regwin":
@@ -1420,6 +1441,7 @@ def test_resize_down_streaming_kernel(nsc, oracle_mod, alg, filt, dims):
     ref_f, ur = _up(nsc, alg, img, ow, oh, options={"force_rows": 1})
     assert ur.kernel_variant == "resize_rows_lds"
     assert np.array_equal(got_f, ref_f) and _maxdiff(got_f, want) <= 1
+    check_fma(oracle_mod, got_f, img, ow, oh, filt, (alg, dims, uf.kernel_variant))
 
 
 @pytest.mark.parametrize("dims", [((464, 64), (232, 32)), ((700, 90), (233, 30)), ((300, 157), (150, 78))])
@@ -1461,6 +1483,7 @@ def test_resize_down_opaque_and_mixed_alpha_rows(nsc, oracle_mod, dims):
         assert ur.kernel_variant == "resize_rows_lds"
         assert np.array_equal(got, ref), (name, dims, _maxdiff(got, ref))
         assert _maxdiff(got, oracle_mod.resize(img, ow, oh, 0)) <= 1, name
+        check_fma(oracle_mod, got, img, ow, oh, 0, (name, dims, u.kernel_variant))
         if name == "opaque":
             assert (got[..., 3] == 255).all()
         for sw in (64, 40):
@@ -1515,6 +1538,7 @@ def test_resize_down_4k_to_1080p_batch(nsc, oracle_mod):
     torch.cuda.synchronize()
     got = fetch(d_out)
     assert _maxdiff(got[0], oracle_mod.resize(frames[0], ow, oh, 0)) <= 1
+    check_fma(oracle_mod, got[0], frames[0], ow, oh, 0, ("4K -> 1080p", u.kernel_variant))
     r = nsc.PyWgpuUpscaler("quality", "lanczos3")
     r.set_option("force_rows", 1)
     r.initialize(w, h, ow, oh)

@@ -3,6 +3,7 @@ in-between frame blend(A, B) and upscale(blend(A, B)) for a batch of pairs from 
 Checked against the three separate stages (bit for bit, every mode) and against the CPU oracle."""
 import numpy as np
 import pytest
+from _resample64 import check_fma  # the FMA-mode contract: float64 resample, round to nearest, ties either way
 from conftest import guarded  # device outputs between poisoned guard bands (tests/conftest.py)
 from nu_scaler_amd.transfer import to_device as put, to_numpy as fetch  # host <-> HBM through nus_upload / nus_download, never
 # torch's pageable copies (docs/d2h_fault_analysis.md)
@@ -66,6 +67,11 @@ def test_unit_step_equals_the_three_stages(nsc, oracle_mod, w, h, th, t):
                 assert torch.equal(mid, want_mid), ("mid", tag)
                 assert torch.equal(up_real, want_real), ("up_real", tag)
                 assert torch.equal(up_mid, want_up_mid), ("up_mid", tag)
+                if mode == "fma" and order == 1:
+                    for i in (0, n - 1):
+                        m = oracle_mod.warp_blend(frames_np[i], frames_np[i + 1], None, t)
+                        check_fma(oracle_mod, fetch(up_real[i]), frames_np[i], 2 * w, 2 * h, 0, ("up_real", i, tag))
+                        check_fma(oracle_mod, fetch(up_mid[i]), m, 2 * w, 2 * h, 0, ("up_mid", i, tag))
         # the in-between frames against the oracle itself (bit-exact: interpolation/mod.rs:407-411 truncation)
         for i in (0, n - 1):
             assert np.array_equal(fetch(mid[i]), oracle_mod.warp_blend(frames_np[i], frames_np[i + 1], None, t))
