@@ -12,6 +12,7 @@
  *   WgpuFrameInterpolator::interpolate_py   nu_scaler_core/src/wgpu_interpolator.rs:215-491
  *   get_last_gpu_duration_ms            nu_scaler_core/src/wgpu_interpolator.rs:494-497
  *   trait FrameInterpolator (shape)     nu_scaler_core/src/interpolation/mod.rs:29-44
+ *   ErrorMetrics::calculate             Nu_scale/src/upscale/common.rs:475-543
  *
  * Frames are tightly packed RGBA8, row-major.  Every function returns NUS_OK (0)
  * or a negative nus_status; the message is available from nus_*_last_error(handle)
@@ -505,6 +506,36 @@ int nus_flow_estimate_device_stream(nus_flow *h, const void *d_frames, uint32_t 
 int nus_flow_interpolate_device_stream(nus_flow *h, const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t hgt,
                                        uint32_t levels, uint32_t coarse_iters, uint32_t refine_iters, float lambda, float time_t,
                                        int flow_format, void *d_flows, void *d_mid, void *stream);
+
+/* ---- Image-quality metrics (ErrorMetrics::calculate, Nu_scale/src/upscale/common.rs:475-543) ------------------
+ * MSE, PSNR and SSIM of RGBA8 frame pairs of one size and channel order; alpha is ignored, so every metric is symmetric in R
+ * and B (BGRA and the X formats need no swizzle).
+ *   MSE  = SSE / (3 W H), SSE = sum over pixels and R, G, B of (a - b)^2, summed in integers (common.rs:494-511): bit-identical
+ *          to the float64 formula.
+ *   PSNR = 20 log10(255 / sqrt(MSE)), +inf at MSE 0 (common.rs:513-519).
+ *   SSIM (common.rs:521 keeps a 0.0 placeholder; here Wang et al. 2004) per channel on 0..255: 11 x 11 Gaussian window,
+ *          sigma 1.5, weights normalised to 1, population statistics, C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2, averaged over
+ *          R, G, B and the (W-10) x (H-10) centres whose window lies inside the frame; within 1e-5 of the float64 definition.
+ *          Needs W >= 11 and H >= 11 (below: NUS_ERR_INVALID_ARGUMENT).
+ * Results are deterministic: the same inputs give the same bytes on every run, at every batch position and whatever else was
+ * asked in the same call.  A metric that was not asked is NaN. */
+typedef enum nus_metric { /* bit mask; PSNR comes with MSE */
+    NUS_METRIC_MSE = 1,
+    NUS_METRIC_SSIM = 2
+} nus_metric;
+/* Workspace bytes nus_metrics_compare_device needs for these frames; 0 (and nus_last_error) for an invalid shape or mask. */
+size_t nus_metrics_workspace_size(uint32_t w, uint32_t h, uint32_t frames, int what);
+/* Enqueue only, allocate nothing: frame i of A at d_a + i*a_stride, of B at d_b + i*b_stride (pointers and strides multiples of
+ * 4 bytes, strides >= w*h*4); d_out receives 3 doubles per frame [mse, psnr, ssim] (NaN for what was not asked), ordered on
+ * `stream` (a hipStream_t; NULL = the null stream).  d_workspace and d_out 8-byte aligned. */
+int nus_metrics_compare_device(const void *d_a, size_t a_stride, const void *d_b, size_t b_stride, uint32_t w, uint32_t h,
+                               uint32_t frames, int what, void *d_workspace, size_t workspace_bytes, double *d_out, void *stream);
+/* Host buffers (pageable is fine): one pair on `device`; out receives [mse, psnr, ssim].  a_len != b_len: NUS_ERR_SIZE_MISMATCH,
+ * "Images must have the same dimensions" (common.rs:486-488); a_len != w*h*4: NUS_ERR_SIZE_MISMATCH.  The bytes travel as
+ * nus_upload / nus_download move them, through device buffers the library keeps per device; same results as
+ * nus_metrics_compare_device. */
+int nus_metrics_compare(int device, const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, uint32_t w, uint32_t h,
+                        int what, double *out);
 
 #ifdef __cplusplus
 }

@@ -28,6 +28,7 @@ QUALITY_ULTRA_PERFORMANCE, QUALITY_ULTRA, QUALITY_QUALITY, QUALITY_BALANCED, QUA
 TECH_NONE, TECH_FSR, TECH_DLSS, TECH_WGPU, TECH_FALLBACK = range(5)
 WG_SQUARE_8X8, WG_SQUARE_16X16, WG_WIDE_32X8, WG_TALL_8X32 = range(4)
 RESIZE_MAX_TAPS = 32
+METRIC_MSE, METRIC_SSIM = 1, 2  # nus_metric (bit mask; PSNR comes with MSE)
 
 # Every symbol include/nuscaler_hip.h declares: (name, restype, argtypes)
 _vp, _cp, _i, _u32, _sz, _i64 = (ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_uint32,
@@ -130,6 +131,9 @@ SIGNATURES = [
     ("nus_flow_estimate_device", _i, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _f, _vp, _vp]),
     ("nus_flow_estimate_device_stream", _i, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _f, _vp, _vp]),
     ("nus_flow_interpolate_device_stream", _i, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _f, _f, _i, _vp, _vp, _vp]),
+    ("nus_metrics_workspace_size", _sz, [_u32, _u32, _u32, _i]),
+    ("nus_metrics_compare_device", _i, [_vp, _sz, _vp, _sz, _u32, _u32, _u32, _i, _vp, _sz, _vp, _vp]),
+    ("nus_metrics_compare", _i, [_i, _vp, _sz, _vp, _sz, _u32, _u32, _i, _dp]),
 ]
 
 

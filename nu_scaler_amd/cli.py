@@ -1,7 +1,8 @@
 """`python -m nu_scaler_amd.cli` -- the image-file commands of the north star's `nu_scaler_cli`
 (SURVEY.md section 8f rank 2): `upscale <in.png> <out.png> --algorithm --scale`, following the
 legacy crate's `upscale_image_file` (Nu_scale/src/upscale/mod.rs:307-338) and the option names of
-its `fullscreen` subcommand (Nu_scale/src/main.rs:36-73: --tech, --quality, --algorithm).
+its `fullscreen` subcommand (Nu_scale/src/main.rs:36-73: --tech, --quality, --algorithm); `compare <a.png> <b.png>`
+prints the `ErrorMetrics` of two images (Nu_scale/src/upscale/common.rs:475-543).
 Everything runs on the HIP device; without one the command fails (no CPU path).
 """
 from __future__ import annotations
@@ -29,6 +30,11 @@ def build_parser() -> argparse.ArgumentParser:
     it.add_argument("--t", type=float, default=0.5, help="time of the new frame between A (0) and B (1)")
     it.add_argument("--flow", action="store_true", help="estimate motion (pyramid + Horn-Schunck) instead of zero flow")
     it.add_argument("--device", type=int, default=0)
+    cp = sub.add_parser("compare", help="MSE, PSNR and SSIM of two PNGs of equal size (ErrorMetrics, "
+                                         "Nu_scale/src/upscale/common.rs:475-543)")
+    cp.add_argument("a")
+    cp.add_argument("b")
+    cp.add_argument("--device", type=int, default=0)
     st = sub.add_parser("stream", help="the sharded frame-queue stream: a synthetic 1080p stream through interpolate + x2 upscale "
                                        "on N GPUs of this node, one process per GPU, frames sharded, LUTs broadcast over RCCL")
     st.add_argument("--gpus", type=int, default=1, help="ranks = GPUs of this node (started as a child process tree)")
@@ -145,6 +151,18 @@ def main(argv=None) -> int:
             ow, oh = imagefile.upscale_image_file(args.input, args.output, args.tech, args.quality, args.scale,
                                                   args.algorithm, device=args.device)
             print(f"{args.output}: {ow}x{oh}")
+        elif args.command == "compare":
+            import numpy as np
+
+            from .metrics import ErrorMetrics
+
+            wa, ha, pa = imagefile.read_png(args.a)
+            wb, hb, pb = imagefile.read_png(args.b)
+            if (wa, ha) != (wb, hb):
+                raise ValueError("Images must have the same dimensions")
+            a = np.frombuffer(pa, np.uint8).reshape(ha, wa, 4)
+            b = np.frombuffer(pb, np.uint8).reshape(hb, wb, 4)
+            print(ErrorMetrics.calculate(a, b, device=args.device).line())
         else:
             w, h = imagefile.interpolate_image_files(args.frame_a, args.frame_b, args.output, args.t, args.flow,
                                                      device=args.device)

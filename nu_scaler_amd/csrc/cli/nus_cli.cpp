@@ -5,6 +5,7 @@
 //
 //   nu_scaler_cli upscale <in.png> <out.png> [--algorithm A] [--scale S] [--tech T] [--quality Q] [--device N]
 //   nu_scaler_cli interpolate <a.png> <b.png> <out.png> [--t X] [--flow] [--device N]
+//   nu_scaler_cli compare <a.png> <b.png> [--device N]   (MSE / PSNR / SSIM, ErrorMetrics: Nu_scale/src/upscale/common.rs:475-543)
 //   nu_scaler_cli png-copy <in.png> <out.png>        (decode + encode only; no GPU: codec self-check)
 //
 // Pixels go through the HIP kernels only: without a device the commands fail.
@@ -34,6 +35,7 @@ int usage(int rc)
                  "                             [--scale S] [--tech fsr|fallback|none] [--quality ultra|quality|balanced|performance]\n"
                  "                             [--device N]\n"
                  "       nu_scaler_cli interpolate <a.png> <b.png> <out.png> [--t X] [--flow] [--device N]\n"
+                 "       nu_scaler_cli compare <a.png> <b.png> [--device N]\n"
                  "       nu_scaler_cli png-copy <in.png> <out.png>\n");
     return rc;
 }
@@ -177,6 +179,27 @@ int cmd_interpolate(const Args &a)
     return 0;
 }
 
+// one line, the same as `python -m nu_scaler_amd.cli compare`: mse=.. psnr=.. ssim=.. (inf / nan where they apply; SSIM is asked
+// only when both sides are at least 11 pixels)
+int cmd_compare(const Args &a)
+{
+    if (a.positional.size() != 2) return usage(2);
+    nus_cli::Image fa, fb;
+    std::string err = nus_cli::read_png(a.positional[0], fa);
+    if (err.empty()) err = nus_cli::read_png(a.positional[1], fb);
+    if (!err.empty()) return fail(err);
+    if (fa.width != fb.width || fa.height != fb.height) return fail("Images must have the same dimensions");
+    const auto d_it = a.options.find("device");
+    const int device = d_it == a.options.end() ? 0 : std::atoi(d_it->second.c_str());
+    const int what = NUS_METRIC_MSE | (fa.width >= 11 && fa.height >= 11 ? NUS_METRIC_SSIM : 0);
+    double m[3] = {0, 0, 0};
+    if (nus_metrics_compare(device, fa.rgba.data(), fa.rgba.size(), fb.rgba.data(), fb.rgba.size(), fa.width, fa.height, what, m) !=
+        NUS_OK)
+        return fail(nus_last_error());
+    std::printf("mse=%.6f psnr=%.6f ssim=%.6f\n", m[0], m[1], m[2]);
+    return 0;
+}
+
 int cmd_png_copy(const Args &a)
 {
     if (a.positional.size() != 2) return usage(2);
@@ -200,6 +223,7 @@ int main(int argc, char **argv)
     if (!parse(argc, argv, a, err)) return fail(err);
     if (cmd == "upscale") return cmd_upscale(a);
     if (cmd == "interpolate") return cmd_interpolate(a);
+    if (cmd == "compare") return cmd_compare(a);
     if (cmd == "png-copy") return cmd_png_copy(a);
     return usage(2);
 }

@@ -9,6 +9,7 @@
 
 #include "nus_flow.hpp"
 #include "nus_host.hpp"
+#include "nus_metrics.hpp"
 #include "nus_queue.hpp"
 #include "nus_ranges.hpp"
 #include "nus_transfer.hpp"
@@ -736,6 +737,31 @@ int nus_flow_interpolate_device_stream(nus_flow *h, const void *d_frames, uint32
                                                      d_flows, d_mid, static_cast<hipStream_t>(stream), flow_format == NUS_FLOW_F16)
                  : null_handle();
     });
+}
+
+size_t nus_metrics_workspace_size(uint32_t w, uint32_t h, uint32_t frames, int what)
+{
+    try {
+        return nus::metrics_workspace_size(w, h, frames, what);
+    } catch (...) {
+        nus::set_thread_error("nus_metrics_workspace_size: unexpected exception");
+        return 0;
+    }
+}
+
+int nus_metrics_compare_device(const void *d_a, size_t a_stride, const void *d_b, size_t b_stride, uint32_t w, uint32_t h,
+                               uint32_t frames, int what, void *d_workspace, size_t workspace_bytes, double *d_out, void *stream)
+{
+    return guarded<int>("nus_metrics_compare_device", [&]() -> int {
+        return nus::metrics_compare_device(d_a, a_stride, d_b, b_stride, w, h, frames, what, d_workspace, workspace_bytes, d_out,
+                                           static_cast<hipStream_t>(stream));
+    });
+}
+
+int nus_metrics_compare(int device, const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, uint32_t w, uint32_t h,
+                        int what, double *out)
+{
+    return guarded<int>("nus_metrics_compare", [&]() -> int { return nus::metrics_compare(device, a, a_len, b, b_len, w, h, what, out); });
 }
 
 } // extern "C"

@@ -253,4 +253,19 @@ hipError_t launch_flow_upsample(const float *src, uint32_t sw, uint32_t sh, floa
 constexpr uint32_t kProbeValuBlocks = 2048;
 hipError_t launch_probe(int kind, const void *d_src, void *d_dst, size_t bytes, uint32_t iters, hipStream_t stream);
 
+// Image-quality metrics of frame pairs (nus_k_metrics.hip; nus_metrics_* in include/nuscaler_hip.h).  Frame i of A at
+// a + i * a_stride, of B at b + i * b_stride (4-byte aligned); the workspace holds per-block partials -- u64 SSE at
+// sse_offset, f64 SSIM at ssim_offset -- and out receives [mse, psnr, ssim] per frame (NaN for what was not asked).
+// SSIM needs w, h >= 11.  Kernels: k_metrics_sse (MSE alone), k_metrics_ssim (SSIM, with the SSE when both are asked),
+// k_metrics_finish.
+constexpr uint32_t kMetricsBlock = 256; // lanes per workgroup of every metrics kernel
+struct MetricsShape {
+    uint32_t sse_blocks = 0, ssim_blocks = 0; // partials per frame
+    uint32_t tiles_x = 0, tiles_y = 0;        // SSIM tiles per frame
+    size_t sse_offset = 0, ssim_offset = 0, workspace_bytes = 0;
+};
+MetricsShape metrics_shape(uint32_t w, uint32_t h, uint32_t frames, bool mse, bool ssim); // host only, no device needed
+hipError_t launch_metrics(const uint8_t *a, size_t a_stride, const uint8_t *b, size_t b_stride, uint32_t w, uint32_t h,
+                          uint32_t frames, bool mse, bool ssim, void *workspace, double *out, hipStream_t stream);
+
 } // namespace nus
