@@ -411,6 +411,30 @@ int nus_interp_interpolate_device(nus_interp *h, const void *d_a, size_t a_strid
                                   const void *d_flow, uint32_t w, uint32_t hgt,
                                   float t, void *d_out, uint32_t n_pairs, void *stream);
 
+/* ---- Several in-between frames per pair (frame-rate multipliers 2x .. 8x) ------------
+ * One launch reads each pair's A, B (and flow) once and writes the frame of every time in the set: frame k is byte for byte what
+ * the single-t entry point writes at times[k], in the handle's mode, flow format and input format.  frame_times of the Python
+ * package gives the times of a multiplier M: k / M for k = 1 .. M - 1.
+ * Unlike nus_interp_interpolate_device, which takes any t, these entry points require 1 <= n_times <= NUS_INTERP_MAX_TIMES and
+ * every time in [0, 1] (NaN is rejected).  Argument errors are NUS_ERR_INVALID_ARGUMENT, returned before any HIP call, with a
+ * last_error text that names the entry point. */
+/* up to 8x frame rate */
+#define NUS_INTERP_MAX_TIMES 7
+
+/* n_pairs pairs as nus_interp_interpolate_device (same pointer, stride and flow alignment); n_times in-between frames per pair, at
+ * times[0..n_times).  Frame (i, k) at d_out + i * out_pair_stride + k * w*h*4; out_pair_stride 0 = n_times * w*h*4 (tightly
+ * packed), else a multiple of 4 of at least n_times * w*h*4.  A stride of (n_times + 1) * w*h*4 leaves a gap per pair, so the
+ * caller can put the real frame there (display order); the gap is not written.  `times` is read during the call and copied into
+ * the launch.  n_pairs == 0: NUS_OK, nothing launched.  Enqueue only: no allocation, no synchronisation. */
+int nus_interp_interpolate_multi_device(nus_interp *h, const void *d_a, size_t a_stride, const void *d_b, size_t b_stride,
+                                        const void *d_flow, uint32_t w, uint32_t hgt, const float *times, uint32_t n_times,
+                                        void *d_out, size_t out_pair_stride, uint32_t n_pairs, void *stream);
+/* Host frames in (as nus_interp_interpolate, whose NUS_ERR_SIZE_MISMATCH and text it shares); n_times frames out, back to back
+ * (out_cap >= n_times * w*h*4).  nus_interp_last_gpu_ms then reports the one multi-time launch. */
+int nus_interp_interpolate_multi(nus_interp *h, const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len,
+                                 const float *flow, uint32_t w, uint32_t hgt, const float *times, uint32_t n_times,
+                                 uint8_t *out, size_t out_cap);
+
 /* get_last_gpu_duration_ms: NUS_OK and *ms_out set, or NUS_ERR_NOT_INITIALIZED when
  * no interpolation has run yet (the reference returns None). */
 int nus_interp_last_gpu_ms(const nus_interp *h, double *ms_out);
@@ -506,6 +530,14 @@ int nus_flow_estimate_device_stream(nus_flow *h, const void *d_frames, uint32_t 
 int nus_flow_interpolate_device_stream(nus_flow *h, const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t hgt,
                                        uint32_t levels, uint32_t coarse_iters, uint32_t refine_iters, float lambda, float time_t,
                                        int flow_format, void *d_flows, void *d_mid, void *stream);
+/* As nus_flow_interpolate_device_stream, but each pair's flow is estimated ONCE and all n_times frames are warped from it (one
+ * multi-time warp launch in FMA mode behind the estimator).  Pair k's frame j goes to d_mid + k * mid_pair_stride + j * w*h*4
+ * (0 = tightly packed; else a multiple of 4 of at least n_times * w*h*4).  Every frame equals the single-t call's at times[j]; the
+ * flows at d_flows (when not NULL) are the same bytes.  Time-set rules and argument checks as nus_interp_interpolate_multi_device. */
+int nus_flow_interpolate_multi_device_stream(nus_flow *h, const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t hgt,
+                                             uint32_t levels, uint32_t coarse_iters, uint32_t refine_iters, float lambda,
+                                             const float *times, uint32_t n_times, int flow_format, void *d_flows,
+                                             void *d_mid, size_t mid_pair_stride, void *stream);
 
 /* ---- Image-quality metrics (ErrorMetrics::calculate, Nu_scale/src/upscale/common.rs:475-543) ------------------
  * MSE, PSNR and SSIM of RGBA8 frame pairs of one size and channel order; alpha is ignored, so every metric is symmetric in R

@@ -14,8 +14,8 @@ from . import _capi, metrics, transfer
 from ._capi import NuScalerLibraryError, PinnedBuffer, build, device_count
 from .benchmark import PyBenchmarkResult, py_benchmark_upscaler, py_run_comparison_benchmark
 from .flow import FlowEstimator
-from .imagefile import interpolate_image_files, upscale_image_file
-from .interpolator import WgpuFrameInterpolator
+from .imagefile import interpolate_image_files, interpolate_image_files_multi, upscale_image_file
+from .interpolator import WgpuFrameInterpolator, frame_times
 from .queue import FrameBuffer, swizzle_bgra_to_rgba_device
 from .launch import launch_ranks
 from .metrics import ErrorMetrics
@@ -49,7 +49,7 @@ def create_fsr_upscaler(_quality: str):
 
 __all__ = [
     "PyWgpuUpscaler", "PyAdvancedWgpuUpscaler", "PyVramStats", "create_advanced_upscaler", "create_fsr_upscaler",
-    "upscale_image_file", "interpolate_image_files",
+    "upscale_image_file", "interpolate_image_files", "interpolate_image_files_multi", "frame_times",
     "PyBenchmarkResult", "py_benchmark_upscaler", "py_run_comparison_benchmark",
     "WgpuFrameInterpolator", "FlowEstimator", "ErrorMetrics", "metrics", "FrameBuffer", "swizzle_bgra_to_rgba_device", "FramePipeline", "shard_frames", "broadcast_tables",
     "ShardedStream", "SyntheticSource", "run_sharded", "gather_rows", "spread", "launch_ranks",

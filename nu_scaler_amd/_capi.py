@@ -28,6 +28,7 @@ QUALITY_ULTRA_PERFORMANCE, QUALITY_ULTRA, QUALITY_QUALITY, QUALITY_BALANCED, QUA
 TECH_NONE, TECH_FSR, TECH_DLSS, TECH_WGPU, TECH_FALLBACK = range(5)
 WG_SQUARE_8X8, WG_SQUARE_16X16, WG_WIDE_32X8, WG_TALL_8X32 = range(4)
 RESIZE_MAX_TAPS = 32
+INTERP_MAX_TIMES = 7  # NUS_INTERP_MAX_TIMES: in-between frames per pair of one multi-time call (up to 8x frame rate)
 METRIC_MSE, METRIC_SSIM = 1, 2  # nus_metric (bit mask; PSNR comes with MSE)
 
 # Every symbol include/nuscaler_hip.h declares: (name, restype, argtypes)
@@ -102,6 +103,8 @@ SIGNATURES = [
     ("nus_interp_quality", _i, [_vp]),
     ("nus_interp_interpolate", _i, [_vp, _vp, _sz, _vp, _sz, _vp, _u32, _u32, _f, _vp, _sz]),
     ("nus_interp_interpolate_device", _i, [_vp, _vp, _sz, _vp, _sz, _vp, _u32, _u32, _f, _vp, _u32, _vp]),
+    ("nus_interp_interpolate_multi_device", _i, [_vp, _vp, _sz, _vp, _sz, _vp, _u32, _u32, _vp, _u32, _vp, _sz, _u32, _vp]),
+    ("nus_interp_interpolate_multi", _i, [_vp, _vp, _sz, _vp, _sz, _vp, _u32, _u32, _vp, _u32, _vp, _sz]),
     ("nus_interp_last_gpu_ms", _i, [_vp, _dp]),
     ("nus_interp_last_error", _cp, [_vp]),
     ("nus_frame_queue_create", _vp, [_sz]),
@@ -131,6 +134,8 @@ SIGNATURES = [
     ("nus_flow_estimate_device", _i, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _f, _vp, _vp]),
     ("nus_flow_estimate_device_stream", _i, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _f, _vp, _vp]),
     ("nus_flow_interpolate_device_stream", _i, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _f, _f, _i, _vp, _vp, _vp]),
+    ("nus_flow_interpolate_multi_device_stream", _i, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _f, _vp, _u32, _i, _vp, _vp, _sz,
+                                                      _vp]),
     ("nus_metrics_workspace_size", _sz, [_u32, _u32, _u32, _i]),
     ("nus_metrics_compare_device", _i, [_vp, _sz, _vp, _sz, _u32, _u32, _u32, _i, _vp, _sz, _vp, _vp]),
     ("nus_metrics_compare", _i, [_i, _vp, _sz, _vp, _sz, _u32, _u32, _i, _dp]),

@@ -27,7 +27,9 @@ def build_parser() -> argparse.ArgumentParser:
     it.add_argument("frame_a")
     it.add_argument("frame_b")
     it.add_argument("output")
-    it.add_argument("--t", type=float, default=0.5, help="time of the new frame between A (0) and B (1)")
+    it.add_argument("--t", type=float, default=None, help="time of the new frame between A (0) and B (1); default 0.5")
+    it.add_argument("--multiplier", type=int, default=None,
+                    help="frame-rate multiplier M (2 .. NUS_INTERP_MAX_TIMES + 1 = 8): the M - 1 frames at t = k / M, written as <stem>_<k><ext>")
     it.add_argument("--flow", action="store_true", help="estimate motion (pyramid + Horn-Schunck) instead of zero flow")
     it.add_argument("--device", type=int, default=0)
     cp = sub.add_parser("compare", help="MSE, PSNR and SSIM of two PNGs of equal size (ErrorMetrics, "
@@ -138,7 +140,15 @@ def stream_command(args, argv) -> int:
 
 
 def main(argv=None) -> int:
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.command == "interpolate" and args.multiplier is not None:  # usage errors: status 2 before anything is read or written
+        if args.t is not None:
+            parser.error("--multiplier and --t exclude each other")
+        from ._capi import INTERP_MAX_TIMES
+
+        if not 2 <= args.multiplier <= INTERP_MAX_TIMES + 1:
+            parser.error(f"--multiplier must be from 2 to {INTERP_MAX_TIMES + 1}, got {args.multiplier}")
     if args.command == "stream":
         try:
             return stream_command(args, list(sys.argv[1:] if argv is None else argv))
@@ -163,9 +173,13 @@ def main(argv=None) -> int:
             a = np.frombuffer(pa, np.uint8).reshape(ha, wa, 4)
             b = np.frombuffer(pb, np.uint8).reshape(hb, wb, 4)
             print(ErrorMetrics.calculate(a, b, device=args.device).line())
+        elif args.multiplier is not None:
+            for path in imagefile.interpolate_image_files_multi(args.frame_a, args.frame_b, args.output, args.multiplier, args.flow,
+                                                                device=args.device):
+                print(path)
         else:
-            w, h = imagefile.interpolate_image_files(args.frame_a, args.frame_b, args.output, args.t, args.flow,
-                                                     device=args.device)
+            t = 0.5 if args.t is None else args.t
+            w, h = imagefile.interpolate_image_files(args.frame_a, args.frame_b, args.output, t, args.flow, device=args.device)
             print(f"{args.output}: {w}x{h}")
     except (OSError, ValueError, RuntimeError) as e:
         print(f"nu_scaler_cli: error: {e}", file=sys.stderr)

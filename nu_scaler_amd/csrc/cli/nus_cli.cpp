@@ -4,7 +4,7 @@
 // (Nu_scale/src/main.rs:36-73: --tech, --quality, --algorithm).
 //
 //   nu_scaler_cli upscale <in.png> <out.png> [--algorithm A] [--scale S] [--tech T] [--quality Q] [--device N]
-//   nu_scaler_cli interpolate <a.png> <b.png> <out.png> [--t X] [--flow] [--device N]
+//   nu_scaler_cli interpolate <a.png> <b.png> <out.png> [--t X | --multiplier M] [--flow] [--device N]
 //   nu_scaler_cli compare <a.png> <b.png> [--device N]   (MSE / PSNR / SSIM, ErrorMetrics: Nu_scale/src/upscale/common.rs:475-543)
 //   nu_scaler_cli png-copy <in.png> <out.png>        (decode + encode only; no GPU: codec self-check)
 //
@@ -34,7 +34,7 @@ int usage(int rc)
                  "usage: nu_scaler_cli upscale <in.png> <out.png> [--algorithm nearest|bilinear|bicubic|lanczos3|triangle|fsr1|easu]\n"
                  "                             [--scale S] [--tech fsr|fallback|none] [--quality ultra|quality|balanced|performance]\n"
                  "                             [--device N]\n"
-                 "       nu_scaler_cli interpolate <a.png> <b.png> <out.png> [--t X] [--flow] [--device N]\n"
+                 "       nu_scaler_cli interpolate <a.png> <b.png> <out.png> [--t X | --multiplier 2..8] [--flow] [--device N]\n"
                  "       nu_scaler_cli compare <a.png> <b.png> [--device N]\n"
                  "       nu_scaler_cli png-copy <in.png> <out.png>\n");
     return rc;
@@ -135,9 +135,33 @@ int cmd_upscale(const Args &a)
     return 0;
 }
 
+// <stem>_<k><ext>: where --multiplier M writes the frame at t = k / M
+std::string multi_path(const std::string &out, uint32_t k)
+{
+    const size_t slash = out.find_last_of('/'), dot = out.find_last_of('.');
+    const bool has_ext = dot != std::string::npos && (slash == std::string::npos || dot > slash);
+    const std::string stem = has_ext ? out.substr(0, dot) : out, ext = has_ext ? out.substr(dot) : "";
+    return stem + "_" + std::to_string(k) + ext;
+}
+
 int cmd_interpolate(const Args &a)
 {
     if (a.positional.size() != 3) return usage(2);
+    const auto m_it = a.options.find("multiplier");
+    uint32_t multiplier = 0; // 0: one frame at --t
+    if (m_it != a.options.end()) { // usage errors before anything is read or written
+        if (a.options.count("t")) {
+            std::fprintf(stderr, "nu_scaler_cli: error: --multiplier and --t exclude each other\n");
+            return usage(2);
+        }
+        char *end = nullptr;
+        const long m = std::strtol(m_it->second.c_str(), &end, 10);
+        if (end == m_it->second.c_str() || *end != '\0' || m < 2 || m > NUS_INTERP_MAX_TIMES + 1) {
+            std::fprintf(stderr, "nu_scaler_cli: error: --multiplier must be from 2 to %d\n", NUS_INTERP_MAX_TIMES + 1);
+            return usage(2);
+        }
+        multiplier = (uint32_t)m;
+    }
     nus_cli::Image fa, fb;
     std::string err = nus_cli::read_png(a.positional[0], fa);
     if (err.empty()) err = nus_cli::read_png(a.positional[1], fb);
@@ -162,6 +186,31 @@ int cmd_interpolate(const Args &a)
     }
     nus_interp *it = nus_interp_create(NUS_WG_WIDE_32X8);
     if (!it) return fail(nus_last_error());
+    if (multiplier) { // the M - 1 frames at t = k / M from one call (the flow, if any, estimated once above)
+        const uint32_t n = multiplier - 1;
+        std::vector<float> times(n);
+        for (uint32_t k = 1; k <= n; ++k) times[k - 1] = (float)((double)k / (double)multiplier);
+        std::vector<uint8_t> frames(fa.rgba.size() * n);
+        int rc = nus_interp_set_device(it, device);
+        if (rc == NUS_OK)
+            rc = nus_interp_interpolate_multi(it, fa.rgba.data(), fa.rgba.size(), fb.rgba.data(), fb.rgba.size(),
+                                              a.flow ? flow.data() : nullptr, fa.width, fa.height, times.data(), n, frames.data(),
+                                              frames.size());
+        const std::string msg = rc == NUS_OK ? "" : nus_interp_last_error(it);
+        nus_interp_destroy(it);
+        if (rc != NUS_OK) return fail(msg);
+        for (uint32_t k = 1; k <= n; ++k) {
+            nus_cli::Image out;
+            out.width = fa.width;
+            out.height = fa.height;
+            out.rgba.assign(frames.begin() + (size_t)(k - 1) * fa.rgba.size(), frames.begin() + (size_t)k * fa.rgba.size());
+            const std::string path = multi_path(a.positional[2], k);
+            err = nus_cli::write_png(path, out);
+            if (!err.empty()) return fail(err);
+            std::printf("%s\n", path.c_str());
+        }
+        return 0;
+    }
     nus_cli::Image out;
     out.width = fa.width;
     out.height = fa.height;

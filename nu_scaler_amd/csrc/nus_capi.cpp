@@ -76,6 +76,8 @@ R guarded(const char *what, F &&f) noexcept
 }
 } // namespace
 
+static_assert(NUS_INTERP_MAX_TIMES == nus::kInterpMaxTimes, "the C header's NUS_INTERP_MAX_TIMES is the kernels' time-set size");
+
 extern "C" {
 
 int nus_abi_version(void) { return NUS_ABI_VERSION; }
@@ -539,6 +541,25 @@ int nus_interp_interpolate_device(nus_interp *h, const void *d_a, size_t a_strid
     });
 }
 
+int nus_interp_interpolate_multi_device(nus_interp *h, const void *d_a, size_t a_stride, const void *d_b, size_t b_stride,
+                                        const void *d_flow, uint32_t w, uint32_t hgt, const float *times, uint32_t n_times,
+                                        void *d_out, size_t out_pair_stride, uint32_t n_pairs, void *stream)
+{
+    return guarded<int>("nus_interp_interpolate_multi_device", [&]() -> int {
+        return h ? h->impl.interpolate_multi_device(d_a, a_stride, d_b, b_stride, d_flow, w, hgt, times, n_times, d_out, out_pair_stride,
+                                                    n_pairs, static_cast<hipStream_t>(stream))
+                 : null_handle();
+    });
+}
+
+int nus_interp_interpolate_multi(nus_interp *h, const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, const float *flow,
+                                 uint32_t w, uint32_t hgt, const float *times, uint32_t n_times, uint8_t *out, size_t out_cap)
+{
+    return guarded<int>("nus_interp_interpolate_multi", [&]() -> int {
+        return h ? h->impl.interpolate_multi(a, a_len, b, b_len, flow, w, hgt, times, n_times, out, out_cap) : null_handle();
+    });
+}
+
 int nus_interp_last_gpu_ms(const nus_interp *h, double *ms_out)
 {
     return guarded<int>("nus_interp_last_gpu_ms", [&]() -> int {
@@ -736,6 +757,23 @@ int nus_flow_interpolate_device_stream(nus_flow *h, const void *d_frames, uint32
         return h ? h->impl.interpolate_device_stream(d_frames, n_frames, w, hgt, levels, coarse_iters, refine_iters, lambda, time_t,
                                                      d_flows, d_mid, static_cast<hipStream_t>(stream), flow_format == NUS_FLOW_F16)
                  : null_handle();
+    });
+}
+
+int nus_flow_interpolate_multi_device_stream(nus_flow *h, const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t hgt,
+                                             uint32_t levels, uint32_t coarse_iters, uint32_t refine_iters, float lambda,
+                                             const float *times, uint32_t n_times, int flow_format, void *d_flows, void *d_mid,
+                                             size_t mid_pair_stride, void *stream)
+{
+    return guarded<int>("nus_flow_interpolate_multi_device_stream", [&]() -> int {
+        if (!h) return null_handle();
+        if (flow_format != NUS_FLOW_F32 && flow_format != NUS_FLOW_F16) {
+            nus::set_thread_error("nus_flow_interpolate_multi_device_stream: flow_format must be NUS_FLOW_F32 or NUS_FLOW_F16");
+            return NUS_ERR_INVALID_ARGUMENT;
+        }
+        return h->impl.interpolate_multi_device_stream(d_frames, n_frames, w, hgt, levels, coarse_iters, refine_iters, lambda, times,
+                                                       n_times, flow_format == NUS_FLOW_F16, d_flows, d_mid, mid_pair_stride,
+                                                       static_cast<hipStream_t>(stream));
     });
 }
 

@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "nus_host.hpp"
+#include "nus_host_util.hpp"
 #include "nus_kernels.hpp"
 #include "nus_transfer.hpp"
 
@@ -389,10 +390,37 @@ int HipFlowEstimator::interpolate_device_stream(const void *d_frames, uint32_t n
     return stream_impl(d_frames, n_frames, w, h, levels, coarse_iters, refine_iters, lambda, d_flows, d_mid, t, stream, flow_half);
 }
 
-// (called with mu_ held)  d_flows may be null when d_mid is not: the caller wants the in-between frames only.
+int HipFlowEstimator::interpolate_multi_device_stream(const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t h, uint32_t levels,
+                                                      uint32_t coarse_iters, uint32_t refine_iters, float lambda, const float *times,
+                                                      uint32_t n_times, bool flow_half, void *d_flows, void *d_mid, size_t mid_pair_stride,
+                                                      hipStream_t stream)
+{
+    static const char *const who = "nus_flow_interpolate_multi_device_stream";
+    std::lock_guard<std::mutex> lk(mu_);
+    if (w == 0 || h == 0 || (uint64_t)w * h >= (1ull << 28)) return fail(kInvalidArgument, std::string(who) + ": bad image dimensions");
+    if (!d_frames || !d_mid) return fail(kInvalidArgument, std::string(who) + ": null device pointer");
+    if (n_frames < 2) return fail(kInvalidArgument, std::string(who) + ": a stream needs at least 2 frames");
+    const std::string bad = check_interp_times(times, n_times);
+    if (!bad.empty()) return fail(kInvalidArgument, std::string(who) + ": " + bad);
+    if ((reinterpret_cast<uintptr_t>(d_mid) % 16) || (reinterpret_cast<uintptr_t>(d_flows) % 16) ||
+        (reinterpret_cast<uintptr_t>(d_frames) % 4))
+        return fail(kInvalidArgument, std::string(who) + ": d_mid and d_flows must be 16-byte aligned, d_frames 4-byte aligned");
+    const size_t frame_bytes = (size_t)w * h * 4;
+    if (mid_pair_stride != 0 && (mid_pair_stride < n_times * frame_bytes || mid_pair_stride % 4))
+        return fail(kInvalidArgument, std::string(who) + ": mid_pair_stride must be 0 or a multiple of 4 of at least n_times * w * h * 4 bytes");
+    MidTimes mt;
+    mt.times = times;
+    mt.n = n_times;
+    mt.pair_stride = mid_pair_stride ? mid_pair_stride : n_times * frame_bytes;
+    return stream_impl(d_frames, n_frames, w, h, levels, coarse_iters, refine_iters, lambda, d_flows, d_mid, times[0], stream, flow_half,
+                       &mt);
+}
+
+// (called with mu_ held)  d_flows may be null when d_mid is not: the caller wants the in-between frames only.  mt: the frames at
+// several times per pair (interpolate_multi_device_stream) instead of the one at t.
 int HipFlowEstimator::stream_impl(const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t h, uint32_t levels,
                                   uint32_t coarse_iters, uint32_t refine_iters, float lambda, void *d_flows, void *d_mid, float t,
-                                  hipStream_t stream, bool flow_half)
+                                  hipStream_t stream, bool flow_half, const MidTimes *mt)
 {
     CHECK_DIMS(w, h);
     if (!d_frames || (!d_flows && !d_mid)) return fail(kInvalidArgument, "flow: null device pointer");
@@ -403,6 +431,7 @@ int HipFlowEstimator::stream_impl(const void *d_frames, uint32_t n_frames, uint3
     const uint8_t *frames = static_cast<const uint8_t *>(d_frames);
     uint8_t *flows = static_cast<uint8_t *>(d_flows), *mid = static_cast<uint8_t *>(d_mid);
     const size_t frame_bytes = (size_t)w * h * 4, flow_bytes = (size_t)w * h * (flow_half ? 4 : 8);
+    const size_t mid_stride = mt ? mt->pair_stride : frame_bytes;
     // the warp kernel behind an estimator that did not warp itself: pairs [k0, k0 + n) with the flows at `fl`
     auto warp_behind = [&](uint32_t k0, uint32_t n, const void *fl) -> int {
         WarpLaunch L;
@@ -412,8 +441,9 @@ int HipFlowEstimator::stream_impl(const void *d_frames, uint32_t n_frames, uint3
         L.flow = static_cast<const float *>(fl);
         L.flow_half = flow_half;
         L.fma = true;
-        L.out = mid + (size_t)k0 * frame_bytes;
+        L.out = mid + (size_t)k0 * mid_stride;
         L.w = w, L.h = h, L.t = t, L.n_pairs = n, L.stream = stream;
+        if (mt) L.times = mt->times, L.n_times = mt->n, L.out_pair_stride = mt->pair_stride;
         NUS_HIP(launch_warp_blend(L));
         return kOk;
     };
@@ -461,8 +491,8 @@ int HipFlowEstimator::stream_impl(const void *d_frames, uint32_t n_frames, uint3
     for (uint32_t c0 = 0; c0 < n_pairs; c0 += chunk) {
         const uint32_t pairs = n_pairs - c0 < chunk ? n_pairs - c0 : chunk;
         if ((rc = solve_batch(frames + (size_t)c0 * frame_bytes, pairs, g, coarse_iters, refine_iters, lambda,
-                              flows ? flows + (size_t)c0 * flow_bytes : nullptr, stream, mid ? mid + (size_t)c0 * frame_bytes : nullptr,
-                              t, flow_half)) != kOk)
+                              flows ? flows + (size_t)c0 * flow_bytes : nullptr, stream, mid ? mid + (size_t)c0 * mid_stride : nullptr,
+                              t, flow_half, mt)) != kOk)
             return rc;
     }
     return kOk;
@@ -471,10 +501,11 @@ int HipFlowEstimator::stream_impl(const void *d_frames, uint32_t n_frames, uint3
 // `pairs` + 1 consecutive RGBA8 frames -> `pairs` flows, every stage one launch over the whole chunk.
 // Workspace (grow-only slots): 0 / 1 the f32 RGBA inputs of the odd / even pyramid levels of all frames,
 // 2 / 3 flow ping-pong [pair][level cells], 4 luminance planes [level][frame][cells], 5 coefficients [pair][cells][3].
-// d_mid != nullptr: also the pairs' in-between frames at time t (see interpolate_device_stream); d_flows may then be null.
+// d_mid != nullptr: also the pairs' in-between frames at time t (see interpolate_device_stream), or at the times of mt; d_flows may
+// then be null.
 int HipFlowEstimator::solve_batch(const uint8_t *d_frames, uint32_t pairs, const Pyramid &g, uint32_t coarse_iters,
                                   uint32_t refine_iters, float lambda, uint8_t *d_flows, hipStream_t stream, uint8_t *d_mid, float t,
-                                  bool flow_half)
+                                  bool flow_half, const MidTimes *mt)
 {
     int rc;
     // The Jacobi kernel of a level.  FAST: k_hs_stream_fast where the level's batch would stream anyway (or the streamed kernel
@@ -526,8 +557,9 @@ int HipFlowEstimator::solve_batch(const uint8_t *d_frames, uint32_t pairs, const
     }
     float *const out = reinterpret_cast<float *>(d_flows);
     // the finest level's last launch warps the pairs itself where it can (HsWarp); `warped` says whether it did
+    // (not with several times, mt: the in-between frames then come from one multi-time warp launch behind the estimator)
     HsWarp hw;
-    hw.frames = d_frames, hw.frame_stride = cells[0] * 4, hw.mid = d_mid, hw.t = t, hw.sel = kSelRGBA;
+    hw.frames = d_frames, hw.frame_stride = cells[0] * 4, hw.mid = mt ? nullptr : d_mid, hw.t = t, hw.sel = kSelRGBA;
     hw.out_half = flow_half ? 1u : 0u;
     bool warped = false, wrote_half = false;
     // Rg16Float hand-off: only the FAST streamed kernel's last launch stores halves itself.  The caller's buffer (4 bytes per cell
@@ -599,6 +631,7 @@ int HipFlowEstimator::solve_batch(const uint8_t *d_frames, uint32_t pairs, const
         W.fma = true;
         W.out = d_mid;
         W.w = g.w[0], W.h = g.h[0], W.t = t, W.n_pairs = pairs, W.stream = stream;
+        if (mt) W.times = mt->times, W.n_times = mt->n, W.out_pair_stride = mt->pair_stride;
         NUS_HIP(launch_warp_blend(W));
     }
     return kOk;

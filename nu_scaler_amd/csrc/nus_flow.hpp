@@ -57,8 +57,19 @@ public:
     int interpolate_device_stream(const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t h, uint32_t levels,
                                   uint32_t coarse_iters, uint32_t refine_iters, float lambda, float t, void *d_flows, void *d_mid,
                                   hipStream_t stream, bool flow_half = false);
+    // As interpolate_device_stream, the frames at n_times times per pair from ONE estimate of each pair's flow: one multi-time
+    // warp launch (FMA mode) behind the estimator, never the fused one.  Frame j of pair k at d_mid + k * mid_pair_stride +
+    // j * w * h * 4 (0: tightly packed).  The arguments are checked before any HIP call; the flows at d_flows are the same bytes.
+    int interpolate_multi_device_stream(const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t h, uint32_t levels,
+                                        uint32_t coarse_iters, uint32_t refine_iters, float lambda, const float *times, uint32_t n_times,
+                                        bool flow_half, void *d_flows, void *d_mid, size_t mid_pair_stride, hipStream_t stream);
 
 private:
+    struct MidTimes { // the multi-time warp behind the estimator (interpolate_multi_device_stream)
+        const float *times = nullptr;
+        uint32_t n = 0;
+        size_t pair_stride = 0; // bytes between the in-between frames of consecutive pairs
+    };
     struct Pyramid { // level geometry; levels are packed at `offset` (16 bytes per pixel reserved)
         uint32_t levels = 0, w[12] = {0}, h[12] = {0};
         size_t offset[12] = {0}, total = 0;
@@ -75,10 +86,11 @@ private:
     static constexpr uint32_t kStreamMaxChunkPairs = 150;
     static constexpr size_t kStreamWorkspaceBytes = (size_t)12 << 30;
     int stream_impl(const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t h, uint32_t levels, uint32_t coarse_iters,
-                    uint32_t refine_iters, float lambda, void *d_flows, void *d_mid, float t, hipStream_t stream, bool flow_half = false);
+                    uint32_t refine_iters, float lambda, void *d_flows, void *d_mid, float t, hipStream_t stream, bool flow_half = false,
+                    const MidTimes *mt = nullptr);
     int solve_batch(const uint8_t *d_frames, uint32_t pairs, const Pyramid &g, uint32_t coarse_iters, uint32_t refine_iters,
                     float lambda, uint8_t *d_flows, hipStream_t stream, uint8_t *d_mid = nullptr, float t = 0.5f,
-                    bool flow_half = false);
+                    bool flow_half = false, const MidTimes *mt = nullptr);
     int fail(int status, const std::string &msg);
     int fail_hip(hipError_t e, const char *what);
     int ensure_device();

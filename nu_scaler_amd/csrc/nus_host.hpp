@@ -319,6 +319,14 @@ public:
     InterpolationQuality quality() const override { return quality_; }
     int interpolate_device(const void *d_a, size_t a_stride, const void *d_b, size_t b_stride, const void *d_flow,
                            uint32_t w, uint32_t h, float t, void *d_out, uint32_t n_pairs, hipStream_t stream);
+    // Several in-between frames per pair from one launch: the frames at times[0 .. n_times), each the bytes the single-time call
+    // writes for that time.  Frame k of pair i at d_out + i * out_pair_stride + k * w * h * 4 (0: tightly packed); the host form
+    // writes the n_times frames back to back.  Arguments are checked before any HIP call (times in [0, 1], 1 .. kInterpMaxTimes).
+    int interpolate_multi_device(const void *d_a, size_t a_stride, const void *d_b, size_t b_stride, const void *d_flow, uint32_t w,
+                                 uint32_t h, const float *times, uint32_t n_times, void *d_out, size_t out_pair_stride,
+                                 uint32_t n_pairs, hipStream_t stream);
+    int interpolate_multi(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, const float *flow, uint32_t w, uint32_t h,
+                          const float *times, uint32_t n_times, uint8_t *out, size_t out_cap);
     const char *name() const override { return "HipWarpBlendInterpolator"; }
     const char *last_error() const override { return error_.c_str(); }
     int set_device(int device);
@@ -334,8 +342,12 @@ public:
 private:
     int fail(int status, const std::string &msg);
     int fail_hip(hipError_t e, const char *what);
-    int ensure(size_t frame_bytes, bool with_flow);
+    int ensure(size_t frame_bytes, bool with_flow, uint32_t n_out = 1);
     void release();
+    // (mu_ held, arguments checked) stage and upload the pair, run one launch of the frames at `t` or at times[0 .. n_times), bring
+    // the n frames back into `out`
+    int host_pass(const uint8_t *a, const uint8_t *b, const float *flow, uint32_t w, uint32_t h, float t, const float *times,
+                  uint32_t n_times, uint8_t *out);
 
     mutable std::mutex mu_;
     int wg_preset_;
@@ -345,12 +357,13 @@ private:
     bool device_ready_ = false;
     int in_format_ = 0; // nus_pixel_format
     size_t cap_bytes_ = 0;
+    uint32_t cap_out_ = 0; // frames d_out_ (and the staging's output part) holds
     bool cap_flow_ = false;
     uint8_t *d_a_ = nullptr, *d_b_ = nullptr, *d_out_ = nullptr;
     bool flow_half_ = false; // interpolate_device reads 2 x f16 per pixel
     bool fma_ = false;       // dense-flow warp in FMA mode
     float *d_flow_ = nullptr;
-    uint8_t *h_stage_ = nullptr; // pinned: a | b | out
+    uint8_t *h_stage_ = nullptr; // pinned: a | b | cap_out_ frames out
     float *h_flow_ = nullptr;    // pinned
     hipStream_t stream_ = nullptr;
     hipEvent_t k_begin_ = nullptr, k_end_ = nullptr, half_done_ = nullptr;

@@ -65,10 +65,11 @@ void HipFrameInterpolator::release()
     h_stage_ = nullptr;
     h_flow_ = nullptr;
     cap_bytes_ = 0;
+    cap_out_ = 0;
     cap_flow_ = false;
 }
 
-int HipFrameInterpolator::ensure(size_t frame_bytes, bool with_flow)
+int HipFrameInterpolator::ensure(size_t frame_bytes, bool with_flow, uint32_t n_out)
 {
     if (!device_ready_) {
         const int n = device_count();
@@ -82,21 +83,23 @@ int HipFrameInterpolator::ensure(size_t frame_bytes, bool with_flow)
         device_ready_ = true;
     }
     NUS_HIP(hipSetDevice(device_));
-    if (frame_bytes > cap_bytes_ || (with_flow && !cap_flow_)) {
+    if (frame_bytes > cap_bytes_ || (with_flow && !cap_flow_) || n_out > cap_out_) {
         // the reference reallocates its textures on every call (wgpu_interpolator.rs:253-321);
         // here buffers persist and only grow.
         const size_t want = frame_bytes > cap_bytes_ ? frame_bytes : cap_bytes_;
+        const uint32_t outs = n_out > cap_out_ ? n_out : cap_out_;
         const bool flow = with_flow || cap_flow_;
         release();
         NUS_HIP(hipMalloc(reinterpret_cast<void **>(&d_a_), want));
         NUS_HIP(hipMalloc(reinterpret_cast<void **>(&d_b_), want));
-        NUS_HIP(hipMalloc(reinterpret_cast<void **>(&d_out_), want));
-        NUS_HIP(pinned_alloc(reinterpret_cast<void **>(&h_stage_), want * 3));
+        NUS_HIP(hipMalloc(reinterpret_cast<void **>(&d_out_), want * outs));
+        NUS_HIP(pinned_alloc(reinterpret_cast<void **>(&h_stage_), want * (2 + outs)));
         if (flow) {
             NUS_HIP(hipMalloc(reinterpret_cast<void **>(&d_flow_), want * 2));
             NUS_HIP(pinned_alloc(reinterpret_cast<void **>(&h_flow_), want * 2));
         }
         cap_bytes_ = want;
+        cap_out_ = outs;
         cap_flow_ = flow;
     }
     return kOk;
@@ -150,7 +153,32 @@ int HipFrameInterpolator::interpolate(const uint8_t *a, size_t a_len, const uint
                                        expected, w, h, a_len, b_len));
     if (!a || !b || !out) return fail(kInvalidArgument, "interpolate: null frame pointer");
     if (out_cap < expected) return fail(kInvalidArgument, "interpolate: output capacity too small");
-    int rc = ensure(expected, flow != nullptr);
+    return host_pass(a, b, flow, w, h, t, nullptr, 0, out);
+}
+
+int HipFrameInterpolator::interpolate_multi(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, const float *flow,
+                                            uint32_t w, uint32_t h, const float *times, uint32_t n_times, uint8_t *out, size_t out_cap)
+{
+    std::lock_guard<std::mutex> lk(mu_);
+    if (w == 0 || h == 0 || (uint64_t)w * h >= (1ull << 31)) return fail(kInvalidArgument, "nus_interp_interpolate_multi: bad dimensions");
+    const size_t expected = (size_t)w * h * 4;
+    if (a_len != expected || b_len != expected) // the text of nus_interp_interpolate (wgpu_interpolator.rs:234-237)
+        return fail(kSizeMismatch, fmt("Expected %zu bytes per frame for %ux%ux4 RGBA, got frame_a: %zu bytes, frame_b: %zu bytes",
+                                       expected, w, h, a_len, b_len));
+    if (!a || !b || !out) return fail(kInvalidArgument, "nus_interp_interpolate_multi: null frame pointer");
+    const std::string bad = check_interp_times(times, n_times);
+    if (!bad.empty()) return fail(kInvalidArgument, "nus_interp_interpolate_multi: " + bad);
+    if (out_cap / n_times < expected)
+        return fail(kInvalidArgument, fmt("nus_interp_interpolate_multi: output capacity %zu below n_times * w * h * 4 = %zu", out_cap,
+                                          (size_t)n_times * expected));
+    return host_pass(a, b, flow, w, h, 0.0f, times, n_times, out);
+}
+
+int HipFrameInterpolator::host_pass(const uint8_t *a, const uint8_t *b, const float *flow, uint32_t w, uint32_t h, float t,
+                                    const float *times, uint32_t n_times, uint8_t *out)
+{
+    const size_t expected = (size_t)w * h * 4, total = expected * (n_times ? n_times : 1);
+    int rc = ensure(expected, flow != nullptr, n_times ? n_times : 1);
     if (rc != kOk) return rc;
     uint8_t *ha = h_stage_, *hb = h_stage_ + cap_bytes_, *ho = h_stage_ + 2 * cap_bytes_;
     // while the pair is staged, uploaded and on the GPU, idle workers of the copy pool make the pages of the result buffer
@@ -159,7 +187,7 @@ int HipFrameInterpolator::interpolate(const uint8_t *a, size_t a_len, const uint
         CopyTicket t;
         ~Populate() { parallel_copy_wait(t); } // on every way out: queued requests point into `out`
     } populate;
-    if (parallel_populate_prepare(out, expected)) parallel_populate_async(out, expected, populate.t);
+    if (parallel_populate_prepare(out, total)) parallel_populate_async(out, total, populate.t);
     // stage A, start its DMA, stage B meanwhile (the reference uploads both synchronously:
     // wgpu_interpolator.rs:253-321)
     parallel_copy(ha, a, expected);
@@ -179,6 +207,8 @@ int HipFrameInterpolator::interpolate(const uint8_t *a, size_t a_len, const uint
     L.w = w;
     L.h = h;
     L.t = t;
+    L.times = times;
+    L.n_times = n_times;
     L.n_pairs = 1;
     L.stream = stream_;
     L.fma = fma_;
@@ -187,16 +217,16 @@ int HipFrameInterpolator::interpolate(const uint8_t *a, size_t a_len, const uint
     hipError_t e = launch_warp_blend(L);
     if (e != hipSuccess) return fail_hip(e, "warp+blend launch");
     NUS_HIP(hipEventRecord(k_end_, stream_));
-    // the frame comes back in two halves: the host copy of the first overlaps the DMA of the second
-    const size_t half = (expected / 2 + 4095) & ~(size_t)4095;
-    const size_t first = half < expected ? half : expected;
+    // the frames come back in two halves: the host copy of the first overlaps the DMA of the second
+    const size_t half = (total / 2 + 4095) & ~(size_t)4095;
+    const size_t first = half < total ? half : total;
     NUS_HIP(hipMemcpyAsync(ho, d_out_, first, hipMemcpyDeviceToHost, stream_));
     NUS_HIP(hipEventRecord(half_done_, stream_));
-    if (first < expected) NUS_HIP(hipMemcpyAsync(ho + first, d_out_ + first, expected - first, hipMemcpyDeviceToHost, stream_));
+    if (first < total) NUS_HIP(hipMemcpyAsync(ho + first, d_out_ + first, total - first, hipMemcpyDeviceToHost, stream_));
     NUS_HIP(hipEventSynchronize(half_done_));
     parallel_copy(out, ho, first);
     NUS_HIP(hipStreamSynchronize(stream_));
-    if (first < expected) parallel_copy(out + first, ho + first, expected - first);
+    if (first < total) parallel_copy(out + first, ho + first, total - first);
     float ms = 0.0f;
     if (hipEventElapsedTime(&ms, k_begin_, k_end_) == hipSuccess) {
         have_ms_ = true;
@@ -239,6 +269,50 @@ int HipFrameInterpolator::interpolate_device(const void *d_a, size_t a_stride, c
     L.in_sel = input_selector(in_format_);
     hipError_t e = launch_warp_blend(L);
     if (e != hipSuccess) return fail_hip(e, "warp+blend launch");
+    return kOk;
+}
+
+int HipFrameInterpolator::interpolate_multi_device(const void *d_a, size_t a_stride, const void *d_b, size_t b_stride,
+                                                   const void *d_flow, uint32_t w, uint32_t h, const float *times, uint32_t n_times,
+                                                   void *d_out, size_t out_pair_stride, uint32_t n_pairs, hipStream_t stream)
+{
+    static const char *const who = "nus_interp_interpolate_multi_device";
+    std::lock_guard<std::mutex> lk(mu_);
+    if (w == 0 || h == 0 || (uint64_t)w * h >= (1ull << 31)) return fail(kInvalidArgument, fmt("%s: bad dimensions", who));
+    if (!d_a || !d_b || !d_out) return fail(kInvalidArgument, fmt("%s: null device pointer", who));
+    const std::string bad = check_interp_times(times, n_times);
+    if (!bad.empty()) return fail(kInvalidArgument, fmt("%s: %s", who, bad.c_str()));
+    if ((reinterpret_cast<uintptr_t>(d_a) % 4) || (reinterpret_cast<uintptr_t>(d_b) % 4) ||
+        (reinterpret_cast<uintptr_t>(d_out) % 4) || (a_stride % 4) || (b_stride % 4) ||
+        (d_flow && reinterpret_cast<uintptr_t>(d_flow) % (flow_half_ ? 4 : 8)))
+        return fail(kInvalidArgument, fmt("%s: pointers/strides must be pixel aligned", who));
+    const size_t frame_bytes = (size_t)w * h * 4;
+    if (out_pair_stride != 0 && (out_pair_stride < n_times * frame_bytes || out_pair_stride % 4))
+        return fail(kInvalidArgument, fmt("%s: out_pair_stride %zu must be 0 or a multiple of 4 of at least n_times * w * h * 4 = %zu", who,
+                                          out_pair_stride, n_times * frame_bytes));
+    if (n_pairs == 0) return kOk;
+    const int n = device_count();
+    if (n <= 0) return fail(kNoDevice, "no HIP device available (the gfx950 path has no CPU fallback)");
+    NUS_HIP(hipSetDevice(device_));
+    WarpLaunch L;
+    L.a = static_cast<const uint8_t *>(d_a);
+    L.b = static_cast<const uint8_t *>(d_b);
+    L.flow = static_cast<const float *>(d_flow);
+    L.flow_half = flow_half_;
+    L.fma = fma_;
+    L.out = static_cast<uint8_t *>(d_out);
+    L.a_stride = a_stride;
+    L.b_stride = b_stride;
+    L.w = w;
+    L.h = h;
+    L.times = times;
+    L.n_times = n_times;
+    L.out_pair_stride = out_pair_stride;
+    L.n_pairs = n_pairs;
+    L.stream = stream;
+    L.in_sel = input_selector(in_format_);
+    hipError_t e = launch_warp_blend(L);
+    if (e != hipSuccess) return fail_hip(e, "multi-time warp+blend launch");
     return kOk;
 }
 

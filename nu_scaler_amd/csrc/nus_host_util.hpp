@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <string>
 
+#include "nus_kernels.hpp"
 #include "nus_ranges.hpp"
 
 namespace nus {
@@ -22,6 +23,17 @@ std::string fmt(const char *f, ...)
     vsnprintf(buf, sizeof buf, f, ap);
     va_end(ap);
     return buf;
+}
+
+// The time set of the multi-time interpolation entry points: 1 .. kInterpMaxTimes times, each in [0, 1] (NaN is not).  Returns
+// what is wrong with it, empty when nothing is.
+std::string check_interp_times(const float *times, uint32_t n_times)
+{
+    if (!times) return "times is null";
+    if (n_times == 0 || n_times > kInterpMaxTimes) return fmt("n_times must be 1..%u, got %u", kInterpMaxTimes, n_times);
+    for (uint32_t k = 0; k < n_times; ++k)
+        if (!(times[k] >= 0.0f && times[k] <= 1.0f)) return fmt("times[%u] = %g is not in [0, 1]", k, (double)times[k]);
+    return std::string();
 }
 
 // True when `p` is host memory the DMA engines can address directly

@@ -18,25 +18,39 @@ namespace {
 // positions are the pixel centres, so the bilinear samples are the pixels themselves
 // and the kernel is a streaming blend, 4 pixels (16 B) per lane.
 
-template <bool VEC>
+// MT: the multi-time form -- each lane loads its A and B pixels once, then blends and stores them once per time of the set (frame
+// k of the pair at out + k * npx * 4).  MT = false is the single-time kernel: the set's one time, no loop.
+template <bool VEC, bool MT>
 __global__ __launch_bounds__(256) void k_blend_zero_flow(
     const uint8_t *__restrict__ a, const uint8_t *__restrict__ b, uint8_t *__restrict__ out,
-    size_t a_stride, size_t b_stride, size_t npx, float t, uint32_t sel)
+    size_t a_stride, size_t b_stride, size_t out_pair_stride, size_t npx, TimeSet ts, uint32_t sel)
 {
-    const float nt = 1.0f - t;
     const uint32_t *pa = reinterpret_cast<const uint32_t *>(a + (size_t)blockIdx.y * a_stride);
     const uint32_t *pb = reinterpret_cast<const uint32_t *>(b + (size_t)blockIdx.y * b_stride);
-    uint32_t *po = reinterpret_cast<uint32_t *>(out) + (size_t)blockIdx.y * npx;
+    uint8_t *const pair_out = out + (size_t)blockIdx.y * out_pair_stride;
     const size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * (VEC ? 4 : 1);
     if (i >= npx) return;
+    const uint32_t nk = MT ? ts.n : 1;
     if (VEC) {
         const uint4 va = *reinterpret_cast<const uint4 *>(pa + i);
         const uint4 vb = *reinterpret_cast<const uint4 *>(pb + i);
-        // per-channel arithmetic: swizzling the blended pixel equals blending swizzled inputs
-        store_out16<false>(po + i, swz4(make_uint4(blend_px(va.x, vb.x, t, nt), blend_px(va.y, vb.y, t, nt),
-                                                             blend_px(va.z, vb.z, t, nt), blend_px(va.w, vb.w, t, nt)), sel));
+        for (uint32_t k = 0; k < nk; ++k) {
+            float t = ts.t[k];
+            if (MT) asm volatile("" : "+v"(t)); // per-lane copy (scalar operands halve the VALU issue rate on gfx950)
+            const float nt = 1.0f - t;
+            uint32_t *po = reinterpret_cast<uint32_t *>(pair_out + (size_t)k * npx * 4);
+            // per-channel arithmetic: swizzling the blended pixel equals blending swizzled inputs
+            store_out16<false>(po + i, swz4(make_uint4(blend_px(va.x, vb.x, t, nt), blend_px(va.y, vb.y, t, nt),
+                                                                 blend_px(va.z, vb.z, t, nt), blend_px(va.w, vb.w, t, nt)), sel));
+        }
     } else {
-        po[i] = swz(blend_px(pa[i], pb[i], t, nt), sel);
+        const uint32_t va = pa[i], vb = pb[i];
+        for (uint32_t k = 0; k < nk; ++k) {
+            float t = ts.t[k];
+            if (MT) asm volatile("" : "+v"(t));
+            const float nt = 1.0f - t;
+            reinterpret_cast<uint32_t *>(pair_out + (size_t)k * npx * 4)[i] = swz(blend_px(va, vb, t, nt), sel);
+        }
     }
 }
 
@@ -96,10 +110,14 @@ __device__ __forceinline__ float4 sample_trunc(const uint32_t *__restrict__ f, u
 #ifndef NUS_WARP_RV
 #define NUS_WARP_RV 2
 #endif
-template <int MODE, bool HALF, int XV, int RV>
+// MT: the multi-time form -- the thread's flow vectors are loaded once, then its pixels are warped, blended and stored once per
+// time of the set (frame k of the pair at out + k * w * h * 4; the gathers of the later times hit the lines the first one brought
+// into the L2).  MT = false is the single-time kernel: the set's one time, no loop.
+template <int MODE, bool HALF, int XV, int RV, bool MT>
 __global__ __launch_bounds__(256) void k_warp_blend_flow(
     const uint8_t *__restrict__ a, const uint8_t *__restrict__ b, const void *__restrict__ flow,
-    uint8_t *__restrict__ out, size_t a_stride, size_t b_stride, uint32_t w, uint32_t h, float t, uint32_t sel)
+    uint8_t *__restrict__ out, size_t a_stride, size_t b_stride, size_t out_pair_stride, uint32_t w, uint32_t h, TimeSet ts,
+    uint32_t sel)
 {
     const uint32_t ybase = __builtin_amdgcn_readfirstlane(blockIdx.y * (4 * RV) + threadIdx.y);
     const uint32_t x0 = (blockIdx.x * kWave + threadIdx.x) * XV;
@@ -111,9 +129,8 @@ __global__ __launch_bounds__(256) void k_warp_blend_flow(
     const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<uint8_t *>(b + (size_t)blockIdx.z * b_stride), 0, frame_bytes, 0x00020000);
     // per-lane copies of the wave-uniform constants: scalar operands halve the VALU issue rate on gfx950
-    float tv = t, wmax = (float)(w - 1), hmax = (float)(h - 1);
-    asm volatile("" : "+v"(tv), "+v"(wmax), "+v"(hmax));
-    const float nt = 1.0f - tv;
+    float wmax = (float)(w - 1), hmax = (float)(h - 1);
+    asm volatile("" : "+v"(wmax), "+v"(hmax));
     const size_t frame0 = (size_t)blockIdx.z * npx;
     float2 f[RV][XV];
 #pragma unroll
@@ -159,37 +176,48 @@ __global__ __launch_bounds__(256) void k_warp_blend_flow(
             }
         }
     }
+    const uint32_t nk = MT ? ts.n : 1;
+    for (uint32_t k = 0; k < nk; ++k) {
+        float tv = ts.t[k];
+        asm volatile("" : "+v"(tv));
+        const float nt = 1.0f - tv;
+        uint32_t *const frame_out = reinterpret_cast<uint32_t *>(out + (size_t)blockIdx.z * out_pair_stride + (size_t)k * npx * 4);
 #pragma unroll
-    for (int j = 0; j < RV; ++j) {
-        const uint32_t y = ybase + 4 * j;
-        if (y >= h) break; // wave-uniform
-        const float yfl = (float)y;
-        uint32_t o[XV];
+        for (int j = 0; j < RV; ++j) {
+            const uint32_t y = ybase + 4 * j;
+            if (y >= h) break; // wave-uniform
+            const float yfl = (float)y;
+            uint32_t o[XV];
 #pragma unroll
-        for (int i = 0; i < XV; ++i) {
-            const uint32_t p = warp_blend_pixel<MODE>(ra, rb, row_bytes, wmax, hmax, w - 2, h - 2, (float)(x0 + i), yfl, f[j][i], tv, nt);
-            o[i] = swz(p, sel);
-        }
-        uint32_t *dst = reinterpret_cast<uint32_t *>(out) + frame0 + (size_t)y * w + x0;
-        if (XV == 4) {
-            store_out16<false>(dst, make_uint4(o[0], o[1], o[2], o[3]));
-        } else if (XV == 2) {
-            store_out8<false>(dst, make_uint2(o[0], o[1]));
-        } else {
+            for (int i = 0; i < XV; ++i) {
+                const uint32_t p = warp_blend_pixel<MODE>(ra, rb, row_bytes, wmax, hmax, w - 2, h - 2, (float)(x0 + i), yfl, f[j][i], tv, nt);
+                o[i] = swz(p, sel);
+            }
+            uint32_t *dst = frame_out + (size_t)y * w + x0;
+            if (XV == 4) {
+                store_out16<false>(dst, make_uint4(o[0], o[1], o[2], o[3]));
+            } else if (XV == 2) {
+                store_out8<false>(dst, make_uint2(o[0], o[1]));
+            } else {
 #pragma unroll
-            for (int i = 0; i < XV; ++i) dst[i] = o[i];
+                for (int i = 0; i < XV; ++i) dst[i] = o[i];
+            }
         }
     }
 }
 
 // Frames narrower or lower than 2 pixels, or of 4 GiB and more: one pixel per thread, 64-bit addressing (EXACT arithmetic).
+// MT: the flow vector is loaded once and the pixel of every time of the set stored (frame k at out + k * w * h * 4); MT = false is
+// the single-time kernel: the set's one time, no loop.
+template <bool MT>
 __global__ __launch_bounds__(256) void k_warp_blend_flow_tiny(
     const uint8_t *__restrict__ a, const uint8_t *__restrict__ b, const void *__restrict__ flow, bool half,
-    uint8_t *__restrict__ out, size_t a_stride, size_t b_stride, uint32_t w, uint32_t h, float t, uint32_t sel)
+    uint8_t *__restrict__ out, size_t a_stride, size_t b_stride, size_t out_pair_stride, uint32_t w, uint32_t h, TimeSet ts,
+    uint32_t sel)
 {
     const uint32_t y = blockIdx.y * 4 + threadIdx.y, x = blockIdx.x * kWave + threadIdx.x;
     if (y >= h || x >= w) return;
-    const size_t npx = (size_t)w * h, idx = (size_t)blockIdx.z * npx + (size_t)y * w + x;
+    const size_t npx = (size_t)w * h, idx = (size_t)blockIdx.z * npx + (size_t)y * w + x, pix = (size_t)y * w + x;
     const uint32_t *fa = reinterpret_cast<const uint32_t *>(a + (size_t)blockIdx.z * a_stride);
     const uint32_t *fb = reinterpret_cast<const uint32_t *>(b + (size_t)blockIdx.z * b_stride);
     float2 f;
@@ -199,15 +227,19 @@ __global__ __launch_bounds__(256) void k_warp_blend_flow_tiny(
     } else {
         f = reinterpret_cast<const float2 *>(flow)[idx];
     }
-    const float nt = 1.0f - t;
-    const float4 sa = sample_trunc(fa, w, h, (float)x - t * f.x, (float)y - t * f.y);
-    const float4 sb = sample_trunc(fb, w, h, (float)x + nt * f.x, (float)y + nt * f.y);
-    uint32_t o = 0;
-    o = pack_trunc_u8(nt * sa.x + t * sb.x, 0, o);
-    o = pack_trunc_u8(nt * sa.y + t * sb.y, 1, o);
-    o = pack_trunc_u8(nt * sa.z + t * sb.z, 2, o);
-    o = pack_trunc_u8(nt * sa.w + t * sb.w, 3, o);
-    reinterpret_cast<uint32_t *>(out)[idx] = swz(o, sel);
+    const uint32_t nk = MT ? ts.n : 1;
+    for (uint32_t k = 0; k < nk; ++k) {
+        const float t = ts.t[k];
+        const float nt = 1.0f - t;
+        const float4 sa = sample_trunc(fa, w, h, (float)x - t * f.x, (float)y - t * f.y);
+        const float4 sb = sample_trunc(fb, w, h, (float)x + nt * f.x, (float)y + nt * f.y);
+        uint32_t o = 0;
+        o = pack_trunc_u8(nt * sa.x + t * sb.x, 0, o);
+        o = pack_trunc_u8(nt * sa.y + t * sb.y, 1, o);
+        o = pack_trunc_u8(nt * sa.z + t * sb.z, 2, o);
+        o = pack_trunc_u8(nt * sa.w + t * sb.w, 3, o);
+        reinterpret_cast<uint32_t *>(out + (size_t)blockIdx.z * out_pair_stride + (size_t)k * npx * 4)[pix] = swz(o, sel);
+    }
 }
 
 // ---------------------------------------------------------------------------------
@@ -248,42 +280,62 @@ hipError_t launch_swizzle_bgra(const uint8_t *in, uint8_t *out, size_t npx, hipS
 hipError_t launch_warp_blend(const WarpLaunch &L)
 {
     const size_t npx = (size_t)L.w * L.h;
+    TimeSet ts{};
+    if (L.n_times == 0) {
+        ts.t[0] = L.t;
+        ts.n = 1;
+    } else {
+        if (L.n_times > kInterpMaxTimes || L.times == nullptr) return hipErrorInvalidValue;
+        for (uint32_t k = 0; k < L.n_times; ++k) ts.t[k] = L.times[k];
+        ts.n = L.n_times;
+    }
+    const bool mt = ts.n > 1;
+    const size_t out_stride = L.out_pair_stride ? L.out_pair_stride : ts.n * npx * 4;
     for (uint32_t done = 0; done < L.n_pairs;) {
         const uint32_t n = L.n_pairs - done < kMaxGridZ ? L.n_pairs - done : kMaxGridZ;
         const uint8_t *a = L.a + (size_t)done * L.a_stride;
         const uint8_t *b = L.b + (size_t)done * L.b_stride;
-        uint8_t *out = L.out + (size_t)done * npx * 4;
+        uint8_t *out = L.out + (size_t)done * out_stride;
         if (L.flow == nullptr) {
-            const bool vec = (npx % 4) == 0 && (L.a_stride % 16) == 0 && (L.b_stride % 16) == 0 &&
+            const bool vec = (npx % 4) == 0 && (L.a_stride % 16) == 0 && (L.b_stride % 16) == 0 && (out_stride % 16) == 0 &&
                              (reinterpret_cast<uintptr_t>(a) % 16) == 0 && (reinterpret_cast<uintptr_t>(b) % 16) == 0 &&
                              (reinterpret_cast<uintptr_t>(out) % 16) == 0;
             const size_t items = vec ? npx / 4 : npx;
             const dim3 block(256), grid((uint32_t)((items + 255) / 256), n);
-            if (vec)
-                hipLaunchKernelGGL(k_blend_zero_flow<true>, grid, block, 0, L.stream, a, b, out, L.a_stride, L.b_stride, npx, L.t, L.in_sel);
-            else
-                hipLaunchKernelGGL(k_blend_zero_flow<false>, grid, block, 0, L.stream, a, b, out, L.a_stride, L.b_stride, npx, L.t, L.in_sel);
+#define NUS_ZB(V, MT) hipLaunchKernelGGL((k_blend_zero_flow<V, MT>), grid, block, 0, L.stream, a, b, out, L.a_stride, L.b_stride, out_stride, npx, ts, L.in_sel)
+            if (vec) {
+                if (mt) NUS_ZB(true, true); else NUS_ZB(true, false);
+            } else {
+                if (mt) NUS_ZB(false, true); else NUS_ZB(false, false);
+            }
+#undef NUS_ZB
         } else {
             const void *fl = reinterpret_cast<const uint8_t *>(L.flow) + (size_t)done * npx * (L.flow_half ? 4 : 8);
             const bool corner = L.w >= 2 && L.h >= 2 && npx * 4 < (1ull << 32) && L.w * 4ull < (1u << 24) && L.h < (1u << 24);
             if (!corner) {
                 const dim3 block(kWave, 4), grid(cdiv(L.w, 64), cdiv(L.h, 4), n);
-                hipLaunchKernelGGL(k_warp_blend_flow_tiny, grid, block, 0, L.stream, a, b, fl, L.flow_half, out, L.a_stride, L.b_stride,
-                                   L.w, L.h, L.t, L.in_sel);
+                if (mt)
+                    hipLaunchKernelGGL(k_warp_blend_flow_tiny<true>, grid, block, 0, L.stream, a, b, fl, L.flow_half, out, L.a_stride,
+                                       L.b_stride, out_stride, L.w, L.h, ts, L.in_sel);
+                else
+                    hipLaunchKernelGGL(k_warp_blend_flow_tiny<false>, grid, block, 0, L.stream, a, b, fl, L.flow_half, out, L.a_stride,
+                                       L.b_stride, out_stride, L.w, L.h, ts, L.in_sel);
             } else {
                 constexpr int XV = NUS_WARP_XV, RV = NUS_WARP_RV;
                 const uintptr_t align = XV == 4 ? 16 : 8; // of the thread's output pixels (its f16 flow vectors: the same bytes)
                 const bool xv_ok = XV == 1 || ((L.w % XV) == 0 && (reinterpret_cast<uintptr_t>(fl) % 16) == 0 &&
-                                               (reinterpret_cast<uintptr_t>(out) % align) == 0);
+                                               (reinterpret_cast<uintptr_t>(out) % align) == 0 && (out_stride % align) == 0);
                 const dim3 block(kWave, 4), grid(cdiv(L.w, 64 * (xv_ok ? XV : 1)), cdiv(L.h, 4 * RV), n);
-#define NUS_WB(M, H, X) hipLaunchKernelGGL((k_warp_blend_flow<M, H, X, RV>), grid, block, 0, L.stream, a, b, fl, out, L.a_stride, L.b_stride, L.w, L.h, L.t, L.in_sel)
-#define NUS_WB_X(M, H) do { if (xv_ok) NUS_WB(M, H, XV); else NUS_WB(M, H, 1); } while (0)
+#define NUS_WB(M, H, X, MT) hipLaunchKernelGGL((k_warp_blend_flow<M, H, X, RV, MT>), grid, block, 0, L.stream, a, b, fl, out, L.a_stride, L.b_stride, out_stride, L.w, L.h, ts, L.in_sel)
+#define NUS_WB_T(M, H, X) do { if (mt) NUS_WB(M, H, X, true); else NUS_WB(M, H, X, false); } while (0)
+#define NUS_WB_X(M, H) do { if (xv_ok) NUS_WB_T(M, H, XV); else NUS_WB_T(M, H, 1); } while (0)
                 if (L.fma) {
                     if (L.flow_half) NUS_WB_X(kWarpFma, true); else NUS_WB_X(kWarpFma, false);
                 } else {
                     if (L.flow_half) NUS_WB_X(kWarpExact, true); else NUS_WB_X(kWarpExact, false);
                 }
 #undef NUS_WB_X
+#undef NUS_WB_T
 #undef NUS_WB
             }
         }

@@ -169,6 +169,14 @@ constexpr uint32_t kLanczosX2EdgeCols = 8; // output columns left to the general
 #endif
 constexpr uint32_t kLanczosX2StripCols = NUS_LZ_STRIP_COLS; // input columns produced per wave (lanes 1 .. StripCols / 4, 4 columns each)
 
+// The in-between times of one warp + blend launch, passed by value in the kernel arguments (no device buffer, no copy): every
+// pair's A, B and flow are read once and the frame of each time is stored (NUS_INTERP_MAX_TIMES in the C header).
+constexpr uint32_t kInterpMaxTimes = 7;
+struct TimeSet {
+    float t[kInterpMaxTimes];
+    uint32_t n;
+};
+
 struct WarpLaunch {
     const uint8_t *a = nullptr, *b = nullptr;
     const float *flow = nullptr; // nullptr: zero flow
@@ -178,11 +186,16 @@ struct WarpLaunch {
     size_t a_stride = 0, b_stride = 0; // bytes between consecutive pairs
     uint32_t w = 0, h = 0;
     float t = 0.5f;
+    const float *times = nullptr; // n_times > 0: the frames at times[0 .. n_times) instead of the one at t
+    uint32_t n_times = 0;
+    size_t out_pair_stride = 0; // bytes between the outputs of consecutive pairs; 0: the pair's frames tightly packed
     uint32_t n_pairs = 1;
     hipStream_t stream = nullptr;
     uint32_t in_sel = kSelRGBA; // channel order of both input frames (the output is RGBA)
 };
 
+// Frame k of pair i goes to out + i * out_pair_stride + k * w * h * 4.  One time runs the single-time kernels; more, their
+// multi-time instantiations (the same per-pixel arithmetic, looped over the times after the loads).
 hipError_t launch_warp_blend(const WarpLaunch &L);
 
 // BGRA -> RGBA (in place allowed: in == out).

@@ -9,6 +9,8 @@ and more Jacobi steps per finer level.  The result is the dense (dx, dy) field t
 """
 from __future__ import annotations
 
+import ctypes
+
 import numpy as np
 
 from . import _capi as C
@@ -139,3 +141,17 @@ class FlowEstimator:
         self._check(self._lib.nus_flow_interpolate_device_stream(self._h, d_frames, n_frames, width, height, self.levels,
                                                                  self.coarse_iterations, self.refine_iterations, self.lambda_,
                                                                  float(time_t), fmt, d_flows or None, d_mid, stream or None))
+
+    def interpolate_multi_device_stream(self, d_frames: int, n_frames: int, width: int, height: int, times, d_mid: int,
+                                        d_flows: int = 0, mid_pair_stride: int = 0, stream: int = 0, flow_format: str = "f32") -> None:
+        """interpolate_device_stream at several times per pair (nus_flow_interpolate_multi_device_stream): each pair's flow is
+        estimated once and all its frames are warped from it; pair k's frame j at d_mid + k * mid_pair_stride + j * w*h*4
+        (0: tightly packed)."""
+        fmt = {"f32": 0, "f16": 1}.get(flow_format)
+        if fmt is None:
+            raise ValueError("flow_format must be 'f32' or 'f16'")
+        ts = (ctypes.c_float * len(times))(*[float(t) for t in times])
+        self._check(self._lib.nus_flow_interpolate_multi_device_stream(self._h, d_frames, n_frames, width, height, self.levels,
+                                                                       self.coarse_iterations, self.refine_iterations, self.lambda_,
+                                                                       ts, len(times), fmt, d_flows or None, d_mid, mid_pair_stride,
+                                                                       stream or None))

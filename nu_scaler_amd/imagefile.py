@@ -8,6 +8,7 @@ because nothing else in the image can read PNGs.  Pixels go through the HIP path
 """
 from __future__ import annotations
 
+import os
 import struct
 import zlib
 
@@ -185,3 +186,32 @@ def interpolate_image_files(path_a: str, path_b: str, output_path: str, time_t: 
     out = it.interpolate_py(a, b, w, h, time_t=time_t, flow=flow) if flow is not None else it.interpolate_py(a, b, w, h, time_t=time_t)
     write_png(output_path, w, h, out)
     return w, h
+
+
+def multi_output_paths(output_path: str, multiplier: int) -> list[str]:
+    """Where `interpolate --multiplier M` writes its M - 1 frames: <stem>_<k><ext> for k = 1 .. M - 1."""
+    stem, ext = os.path.splitext(output_path)
+    return [f"{stem}_{k}{ext}" for k in range(1, int(multiplier))]
+
+
+def interpolate_image_files_multi(path_a: str, path_b: str, output_path: str, multiplier: int, estimate_flow: bool = False,
+                                  device: int = 0) -> list[str]:
+    """The M - 1 in-between frames of a frame-rate multiplier M (t = k / M) from one multi-time call, written to
+    multi_output_paths(output_path, M); with `estimate_flow` the flow is estimated once for all of them."""
+    from .interpolator import frame_times
+
+    times = frame_times(multiplier)
+    w, h, a = read_png(path_a)
+    wb, hb, b = read_png(path_b)
+    if (w, h) != (wb, hb):
+        raise ValueError(f"frame sizes differ: {w}x{h} vs {wb}x{hb}")
+    it = WgpuFrameInterpolator(device=device)
+    flow = None
+    if estimate_flow:
+        from .flow import FlowEstimator
+        flow = FlowEstimator(device=device).estimate(a, b, w, h)
+    frames = it.interpolate_multi_py(a, b, w, h, times=times, flow=flow)
+    paths = multi_output_paths(output_path, multiplier)
+    for path, out in zip(paths, frames):
+        write_png(path, w, h, out)
+    return paths

@@ -3,7 +3,10 @@
 from __future__ import annotations
 
 import ctypes
-from typing import Optional
+import math
+from typing import Optional, Sequence
+
+import numpy as np
 
 from . import _capi as C
 from .upscaler import _as_buffer, _out_buffer
@@ -14,6 +17,31 @@ _PRESETS = {  # wgpu_interpolator.rs:117-125
     "32x8": C.WG_WIDE_32X8, "wide32x8": C.WG_WIDE_32X8, "wide": C.WG_WIDE_32X8,
     "8x32": C.WG_TALL_8X32, "tall8x32": C.WG_TALL_8X32, "tall": C.WG_TALL_8X32,
 }
+
+
+def frame_times(multiplier: int) -> list[float]:
+    """The in-between times of a frame-rate multiplier M (the GUI's "Frame Generation" slider: 2x, 3x, 4x ...): k / M for
+    k = 1 .. M - 1, each rounded to float32 as the kernels take it.  M from 2 to INTERP_MAX_TIMES + 1 (8)."""
+    if isinstance(multiplier, bool) or not isinstance(multiplier, (int, np.integer)):
+        raise ValueError(f"multiplier must be an integer from 2 to {C.INTERP_MAX_TIMES + 1}, got {multiplier!r}")
+    m = int(multiplier)
+    if not 2 <= m <= C.INTERP_MAX_TIMES + 1:
+        raise ValueError(f"multiplier must be from 2 to {C.INTERP_MAX_TIMES + 1}, got {m}")
+    return [float(np.float32(k / m)) for k in range(1, m)]
+
+
+def _time_array(times=None, multiplier=None) -> "ctypes.Array":
+    """The float32 time set of a multi-time call: exactly one of `times` and `multiplier`, checked here (ValueError) before any
+    GPU work, with the library's rules: 1 .. INTERP_MAX_TIMES times, each in [0, 1]."""
+    if (times is None) == (multiplier is None):
+        raise ValueError("give exactly one of times and multiplier")
+    ts = frame_times(multiplier) if multiplier is not None else [float(np.float32(t)) for t in times]
+    if not 1 <= len(ts) <= C.INTERP_MAX_TIMES:
+        raise ValueError(f"between 1 and {C.INTERP_MAX_TIMES} times per call, got {len(ts)}")
+    for t in ts:
+        if math.isnan(t) or not 0.0 <= t <= 1.0:
+            raise ValueError(f"every time must be in [0, 1], got {t}")
+    return (ctypes.c_float * len(ts))(*ts)
 
 
 class WgpuFrameInterpolator:
@@ -66,6 +94,38 @@ class WgpuFrameInterpolator:
         del oarr, ka, kb, kf
         self._raise(st)
         return out
+
+    def interpolate_multi_py(self, frame_a_bytes, frame_b_bytes, width: int, height: int, *, times: Optional[Sequence[float]] = None,
+                             multiplier: Optional[int] = None, flow=None) -> list[bytes]:
+        """The in-between frames of one pair at several times from one launch (nus_interp_interpolate_multi): at `times`, or at
+        frame_times(multiplier).  Each frame is what interpolate_py returns at that time.  Argument errors raise ValueError
+        before any GPU work."""
+        ts = _time_array(times, multiplier)
+        n = len(ts)
+        a_addr, a_len, ka = _as_buffer(frame_a_bytes)
+        b_addr, b_len, kb = _as_buffer(frame_b_bytes)
+        f_addr, kf = None, None
+        expected = int(width) * int(height) * 4
+        if flow is not None:
+            f_addr, f_len, kf = _as_buffer(flow)
+            if f_len != expected * 2:
+                raise ValueError(f"Expected {expected * 2} bytes of flow for {width}x{height}x2 f32, got {f_len}")
+        out, oarr, oaddr = _out_buffer(expected * n)
+        st = self._lib.nus_interp_interpolate_multi(self._h, a_addr, a_len, b_addr, b_len, f_addr, width, height, ts, n, oaddr,
+                                                    expected * n)
+        del oarr, ka, kb, kf
+        self._raise(st)
+        mv = memoryview(out)
+        return [bytes(mv[k * expected:(k + 1) * expected]) for k in range(n)]
+
+    def interpolate_multi_device(self, d_a: int, a_stride: int, d_b: int, b_stride: int, d_flow: int, width: int, height: int,
+                                 times: Sequence[float], d_out: int, out_pair_stride: int = 0, n_pairs: int = 1,
+                                 stream: int = 0) -> None:
+        """nus_interp_interpolate_multi_device: frame (i, k) at d_out + i * out_pair_stride + k * w*h*4 (0: tightly packed)."""
+        ts = (ctypes.c_float * len(times))(*[float(t) for t in times])
+        self._raise(self._lib.nus_interp_interpolate_multi_device(self._h, d_a, a_stride, d_b, b_stride, d_flow or None, width,
+                                                                  height, ts, len(times), d_out, out_pair_stride, n_pairs,
+                                                                  stream or None))
 
     # -- trait FrameInterpolator (nu_scaler_core/src/interpolation/mod.rs:29-44; dead code in the reference, same shape here)
     def initialize(self, width: int, height: int) -> None:
