@@ -13,6 +13,7 @@
  *   get_last_gpu_duration_ms            nu_scaler_core/src/wgpu_interpolator.rs:494-497
  *   trait FrameInterpolator (shape)     nu_scaler_core/src/interpolation/mod.rs:29-44
  *   ErrorMetrics::calculate             Nu_scale/src/upscale/common.rs:475-543
+ *   BlockMatchingInterpolator           nu_scaler_core/src/interpolation/mod.rs:513-911
  *
  * Frames are tightly packed RGBA8, row-major.  Every function returns NUS_OK (0)
  * or a negative nus_status; the message is available from nus_*_last_error(handle)
@@ -568,6 +569,65 @@ int nus_metrics_compare_device(const void *d_a, size_t a_stride, const void *d_b
  * nus_metrics_compare_device. */
 int nus_metrics_compare(int device, const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, uint32_t w, uint32_t h,
                         int what, double *out);
+
+/* ---- Block-matching motion estimator (BlockMatchingInterpolator, nu_scaler_core/src/interpolation/mod.rs:513-911) --------
+ * The second motion estimator of the reference, for displacements the Horn-Schunck front end cannot follow (up to 24 pixels).
+ * Integer work throughout, so vectors, SADs and flags are the same bytes on every run and at every batch position.
+ *   Blocks   block_size bs in {8, 16, 32}; blocks_x = ceil(w / bs), blocks_y = ceil(h / bs); block (bx, by) of frame A starts at
+ *            (bx bs, by bs).  Block (bx, by) of pair i is entry (i * blocks_y + by) * blocks_x + bx of every per-block output.
+ *   Search   (find_best_match :584-622, calculate_sad :555-581) candidates (dx, dy) in [-R, R]^2, R = search_radius in 1 .. 24.  A
+ *            candidate is admitted iff the block shifted by it lies wholly inside frame B.  Its SAD is the sum of
+ *            |dR| + |dG| + |dB| (alpha ignored, :572-576; so every channel order gives the same result) over the block pixels
+ *            that lie inside frame A: partial blocks at the right and bottom edge get vectors.  The admitted candidate with the
+ *            smallest SAD wins; with none admitted the vector is (0, 0) and the SAD reads 0xFFFFFFFF.
+ *   Ties     NUS_BM_TIES_SCAN is the reference's order (dy outer, dx inner, ascending, first minimum wins): every flat block
+ *            gets (-R, -R).  NUS_BM_TIES_CENTER (default) takes the smallest dx^2 + dy^2 first, then scan order: a flat block
+ *            stays at (0, 0).
+ *   Confidence pass (handle_occlusions :795-910; nus_bm_set_refine, default on).  The pair's motion is smooth iff no block with
+ *            bx >= 1 and by >= 1 differs from its left or top neighbour by more than 10 in L1.  If it is not, every interior block
+ *            whose L1 differences to its 8 neighbours sum to 35 or more (the reference's 1 / (1 + 0.1 sum / 8) < 0.7, in
+ *            integers) is replaced by the direct blend of the two frames -- byte for byte the warp at a zero vector, so the pass
+ *            zeroes the block's vector and sets a flag.
+ *   Flow     the vectors expanded to [h][w][2], every pixel its block's (dx, dy): the pixel delta from frame A to frame B, the
+ *            flow nus_interp_interpolate_device defines (A is sampled at p - t v, B at p + (1 - t) v).  The reference's CPU text
+ *            (:738-742) has the opposite sign, which under its own matcher moves content the wrong way: B = A shifted by +s
+ *            gives v = +s, and the true mid-frame is A sampled at p - s / 2.
+ * Quality presets (:531-542): High 8 / 24, Medium 16 / 16 (default), Low 32 / 8. */
+typedef struct nus_blockmatch nus_blockmatch;
+typedef enum nus_bm_tie_order { NUS_BM_TIES_SCAN = 0, NUS_BM_TIES_CENTER = 1 } nus_bm_tie_order;
+#define NUS_BM_MAX_RADIUS 24
+#define NUS_BM_NO_MATCH 0xFFFFFFFFu
+
+nus_blockmatch *nus_bm_create(void); /* never touches the GPU */
+void nus_bm_destroy(nus_blockmatch *h);
+int nus_bm_set_device(nus_blockmatch *h, int device); /* before the first estimate */
+const char *nus_bm_last_error(const nus_blockmatch *h);
+int nus_bm_set_params(nus_blockmatch *h, uint32_t block_size, uint32_t search_radius);
+int nus_bm_set_quality(nus_blockmatch *h, int quality); /* nus_interp_quality_level */
+int nus_bm_set_tie_order(nus_blockmatch *h, int order);
+int nus_bm_set_refine(nus_blockmatch *h, int enabled);
+/* Workspace bytes nus_bm_estimate_device needs at the handle's block size; 0 (and the reason in nus_bm_last_error) for an invalid
+ * shape. */
+size_t nus_bm_workspace_size(nus_blockmatch *h, uint32_t w, uint32_t hgt, uint32_t n_pairs);
+/* n_pairs pairs as nus_interp_interpolate_device (same pointers and strides).  Per block: d_vectors 2 x int16 (dx, dy), after the
+ * confidence pass (the raw winners with refine off); d_sad (may be NULL) the raw winner's SAD, u32; d_flags (may be NULL) u8, bit 0
+ * = the pass zeroed this block, bit 1 = the pair's motion was not smooth (set on every block of the pair alike).  d_flow (may be
+ * NULL): the dense flow, w*h*8 bytes per pair and 8-byte aligned (NUS_FLOW_F32) or w*h*4 and 4-byte aligned (NUS_FLOW_F16; the
+ * vectors are integers of magnitude <= 24, exact in f16).  d_workspace 16-byte aligned.  n_pairs == 0: NUS_OK, nothing launched.
+ * Enqueue only on `stream`: no allocation, no synchronisation (a handle's first call puts its 163 KiB of rank tables on the
+ * device).  Argument errors are NUS_ERR_INVALID_ARGUMENT, returned before any HIP call, with a text that names the entry point. */
+int nus_bm_estimate_device(nus_blockmatch *h, const void *d_a, size_t a_stride, const void *d_b, size_t b_stride, uint32_t w,
+                           uint32_t hgt, uint32_t n_pairs, void *d_workspace, size_t workspace_bytes, void *d_vectors, void *d_sad,
+                           void *d_flags, void *d_flow, int flow_format, void *stream);
+/* Host frames in (pageable is fine: the bytes travel as nus_upload / nus_download move them), per-block results out: vectors_out
+ * blocks_x * blocks_y * 2 int16; sad_out / flags_out may be NULL.  a_len / b_len != w*h*4: nus_interp_interpolate's
+ * NUS_ERR_SIZE_MISMATCH and text. */
+int nus_bm_estimate(nus_blockmatch *h, const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, uint32_t w, uint32_t hgt,
+                    void *vectors_out, uint32_t *sad_out, uint8_t *flags_out);
+/* Motion-compensated in-between frames of one host pair: estimate -> dense flow (NUS_FLOW_F16) -> the multi-time warp of
+ * nus_interp_interpolate_multi_device in `mode` (nus_interp_mode_t).  Time-set rules as there; n_times frames back to back in out. */
+int nus_bm_interpolate(nus_blockmatch *h, const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, uint32_t w, uint32_t hgt,
+                       const float *times, uint32_t n_times, int mode, uint8_t *out, size_t out_cap);
 
 #ifdef __cplusplus
 }

@@ -12,6 +12,7 @@ libamdhip64 (pulled in by libnuscaler_hip.so) is loaded first.
 """
 from . import _capi, metrics, transfer
 from ._capi import NuScalerLibraryError, PinnedBuffer, build, device_count
+from .blockmatch import BlockMatcher, PyFrameInterpolator
 from .benchmark import PyBenchmarkResult, py_benchmark_upscaler, py_run_comparison_benchmark
 from .flow import FlowEstimator
 from .imagefile import interpolate_image_files, interpolate_image_files_multi, upscale_image_file
@@ -51,7 +52,7 @@ __all__ = [
     "PyWgpuUpscaler", "PyAdvancedWgpuUpscaler", "PyVramStats", "create_advanced_upscaler", "create_fsr_upscaler",
     "upscale_image_file", "interpolate_image_files", "interpolate_image_files_multi", "frame_times",
     "PyBenchmarkResult", "py_benchmark_upscaler", "py_run_comparison_benchmark",
-    "WgpuFrameInterpolator", "FlowEstimator", "ErrorMetrics", "metrics", "FrameBuffer", "swizzle_bgra_to_rgba_device", "FramePipeline", "shard_frames", "broadcast_tables",
+    "WgpuFrameInterpolator", "BlockMatcher", "PyFrameInterpolator", "FlowEstimator", "ErrorMetrics", "metrics", "FrameBuffer", "swizzle_bgra_to_rgba_device", "FramePipeline", "shard_frames", "broadcast_tables",
     "ShardedStream", "SyntheticSource", "run_sharded", "gather_rows", "spread", "launch_ranks",
     "broadcast_blob", "build_tables_blob", "validate_tables_blob",
     "NuScalerLibraryError", "PinnedBuffer", "build", "device_count", "download", "upload", "transfer", "install_fatal_trace",

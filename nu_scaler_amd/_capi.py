@@ -30,6 +30,12 @@ WG_SQUARE_8X8, WG_SQUARE_16X16, WG_WIDE_32X8, WG_TALL_8X32 = range(4)
 RESIZE_MAX_TAPS = 32
 INTERP_MAX_TIMES = 7  # NUS_INTERP_MAX_TIMES: in-between frames per pair of one multi-time call (up to 8x frame rate)
 METRIC_MSE, METRIC_SSIM = 1, 2  # nus_metric (bit mask; PSNR comes with MSE)
+INTERP_QUALITY_HIGH, INTERP_QUALITY_MEDIUM, INTERP_QUALITY_LOW = 0, 1, 2  # nus_interp_quality_level
+FLOW_F32, FLOW_F16 = 0, 1  # nus_flow_format
+INTERP_MODE_EXACT, INTERP_MODE_FMA = 0, 1  # nus_interp_mode_t
+BM_TIES_SCAN, BM_TIES_CENTER = 0, 1  # nus_bm_tie_order
+BM_MAX_RADIUS = 24  # NUS_BM_MAX_RADIUS
+BM_NO_MATCH = 0xFFFFFFFF  # NUS_BM_NO_MATCH: the SAD of a block with no admitted candidate
 
 # Every symbol include/nuscaler_hip.h declares: (name, restype, argtypes)
 _vp, _cp, _i, _u32, _sz, _i64 = (ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_uint32,
@@ -139,6 +145,18 @@ SIGNATURES = [
     ("nus_metrics_workspace_size", _sz, [_u32, _u32, _u32, _i]),
     ("nus_metrics_compare_device", _i, [_vp, _sz, _vp, _sz, _u32, _u32, _u32, _i, _vp, _sz, _vp, _vp]),
     ("nus_metrics_compare", _i, [_i, _vp, _sz, _vp, _sz, _u32, _u32, _i, _dp]),
+    ("nus_bm_create", _vp, []),
+    ("nus_bm_destroy", None, [_vp]),
+    ("nus_bm_set_device", _i, [_vp, _i]),
+    ("nus_bm_last_error", _cp, [_vp]),
+    ("nus_bm_set_params", _i, [_vp, _u32, _u32]),
+    ("nus_bm_set_quality", _i, [_vp, _i]),
+    ("nus_bm_set_tie_order", _i, [_vp, _i]),
+    ("nus_bm_set_refine", _i, [_vp, _i]),
+    ("nus_bm_workspace_size", _sz, [_vp, _u32, _u32, _u32]),
+    ("nus_bm_estimate_device", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _vp, _sz, _vp, _vp, _vp, _vp, _i, _vp]),
+    ("nus_bm_estimate", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _vp, _vp, _vp]),
+    ("nus_bm_interpolate", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _vp, _u32, _i, _vp, _sz]),
 ]
 
 

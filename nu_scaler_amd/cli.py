@@ -1,7 +1,8 @@
 """`python -m nu_scaler_amd.cli` -- the image-file commands of the north star's `nu_scaler_cli`
 (SURVEY.md section 8f rank 2): `upscale <in.png> <out.png> --algorithm --scale`, following the
 legacy crate's `upscale_image_file` (Nu_scale/src/upscale/mod.rs:307-338) and the option names of
-its `fullscreen` subcommand (Nu_scale/src/main.rs:36-73: --tech, --quality, --algorithm); `compare <a.png> <b.png>`
+its `fullscreen` subcommand (Nu_scale/src/main.rs:36-73: --tech, --quality, --algorithm); `interpolate <a.png> <b.png> <out.png>`
+with zero flow, `--flow` (Horn-Schunck) or `--method block_matching [--quality high|medium|low]`; `compare <a.png> <b.png>`
 prints the `ErrorMetrics` of two images (Nu_scale/src/upscale/common.rs:475-543).
 Everything runs on the HIP device; without one the command fails (no CPU path).
 """
@@ -31,6 +32,8 @@ def build_parser() -> argparse.ArgumentParser:
     it.add_argument("--multiplier", type=int, default=None,
                     help="frame-rate multiplier M (2 .. NUS_INTERP_MAX_TIMES + 1 = 8): the M - 1 frames at t = k / M, written as <stem>_<k><ext>")
     it.add_argument("--flow", action="store_true", help="estimate motion (pyramid + Horn-Schunck) instead of zero flow")
+    it.add_argument("--method", default=None, help="block_matching: the full-search block matcher supplies the motion field")
+    it.add_argument("--quality", default="medium", help="block matching preset: high (8 / 24), medium (16 / 16) or low (32 / 8)")
     it.add_argument("--device", type=int, default=0)
     cp = sub.add_parser("compare", help="MSE, PSNR and SSIM of two PNGs of equal size (ErrorMetrics, "
                                          "Nu_scale/src/upscale/common.rs:475-543)")
@@ -149,6 +152,13 @@ def main(argv=None) -> int:
 
         if not 2 <= args.multiplier <= INTERP_MAX_TIMES + 1:
             parser.error(f"--multiplier must be from 2 to {INTERP_MAX_TIMES + 1}, got {args.multiplier}")
+    if args.command == "interpolate" and args.method is not None:
+        if args.flow:
+            parser.error("--method and --flow exclude each other")
+        if args.method.lower() != "block_matching":
+            parser.error(f"--method must be block_matching, got {args.method}")
+        if args.quality.lower() not in ("high", "medium", "low"):
+            parser.error(f"--quality must be high, medium or low, got {args.quality}")
     if args.command == "stream":
         try:
             return stream_command(args, list(sys.argv[1:] if argv is None else argv))
@@ -173,6 +183,12 @@ def main(argv=None) -> int:
             a = np.frombuffer(pa, np.uint8).reshape(ha, wa, 4)
             b = np.frombuffer(pb, np.uint8).reshape(hb, wb, 4)
             print(ErrorMetrics.calculate(a, b, device=args.device).line())
+        elif args.method is not None:
+            paths = imagefile.interpolate_image_files_block_matching(args.frame_a, args.frame_b, args.output, args.quality.lower(),
+                                                                     0.5 if args.t is None else args.t, args.multiplier,
+                                                                     device=args.device)
+            for path in paths:
+                print(path)
         elif args.multiplier is not None:
             for path in imagefile.interpolate_image_files_multi(args.frame_a, args.frame_b, args.output, args.multiplier, args.flow,
                                                                 device=args.device):

@@ -5,6 +5,7 @@
 //
 //   nu_scaler_cli upscale <in.png> <out.png> [--algorithm A] [--scale S] [--tech T] [--quality Q] [--device N]
 //   nu_scaler_cli interpolate <a.png> <b.png> <out.png> [--t X | --multiplier M] [--flow] [--device N]
+//                             [--method block_matching [--quality high|medium|low]]
 //   nu_scaler_cli compare <a.png> <b.png> [--device N]   (MSE / PSNR / SSIM, ErrorMetrics: Nu_scale/src/upscale/common.rs:475-543)
 //   nu_scaler_cli png-copy <in.png> <out.png>        (decode + encode only; no GPU: codec self-check)
 //
@@ -35,6 +36,7 @@ int usage(int rc)
                  "                             [--scale S] [--tech fsr|fallback|none] [--quality ultra|quality|balanced|performance]\n"
                  "                             [--device N]\n"
                  "       nu_scaler_cli interpolate <a.png> <b.png> <out.png> [--t X | --multiplier 2..8] [--flow] [--device N]\n"
+                 "                             [--method block_matching [--quality high|medium|low]]\n"
                  "       nu_scaler_cli compare <a.png> <b.png> [--device N]\n"
                  "       nu_scaler_cli png-copy <in.png> <out.png>\n");
     return rc;
@@ -162,6 +164,25 @@ int cmd_interpolate(const Args &a)
         }
         multiplier = (uint32_t)m;
     }
+    const auto method_it = a.options.find("method");
+    int bm_quality = -1; // >= 0: --method block_matching at this nus_interp_quality_level
+    if (method_it != a.options.end()) {
+        if (a.flow) {
+            std::fprintf(stderr, "nu_scaler_cli: error: --method and --flow exclude each other\n");
+            return usage(2);
+        }
+        if (lower(method_it->second) != "block_matching") {
+            std::fprintf(stderr, "nu_scaler_cli: error: --method must be block_matching, got %s\n", method_it->second.c_str());
+            return usage(2);
+        }
+        const auto q_it = a.options.find("quality");
+        const std::string q = q_it == a.options.end() ? "medium" : lower(q_it->second);
+        bm_quality = q == "high" ? NUS_INTERP_QUALITY_HIGH : q == "medium" ? NUS_INTERP_QUALITY_MEDIUM : q == "low" ? NUS_INTERP_QUALITY_LOW : -1;
+        if (bm_quality < 0) {
+            std::fprintf(stderr, "nu_scaler_cli: error: --quality must be high, medium or low, got %s\n", q.c_str());
+            return usage(2);
+        }
+    }
     nus_cli::Image fa, fb;
     std::string err = nus_cli::read_png(a.positional[0], fa);
     if (err.empty()) err = nus_cli::read_png(a.positional[1], fb);
@@ -171,6 +192,33 @@ int cmd_interpolate(const Args &a)
     const float t = t_it == a.options.end() ? 0.5f : (float)std::atof(t_it->second.c_str());
     const auto d_it = a.options.find("device");
     const int device = d_it == a.options.end() ? 0 : std::atoi(d_it->second.c_str());
+    if (bm_quality >= 0) { // block matching -> dense flow -> warp, one library call for all the frames
+        const uint32_t n = multiplier ? multiplier - 1 : 1;
+        std::vector<float> times(n, t);
+        for (uint32_t k = 1; multiplier && k <= n; ++k) times[k - 1] = (float)((double)k / (double)multiplier);
+        std::vector<uint8_t> frames(fa.rgba.size() * n);
+        nus_blockmatch *bm = nus_bm_create();
+        if (!bm) return fail(nus_last_error());
+        int rc = nus_bm_set_device(bm, device);
+        if (rc == NUS_OK) rc = nus_bm_set_quality(bm, bm_quality);
+        if (rc == NUS_OK)
+            rc = nus_bm_interpolate(bm, fa.rgba.data(), fa.rgba.size(), fb.rgba.data(), fb.rgba.size(), fa.width, fa.height, times.data(),
+                                    n, NUS_INTERP_MODE_EXACT, frames.data(), frames.size());
+        const std::string msg = rc == NUS_OK ? "" : nus_bm_last_error(bm);
+        nus_bm_destroy(bm);
+        if (rc != NUS_OK) return fail(msg);
+        for (uint32_t k = 1; k <= n; ++k) {
+            nus_cli::Image out;
+            out.width = fa.width;
+            out.height = fa.height;
+            out.rgba.assign(frames.begin() + (size_t)(k - 1) * fa.rgba.size(), frames.begin() + (size_t)k * fa.rgba.size());
+            const std::string path = multiplier ? multi_path(a.positional[2], k) : a.positional[2];
+            err = nus_cli::write_png(path, out);
+            if (!err.empty()) return fail(err);
+            std::printf("%s\n", path.c_str());
+        }
+        return 0;
+    }
     std::vector<float> flow;
     if (a.flow) { // pyramid + Horn-Schunck front end instead of the reference's zero flow
         nus_flow *f = nus_flow_create();

@@ -1,0 +1,327 @@
+// nus_blockmatch.cpp -- host side of the block-matching motion estimator: the rank tables of the tie orders, the argument
+// checks (all before any HIP call), the enqueue of the device entry point and the host entry points' device buffers.
+#include "nus_blockmatch.hpp"
+
+#include <algorithm>
+
+#include "nus_host.hpp"
+#include "nus_host_util.hpp"
+#include "nus_transfer.hpp"
+
+namespace nus {
+
+namespace {
+
+// where the tables of (R, order) start in the handle's device array: per radius 1 .. kBmMaxRadius and per order, rank then cand
+size_t table_offset(uint32_t R, int order)
+{
+    size_t o = 0;
+    for (uint32_t r = 1; r < R; ++r) o += (size_t)4 * (2 * r + 1) * (2 * r + 1);
+    return o + (size_t)order * 2 * (2 * R + 1) * (2 * R + 1);
+}
+
+bool misaligned(const void *p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) % to) != 0; }
+
+size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
+
+} // namespace
+
+void bm_rank_tables(uint32_t R, int order, std::vector<uint16_t> &rank, std::vector<uint16_t> &cand)
+{
+    const int D = 2 * (int)R + 1, n = D * D;
+    cand.resize(n);
+    rank.resize(n);
+    for (int c = 0; c < n; ++c) cand[c] = (uint16_t)c; // scan order: dy outer, dx inner, ascending
+    if (order == kBmTiesCenter) {
+        const auto d2 = [&](int c) {
+            const int dy = c / D - (int)R, dx = c % D - (int)R;
+            return dx * dx + dy * dy;
+        };
+        std::stable_sort(cand.begin(), cand.end(), [&](uint16_t p, uint16_t q) { return d2(p) < d2(q); });
+    }
+    for (int r = 0; r < n; ++r) rank[cand[r]] = (uint16_t)r;
+}
+
+BlockMatcher::~BlockMatcher()
+{
+    if (!d_tables_ && !arena_ && !stream_) return;
+    (void)hipSetDevice(device_);
+    if (stream_) {
+        (void)hipStreamSynchronize(stream_);
+        (void)hipStreamDestroy(stream_);
+    }
+    if (arena_) (void)hipFree(arena_);
+    if (d_tables_) (void)hipFree(d_tables_);
+}
+
+int BlockMatcher::fail(int status, const std::string &msg)
+{
+    error_ = msg;
+    set_thread_error(msg);
+    return status;
+}
+
+int BlockMatcher::fail_hip(hipError_t e, const char *what)
+{
+    (void)hipGetLastError();
+    return fail(e == hipErrorOutOfMemory ? kOutOfMemory : kHipError, fmt("HIP error in %s: %s", what, hipGetErrorString(e)));
+}
+
+int BlockMatcher::set_device(int device)
+{
+    std::lock_guard<std::mutex> lk(mu_);
+    if (device < 0) return fail(kInvalidArgument, "nus_bm_set_device: negative device index");
+    if (d_tables_) return fail(kInvalidArgument, "nus_bm_set_device: must precede the first estimate");
+    device_ = device;
+    return kOk;
+}
+
+int BlockMatcher::set_params(uint32_t block_size, uint32_t search_radius)
+{
+    std::lock_guard<std::mutex> lk(mu_);
+    if (block_size != 8 && block_size != 16 && block_size != 32)
+        return fail(kInvalidArgument, fmt("nus_bm_set_params: block_size must be 8, 16 or 32, got %u", block_size));
+    if (search_radius < 1 || search_radius > kBmMaxRadius)
+        return fail(kInvalidArgument, fmt("nus_bm_set_params: search_radius must be 1..%u, got %u", kBmMaxRadius, search_radius));
+    bs_ = block_size;
+    radius_ = search_radius;
+    return kOk;
+}
+
+int BlockMatcher::set_quality(int quality)
+{
+    std::lock_guard<std::mutex> lk(mu_);
+    static const uint32_t preset[3][2] = {{8, 24}, {16, 16}, {32, 8}}; // interpolation/mod.rs:531-542
+    if (quality < 0 || quality > 2) return fail(kInvalidArgument, fmt("nus_bm_set_quality: unknown interpolation quality %d", quality));
+    bs_ = preset[quality][0];
+    radius_ = preset[quality][1];
+    return kOk;
+}
+
+int BlockMatcher::set_tie_order(int order)
+{
+    std::lock_guard<std::mutex> lk(mu_);
+    if (order != kBmTiesScan && order != kBmTiesCenter)
+        return fail(kInvalidArgument, fmt("nus_bm_set_tie_order: order must be NUS_BM_TIES_SCAN or NUS_BM_TIES_CENTER, got %d", order));
+    order_ = order;
+    return kOk;
+}
+
+int BlockMatcher::set_refine(int enabled)
+{
+    std::lock_guard<std::mutex> lk(mu_);
+    if (enabled != 0 && enabled != 1) return fail(kInvalidArgument, fmt("nus_bm_set_refine: 0 or 1, got %d", enabled));
+    refine_ = enabled == 1;
+    return kOk;
+}
+
+int BlockMatcher::check_shape(const char *who, uint32_t w, uint32_t h, uint32_t n_pairs)
+{
+    if (w == 0 || h == 0 || (uint64_t)w * h >= (1ull << 31)) return fail(kInvalidArgument, fmt("%s: bad dimensions", who));
+    // the search grid is (runs, block rows, pairs): 65535 on its second and third axis
+    if ((h + bs_ - 1) / bs_ > 65535u || n_pairs > 65535u)
+        return fail(kInvalidArgument, fmt("%s: %u pairs of %ux%u are too many for one launch (at most 65535 pairs and block rows)", who,
+                                          n_pairs, w, h));
+    return kOk;
+}
+
+size_t BlockMatcher::workspace_size(uint32_t w, uint32_t h, uint32_t n_pairs)
+{
+    std::lock_guard<std::mutex> lk(mu_);
+    if (check_shape("nus_bm_workspace_size", w, h, n_pairs) != kOk) return 0;
+    return bm_shape(w, h, bs_, n_pairs ? n_pairs : 1).workspace_bytes;
+}
+
+int BlockMatcher::ensure_tables()
+{
+    const int n = device_count();
+    if (n <= 0) return fail(kNoDevice, "no HIP device available (the gfx950 path has no CPU fallback)");
+    if (device_ >= n) return fail(kNoDevice, fmt("HIP device %d requested but only %d present", device_, n));
+    NUS_HIP(hipSetDevice(device_));
+    if (d_tables_) return kOk;
+    std::vector<uint16_t> all, rank, cand;
+    for (uint32_t R = 1; R <= kBmMaxRadius; ++R)
+        for (int order = 0; order < 2; ++order) {
+            bm_rank_tables(R, order, rank, cand);
+            all.insert(all.end(), rank.begin(), rank.end());
+            all.insert(all.end(), cand.begin(), cand.end());
+        }
+    uint16_t *d = nullptr;
+    NUS_HIP(hipMalloc(reinterpret_cast<void **>(&d), all.size() * sizeof(uint16_t)));
+    int rc = upload(d, all.data(), all.size() * sizeof(uint16_t), nullptr);
+    if (rc == kOk) {
+        const hipError_t e = hipStreamSynchronize(nullptr); // in place for every stream from here on
+        if (e != hipSuccess) rc = fail_hip(e, "hipStreamSynchronize");
+    } else {
+        error_ = thread_error();
+    }
+    if (rc != kOk) {
+        (void)hipFree(d);
+        return rc;
+    }
+    d_tables_ = d;
+    return kOk;
+}
+
+int BlockMatcher::enqueue(const void *d_a, size_t a_stride, const void *d_b, size_t b_stride, uint32_t w, uint32_t h, uint32_t n_pairs,
+                          void *d_workspace, void *d_vectors, void *d_sad, void *d_flags, void *d_flow, int flow_format,
+                          hipStream_t stream)
+{
+    const int rc = ensure_tables();
+    if (rc != kOk) return rc;
+    BmLaunch L;
+    L.a = static_cast<const uint8_t *>(d_a);
+    L.b = static_cast<const uint8_t *>(d_b);
+    L.a_stride = a_stride;
+    L.b_stride = b_stride;
+    L.w = w;
+    L.h = h;
+    L.n_pairs = n_pairs;
+    L.bs = bs_;
+    L.R = radius_;
+    L.rank = d_tables_ + table_offset(radius_, order_);
+    L.cand = L.rank + (size_t)(2 * radius_ + 1) * (2 * radius_ + 1);
+    L.workspace = d_workspace;
+    L.refine = refine_;
+    L.vectors = static_cast<int16_t *>(d_vectors);
+    L.sad = static_cast<uint32_t *>(d_sad);
+    L.flags = static_cast<uint8_t *>(d_flags);
+    L.flow = d_flow;
+    L.flow_half = flow_format == 1;
+    L.stream = stream;
+    const hipError_t e = launch_blockmatch(L);
+    if (e != hipSuccess) return fail_hip(e, "block-matching launch");
+    return kOk;
+}
+
+int BlockMatcher::estimate_device(const void *d_a, size_t a_stride, const void *d_b, size_t b_stride, uint32_t w, uint32_t h,
+                                  uint32_t n_pairs, void *d_workspace, size_t workspace_bytes, void *d_vectors, void *d_sad,
+                                  void *d_flags, void *d_flow, int flow_format, hipStream_t stream)
+{
+    static const char *const who = "nus_bm_estimate_device";
+    std::lock_guard<std::mutex> lk(mu_);
+    const int st = check_shape(who, w, h, n_pairs);
+    if (st != kOk) return st;
+    if (!d_a || !d_b || !d_workspace || !d_vectors) return fail(kInvalidArgument, fmt("%s: null device pointer", who));
+    if (flow_format != 0 && flow_format != 1)
+        return fail(kInvalidArgument, fmt("%s: flow_format must be NUS_FLOW_F32 or NUS_FLOW_F16", who));
+    if (misaligned(d_a, 4) || misaligned(d_b, 4) || a_stride % 4 || b_stride % 4 || misaligned(d_vectors, 4) || misaligned(d_sad, 4) ||
+        misaligned(d_flow, flow_format == 1 ? 4 : 8))
+        return fail(kInvalidArgument, fmt("%s: pointers/strides must be pixel aligned", who));
+    if (misaligned(d_workspace, 16)) return fail(kInvalidArgument, fmt("%s: workspace must be 16-byte aligned", who));
+    const size_t need = bm_shape(w, h, bs_, n_pairs ? n_pairs : 1).workspace_bytes;
+    if (workspace_bytes < need)
+        return fail(kInvalidArgument, fmt("%s: workspace of %zu bytes, %zu needed (nus_bm_workspace_size)", who, workspace_bytes, need));
+    if (n_pairs == 0) return kOk;
+    return enqueue(d_a, a_stride, d_b, b_stride, w, h, n_pairs, d_workspace, d_vectors, d_sad, d_flags, d_flow, flow_format, stream);
+}
+
+int BlockMatcher::check_host_frames(const char *who, const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, uint32_t w,
+                                    uint32_t h)
+{
+    const int st = check_shape(who, w, h, 1);
+    if (st != kOk) return st;
+    const size_t expected = (size_t)w * h * 4;
+    if (a_len != expected || b_len != expected) // status and text of nus_interp_interpolate (wgpu_interpolator.rs:234-237)
+        return fail(kSizeMismatch, fmt("Expected %zu bytes per frame for %ux%ux4 RGBA, got frame_a: %zu bytes, frame_b: %zu bytes",
+                                       expected, w, h, a_len, b_len));
+    if (!a || !b) return fail(kInvalidArgument, fmt("%s: null frame pointer", who));
+    return kOk;
+}
+
+int BlockMatcher::ensure_host(size_t bytes)
+{
+    const int rc = ensure_tables();
+    if (rc != kOk) return rc;
+    if (!stream_) NUS_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+    if (arena_bytes_ < bytes) {
+        NUS_HIP(hipStreamSynchronize(stream_));
+        if (arena_) (void)hipFree(arena_);
+        arena_ = nullptr;
+        arena_bytes_ = 0;
+        NUS_HIP(hipMalloc(reinterpret_cast<void **>(&arena_), bytes));
+        arena_bytes_ = bytes;
+    }
+    return kOk;
+}
+
+#define NUS_BM_TRY(call)                  \
+    do {                                  \
+        const int rc_ = (call);           \
+        if (rc_ != kOk) {                 \
+            error_ = thread_error();      \
+            return rc_;                   \
+        }                                 \
+    } while (0)
+
+int BlockMatcher::estimate(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, uint32_t w, uint32_t h, int16_t *vectors_out,
+                           uint32_t *sad_out, uint8_t *flags_out)
+{
+    static const char *const who = "nus_bm_estimate";
+    std::lock_guard<std::mutex> lk(mu_);
+    const int st = check_host_frames(who, a, a_len, b, b_len, w, h);
+    if (st != kOk) return st;
+    if (!vectors_out) return fail(kInvalidArgument, fmt("%s: vectors_out is null", who));
+    const BmShape s = bm_shape(w, h, bs_, 1);
+    const size_t frame = up16((size_t)w * h * 4), nb = (size_t)s.blocks_x * s.blocks_y;
+    const size_t o_b = frame, o_ws = 2 * frame, o_vec = o_ws + up16(s.workspace_bytes), o_sad = o_vec + up16(nb * 4),
+                 o_flags = o_sad + up16(nb * 4), total = o_flags + up16(nb);
+    int rc = ensure_host(total);
+    if (rc != kOk) return rc;
+    NUS_BM_TRY(upload(arena_, a, a_len, stream_));
+    NUS_BM_TRY(upload(arena_ + o_b, b, b_len, stream_));
+    rc = enqueue(arena_, a_len, arena_ + o_b, b_len, w, h, 1, arena_ + o_ws, arena_ + o_vec, arena_ + o_sad, arena_ + o_flags, nullptr, 0,
+                 stream_);
+    if (rc != kOk) return rc;
+    NUS_BM_TRY(download(vectors_out, arena_ + o_vec, nb * 4, stream_));
+    if (sad_out) NUS_BM_TRY(download(sad_out, arena_ + o_sad, nb * 4, stream_));
+    if (flags_out) NUS_BM_TRY(download(flags_out, arena_ + o_flags, nb, stream_));
+    return kOk;
+}
+
+int BlockMatcher::interpolate(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, uint32_t w, uint32_t h, const float *times,
+                              uint32_t n_times, int mode, uint8_t *out, size_t out_cap)
+{
+    static const char *const who = "nus_bm_interpolate";
+    std::lock_guard<std::mutex> lk(mu_);
+    const int st = check_host_frames(who, a, a_len, b, b_len, w, h);
+    if (st != kOk) return st;
+    if (!out) return fail(kInvalidArgument, fmt("%s: null frame pointer", who));
+    const std::string bad = check_interp_times(times, n_times);
+    if (!bad.empty()) return fail(kInvalidArgument, fmt("%s: %s", who, bad.c_str()));
+    if (mode != 0 && mode != 1) return fail(kInvalidArgument, fmt("%s: mode must be NUS_INTERP_MODE_EXACT or NUS_INTERP_MODE_FMA", who));
+    const size_t expected = (size_t)w * h * 4;
+    if (out_cap / n_times < expected)
+        return fail(kInvalidArgument, fmt("%s: output capacity %zu below n_times * w * h * 4 = %zu", who, out_cap, (size_t)n_times * expected));
+    const BmShape s = bm_shape(w, h, bs_, 1);
+    const size_t frame = up16(expected), nb = (size_t)s.blocks_x * s.blocks_y;
+    const size_t o_b = frame, o_ws = 2 * frame, o_vec = o_ws + up16(s.workspace_bytes), o_flow = o_vec + up16(nb * 4), o_out = o_flow + frame,
+                 total = o_out + (size_t)n_times * expected;
+    int rc = ensure_host(total);
+    if (rc != kOk) return rc;
+    NUS_BM_TRY(upload(arena_, a, a_len, stream_));
+    NUS_BM_TRY(upload(arena_ + o_b, b, b_len, stream_));
+    // estimate -> dense flow as 2 x f16 per pixel (the vectors are integers of magnitude <= 24: exact) -> multi-time warp
+    rc = enqueue(arena_, a_len, arena_ + o_b, b_len, w, h, 1, arena_ + o_ws, arena_ + o_vec, nullptr, nullptr, arena_ + o_flow, 1, stream_);
+    if (rc != kOk) return rc;
+    WarpLaunch L;
+    L.a = arena_;
+    L.b = arena_ + o_b;
+    L.flow = reinterpret_cast<const float *>(arena_ + o_flow);
+    L.flow_half = true;
+    L.fma = mode == 1;
+    L.out = arena_ + o_out;
+    L.a_stride = L.b_stride = expected;
+    L.w = w;
+    L.h = h;
+    L.times = times;
+    L.n_times = n_times;
+    L.n_pairs = 1;
+    L.stream = stream_;
+    const hipError_t e = launch_warp_blend(L);
+    if (e != hipSuccess) return fail_hip(e, "multi-time warp+blend launch");
+    NUS_BM_TRY(download(out, arena_ + o_out, (size_t)n_times * expected, stream_));
+    return kOk;
+}
+
+} // namespace nus

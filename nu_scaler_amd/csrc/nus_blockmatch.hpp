@@ -1,0 +1,66 @@
+// nus_blockmatch.hpp -- host side of the block-matching motion estimator (nus_bm_* of include/nuscaler_hip.h; kernels in
+// nus_k_blockmatch.hip): BlockMatchingInterpolator of nu_scaler_core/src/interpolation/mod.rs:513-911.  Every function returns a
+// Status (nus_host.hpp); argument checks come before any HIP call and their texts name the C entry point.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+#include <mutex>
+#include <string>
+#include <vector>
+
+namespace nus {
+
+constexpr int kBmTiesScan = 0, kBmTiesCenter = 1; // nus_bm_tie_order
+
+// Place of every candidate of a (2R + 1)^2 search in the tie order (rank[(dy + R) * (2R + 1) + dx + R]) and the inverse
+// (cand[rank]).  Host only.
+void bm_rank_tables(uint32_t R, int order, std::vector<uint16_t> &rank, std::vector<uint16_t> &cand);
+
+class BlockMatcher {
+public:
+    BlockMatcher() = default;
+    ~BlockMatcher();
+    BlockMatcher(const BlockMatcher &) = delete;
+    BlockMatcher &operator=(const BlockMatcher &) = delete;
+
+    int set_device(int device);
+    int set_params(uint32_t block_size, uint32_t search_radius);
+    int set_quality(int quality); // nus_interp_quality_level: High 8 / 24, Medium 16 / 16, Low 32 / 8 (interpolation/mod.rs:531-542)
+    int set_tie_order(int order);
+    int set_refine(int enabled);
+    size_t workspace_size(uint32_t w, uint32_t h, uint32_t n_pairs); // 0 and the reason for an invalid shape
+    int estimate_device(const void *d_a, size_t a_stride, const void *d_b, size_t b_stride, uint32_t w, uint32_t h, uint32_t n_pairs,
+                        void *d_workspace, size_t workspace_bytes, void *d_vectors, void *d_sad, void *d_flags, void *d_flow,
+                        int flow_format, hipStream_t stream);
+    int estimate(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, uint32_t w, uint32_t h, int16_t *vectors_out,
+                 uint32_t *sad_out, uint8_t *flags_out);
+    int interpolate(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, uint32_t w, uint32_t h, const float *times,
+                    uint32_t n_times, int mode, uint8_t *out, size_t out_cap);
+    const char *last_error() const { return error_.c_str(); }
+
+private:
+    int fail(int status, const std::string &msg);
+    int fail_hip(hipError_t e, const char *what);
+    int check_shape(const char *who, uint32_t w, uint32_t h, uint32_t n_pairs);
+    int check_host_frames(const char *who, const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, uint32_t w, uint32_t h);
+    int ensure_tables();                 // first device use: the rank tables of every radius and both orders, once
+    int ensure_host(size_t bytes);       // the host entry points' device arena
+    int enqueue(const void *d_a, size_t a_stride, const void *d_b, size_t b_stride, uint32_t w, uint32_t h, uint32_t n_pairs,
+                void *d_workspace, void *d_vectors, void *d_sad, void *d_flags, void *d_flow, int flow_format, hipStream_t stream);
+
+    mutable std::mutex mu_;
+    int device_ = 0;
+    uint32_t bs_ = 16, radius_ = 16; // Medium
+    int order_ = kBmTiesCenter;
+    bool refine_ = true;
+    std::string error_;
+    uint16_t *d_tables_ = nullptr;
+    hipStream_t stream_ = nullptr;
+    uint8_t *arena_ = nullptr;
+    size_t arena_bytes_ = 0;
+};
+
+} // namespace nus

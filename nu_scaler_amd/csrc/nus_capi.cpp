@@ -9,6 +9,7 @@
 
 #include "nus_flow.hpp"
 #include "nus_host.hpp"
+#include "nus_blockmatch.hpp"
 #include "nus_metrics.hpp"
 #include "nus_queue.hpp"
 #include "nus_ranges.hpp"
@@ -26,6 +27,10 @@ struct nus_frame_queue {
 
 struct nus_flow {
     nus::HipFlowEstimator impl;
+};
+
+struct nus_blockmatch {
+    nus::BlockMatcher impl;
 };
 
 struct nus_interp {
@@ -76,6 +81,8 @@ R guarded(const char *what, F &&f) noexcept
 }
 } // namespace
 
+static_assert(NUS_BM_MAX_RADIUS == nus::kBmMaxRadius && NUS_BM_TIES_SCAN == nus::kBmTiesScan && NUS_BM_TIES_CENTER == nus::kBmTiesCenter,
+              "the C header's block-matching constants are the kernels'");
 static_assert(NUS_INTERP_MAX_TIMES == nus::kInterpMaxTimes, "the C header's NUS_INTERP_MAX_TIMES is the kernels' time-set size");
 
 extern "C" {
@@ -800,6 +807,70 @@ int nus_metrics_compare(int device, const uint8_t *a, size_t a_len, const uint8_
                         int what, double *out)
 {
     return guarded<int>("nus_metrics_compare", [&]() -> int { return nus::metrics_compare(device, a, a_len, b, b_len, w, h, what, out); });
+}
+
+nus_blockmatch *nus_bm_create(void)
+{
+    return guarded<nus_blockmatch *>("nus_bm_create", [&]() -> nus_blockmatch * { return new (std::nothrow) nus_blockmatch(); });
+}
+void nus_bm_destroy(nus_blockmatch *h) { delete h; }
+const char *nus_bm_last_error(const nus_blockmatch *h) { return h ? h->impl.last_error() : "null handle"; }
+int nus_bm_set_device(nus_blockmatch *h, int device)
+{
+    return guarded<int>("nus_bm_set_device", [&]() -> int { return h ? h->impl.set_device(device) : null_handle(); });
+}
+int nus_bm_set_params(nus_blockmatch *h, uint32_t block_size, uint32_t search_radius)
+{
+    return guarded<int>("nus_bm_set_params", [&]() -> int { return h ? h->impl.set_params(block_size, search_radius) : null_handle(); });
+}
+int nus_bm_set_quality(nus_blockmatch *h, int quality)
+{
+    return guarded<int>("nus_bm_set_quality", [&]() -> int { return h ? h->impl.set_quality(quality) : null_handle(); });
+}
+int nus_bm_set_tie_order(nus_blockmatch *h, int order)
+{
+    return guarded<int>("nus_bm_set_tie_order", [&]() -> int { return h ? h->impl.set_tie_order(order) : null_handle(); });
+}
+int nus_bm_set_refine(nus_blockmatch *h, int enabled)
+{
+    return guarded<int>("nus_bm_set_refine", [&]() -> int { return h ? h->impl.set_refine(enabled) : null_handle(); });
+}
+size_t nus_bm_workspace_size(nus_blockmatch *h, uint32_t w, uint32_t hgt, uint32_t n_pairs)
+{
+    try {
+        if (!h) {
+            null_handle();
+            return 0;
+        }
+        return h->impl.workspace_size(w, hgt, n_pairs);
+    } catch (...) {
+        nus::set_thread_error("nus_bm_workspace_size: unexpected exception");
+        return 0;
+    }
+}
+int nus_bm_estimate_device(nus_blockmatch *h, const void *d_a, size_t a_stride, const void *d_b, size_t b_stride, uint32_t w,
+                           uint32_t hgt, uint32_t n_pairs, void *d_workspace, size_t workspace_bytes, void *d_vectors, void *d_sad,
+                           void *d_flags, void *d_flow, int flow_format, void *stream)
+{
+    return guarded<int>("nus_bm_estimate_device", [&]() -> int {
+        return h ? h->impl.estimate_device(d_a, a_stride, d_b, b_stride, w, hgt, n_pairs, d_workspace, workspace_bytes, d_vectors, d_sad,
+                                           d_flags, d_flow, flow_format, static_cast<hipStream_t>(stream))
+                 : null_handle();
+    });
+}
+int nus_bm_estimate(nus_blockmatch *h, const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, uint32_t w, uint32_t hgt,
+                    void *vectors_out, uint32_t *sad_out, uint8_t *flags_out)
+{
+    return guarded<int>("nus_bm_estimate", [&]() -> int {
+        return h ? h->impl.estimate(a, a_len, b, b_len, w, hgt, static_cast<int16_t *>(vectors_out), sad_out, flags_out) : null_handle();
+    });
+}
+int nus_bm_interpolate(nus_blockmatch *h, const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, uint32_t w, uint32_t hgt,
+                       const float *times, uint32_t n_times, int mode, uint8_t *out, size_t out_cap)
+{
+    return guarded<int>("nus_bm_interpolate", [&]() -> int {
+        return h ? h->impl.interpolate(a, a_len, b, b_len, w, hgt, times, n_times, mode, out, out_cap) : null_handle();
+    });
 }
 
 } // extern "C"

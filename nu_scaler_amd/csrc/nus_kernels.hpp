@@ -281,4 +281,33 @@ MetricsShape metrics_shape(uint32_t w, uint32_t h, uint32_t frames, bool mse, bo
 hipError_t launch_metrics(const uint8_t *a, size_t a_stride, const uint8_t *b, size_t b_stride, uint32_t w, uint32_t h,
                           uint32_t frames, bool mse, bool ssim, void *workspace, double *out, hipStream_t stream);
 
+// Block-matching motion estimation (nus_k_blockmatch.hip; nus_bm_* in include/nuscaler_hip.h).  Pair i reads A at
+// a + i * a_stride and B at b + i * b_stride (4-byte aligned); block (bx, by) of pair i is entry (i * blocks_y + by) * blocks_x + bx
+// of vectors (2 x int16: dx, dy), sad and flags.  The workspace holds the raw winners (2 x int16 per block) and, at rough_offset,
+// one word per 256 blocks for the smoothness test.
+constexpr uint32_t kBmRunPixels = 64; // frame-A pixels per search workgroup along x: 64 / bs neighbouring blocks share one LDS window
+constexpr uint32_t kBmMaxRadius = 24;
+struct BmShape {
+    uint32_t blocks_x = 0, blocks_y = 0, runs_x = 0, rough_groups = 0;
+    size_t rough_offset = 0, workspace_bytes = 0;
+};
+BmShape bm_shape(uint32_t w, uint32_t h, uint32_t bs, uint32_t n_pairs); // host only
+size_t bm_lds_bytes(uint32_t bs, uint32_t R);                            // dynamic LDS of one search workgroup
+struct BmLaunch {
+    const uint8_t *a = nullptr, *b = nullptr;
+    size_t a_stride = 0, b_stride = 0;
+    uint32_t w = 0, h = 0, n_pairs = 1;
+    uint32_t bs = 16, R = 16;                       // bs in {8, 16, 32}, R in 1 .. kBmMaxRadius
+    const uint16_t *rank = nullptr, *cand = nullptr; // (2R + 1)^2 entries each: candidate -> place in the tie order, and back
+    void *workspace = nullptr;
+    bool refine = true;        // confidence pass; off: vectors are the raw winners, flags 0
+    int16_t *vectors = nullptr;
+    uint32_t *sad = nullptr;   // may be null
+    uint8_t *flags = nullptr;  // may be null
+    void *flow = nullptr;      // may be null; w * h cells per pair, 2 x f32 or 2 x f16
+    bool flow_half = false;
+    hipStream_t stream = nullptr;
+};
+hipError_t launch_blockmatch(const BmLaunch &L);
+
 } // namespace nus

@@ -215,3 +215,24 @@ def interpolate_image_files_multi(path_a: str, path_b: str, output_path: str, mu
     for path, out in zip(paths, frames):
         write_png(path, w, h, out)
     return paths
+
+
+def interpolate_image_files_block_matching(path_a: str, path_b: str, output_path: str, quality: str = "medium",
+                                           time_t: float = 0.5, multiplier: int | None = None, device: int = 0) -> list[str]:
+    """`interpolate --method block_matching`: the block matcher's vectors (preset of `quality`) drive the warp.  One frame at
+    `time_t` written to output_path, or with `multiplier` the M - 1 frames at multi_output_paths(output_path, M).  Returns the
+    paths written."""
+    from .blockmatch import BlockMatcher
+
+    w, h, a = read_png(path_a)
+    wb, hb, b = read_png(path_b)
+    if (w, h) != (wb, hb):
+        raise ValueError(f"frame sizes differ: {w}x{h} vs {wb}x{hb}")
+    bm = BlockMatcher(quality, device=device)
+    if multiplier is not None:
+        frames, paths = bm.interpolate(a, b, w, h, multiplier=multiplier), multi_output_paths(output_path, multiplier)
+    else:
+        frames, paths = bm.interpolate(a, b, w, h, times=[time_t]), [output_path]
+    for path, out in zip(paths, frames):
+        write_png(path, w, h, out)
+    return paths
