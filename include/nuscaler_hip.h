@@ -629,6 +629,59 @@ int nus_bm_estimate(nus_blockmatch *h, const uint8_t *a, size_t a_len, const uin
 int nus_bm_interpolate(nus_blockmatch *h, const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, uint32_t w, uint32_t hgt,
                        const float *times, uint32_t n_times, int mode, uint8_t *out, size_t out_cap);
 
+/* ---- Scene-cut detection and the cut-aware output rule ------------------------------------------------------------
+ * BUILD-DEFINED: the reference has no such stage; its GUI interpolates every pair of a stream, the one that straddles a cut
+ * included (nu_scaler_py/nu_scaler/main.py:999-1008).  Across a cut there is no motion to estimate, so for a pair flagged
+ * here the multi-frame entry points write repeats of the nearer real frame instead of blends.  Everything is opt-in.
+ * Per pair (A, B) of frames of one size and channel order, two integer measures:
+ *   sad      u64: sum over pixels of |dR| + |dG| + |dB|; alpha ignored.
+ *   hist_l1  u32: sum over 32 bins of |H_A[k] - H_B[k]|, H_F the histogram over the frame's pixels of Y >> 3,
+ *            Y = (77 R + 150 G + 29 B + 128) >> 8 (the weights sum to 256, so Y <= 255).  0 .. 2 W H.  Luma is not symmetric in
+ *            R and B, hence `format` (nus_pixel_format): BGRA gives the numbers of the swizzled RGBA; the X byte is ignored.
+ * Decision, in 64-bit integer products (no float compare):
+ *   cut  <=>  sad >= mad_threshold * 3 W H   and   hist_l1 * 1000 >= hist_permille * 2 W H
+ * mad_threshold 0 .. 255 (default 20), hist_permille 0 .. 1000 (default 400).  Both must hold: the SAD term rejects slow fades
+ * (a global +8 step: histogram 270 permille, mean absolute difference 8), the histogram term fast motion (a 24-pixel pan: MAD
+ * 19 .. 85, histogram <= 6 permille).  The defaults are SETTINGS, NOT MEASUREMENTS: nobody has run this on real footage.  A global
+ * histogram cannot tell two unrelated frames of the same luma distribution apart (two noise frames: MAD 86, 10 permille: no cut).
+ * Results are deterministic: the same bytes on every run, at every batch position, whatever the batch size (per-workgroup
+ * partials in a workspace, added by a finish kernel; no float, no global atomics). */
+typedef struct nus_scene_measures {
+    uint64_t sad;
+    uint32_t hist_l1;
+    uint32_t reserved; /* written as 0 */
+} nus_scene_measures;
+#define NUS_SCENE_DEFAULT_MAD 20
+#define NUS_SCENE_DEFAULT_HIST_PERMILLE 400
+/* Workspace bytes nus_scene_detect_device needs; 0 (and nus_last_error) for an invalid shape. */
+size_t nus_scene_workspace_size(uint32_t w, uint32_t h, uint32_t n_pairs);
+/* n_pairs pairs addressed as nus_interp_interpolate_device addresses them (a sliding stream: d_b = d_a + frame_bytes, both strides
+ * frame_bytes; pointers and strides multiples of 4, strides >= w*h*4).  Per pair d_measures (may be NULL; 8-byte aligned) receives
+ * a nus_scene_measures and d_cut one u8, 0 or 1.  d_workspace 8-byte aligned.  Enqueue only on `stream`: no allocation, no
+ * synchronisation.  n_pairs == 0: NUS_OK, nothing launched.  Argument errors are NUS_ERR_INVALID_ARGUMENT, returned before any HIP
+ * call, with a text that names the entry point. */
+int nus_scene_detect_device(const void *d_a, size_t a_stride, const void *d_b, size_t b_stride, uint32_t w, uint32_t h, uint32_t n_pairs,
+                            int format, uint32_t mad_threshold, uint32_t hist_permille, void *d_workspace, size_t workspace_bytes,
+                            nus_scene_measures *d_measures, uint8_t *d_cut, void *stream);
+/* One host pair on `device` (pageable is fine: the bytes travel as nus_upload / nus_download move them, through device buffers
+ * the library keeps per device); measures_out may be NULL.  Size errors as nus_metrics_compare. */
+int nus_scene_detect(int device, const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, uint32_t w, uint32_t h, int format,
+                     uint32_t mad_threshold, uint32_t hist_permille, nus_scene_measures *measures_out, uint8_t *cut_out);
+/* The cut-aware output rule as a pass BEHIND an unchanged multi-time interpolation.  For every pair with d_cut[i] != 0, frame
+ * (i, k) at d_out + i * out_pair_stride + k * w*h*4 is overwritten with a copy of A_i if times[k] < 0.5, else of B_i.  "Copy": the
+ * bytes the zero-flow nus_interp_interpolate_device writes for that input `format` at t = 0 (A) and t = 1 (B) -- RGBA order out,
+ * so a BGRA input is swizzled and the X formats get alpha 255.  Pairs with d_cut[i] == 0 are neither read nor written.  Time-set
+ * rules, strides and gaps exactly as nus_interp_interpolate_multi_device; the gap of a display-order stride stays unwritten. */
+int nus_scene_apply_cuts_device(const void *d_a, size_t a_stride, const void *d_b, size_t b_stride, uint32_t w, uint32_t h, int format,
+                                const float *times, uint32_t n_times, const uint8_t *d_cut, void *d_out, size_t out_pair_stride,
+                                uint32_t n_pairs, void *stream);
+/* Detection wired into the entry points that write several frames per pair without the host in between: default off (every
+ * byte as before).  On, nus_flow_interpolate_multi_device_stream / nus_bm_interpolate run the estimate + warp as before, the
+ * detector, and then the apply pass, frames read as NUS_FORMAT_RGBA8.  A flagged pair's estimate and warp are still computed and
+ * then overwritten. */
+int nus_flow_set_scene_detect(nus_flow *h, int enabled, uint32_t mad_threshold, uint32_t hist_permille);
+int nus_bm_set_scene_detect(nus_blockmatch *h, int enabled, uint32_t mad_threshold, uint32_t hist_permille);
+
 #ifdef __cplusplus
 }
 #endif

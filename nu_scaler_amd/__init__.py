@@ -10,7 +10,7 @@ When the same process also uses PyTorch-ROCm (bench.py, the device-resident test
 BEFORE this package: torch ships its own HIP runtime and fails to see the GPU if /opt/rocm's
 libamdhip64 (pulled in by libnuscaler_hip.so) is loaded first.
 """
-from . import _capi, metrics, transfer
+from . import _capi, metrics, scene, transfer
 from ._capi import NuScalerLibraryError, PinnedBuffer, build, device_count
 from .blockmatch import BlockMatcher, PyFrameInterpolator
 from .benchmark import PyBenchmarkResult, py_benchmark_upscaler, py_run_comparison_benchmark
@@ -20,6 +20,7 @@ from .interpolator import WgpuFrameInterpolator, frame_times
 from .queue import FrameBuffer, swizzle_bgra_to_rgba_device
 from .launch import launch_ranks
 from .metrics import ErrorMetrics
+from .scene import SceneDetector
 from .stream import (FramePipeline, ShardedStream, SyntheticSource, broadcast_blob, broadcast_tables, build_tables_blob,
                      gather_rows, run_sharded, shard_frames, spread, validate_tables_blob)
 from .transfer import download, upload
@@ -52,7 +53,7 @@ __all__ = [
     "PyWgpuUpscaler", "PyAdvancedWgpuUpscaler", "PyVramStats", "create_advanced_upscaler", "create_fsr_upscaler",
     "upscale_image_file", "interpolate_image_files", "interpolate_image_files_multi", "frame_times",
     "PyBenchmarkResult", "py_benchmark_upscaler", "py_run_comparison_benchmark",
-    "WgpuFrameInterpolator", "BlockMatcher", "PyFrameInterpolator", "FlowEstimator", "ErrorMetrics", "metrics", "FrameBuffer", "swizzle_bgra_to_rgba_device", "FramePipeline", "shard_frames", "broadcast_tables",
+    "WgpuFrameInterpolator", "BlockMatcher", "PyFrameInterpolator", "FlowEstimator", "ErrorMetrics", "metrics", "SceneDetector", "scene", "FrameBuffer", "swizzle_bgra_to_rgba_device", "FramePipeline", "shard_frames", "broadcast_tables",
     "ShardedStream", "SyntheticSource", "run_sharded", "gather_rows", "spread", "launch_ranks",
     "broadcast_blob", "build_tables_blob", "validate_tables_blob",
     "NuScalerLibraryError", "PinnedBuffer", "build", "device_count", "download", "upload", "transfer", "install_fatal_trace",

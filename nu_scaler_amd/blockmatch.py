@@ -43,6 +43,7 @@ class BlockMatcher:
         self.set_params(bs if block_size is None else block_size, radius if search_radius is None else search_radius)
         self.set_tie_order(tie_order)
         self.set_refine(refine)
+        self.scene_detect, self._scene_thresholds = False, (C.SCENE_DEFAULT_MAD, C.SCENE_DEFAULT_HIST_PERMILLE)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -76,6 +77,16 @@ class BlockMatcher:
     def set_refine(self, enabled: bool) -> None:
         self._check(self._lib.nus_bm_set_refine(self._h, 1 if enabled else 0))
         self.refine = bool(enabled)
+
+    def set_scene_detect(self, enabled: bool, mad_threshold: int = C.SCENE_DEFAULT_MAD,
+                         hist_permille: int = C.SCENE_DEFAULT_HIST_PERMILLE) -> None:
+        """Scene-cut detection in front of `interpolate` (nus_bm_set_scene_detect; off by default): the frames of a pair the
+        detector flags are repeats of the nearer real frame."""
+        from .scene import check_thresholds
+
+        mad, hist = check_thresholds(mad_threshold, hist_permille)
+        self._check(self._lib.nus_bm_set_scene_detect(self._h, 1 if enabled else 0, mad, hist))
+        self.scene_detect, self._scene_thresholds = bool(enabled), (mad, hist)
 
     def block_grid(self, w: int, h: int) -> tuple[int, int]:
         return block_grid(w, h, self.block_size)
@@ -115,11 +126,19 @@ class BlockMatcher:
         return vec, sad, flags
 
     def interpolate(self, frame_a, frame_b, w: int, h: int, *, times: Optional[Sequence[float]] = None,
-                    multiplier: Optional[int] = None, mode: str = "exact") -> list[bytes]:
-        """Motion-compensated in-between frames of one pair (nus_bm_interpolate): at `times`, or at frame_times(multiplier)."""
+                    multiplier: Optional[int] = None, mode: str = "exact", scene_detect: bool = False) -> list[bytes]:
+        """Motion-compensated in-between frames of one pair (nus_bm_interpolate): at `times`, or at frame_times(multiplier).
+        `scene_detect=True` runs the scene-cut detector for this call only, with the thresholds of the last set_scene_detect
+        (the defaults if there was none); what set_scene_detect left on the object is not changed."""
         m = _MODE.get(str(mode).lower())
         if m is None:
             raise ValueError("mode must be 'exact' or 'fma'")
+        if scene_detect and not self.scene_detect:  # on for this call, off again behind it
+            self._check(self._lib.nus_bm_set_scene_detect(self._h, 1, *self._scene_thresholds))
+            try:
+                return self.interpolate(frame_a, frame_b, w, h, times=times, multiplier=multiplier, mode=mode)
+            finally:
+                self._lib.nus_bm_set_scene_detect(self._h, 0, *self._scene_thresholds)
         ts = _time_array(times, multiplier)
         n = len(ts)
         a_addr, a_len, ka = _as_buffer(frame_a)
@@ -139,8 +158,9 @@ class PyFrameInterpolator:
     any unknown method -- is the pyramid + Horn-Schunck estimator followed by the dense-flow warp (name "OpticalFlow"; the quality
     is kept and reported).  Unknown quality strings in the constructor mean "medium"; the setter raises."""
 
-    def __init__(self, method: str = "optical_flow", quality: str = "medium", *, device: int = 0):
+    def __init__(self, method: str = "optical_flow", quality: str = "medium", *, device: int = 0, scene_detect: bool = False):
         m = str(method).lower()
+        self._scene = None  # (not in the reference) a pair flagged as a scene cut gives a repeat of the nearer frame, not a blend
         self._block = m in ("block_matching", "simplified")
         q = str(quality).lower()
         self._quality = q if q in _QUALITY else "medium"
@@ -148,10 +168,16 @@ class PyFrameInterpolator:
         self._device = int(device)
         if self._block:
             self._bm = BlockMatcher(self._quality, device=device)
+            if scene_detect:
+                self._bm.set_scene_detect(True)
         else:
             from .flow import FlowEstimator
 
             self._flow = FlowEstimator(device=device)
+            if scene_detect:
+                from .scene import SceneDetector
+
+                self._scene = SceneDetector(device=device)
             self._warp = WgpuFrameInterpolator(device=device)
 
     @staticmethod
@@ -175,6 +201,8 @@ class PyFrameInterpolator:
                 return self._bm.interpolate(frame1, frame2, w, h, times=[t])[0]
             except ValueError as e:  # the pyclass raises PyRuntimeError for everything (:1011-1019)
                 raise RuntimeError(str(e)) from e
+        if self._scene is not None and self._scene.detect(frame1, frame2, w, h)[0]:
+            return self._warp.interpolate_py(frame1, frame2, w, h, time_t=0.0 if float(t) < 0.5 else 1.0)
         flow = self._flow.estimate(frame1, frame2, w, h)
         return self._warp.interpolate_py(frame1, frame2, w, h, time_t=float(t), flow=flow)
 

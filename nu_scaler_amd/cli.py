@@ -3,7 +3,8 @@
 legacy crate's `upscale_image_file` (Nu_scale/src/upscale/mod.rs:307-338) and the option names of
 its `fullscreen` subcommand (Nu_scale/src/main.rs:36-73: --tech, --quality, --algorithm); `interpolate <a.png> <b.png> <out.png>`
 with zero flow, `--flow` (Horn-Schunck) or `--method block_matching [--quality high|medium|low]`; `compare <a.png> <b.png>`
-prints the `ErrorMetrics` of two images (Nu_scale/src/upscale/common.rs:475-543).
+prints the `ErrorMetrics` of two images (Nu_scale/src/upscale/common.rs:475-543); `scene <a.png> <b.png>` prints the scene-cut
+detector's verdict on the pair, and `interpolate --multiplier M --scene-detect` writes repeats instead of blends across a cut.
 Everything runs on the HIP device; without one the command fails (no CPU path).
 """
 from __future__ import annotations
@@ -34,7 +35,15 @@ def build_parser() -> argparse.ArgumentParser:
     it.add_argument("--flow", action="store_true", help="estimate motion (pyramid + Horn-Schunck) instead of zero flow")
     it.add_argument("--method", default=None, help="block_matching: the full-search block matcher supplies the motion field")
     it.add_argument("--quality", default="medium", help="block matching preset: high (8 / 24), medium (16 / 16) or low (32 / 8)")
+    it.add_argument("--scene-detect", action="store_true",
+                    help="with --multiplier: if the scene-cut detector flags the pair, write repeats of the nearer frame, not blends")
     it.add_argument("--device", type=int, default=0)
+    sc = sub.add_parser("scene", help="scene-cut detector on two PNGs of equal size: prints cut=0|1 mad=.. hist_permille=..")
+    sc.add_argument("a")
+    sc.add_argument("b")
+    sc.add_argument("--mad", type=int, default=20, help="mean-absolute-difference threshold, 0 .. 255 (a setting, not a measurement)")
+    sc.add_argument("--hist", type=int, default=400, help="luma-histogram threshold in permille, 0 .. 1000 (likewise)")
+    sc.add_argument("--device", type=int, default=0)
     cp = sub.add_parser("compare", help="MSE, PSNR and SSIM of two PNGs of equal size (ErrorMetrics, "
                                          "Nu_scale/src/upscale/common.rs:475-543)")
     cp.add_argument("a")
@@ -142,6 +151,12 @@ def stream_command(args, argv) -> int:
     return 0
 
 
+def scene_line(cut: bool, sad: int, hist_l1: int, w: int, h: int) -> str:
+    """The line `scene` prints: the flag and the two measures in the units of their thresholds (for reading; the decision
+    itself is taken in integers on the device)."""
+    return f"cut={1 if cut else 0} mad={sad / (3 * w * h):.3f} hist_permille={hist_l1 * 1000 / (2 * w * h):.1f}"
+
+
 def main(argv=None) -> int:
     parser = build_parser()
     args = parser.parse_args(argv)
@@ -152,6 +167,13 @@ def main(argv=None) -> int:
 
         if not 2 <= args.multiplier <= INTERP_MAX_TIMES + 1:
             parser.error(f"--multiplier must be from 2 to {INTERP_MAX_TIMES + 1}, got {args.multiplier}")
+    if args.command == "interpolate" and args.scene_detect and args.multiplier is None:
+        parser.error("--scene-detect needs --multiplier")
+    if args.command == "scene":
+        if not 0 <= args.mad <= 255:
+            parser.error(f"--mad must be from 0 to 255, got {args.mad}")
+        if not 0 <= args.hist <= 1000:
+            parser.error(f"--hist must be from 0 to 1000, got {args.hist}")
     if args.command == "interpolate" and args.method is not None:
         if args.flow:
             parser.error("--method and --flow exclude each other")
@@ -183,15 +205,24 @@ def main(argv=None) -> int:
             a = np.frombuffer(pa, np.uint8).reshape(ha, wa, 4)
             b = np.frombuffer(pb, np.uint8).reshape(hb, wb, 4)
             print(ErrorMetrics.calculate(a, b, device=args.device).line())
+        elif args.command == "scene":
+            from .scene import SceneDetector
+
+            wa, ha, pa = imagefile.read_png(args.a)
+            wb, hb, pb = imagefile.read_png(args.b)
+            if (wa, ha) != (wb, hb):
+                raise ValueError("Images must have the same dimensions")
+            cut, sad, hist = SceneDetector(args.mad, args.hist, device=args.device).detect(pa, pb, wa, ha)
+            print(scene_line(cut, sad, hist, wa, ha))
         elif args.method is not None:
             paths = imagefile.interpolate_image_files_block_matching(args.frame_a, args.frame_b, args.output, args.quality.lower(),
                                                                      0.5 if args.t is None else args.t, args.multiplier,
-                                                                     device=args.device)
+                                                                     device=args.device, scene_detect=args.scene_detect)
             for path in paths:
                 print(path)
         elif args.multiplier is not None:
             for path in imagefile.interpolate_image_files_multi(args.frame_a, args.frame_b, args.output, args.multiplier, args.flow,
-                                                                device=args.device):
+                                                                device=args.device, scene_detect=args.scene_detect):
                 print(path)
         else:
             t = 0.5 if args.t is None else args.t

@@ -6,6 +6,7 @@
 //   nu_scaler_cli upscale <in.png> <out.png> [--algorithm A] [--scale S] [--tech T] [--quality Q] [--device N]
 //   nu_scaler_cli interpolate <a.png> <b.png> <out.png> [--t X | --multiplier M] [--flow] [--device N]
 //                             [--method block_matching [--quality high|medium|low]]
+//   nu_scaler_cli scene <a.png> <b.png> [--mad N] [--hist N] [--device N]   (the scene-cut detector: cut=0|1 mad=.. hist_permille=..)
 //   nu_scaler_cli compare <a.png> <b.png> [--device N]   (MSE / PSNR / SSIM, ErrorMetrics: Nu_scale/src/upscale/common.rs:475-543)
 //   nu_scaler_cli png-copy <in.png> <out.png>        (decode + encode only; no GPU: codec self-check)
 //
@@ -36,7 +37,8 @@ int usage(int rc)
                  "                             [--scale S] [--tech fsr|fallback|none] [--quality ultra|quality|balanced|performance]\n"
                  "                             [--device N]\n"
                  "       nu_scaler_cli interpolate <a.png> <b.png> <out.png> [--t X | --multiplier 2..8] [--flow] [--device N]\n"
-                 "                             [--method block_matching [--quality high|medium|low]]\n"
+                 "                             [--method block_matching [--quality high|medium|low]] [--scene-detect]\n"
+                 "       nu_scaler_cli scene <a.png> <b.png> [--mad 0..255] [--hist 0..1000] [--device N]\n"
                  "       nu_scaler_cli compare <a.png> <b.png> [--device N]\n"
                  "       nu_scaler_cli png-copy <in.png> <out.png>\n");
     return rc;
@@ -46,6 +48,7 @@ struct Args {
     std::vector<std::string> positional;
     std::map<std::string, std::string> options;
     bool flow = false;
+    bool scene_detect = false;
 };
 
 bool parse(int argc, char **argv, Args &a, std::string &err)
@@ -54,6 +57,8 @@ bool parse(int argc, char **argv, Args &a, std::string &err)
         const std::string s = argv[i];
         if (s == "--flow") {
             a.flow = true;
+        } else if (s == "--scene-detect") {
+            a.scene_detect = true;
         } else if (s.rfind("--", 0) == 0) {
             if (i + 1 >= argc) {
                 err = "option " + s + " needs a value";
@@ -150,6 +155,10 @@ int cmd_interpolate(const Args &a)
 {
     if (a.positional.size() != 3) return usage(2);
     const auto m_it = a.options.find("multiplier");
+    if (a.scene_detect && m_it == a.options.end()) {
+        std::fprintf(stderr, "nu_scaler_cli: error: --scene-detect needs --multiplier\n");
+        return usage(2);
+    }
     uint32_t multiplier = 0; // 0: one frame at --t
     if (m_it != a.options.end()) { // usage errors before anything is read or written
         if (a.options.count("t")) {
@@ -201,6 +210,7 @@ int cmd_interpolate(const Args &a)
         if (!bm) return fail(nus_last_error());
         int rc = nus_bm_set_device(bm, device);
         if (rc == NUS_OK) rc = nus_bm_set_quality(bm, bm_quality);
+        if (rc == NUS_OK && a.scene_detect) rc = nus_bm_set_scene_detect(bm, 1, NUS_SCENE_DEFAULT_MAD, NUS_SCENE_DEFAULT_HIST_PERMILLE);
         if (rc == NUS_OK)
             rc = nus_bm_interpolate(bm, fa.rgba.data(), fa.rgba.size(), fb.rgba.data(), fb.rgba.size(), fa.width, fa.height, times.data(),
                                     n, NUS_INTERP_MODE_EXACT, frames.data(), frames.size());
@@ -239,10 +249,19 @@ int cmd_interpolate(const Args &a)
         std::vector<float> times(n);
         for (uint32_t k = 1; k <= n; ++k) times[k - 1] = (float)((double)k / (double)multiplier);
         std::vector<uint8_t> frames(fa.rgba.size() * n);
+        uint8_t cut = 0;
+        if (a.scene_detect && nus_scene_detect(device, fa.rgba.data(), fa.rgba.size(), fb.rgba.data(), fb.rgba.size(), fa.width, fa.height,
+                                               NUS_FORMAT_RGBA8, NUS_SCENE_DEFAULT_MAD, NUS_SCENE_DEFAULT_HIST_PERMILLE, nullptr,
+                                               &cut) != NUS_OK) {
+            nus_interp_destroy(it);
+            return fail(nus_last_error());
+        }
+        if (cut) // a scene cut: repeats of the nearer frame -- the zero-flow launch at t = 0 / 1 (nus_scene_apply_cuts_device's copy)
+            for (float &tk : times) tk = tk < 0.5f ? 0.0f : 1.0f;
         int rc = nus_interp_set_device(it, device);
         if (rc == NUS_OK)
             rc = nus_interp_interpolate_multi(it, fa.rgba.data(), fa.rgba.size(), fb.rgba.data(), fb.rgba.size(),
-                                              a.flow ? flow.data() : nullptr, fa.width, fa.height, times.data(), n, frames.data(),
+                                              a.flow && !cut ? flow.data() : nullptr, fa.width, fa.height, times.data(), n, frames.data(),
                                               frames.size());
         const std::string msg = rc == NUS_OK ? "" : nus_interp_last_error(it);
         nus_interp_destroy(it);
@@ -297,6 +316,35 @@ int cmd_compare(const Args &a)
     return 0;
 }
 
+// one line, the same as `python -m nu_scaler_amd.cli scene`
+int cmd_scene(const Args &a)
+{
+    if (a.positional.size() != 2) return usage(2);
+    long mad = NUS_SCENE_DEFAULT_MAD, hist = NUS_SCENE_DEFAULT_HIST_PERMILLE;
+    const auto m_it = a.options.find("mad"), h_it = a.options.find("hist");
+    if (m_it != a.options.end()) mad = std::atol(m_it->second.c_str());
+    if (h_it != a.options.end()) hist = std::atol(h_it->second.c_str());
+    if (mad < 0 || mad > 255 || hist < 0 || hist > 1000) { // usage errors before anything is read
+        std::fprintf(stderr, "nu_scaler_cli: error: --mad must be from 0 to 255 and --hist from 0 to 1000\n");
+        return usage(2);
+    }
+    nus_cli::Image fa, fb;
+    std::string err = nus_cli::read_png(a.positional[0], fa);
+    if (err.empty()) err = nus_cli::read_png(a.positional[1], fb);
+    if (!err.empty()) return fail(err);
+    if (fa.width != fb.width || fa.height != fb.height) return fail("Images must have the same dimensions");
+    const auto d_it = a.options.find("device");
+    const int device = d_it == a.options.end() ? 0 : std::atoi(d_it->second.c_str());
+    nus_scene_measures m = {0, 0, 0};
+    uint8_t cut = 0;
+    if (nus_scene_detect(device, fa.rgba.data(), fa.rgba.size(), fb.rgba.data(), fb.rgba.size(), fa.width, fa.height, NUS_FORMAT_RGBA8,
+                         (uint32_t)mad, (uint32_t)hist, &m, &cut) != NUS_OK)
+        return fail(nus_last_error());
+    const double px = (double)fa.width * fa.height;
+    std::printf("cut=%d mad=%.3f hist_permille=%.1f\n", (int)cut, (double)m.sad / (3.0 * px), (double)m.hist_l1 * 1000.0 / (2.0 * px));
+    return 0;
+}
+
 int cmd_png_copy(const Args &a)
 {
     if (a.positional.size() != 2) return usage(2);
@@ -321,6 +369,7 @@ int main(int argc, char **argv)
     if (cmd == "upscale") return cmd_upscale(a);
     if (cmd == "interpolate") return cmd_interpolate(a);
     if (cmd == "compare") return cmd_compare(a);
+    if (cmd == "scene") return cmd_scene(a);
     if (cmd == "png-copy") return cmd_png_copy(a);
     return usage(2);
 }

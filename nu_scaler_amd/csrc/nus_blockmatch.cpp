@@ -6,6 +6,7 @@
 
 #include "nus_host.hpp"
 #include "nus_host_util.hpp"
+#include "nus_scene.hpp"
 #include "nus_transfer.hpp"
 
 namespace nus {
@@ -112,6 +113,18 @@ int BlockMatcher::set_refine(int enabled)
     std::lock_guard<std::mutex> lk(mu_);
     if (enabled != 0 && enabled != 1) return fail(kInvalidArgument, fmt("nus_bm_set_refine: 0 or 1, got %d", enabled));
     refine_ = enabled == 1;
+    return kOk;
+}
+
+int BlockMatcher::set_scene_detect(int enabled, uint32_t mad_threshold, uint32_t hist_permille)
+{
+    std::lock_guard<std::mutex> lk(mu_);
+    if (enabled != 0 && enabled != 1) return fail(kInvalidArgument, fmt("nus_bm_set_scene_detect: 0 or 1, got %d", enabled));
+    const std::string bad = check_scene_thresholds(mad_threshold, hist_permille);
+    if (!bad.empty()) return fail(kInvalidArgument, fmt("nus_bm_set_scene_detect: %s", bad.c_str()));
+    scene_ = enabled == 1;
+    scene_mad_ = mad_threshold;
+    scene_hist_ = hist_permille;
     return kOk;
 }
 
@@ -296,11 +309,24 @@ int BlockMatcher::interpolate(const uint8_t *a, size_t a_len, const uint8_t *b, 
     const BmShape s = bm_shape(w, h, bs_, 1);
     const size_t frame = up16(expected), nb = (size_t)s.blocks_x * s.blocks_y;
     const size_t o_b = frame, o_ws = 2 * frame, o_vec = o_ws + up16(s.workspace_bytes), o_flow = o_vec + up16(nb * 4), o_out = o_flow + frame,
-                 total = o_out + (size_t)n_times * expected;
+                 out_end = o_out + (size_t)n_times * expected,
+                 // with detection on: the detector's workspace and the pair's flag byte behind the frames
+                 o_scene = up16(out_end), scene_ws = up16(scene_shape(w, h, 1).workspace_bytes),
+                 total = scene_ ? o_scene + scene_ws + 16 : out_end;
     int rc = ensure_host(total);
     if (rc != kOk) return rc;
     NUS_BM_TRY(upload(arena_, a, a_len, stream_));
     NUS_BM_TRY(upload(arena_ + o_b, b, b_len, stream_));
+    SceneLaunch S; // detect -> estimate + warp as without detection -> a flagged pair's frames overwritten with repeats
+    S.a = arena_;
+    S.b = arena_ + o_b;
+    S.a_stride = S.b_stride = expected;
+    S.w = w, S.h = h, S.stream = stream_;
+    uint8_t *const cut = arena_ + o_scene + scene_ws;
+    if (scene_) {
+        const hipError_t es = launch_scene_detect(S, scene_mad_, scene_hist_, arena_ + o_scene, nullptr, cut);
+        if (es != hipSuccess) return fail_hip(es, "scene-detect launch");
+    }
     // estimate -> dense flow as 2 x f16 per pixel (the vectors are integers of magnitude <= 24: exact) -> multi-time warp
     rc = enqueue(arena_, a_len, arena_ + o_b, b_len, w, h, 1, arena_ + o_ws, arena_ + o_vec, nullptr, nullptr, arena_ + o_flow, 1, stream_);
     if (rc != kOk) return rc;
@@ -320,6 +346,10 @@ int BlockMatcher::interpolate(const uint8_t *a, size_t a_len, const uint8_t *b, 
     L.stream = stream_;
     const hipError_t e = launch_warp_blend(L);
     if (e != hipSuccess) return fail_hip(e, "multi-time warp+blend launch");
+    if (scene_) {
+        const hipError_t es = launch_scene_apply(S, n_times, scene_from_a_mask(times, n_times), cut, arena_ + o_out, (size_t)n_times * expected);
+        if (es != hipSuccess) return fail_hip(es, "scene-apply launch");
+    }
     NUS_BM_TRY(download(out, arena_ + o_out, (size_t)n_times * expected, stream_));
     return kOk;
 }

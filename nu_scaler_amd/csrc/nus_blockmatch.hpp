@@ -31,6 +31,9 @@ public:
     int set_quality(int quality); // nus_interp_quality_level: High 8 / 24, Medium 16 / 16, Low 32 / 8 (interpolation/mod.rs:531-542)
     int set_tie_order(int order);
     int set_refine(int enabled);
+    // Scene-cut detection in front of interpolate() and the cut-aware output rule behind it (nus_scene_* of the C header): off by
+    // default.  On, the frames of a pair the detector flags are repeats of the nearer real frame.
+    int set_scene_detect(int enabled, uint32_t mad_threshold, uint32_t hist_permille);
     size_t workspace_size(uint32_t w, uint32_t h, uint32_t n_pairs); // 0 and the reason for an invalid shape
     int estimate_device(const void *d_a, size_t a_stride, const void *d_b, size_t b_stride, uint32_t w, uint32_t h, uint32_t n_pairs,
                         void *d_workspace, size_t workspace_bytes, void *d_vectors, void *d_sad, void *d_flags, void *d_flow,
@@ -56,6 +59,8 @@ private:
     uint32_t bs_ = 16, radius_ = 16; // Medium
     int order_ = kBmTiesCenter;
     bool refine_ = true;
+    bool scene_ = false;
+    uint32_t scene_mad_ = 20, scene_hist_ = 400;
     std::string error_;
     uint16_t *d_tables_ = nullptr;
     hipStream_t stream_ = nullptr;

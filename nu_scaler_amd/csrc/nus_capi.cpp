@@ -13,6 +13,7 @@
 #include "nus_metrics.hpp"
 #include "nus_queue.hpp"
 #include "nus_ranges.hpp"
+#include "nus_scene.hpp"
 #include "nus_transfer.hpp"
 
 struct nus_upscaler {
@@ -83,6 +84,9 @@ R guarded(const char *what, F &&f) noexcept
 
 static_assert(NUS_BM_MAX_RADIUS == nus::kBmMaxRadius && NUS_BM_TIES_SCAN == nus::kBmTiesScan && NUS_BM_TIES_CENTER == nus::kBmTiesCenter,
               "the C header's block-matching constants are the kernels'");
+static_assert(sizeof(nus_scene_measures) == 16 && NUS_SCENE_DEFAULT_MAD == nus::kSceneDefaultMad &&
+                  NUS_SCENE_DEFAULT_HIST_PERMILLE == nus::kSceneDefaultHistPermille,
+              "the C header's scene-detector layout and defaults are the kernels'");
 static_assert(NUS_INTERP_MAX_TIMES == nus::kInterpMaxTimes, "the C header's NUS_INTERP_MAX_TIMES is the kernels' time-set size");
 
 extern "C" {
@@ -870,6 +874,51 @@ int nus_bm_interpolate(nus_blockmatch *h, const uint8_t *a, size_t a_len, const 
 {
     return guarded<int>("nus_bm_interpolate", [&]() -> int {
         return h ? h->impl.interpolate(a, a_len, b, b_len, w, hgt, times, n_times, mode, out, out_cap) : null_handle();
+    });
+}
+int nus_bm_set_scene_detect(nus_blockmatch *h, int enabled, uint32_t mad_threshold, uint32_t hist_permille)
+{
+    return guarded<int>("nus_bm_set_scene_detect",
+                        [&]() -> int { return h ? h->impl.set_scene_detect(enabled, mad_threshold, hist_permille) : null_handle(); });
+}
+int nus_flow_set_scene_detect(nus_flow *h, int enabled, uint32_t mad_threshold, uint32_t hist_permille)
+{
+    return guarded<int>("nus_flow_set_scene_detect",
+                        [&]() -> int { return h ? h->impl.set_scene_detect(enabled, mad_threshold, hist_permille) : null_handle(); });
+}
+
+size_t nus_scene_workspace_size(uint32_t w, uint32_t h, uint32_t n_pairs)
+{
+    try {
+        return nus::scene_workspace_size(w, h, n_pairs);
+    } catch (...) {
+        nus::set_thread_error("nus_scene_workspace_size: unexpected exception");
+        return 0;
+    }
+}
+int nus_scene_detect_device(const void *d_a, size_t a_stride, const void *d_b, size_t b_stride, uint32_t w, uint32_t h, uint32_t n_pairs,
+                            int format, uint32_t mad_threshold, uint32_t hist_permille, void *d_workspace, size_t workspace_bytes,
+                            nus_scene_measures *d_measures, uint8_t *d_cut, void *stream)
+{
+    return guarded<int>("nus_scene_detect_device", [&]() -> int {
+        return nus::scene_detect_device(d_a, a_stride, d_b, b_stride, w, h, n_pairs, format, mad_threshold, hist_permille, d_workspace,
+                                        workspace_bytes, d_measures, d_cut, static_cast<hipStream_t>(stream));
+    });
+}
+int nus_scene_detect(int device, const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, uint32_t w, uint32_t h, int format,
+                     uint32_t mad_threshold, uint32_t hist_permille, nus_scene_measures *measures_out, uint8_t *cut_out)
+{
+    return guarded<int>("nus_scene_detect", [&]() -> int {
+        return nus::scene_detect(device, a, a_len, b, b_len, w, h, format, mad_threshold, hist_permille, measures_out, cut_out);
+    });
+}
+int nus_scene_apply_cuts_device(const void *d_a, size_t a_stride, const void *d_b, size_t b_stride, uint32_t w, uint32_t h, int format,
+                                const float *times, uint32_t n_times, const uint8_t *d_cut, void *d_out, size_t out_pair_stride,
+                                uint32_t n_pairs, void *stream)
+{
+    return guarded<int>("nus_scene_apply_cuts_device", [&]() -> int {
+        return nus::scene_apply_cuts_device(d_a, a_stride, d_b, b_stride, w, h, format, times, n_times, d_cut, d_out, out_pair_stride,
+                                            n_pairs, static_cast<hipStream_t>(stream));
     });
 }
 

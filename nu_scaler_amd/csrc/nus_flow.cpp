@@ -8,6 +8,7 @@
 #include "nus_host.hpp"
 #include "nus_host_util.hpp"
 #include "nus_kernels.hpp"
+#include "nus_scene.hpp"
 #include "nus_transfer.hpp"
 
 namespace nus {
@@ -412,8 +413,39 @@ int HipFlowEstimator::interpolate_multi_device_stream(const void *d_frames, uint
     mt.times = times;
     mt.n = n_times;
     mt.pair_stride = mid_pair_stride ? mid_pair_stride : n_times * frame_bytes;
-    return stream_impl(d_frames, n_frames, w, h, levels, coarse_iters, refine_iters, lambda, d_flows, d_mid, times[0], stream, flow_half,
-                       &mt);
+    if (!scene_)
+        return stream_impl(d_frames, n_frames, w, h, levels, coarse_iters, refine_iters, lambda, d_flows, d_mid, times[0], stream, flow_half,
+                           &mt);
+    // estimate + warp as without detection, then the detector (it reads the frames only, so its place in the order is free) and
+    // the flagged pairs' frames overwritten with repeats
+    const uint32_t n_pairs = n_frames - 1;
+    const std::string too_many = check_scene_launch(w, h, n_pairs);
+    if (!too_many.empty()) return fail(kInvalidArgument, std::string(who) + ": " + too_many);
+    int rc = stream_impl(d_frames, n_frames, w, h, levels, coarse_iters, refine_iters, lambda, d_flows, d_mid, times[0], stream, flow_half, &mt);
+    if (rc != kOk) return rc;
+    const size_t ws_bytes = scene_shape(w, h, n_pairs).workspace_bytes;
+    if ((rc = reserve(ws_bytes + n_pairs, 11)) != kOk) return rc;
+    uint8_t *cut = static_cast<uint8_t *>(slot_[11]) + ws_bytes;
+    SceneLaunch S;
+    S.a = static_cast<const uint8_t *>(d_frames);
+    S.b = S.a + frame_bytes;
+    S.a_stride = S.b_stride = frame_bytes;
+    S.w = w, S.h = h, S.n_pairs = n_pairs, S.stream = stream;
+    NUS_HIP(launch_scene_detect(S, scene_mad_, scene_hist_, slot_[11], nullptr, cut));
+    NUS_HIP(launch_scene_apply(S, n_times, scene_from_a_mask(times, n_times), cut, static_cast<uint8_t *>(d_mid), mt.pair_stride));
+    return kOk;
+}
+
+int HipFlowEstimator::set_scene_detect(int enabled, uint32_t mad_threshold, uint32_t hist_permille)
+{
+    std::lock_guard<std::mutex> lk(mu_);
+    if (enabled != 0 && enabled != 1) return fail(kInvalidArgument, fmt("nus_flow_set_scene_detect: 0 or 1, got %d", enabled));
+    const std::string bad = check_scene_thresholds(mad_threshold, hist_permille);
+    if (!bad.empty()) return fail(kInvalidArgument, "nus_flow_set_scene_detect: " + bad);
+    scene_ = enabled == 1;
+    scene_mad_ = mad_threshold;
+    scene_hist_ = hist_permille;
+    return kOk;
 }
 
 // (called with mu_ held)  d_flows may be null when d_mid is not: the caller wants the in-between frames only.  mt: the frames at

@@ -42,6 +42,9 @@ public:
     // The primitives (blur, downsample, horn_schunck, upsample) are always exact.
     int set_mode(int mode);
     int mode() const { return fast_ ? 1 : 0; }
+    // Scene-cut detection in front of interpolate_multi_device_stream and the cut-aware output rule behind it (nus_scene_* of the C
+    // header): off by default.  On, the in-between frames of a pair the detector flags are repeats of the nearer real frame.
+    int set_scene_detect(int enabled, uint32_t mad_threshold, uint32_t hist_permille);
     int estimate_device(const void *d_a, const void *d_b, uint32_t w, uint32_t h, uint32_t levels,
                         uint32_t coarse_iters, uint32_t refine_iters, float lambda, void *d_flow_out,
                         hipStream_t stream);
@@ -104,7 +107,9 @@ private:
     int jacobi_ = 0; // JacobiKernel
     bool fast_ = false; // set_mode(1): the estimator's Jacobi steps in FAST arithmetic (k_hs_stream_fast), every level streamed
     hipStream_t stream_ = nullptr;
-    static constexpr int kSlotCount = 11; // 0-5 pyramids / flows / planes, 6-7 the host entry point's frames, 8 the FAST pair, 9 one pair's flow, 10 a chunk's flows as f16
+    bool scene_ = false; // set_scene_detect
+    uint32_t scene_mad_ = 20, scene_hist_ = 400;
+    static constexpr int kSlotCount = 12; // 0-5 pyramids / flows / planes, 6-7 the host entry point's frames, 8 the FAST pair, 9 one pair's flow, 10 a chunk's flows as f16, 11 the scene detector's workspace and flags
     void *slot_[kSlotCount] = {nullptr};
     size_t slot_cap_[kSlotCount] = {0};
     std::string error_;

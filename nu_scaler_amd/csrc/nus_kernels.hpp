@@ -310,4 +310,28 @@ struct BmLaunch {
 };
 hipError_t launch_blockmatch(const BmLaunch &L);
 
+// Scene-cut detection and the cut-aware output rule (nus_k_scene.hip; nus_scene_* in include/nuscaler_hip.h).  Pair i reads A at
+// a + i * a_stride and B at b + i * b_stride (4-byte aligned).  The workspace holds the measure kernel's per-workgroup partials:
+// u64 SADs at sad_offset, 64 u32 bins (32 of A, 32 of B) at hist_offset.
+constexpr uint32_t kSceneBlock = 256; // lanes per workgroup of every scene kernel
+struct SceneShape {
+    uint32_t measure_blocks = 0, apply_blocks = 0; // workgroups per pair
+    size_t sad_offset = 0, hist_offset = 0, workspace_bytes = 0;
+};
+SceneShape scene_shape(uint32_t w, uint32_t h, uint32_t n_pairs); // host only
+struct SceneLaunch {
+    const uint8_t *a = nullptr, *b = nullptr;
+    size_t a_stride = 0, b_stride = 0;
+    uint32_t w = 0, h = 0, n_pairs = 1;
+    int format = 0; // nus_pixel_format of both frames
+    hipStream_t stream = nullptr;
+};
+// measures (may be null): per pair {u64 sad, u32 hist_l1, u32 0}; cut: one u8 0 / 1 per pair
+hipError_t launch_scene_detect(const SceneLaunch &L, uint32_t mad_threshold, uint32_t hist_permille, void *workspace, void *measures,
+                               uint8_t *cut);
+// for every pair with cut[i] != 0: frame k of the pair at out + i * out_pair_stride + k * w * h * 4 becomes a copy of A (bit k of
+// from_a set) or of B, through the input selector of L.format; other pairs are neither read nor written
+hipError_t launch_scene_apply(const SceneLaunch &L, uint32_t n_times, uint32_t from_a, const uint8_t *cut, uint8_t *out,
+                              size_t out_pair_stride);
+
 } // namespace nus

@@ -46,6 +46,15 @@ class FlowEstimator:
             raise ValueError("mode must be 'exact' or 'fast'")
         self._check(self._lib.nus_flow_set_mode(self._h, m))
 
+    def set_scene_detect(self, enabled: bool, mad_threshold: int = C.SCENE_DEFAULT_MAD,
+                         hist_permille: int = C.SCENE_DEFAULT_HIST_PERMILLE) -> None:
+        """Scene-cut detection in front of `interpolate_multi_device_stream` (nus_flow_set_scene_detect; off by default): the
+        in-between frames of a pair the detector flags are repeats of the nearer real frame."""
+        from .scene import check_thresholds
+
+        mad, hist = check_thresholds(mad_threshold, hist_permille)
+        self._check(self._lib.nus_flow_set_scene_detect(self._h, 1 if enabled else 0, mad, hist))
+
     @property
     def mode(self) -> str:
         return "fast" if self._lib.nus_flow_mode(self._h) == 1 else "exact"

@@ -195,9 +195,10 @@ def multi_output_paths(output_path: str, multiplier: int) -> list[str]:
 
 
 def interpolate_image_files_multi(path_a: str, path_b: str, output_path: str, multiplier: int, estimate_flow: bool = False,
-                                  device: int = 0) -> list[str]:
+                                  device: int = 0, scene_detect: bool = False) -> list[str]:
     """The M - 1 in-between frames of a frame-rate multiplier M (t = k / M) from one multi-time call, written to
-    multi_output_paths(output_path, M); with `estimate_flow` the flow is estimated once for all of them."""
+    multi_output_paths(output_path, M); with `estimate_flow` the flow is estimated once for all of them.  `scene_detect`: a
+    pair the scene-cut detector flags gives repeats of the nearer frame instead of blends."""
     from .interpolator import frame_times
 
     times = frame_times(multiplier)
@@ -210,7 +211,7 @@ def interpolate_image_files_multi(path_a: str, path_b: str, output_path: str, mu
     if estimate_flow:
         from .flow import FlowEstimator
         flow = FlowEstimator(device=device).estimate(a, b, w, h)
-    frames = it.interpolate_multi_py(a, b, w, h, times=times, flow=flow)
+    frames = it.interpolate_multi_py(a, b, w, h, times=times, flow=flow, scene_detect=scene_detect)
     paths = multi_output_paths(output_path, multiplier)
     for path, out in zip(paths, frames):
         write_png(path, w, h, out)
@@ -218,7 +219,8 @@ def interpolate_image_files_multi(path_a: str, path_b: str, output_path: str, mu
 
 
 def interpolate_image_files_block_matching(path_a: str, path_b: str, output_path: str, quality: str = "medium",
-                                           time_t: float = 0.5, multiplier: int | None = None, device: int = 0) -> list[str]:
+                                           time_t: float = 0.5, multiplier: int | None = None, device: int = 0,
+                                           scene_detect: bool = False) -> list[str]:
     """`interpolate --method block_matching`: the block matcher's vectors (preset of `quality`) drive the warp.  One frame at
     `time_t` written to output_path, or with `multiplier` the M - 1 frames at multi_output_paths(output_path, M).  Returns the
     paths written."""
@@ -229,6 +231,8 @@ def interpolate_image_files_block_matching(path_a: str, path_b: str, output_path
     if (w, h) != (wb, hb):
         raise ValueError(f"frame sizes differ: {w}x{h} vs {wb}x{hb}")
     bm = BlockMatcher(quality, device=device)
+    if scene_detect:
+        bm.set_scene_detect(True)
     if multiplier is not None:
         frames, paths = bm.interpolate(a, b, w, h, multiplier=multiplier), multi_output_paths(output_path, multiplier)
     else:

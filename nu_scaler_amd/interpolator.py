@@ -58,6 +58,7 @@ class WgpuFrameInterpolator:
             raise RuntimeError(C.last_error())
         if self._lib.nus_interp_set_device(self._h, int(device)) != C.OK:
             raise RuntimeError(self._err())
+        self._device, self._format = int(device), C.FORMAT_RGBA8
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -96,12 +97,20 @@ class WgpuFrameInterpolator:
         return out
 
     def interpolate_multi_py(self, frame_a_bytes, frame_b_bytes, width: int, height: int, *, times: Optional[Sequence[float]] = None,
-                             multiplier: Optional[int] = None, flow=None) -> list[bytes]:
+                             multiplier: Optional[int] = None, flow=None, scene_detect=False) -> list[bytes]:
         """The in-between frames of one pair at several times from one launch (nus_interp_interpolate_multi): at `times`, or at
         frame_times(multiplier).  Each frame is what interpolate_py returns at that time.  Argument errors raise ValueError
-        before any GPU work."""
+        before any GPU work.  `scene_detect` (False; True for the default thresholds, or a `SceneDetector`): if the detector
+        flags the pair as a scene cut, every frame is a repeat of the nearer real frame -- the zero-flow launch at t = 0 (times
+        below one half) or t = 1, which is the copy nus_scene_apply_cuts_device defines."""
         ts = _time_array(times, multiplier)
         n = len(ts)
+        if scene_detect:
+            from .scene import SceneDetector
+
+            det = scene_detect if isinstance(scene_detect, SceneDetector) else SceneDetector(device=self._device)
+            if det.detect(frame_a_bytes, frame_b_bytes, width, height, fmt=self._format)[0]:
+                ts, flow = (ctypes.c_float * n)(*[0.0 if t < 0.5 else 1.0 for t in ts]), None
         a_addr, a_len, ka = _as_buffer(frame_a_bytes)
         b_addr, b_len, kb = _as_buffer(frame_b_bytes)
         f_addr, kf = None, None
@@ -166,6 +175,7 @@ class WgpuFrameInterpolator:
         if f is None:
             raise ValueError("input format must be 'rgba', 'bgra', 'rgbx' or 'bgrx'")
         self._raise(self._lib.nus_interp_set_input_format(self._h, f))
+        self._format = f
 
     def set_mode(self, mode: str) -> None:
         """Arithmetic of the dense-flow warp: "exact" (default; the CPU's roundings, bit-exact against the oracle) or "fma"
