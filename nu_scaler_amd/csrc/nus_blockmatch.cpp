@@ -21,7 +21,7 @@ size_t table_offset(uint32_t R, int order)
     return o + (size_t)order * 2 * (2 * R + 1) * (2 * R + 1);
 }
 
-bool misaligned(const void *p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) % to) != 0; }
+constexpr uint64_t kMaxPixels = (1ull << 31) - 1;
 
 size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
 
@@ -45,27 +45,14 @@ void bm_rank_tables(uint32_t R, int order, std::vector<uint16_t> &rank, std::vec
 
 BlockMatcher::~BlockMatcher()
 {
-    if (!d_tables_ && !arena_ && !stream_) return;
+    if (!d_tables_ && !arena_.get() && !stream_) return;
     (void)hipSetDevice(device_);
     if (stream_) {
         (void)hipStreamSynchronize(stream_);
         (void)hipStreamDestroy(stream_);
     }
-    if (arena_) (void)hipFree(arena_);
+    arena_.release();
     if (d_tables_) (void)hipFree(d_tables_);
-}
-
-int BlockMatcher::fail(int status, const std::string &msg)
-{
-    error_ = msg;
-    set_thread_error(msg);
-    return status;
-}
-
-int BlockMatcher::fail_hip(hipError_t e, const char *what)
-{
-    (void)hipGetLastError();
-    return fail(e == hipErrorOutOfMemory ? kOutOfMemory : kHipError, fmt("HIP error in %s: %s", what, hipGetErrorString(e)));
 }
 
 int BlockMatcher::set_device(int device)
@@ -130,7 +117,8 @@ int BlockMatcher::set_scene_detect(int enabled, uint32_t mad_threshold, uint32_t
 
 int BlockMatcher::check_shape(const char *who, uint32_t w, uint32_t h, uint32_t n_pairs)
 {
-    if (w == 0 || h == 0 || (uint64_t)w * h >= (1ull << 31)) return fail(kInvalidArgument, fmt("%s: bad dimensions", who));
+    const int st = pass(check_dims(who, w, h, kMaxPixels));
+    if (st != kOk) return st;
     // the search grid is (runs, block rows, pairs): 65535 on its second and third axis
     if ((h + bs_ - 1) / bs_ > 65535u || n_pairs > 65535u)
         return fail(kInvalidArgument, fmt("%s: %u pairs of %ux%u are too many for one launch (at most 65535 pairs and block rows)", who,
@@ -147,11 +135,8 @@ size_t BlockMatcher::workspace_size(uint32_t w, uint32_t h, uint32_t n_pairs)
 
 int BlockMatcher::ensure_tables()
 {
-    const int n = device_count();
-    if (n <= 0) return fail(kNoDevice, "no HIP device available (the gfx950 path has no CPU fallback)");
-    if (device_ >= n) return fail(kNoDevice, fmt("HIP device %d requested but only %d present", device_, n));
-    NUS_HIP(hipSetDevice(device_));
-    if (d_tables_) return kOk;
+    int rc = select_device(device_);
+    if (rc != kOk || d_tables_) return rc;
     std::vector<uint16_t> all, rank, cand;
     for (uint32_t R = 1; R <= kBmMaxRadius; ++R)
         for (int order = 0; order < 2; ++order) {
@@ -161,12 +146,10 @@ int BlockMatcher::ensure_tables()
         }
     uint16_t *d = nullptr;
     NUS_HIP(hipMalloc(reinterpret_cast<void **>(&d), all.size() * sizeof(uint16_t)));
-    int rc = upload(d, all.data(), all.size() * sizeof(uint16_t), nullptr);
+    rc = pass(upload(d, all.data(), all.size() * sizeof(uint16_t), nullptr));
     if (rc == kOk) {
         const hipError_t e = hipStreamSynchronize(nullptr); // in place for every stream from here on
         if (e != hipSuccess) rc = fail_hip(e, "hipStreamSynchronize");
-    } else {
-        error_ = thread_error();
     }
     if (rc != kOk) {
         (void)hipFree(d);
@@ -213,18 +196,15 @@ int BlockMatcher::estimate_device(const void *d_a, size_t a_stride, const void *
 {
     static const char *const who = "nus_bm_estimate_device";
     std::lock_guard<std::mutex> lk(mu_);
-    const int st = check_shape(who, w, h, n_pairs);
+    int st = check_shape(who, w, h, n_pairs);
     if (st != kOk) return st;
     if (!d_a || !d_b || !d_workspace || !d_vectors) return fail(kInvalidArgument, fmt("%s: null device pointer", who));
     if (flow_format != 0 && flow_format != 1)
         return fail(kInvalidArgument, fmt("%s: flow_format must be NUS_FLOW_F32 or NUS_FLOW_F16", who));
-    if (misaligned(d_a, 4) || misaligned(d_b, 4) || a_stride % 4 || b_stride % 4 || misaligned(d_vectors, 4) || misaligned(d_sad, 4) ||
-        misaligned(d_flow, flow_format == 1 ? 4 : 8))
-        return fail(kInvalidArgument, fmt("%s: pointers/strides must be pixel aligned", who));
+    if ((st = pass(check_pixel_aligned(who, d_a, a_stride, d_b, b_stride, d_vectors, d_flow, flow_format == 1 ? 4 : 8, d_sad))) != kOk) return st;
     if (misaligned(d_workspace, 16)) return fail(kInvalidArgument, fmt("%s: workspace must be 16-byte aligned", who));
     const size_t need = bm_shape(w, h, bs_, n_pairs ? n_pairs : 1).workspace_bytes;
-    if (workspace_bytes < need)
-        return fail(kInvalidArgument, fmt("%s: workspace of %zu bytes, %zu needed (nus_bm_workspace_size)", who, workspace_bytes, need));
+    if ((st = pass(check_workspace(who, workspace_bytes, need, "nus_bm_workspace_size"))) != kOk) return st;
     if (n_pairs == 0) return kOk;
     return enqueue(d_a, a_stride, d_b, b_stride, w, h, n_pairs, d_workspace, d_vectors, d_sad, d_flags, d_flow, flow_format, stream);
 }
@@ -232,12 +212,8 @@ int BlockMatcher::estimate_device(const void *d_a, size_t a_stride, const void *
 int BlockMatcher::check_host_frames(const char *who, const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, uint32_t w,
                                     uint32_t h)
 {
-    const int st = check_shape(who, w, h, 1);
-    if (st != kOk) return st;
-    const size_t expected = (size_t)w * h * 4;
-    if (a_len != expected || b_len != expected) // status and text of nus_interp_interpolate (wgpu_interpolator.rs:234-237)
-        return fail(kSizeMismatch, fmt("Expected %zu bytes per frame for %ux%ux4 RGBA, got frame_a: %zu bytes, frame_b: %zu bytes",
-                                       expected, w, h, a_len, b_len));
+    int st = check_shape(who, w, h, 1);
+    if (st != kOk || (st = pass(check_frame_lengths(a_len, b_len, w, h))) != kOk) return st; // as nus_interp_interpolate
     if (!a || !b) return fail(kInvalidArgument, fmt("%s: null frame pointer", who));
     return kOk;
 }
@@ -247,25 +223,8 @@ int BlockMatcher::ensure_host(size_t bytes)
     const int rc = ensure_tables();
     if (rc != kOk) return rc;
     if (!stream_) NUS_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-    if (arena_bytes_ < bytes) {
-        NUS_HIP(hipStreamSynchronize(stream_));
-        if (arena_) (void)hipFree(arena_);
-        arena_ = nullptr;
-        arena_bytes_ = 0;
-        NUS_HIP(hipMalloc(reinterpret_cast<void **>(&arena_), bytes));
-        arena_bytes_ = bytes;
-    }
-    return kOk;
+    return pass(arena_.reserve(bytes, stream_));
 }
-
-#define NUS_BM_TRY(call)                  \
-    do {                                  \
-        const int rc_ = (call);           \
-        if (rc_ != kOk) {                 \
-            error_ = thread_error();      \
-            return rc_;                   \
-        }                                 \
-    } while (0)
 
 int BlockMatcher::estimate(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, uint32_t w, uint32_t h, int16_t *vectors_out,
                            uint32_t *sad_out, uint8_t *flags_out)
@@ -281,14 +240,15 @@ int BlockMatcher::estimate(const uint8_t *a, size_t a_len, const uint8_t *b, siz
                  o_flags = o_sad + up16(nb * 4), total = o_flags + up16(nb);
     int rc = ensure_host(total);
     if (rc != kOk) return rc;
-    NUS_BM_TRY(upload(arena_, a, a_len, stream_));
-    NUS_BM_TRY(upload(arena_ + o_b, b, b_len, stream_));
-    rc = enqueue(arena_, a_len, arena_ + o_b, b_len, w, h, 1, arena_ + o_ws, arena_ + o_vec, arena_ + o_sad, arena_ + o_flags, nullptr, 0,
+    uint8_t *const arena = static_cast<uint8_t *>(arena_.get());
+    if ((rc = pass(upload(arena, a, a_len, stream_))) != kOk) return rc;
+    if ((rc = pass(upload(arena + o_b, b, b_len, stream_))) != kOk) return rc;
+    rc = enqueue(arena, a_len, arena + o_b, b_len, w, h, 1, arena + o_ws, arena + o_vec, arena + o_sad, arena + o_flags, nullptr, 0,
                  stream_);
     if (rc != kOk) return rc;
-    NUS_BM_TRY(download(vectors_out, arena_ + o_vec, nb * 4, stream_));
-    if (sad_out) NUS_BM_TRY(download(sad_out, arena_ + o_sad, nb * 4, stream_));
-    if (flags_out) NUS_BM_TRY(download(flags_out, arena_ + o_flags, nb, stream_));
+    if ((rc = pass(download(vectors_out, arena + o_vec, nb * 4, stream_))) != kOk) return rc;
+    if (sad_out && (rc = pass(download(sad_out, arena + o_sad, nb * 4, stream_))) != kOk) return rc;
+    if (flags_out && (rc = pass(download(flags_out, arena + o_flags, nb, stream_))) != kOk) return rc;
     return kOk;
 }
 
@@ -297,11 +257,10 @@ int BlockMatcher::interpolate(const uint8_t *a, size_t a_len, const uint8_t *b, 
 {
     static const char *const who = "nus_bm_interpolate";
     std::lock_guard<std::mutex> lk(mu_);
-    const int st = check_host_frames(who, a, a_len, b, b_len, w, h);
+    int st = check_host_frames(who, a, a_len, b, b_len, w, h);
     if (st != kOk) return st;
     if (!out) return fail(kInvalidArgument, fmt("%s: null frame pointer", who));
-    const std::string bad = check_interp_times(times, n_times);
-    if (!bad.empty()) return fail(kInvalidArgument, fmt("%s: %s", who, bad.c_str()));
+    if ((st = pass(check_interp_times(who, times, n_times))) != kOk) return st;
     if (mode != 0 && mode != 1) return fail(kInvalidArgument, fmt("%s: mode must be NUS_INTERP_MODE_EXACT or NUS_INTERP_MODE_FMA", who));
     const size_t expected = (size_t)w * h * 4;
     if (out_cap / n_times < expected)
@@ -315,28 +274,29 @@ int BlockMatcher::interpolate(const uint8_t *a, size_t a_len, const uint8_t *b, 
                  total = scene_ ? o_scene + scene_ws + 16 : out_end;
     int rc = ensure_host(total);
     if (rc != kOk) return rc;
-    NUS_BM_TRY(upload(arena_, a, a_len, stream_));
-    NUS_BM_TRY(upload(arena_ + o_b, b, b_len, stream_));
+    uint8_t *const arena = static_cast<uint8_t *>(arena_.get());
+    if ((rc = pass(upload(arena, a, a_len, stream_))) != kOk) return rc;
+    if ((rc = pass(upload(arena + o_b, b, b_len, stream_))) != kOk) return rc;
     SceneLaunch S; // detect -> estimate + warp as without detection -> a flagged pair's frames overwritten with repeats
-    S.a = arena_;
-    S.b = arena_ + o_b;
+    S.a = arena;
+    S.b = arena + o_b;
     S.a_stride = S.b_stride = expected;
     S.w = w, S.h = h, S.stream = stream_;
-    uint8_t *const cut = arena_ + o_scene + scene_ws;
+    uint8_t *const cut = arena + o_scene + scene_ws;
     if (scene_) {
-        const hipError_t es = launch_scene_detect(S, scene_mad_, scene_hist_, arena_ + o_scene, nullptr, cut);
+        const hipError_t es = launch_scene_detect(S, scene_mad_, scene_hist_, arena + o_scene, nullptr, cut);
         if (es != hipSuccess) return fail_hip(es, "scene-detect launch");
     }
     // estimate -> dense flow as 2 x f16 per pixel (the vectors are integers of magnitude <= 24: exact) -> multi-time warp
-    rc = enqueue(arena_, a_len, arena_ + o_b, b_len, w, h, 1, arena_ + o_ws, arena_ + o_vec, nullptr, nullptr, arena_ + o_flow, 1, stream_);
+    rc = enqueue(arena, a_len, arena + o_b, b_len, w, h, 1, arena + o_ws, arena + o_vec, nullptr, nullptr, arena + o_flow, 1, stream_);
     if (rc != kOk) return rc;
     WarpLaunch L;
-    L.a = arena_;
-    L.b = arena_ + o_b;
-    L.flow = reinterpret_cast<const float *>(arena_ + o_flow);
+    L.a = arena;
+    L.b = arena + o_b;
+    L.flow = reinterpret_cast<const float *>(arena + o_flow);
     L.flow_half = true;
     L.fma = mode == 1;
-    L.out = arena_ + o_out;
+    L.out = arena + o_out;
     L.a_stride = L.b_stride = expected;
     L.w = w;
     L.h = h;
@@ -347,11 +307,10 @@ int BlockMatcher::interpolate(const uint8_t *a, size_t a_len, const uint8_t *b, 
     const hipError_t e = launch_warp_blend(L);
     if (e != hipSuccess) return fail_hip(e, "multi-time warp+blend launch");
     if (scene_) {
-        const hipError_t es = launch_scene_apply(S, n_times, scene_from_a_mask(times, n_times), cut, arena_ + o_out, (size_t)n_times * expected);
+        const hipError_t es = launch_scene_apply(S, n_times, scene_from_a_mask(times, n_times), cut, arena + o_out, (size_t)n_times * expected);
         if (es != hipSuccess) return fail_hip(es, "scene-apply launch");
     }
-    NUS_BM_TRY(download(out, arena_ + o_out, (size_t)n_times * expected, stream_));
-    return kOk;
+    return pass(download(out, arena + o_out, (size_t)n_times * expected, stream_));
 }
 
 } // namespace nus

@@ -11,6 +11,8 @@
 #include <string>
 #include <vector>
 
+#include "nus_host_util.hpp"
+
 namespace nus {
 
 constexpr int kBmTiesScan = 0, kBmTiesCenter = 1; // nus_bm_tie_order
@@ -19,7 +21,7 @@ constexpr int kBmTiesScan = 0, kBmTiesCenter = 1; // nus_bm_tie_order
 // (cand[rank]).  Host only.
 void bm_rank_tables(uint32_t R, int order, std::vector<uint16_t> &rank, std::vector<uint16_t> &cand);
 
-class BlockMatcher {
+class BlockMatcher : public HostErrors {
 public:
     BlockMatcher() = default;
     ~BlockMatcher();
@@ -42,11 +44,8 @@ public:
                  uint32_t *sad_out, uint8_t *flags_out);
     int interpolate(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, uint32_t w, uint32_t h, const float *times,
                     uint32_t n_times, int mode, uint8_t *out, size_t out_cap);
-    const char *last_error() const { return error_.c_str(); }
 
 private:
-    int fail(int status, const std::string &msg);
-    int fail_hip(hipError_t e, const char *what);
     int check_shape(const char *who, uint32_t w, uint32_t h, uint32_t n_pairs);
     int check_host_frames(const char *who, const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, uint32_t w, uint32_t h);
     int ensure_tables();                 // first device use: the rank tables of every radius and both orders, once
@@ -61,11 +60,9 @@ private:
     bool refine_ = true;
     bool scene_ = false;
     uint32_t scene_mad_ = 20, scene_hist_ = 400;
-    std::string error_;
     uint16_t *d_tables_ = nullptr;
     hipStream_t stream_ = nullptr;
-    uint8_t *arena_ = nullptr;
-    size_t arena_bytes_ = 0;
+    DeviceBuffer arena_;
 };
 
 } // namespace nus

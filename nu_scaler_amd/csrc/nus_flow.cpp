@@ -14,46 +14,18 @@
 namespace nus {
 
 namespace {
-int device_count_()
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) {
-        (void)hipGetLastError();
-        return 0;
-    }
-    return n;
-}
+constexpr uint64_t kMaxPixels = (1ull << 28) - 1;
 } // namespace
-
-#define NUS_HIP(call)                                     \
-    do {                                                  \
-        hipError_t e_ = (call);                           \
-        if (e_ != hipSuccess) return fail_hip(e_, #call); \
-    } while (0)
 
 // The host entry points move their images through the library's own pinned ring (nus_transfer.hpp): a caller's pageable
 // buffer is never handed to the runtime's copy.
 #define NUS_XFER(call)                                        \
     do {                                                      \
-        const int x_ = (call);                                \
-        if (x_ != kOk) return fail(x_, thread_error());       \
+        const int x_ = pass(call);                            \
+        if (x_ != kOk) return x_;                             \
     } while (0)
 
 HipFlowEstimator::~HipFlowEstimator() { release(); }
-
-int HipFlowEstimator::fail(int status, const std::string &msg)
-{
-    error_ = msg;
-    set_thread_error(msg);
-    return status;
-}
-
-int HipFlowEstimator::fail_hip(hipError_t e, const char *what)
-{
-    (void)hipGetLastError();
-    return fail(e == hipErrorOutOfMemory ? kOutOfMemory : kHipError,
-                std::string("HIP error in ") + what + ": " + hipGetErrorString(e));
-}
 
 int HipFlowEstimator::set_tiled(int mode)
 {
@@ -83,7 +55,7 @@ int HipFlowEstimator::set_device(int device)
 
 int HipFlowEstimator::ensure_device()
 {
-    const int n = device_count_();
+    const int n = device_count();
     if (n <= 0) return fail(kNoDevice, "no HIP device available (the gfx950 path has no CPU fallback)");
     if (device_ >= n) return fail(kNoDevice, "requested HIP device not present");
     NUS_HIP(hipSetDevice(device_));
@@ -94,37 +66,20 @@ int HipFlowEstimator::ensure_device()
     return kOk;
 }
 
-int HipFlowEstimator::reserve(size_t bytes, int slot)
-{
-    if (bytes <= slot_cap_[slot]) return kOk;
-    if (slot_[slot]) {
-        NUS_HIP(hipStreamSynchronize(stream_));
-        NUS_HIP(hipFree(slot_[slot]));
-        slot_[slot] = nullptr;
-        slot_cap_[slot] = 0;
-    }
-    NUS_HIP(hipMalloc(&slot_[slot], bytes));
-    slot_cap_[slot] = bytes;
-    return kOk;
-}
+int HipFlowEstimator::reserve(size_t bytes, int slot) { return pass(slot_[slot].reserve(bytes, stream_)); }
 
 void HipFlowEstimator::release()
 {
     if (!ready_) return;
     (void)hipSetDevice(device_);
     (void)hipStreamSynchronize(stream_);
-    for (int i = 0; i < kSlotCount; ++i) {
-        if (slot_[i]) (void)hipFree(slot_[i]);
-        slot_[i] = nullptr;
-        slot_cap_[i] = 0;
-    }
+    for (DeviceBuffer &s : slot_) s.release();
     (void)hipStreamDestroy(stream_);
     ready_ = false;
 }
 
 #define CHECK_DIMS(w, h)                                                             \
-    if ((w) == 0 || (h) == 0 || (uint64_t)(w) * (h) >= (1ull << 28))                 \
-        return fail(kInvalidArgument, "flow: bad image dimensions");
+    if (pass(check_dims("flow", w, h, kMaxPixels, "bad image dimensions")) != kOk) return kInvalidArgument;
 
 int HipFlowEstimator::rgba8_to_f32(const uint8_t *in, uint32_t w, uint32_t h, float *out)
 {
@@ -135,9 +90,9 @@ int HipFlowEstimator::rgba8_to_f32(const uint8_t *in, uint32_t w, uint32_t h, fl
     if (rc != kOk) return rc;
     const size_t npx = (size_t)w * h;
     if ((rc = reserve(npx * 4, 0)) != kOk || (rc = reserve(npx * 16, 1)) != kOk) return rc;
-    NUS_XFER(upload(slot_[0], in, npx * 4, stream_));
-    NUS_HIP(launch_rgba8_to_f32(static_cast<const uint8_t *>(slot_[0]), static_cast<float *>(slot_[1]), w, h, stream_));
-    NUS_XFER(download(out, slot_[1], npx * 16, stream_));
+    NUS_XFER(upload(slot_[0].get(), in, npx * 4, stream_));
+    NUS_HIP(launch_rgba8_to_f32(static_cast<const uint8_t *>(slot_[0].get()), static_cast<float *>(slot_[1].get()), w, h, stream_));
+    NUS_XFER(download(out, slot_[1].get(), npx * 16, stream_));
     NUS_HIP(hipStreamSynchronize(stream_));
     return kOk;
 }
@@ -151,7 +106,7 @@ int HipFlowEstimator::blur(const float *in, uint32_t w, uint32_t h, float *out)
     if (rc != kOk) return rc;
     const size_t bytes = (size_t)w * h * 16;
     if ((rc = reserve(bytes, 0)) != kOk || (rc = reserve(bytes, 1)) != kOk) return rc;
-    float *d0 = static_cast<float *>(slot_[0]), *d1 = static_cast<float *>(slot_[1]);
+    float *d0 = static_cast<float *>(slot_[0].get()), *d1 = static_cast<float *>(slot_[1].get());
     NUS_XFER(upload(d0, in, bytes, stream_));
     NUS_HIP(launch_blur(d0, d1, w, h, true, stream_));
     NUS_HIP(launch_blur(d1, d0, w, h, false, stream_));
@@ -169,9 +124,9 @@ int HipFlowEstimator::downsample(const float *in, uint32_t w, uint32_t h, float 
     if (rc != kOk) return rc;
     const size_t bytes = (size_t)w * h * 16, obytes = (size_t)((w + 1) / 2) * ((h + 1) / 2) * 16;
     if ((rc = reserve(bytes, 0)) != kOk || (rc = reserve(obytes, 1)) != kOk) return rc;
-    NUS_XFER(upload(slot_[0], in, bytes, stream_));
-    NUS_HIP(launch_downsample(static_cast<const float *>(slot_[0]), static_cast<float *>(slot_[1]), w, h, stream_));
-    NUS_XFER(download(out, slot_[1], obytes, stream_));
+    NUS_XFER(upload(slot_[0].get(), in, bytes, stream_));
+    NUS_HIP(launch_downsample(static_cast<const float *>(slot_[0].get()), static_cast<float *>(slot_[1].get()), w, h, stream_));
+    NUS_XFER(download(out, slot_[1].get(), obytes, stream_));
     NUS_HIP(hipStreamSynchronize(stream_));
     return kOk;
 }
@@ -188,21 +143,21 @@ int HipFlowEstimator::horn_schunck(const float *i1, const float *i2, const float
     if ((rc = reserve(ib, 0)) != kOk || (rc = reserve(ib, 1)) != kOk || (rc = reserve(fb, 2)) != kOk ||
         (rc = reserve(fb, 3)) != kOk)
         return rc;
-    NUS_XFER(upload(slot_[0], i1, ib, stream_));
-    NUS_XFER(upload(slot_[1], i2, ib, stream_));
+    NUS_XFER(upload(slot_[0].get(), i1, ib, stream_));
+    NUS_XFER(upload(slot_[1].get(), i2, ib, stream_));
     if (flow_in)
-        NUS_XFER(upload(slot_[2], flow_in, fb, stream_));
+        NUS_XFER(upload(slot_[2].get(), flow_in, fb, stream_));
     else
-        NUS_HIP(hipMemsetAsync(slot_[2], 0, fb, stream_)); // compute_coarse_flow clears the flow (:1136-1154)
-    float *f0 = static_cast<float *>(slot_[2]), *f1 = static_cast<float *>(slot_[3]);
+        NUS_HIP(hipMemsetAsync(slot_[2].get(), 0, fb, stream_)); // compute_coarse_flow clears the flow (:1136-1154)
+    float *f0 = static_cast<float *>(slot_[2].get()), *f1 = static_cast<float *>(slot_[3].get());
     if (tiled_) {
         if ((rc = reserve(ib, 4)) != kOk) return rc; // 3 floats of coefficients per cell
-        float *coef = static_cast<float *>(slot_[4]);
-        NUS_HIP(launch_hs_prepare(static_cast<const float *>(slot_[0]), static_cast<const float *>(slot_[1]), false, coef, w, h, stream_));
+        float *coef = static_cast<float *>(slot_[4].get());
+        NUS_HIP(launch_hs_prepare(static_cast<const float *>(slot_[0].get()), static_cast<const float *>(slot_[1].get()), false, coef, w, h, stream_));
         NUS_HIP(launch_hs_iterate(coef, lambda, &f0, &f1, w, h, iterations, false, nullptr, stream_, 1, 0, 0, 0, jacobi_));
     } else {
         for (uint32_t i = 0; i < iterations; ++i) { // ping-pong as :1156-1193
-            NUS_HIP(launch_horn_schunck(static_cast<const float *>(slot_[0]), static_cast<const float *>(slot_[1]), f0, f1, w, h, lambda, stream_));
+            NUS_HIP(launch_horn_schunck(static_cast<const float *>(slot_[0].get()), static_cast<const float *>(slot_[1].get()), f0, f1, w, h, lambda, stream_));
             float *t = f0;
             f0 = f1;
             f1 = t;
@@ -223,9 +178,9 @@ int HipFlowEstimator::upsample(const float *src, uint32_t sw, uint32_t sh, float
     if (rc != kOk) return rc;
     const size_t sb = (size_t)sw * sh * 8, db = (size_t)dw * dh * 8;
     if ((rc = reserve(sb, 2)) != kOk || (rc = reserve(db, 3)) != kOk) return rc;
-    NUS_XFER(upload(slot_[2], src, sb, stream_));
-    NUS_HIP(launch_flow_upsample(static_cast<const float *>(slot_[2]), sw, sh, static_cast<float *>(slot_[3]), dw, dh, scale, stream_));
-    NUS_XFER(download(dst, slot_[3], db, stream_));
+    NUS_XFER(upload(slot_[2].get(), src, sb, stream_));
+    NUS_HIP(launch_flow_upsample(static_cast<const float *>(slot_[2].get()), sw, sh, static_cast<float *>(slot_[3].get()), dw, dh, scale, stream_));
+    NUS_XFER(download(dst, slot_[3].get(), db, stream_));
     NUS_HIP(hipStreamSynchronize(stream_));
     return kOk;
 }
@@ -262,8 +217,8 @@ int HipFlowEstimator::plan(uint32_t w, uint32_t h, uint32_t levels, Pyramid &g)
 // Pyramid of one RGBA8 frame into slot `pyr_slot` (4 or 5).
 int HipFlowEstimator::build_pyramid(const void *frame, int pyr_slot, const Pyramid &g, hipStream_t stream)
 {
-    float *cur = static_cast<float *>(slot_[0]), *tmp = static_cast<float *>(slot_[1]);
-    uint8_t *pyr = static_cast<uint8_t *>(slot_[pyr_slot]);
+    float *cur = static_cast<float *>(slot_[0].get()), *tmp = static_cast<float *>(slot_[1].get());
+    uint8_t *pyr = static_cast<uint8_t *>(slot_[pyr_slot].get());
     if (tiled_) {
         // fused level kernel: writes the level's luminance plane (at the level's offset; the
         // f32 RGBA level itself is not needed) and the downsampled input of level l+1, which
@@ -293,9 +248,9 @@ int HipFlowEstimator::solve(int slot_a, int slot_b, const Pyramid &g, uint32_t c
                             float lambda, void *d_flow_out, hipStream_t stream)
 {
     int rc;
-    const uint8_t *pa = static_cast<const uint8_t *>(slot_[slot_a]), *pb = static_cast<const uint8_t *>(slot_[slot_b]);
-    float *f0 = static_cast<float *>(slot_[2]), *f1 = static_cast<float *>(slot_[3]);
-    float *coef = static_cast<float *>(slot_[1]); // the blur temp is free once the pyramids exist
+    const uint8_t *pa = static_cast<const uint8_t *>(slot_[slot_a].get()), *pb = static_cast<const uint8_t *>(slot_[slot_b].get());
+    float *f0 = static_cast<float *>(slot_[2].get()), *f1 = static_cast<float *>(slot_[3].get());
+    float *coef = static_cast<float *>(slot_[1].get()); // the blur temp is free once the pyramids exist
     const uint32_t L = g.levels - 1;
     // compute_coarse_flow starts from zero flow (:1136-1154): the tiled kernel takes that as a null input;
     // the last launch of the finest level writes the caller's buffer directly
@@ -357,7 +312,7 @@ int HipFlowEstimator::estimate_device(const void *d_a, const void *d_b, uint32_t
     if (fast_ && (jacobi_ == kJacobiStream || (jacobi_ == kJacobiAuto && hs_iterate_streams(g.w[0], g.h[0], 1, kJacobiAuto)))) {
         const size_t fb = (size_t)w * h * 4;
         if ((rc = reserve(2 * fb, 8)) != kOk) return rc;
-        uint8_t *two = static_cast<uint8_t *>(slot_[8]);
+        uint8_t *two = static_cast<uint8_t *>(slot_[8].get());
         NUS_HIP(hipMemcpyAsync(two, d_a, fb, hipMemcpyDeviceToDevice, stream));
         NUS_HIP(hipMemcpyAsync(two + fb, d_b, fb, hipMemcpyDeviceToDevice, stream));
         return solve_batch(two, 1, g, coarse_iters, refine_iters, lambda, static_cast<uint8_t *>(d_flow_out), stream);
@@ -386,7 +341,7 @@ int HipFlowEstimator::interpolate_device_stream(const void *d_frames, uint32_t n
     std::lock_guard<std::mutex> lk(mu_);
     if (!d_mid) return fail(kInvalidArgument, "flow: null device pointer");
     if (!(t >= 0.0f && t <= 1.0f)) return fail(kInvalidArgument, "flow: t must be in [0, 1]");
-    if ((reinterpret_cast<uintptr_t>(d_mid) % 16) || (reinterpret_cast<uintptr_t>(d_flows) % 16))
+    if (misaligned(d_mid, 16) || misaligned(d_flows, 16))
         return fail(kInvalidArgument, "flow: device pointers must be 16-byte aligned");
     return stream_impl(d_frames, n_frames, w, h, levels, coarse_iters, refine_iters, lambda, d_flows, d_mid, t, stream, flow_half);
 }
@@ -398,13 +353,12 @@ int HipFlowEstimator::interpolate_multi_device_stream(const void *d_frames, uint
 {
     static const char *const who = "nus_flow_interpolate_multi_device_stream";
     std::lock_guard<std::mutex> lk(mu_);
-    if (w == 0 || h == 0 || (uint64_t)w * h >= (1ull << 28)) return fail(kInvalidArgument, std::string(who) + ": bad image dimensions");
+    int rc = pass(check_dims(who, w, h, kMaxPixels, "bad image dimensions"));
+    if (rc != kOk) return rc;
     if (!d_frames || !d_mid) return fail(kInvalidArgument, std::string(who) + ": null device pointer");
     if (n_frames < 2) return fail(kInvalidArgument, std::string(who) + ": a stream needs at least 2 frames");
-    const std::string bad = check_interp_times(times, n_times);
-    if (!bad.empty()) return fail(kInvalidArgument, std::string(who) + ": " + bad);
-    if ((reinterpret_cast<uintptr_t>(d_mid) % 16) || (reinterpret_cast<uintptr_t>(d_flows) % 16) ||
-        (reinterpret_cast<uintptr_t>(d_frames) % 4))
+    if ((rc = pass(check_interp_times(who, times, n_times))) != kOk) return rc;
+    if (misaligned(d_mid, 16) || misaligned(d_flows, 16) || misaligned(d_frames, 4))
         return fail(kInvalidArgument, std::string(who) + ": d_mid and d_flows must be 16-byte aligned, d_frames 4-byte aligned");
     const size_t frame_bytes = (size_t)w * h * 4;
     if (mid_pair_stride != 0 && (mid_pair_stride < n_times * frame_bytes || mid_pair_stride % 4))
@@ -421,17 +375,17 @@ int HipFlowEstimator::interpolate_multi_device_stream(const void *d_frames, uint
     const uint32_t n_pairs = n_frames - 1;
     const std::string too_many = check_scene_launch(w, h, n_pairs);
     if (!too_many.empty()) return fail(kInvalidArgument, std::string(who) + ": " + too_many);
-    int rc = stream_impl(d_frames, n_frames, w, h, levels, coarse_iters, refine_iters, lambda, d_flows, d_mid, times[0], stream, flow_half, &mt);
+    rc = stream_impl(d_frames, n_frames, w, h, levels, coarse_iters, refine_iters, lambda, d_flows, d_mid, times[0], stream, flow_half, &mt);
     if (rc != kOk) return rc;
     const size_t ws_bytes = scene_shape(w, h, n_pairs).workspace_bytes;
     if ((rc = reserve(ws_bytes + n_pairs, 11)) != kOk) return rc;
-    uint8_t *cut = static_cast<uint8_t *>(slot_[11]) + ws_bytes;
+    uint8_t *cut = static_cast<uint8_t *>(slot_[11].get()) + ws_bytes;
     SceneLaunch S;
     S.a = static_cast<const uint8_t *>(d_frames);
     S.b = S.a + frame_bytes;
     S.a_stride = S.b_stride = frame_bytes;
     S.w = w, S.h = h, S.n_pairs = n_pairs, S.stream = stream;
-    NUS_HIP(launch_scene_detect(S, scene_mad_, scene_hist_, slot_[11], nullptr, cut));
+    NUS_HIP(launch_scene_detect(S, scene_mad_, scene_hist_, slot_[11].get(), nullptr, cut));
     NUS_HIP(launch_scene_apply(S, n_times, scene_from_a_mask(times, n_times), cut, static_cast<uint8_t *>(d_mid), mt.pair_stride));
     return kOk;
 }
@@ -489,10 +443,10 @@ int HipFlowEstimator::stream_impl(const void *d_frames, uint32_t n_frames, uint3
         for (uint32_t k = 0; k + 1 < n_frames; ++k) {
             const int slot_a = 4 + (int)(k & 1), slot_b = 5 - (int)(k & 1);
             if ((rc = build_pyramid(frames + (size_t)(k + 1) * frame_bytes, slot_b, g, stream)) != kOk) return rc;
-            void *fl = flows && !flow_half ? static_cast<void *>(flows + (size_t)k * flow_bytes) : slot_[9];
+            void *fl = flows && !flow_half ? static_cast<void *>(flows + (size_t)k * flow_bytes) : slot_[9].get();
             if ((rc = solve(slot_a, slot_b, g, coarse_iters, refine_iters, lambda, fl, stream)) != kOk) return rc;
             if (flow_half) {
-                void *hf = flows ? static_cast<void *>(flows + (size_t)k * flow_bytes) : slot_[10];
+                void *hf = flows ? static_cast<void *>(flows + (size_t)k * flow_bytes) : slot_[10].get();
                 NUS_HIP(launch_flow_to_half(static_cast<const float *>(fl), hf, (size_t)w * h, stream));
                 fl = hf;
             }
@@ -571,9 +525,9 @@ int HipFlowEstimator::solve_batch(const uint8_t *d_frames, uint32_t pairs, const
     for (uint32_t l = 0; l < nl; ++l)
         if (!from_planes(l) && cells[l] > coef_cells) coef_cells = cells[l];
     if (coef_cells != 0 && (rc = reserve(coef_cells * pairs * 12, 5)) != kOk) return rc;
-    float *level_in[2] = {static_cast<float *>(slot_[0]), static_cast<float *>(slot_[1])}; // input of level l: [(l - 1) & 1]
-    float *lum = static_cast<float *>(slot_[4]), *coef = static_cast<float *>(slot_[5]);
-    float *f0 = static_cast<float *>(slot_[2]), *f1 = static_cast<float *>(slot_[3]);
+    float *level_in[2] = {static_cast<float *>(slot_[0].get()), static_cast<float *>(slot_[1].get())}; // input of level l: [(l - 1) & 1]
+    float *lum = static_cast<float *>(slot_[4].get()), *coef = static_cast<float *>(slot_[5].get());
+    float *f0 = static_cast<float *>(slot_[2].get()), *f1 = static_cast<float *>(slot_[3].get());
     // pyramids of all frames, level by level
     for (uint32_t l = 0; l < nl; ++l) {
         const void *src = l == 0 ? static_cast<const void *>(d_frames) : level_in[(l - 1) & 1];
@@ -648,7 +602,7 @@ int HipFlowEstimator::solve_batch(const uint8_t *d_frames, uint32_t pairs, const
         void *dst = out;
         if (!dst) {
             if ((rc = reserve(cells[0] * pairs * 4, 10)) != kOk) return rc;
-            dst = slot_[10];
+            dst = slot_[10].get();
         }
         NUS_HIP(launch_flow_to_half(f0, dst, cells[0] * pairs, stream));
         final_flow = dst;
@@ -680,15 +634,15 @@ int HipFlowEstimator::estimate(const uint8_t *a, const uint8_t *b, uint32_t w, u
         if (rc != kOk) return rc;
         const size_t fbytes = (size_t)w * h * 4;
         if ((rc = reserve(fbytes, 6)) != kOk || (rc = reserve(fbytes > (size_t)w * h * 8 ? fbytes : (size_t)w * h * 8, 7)) != kOk) return rc;
-        NUS_XFER(upload(slot_[6], a, fbytes, stream_));
-        NUS_XFER(upload(slot_[7], b, fbytes, stream_));
+        NUS_XFER(upload(slot_[6].get(), a, fbytes, stream_));
+        NUS_XFER(upload(slot_[7].get(), b, fbytes, stream_));
     }
     // slot 7 doubles as the flow output once frame B has been converted (estimate_device copies
     // into it last, after every reader of frame B has been enqueued on the same stream)
-    int rc = estimate_device(slot_[6], slot_[7], w, h, levels, coarse_iters, refine_iters, lambda, slot_[7], stream_);
+    int rc = estimate_device(slot_[6].get(), slot_[7].get(), w, h, levels, coarse_iters, refine_iters, lambda, slot_[7].get(), stream_);
     if (rc != kOk) return rc;
     std::lock_guard<std::mutex> lk(mu_);
-    NUS_XFER(download(flow_out, slot_[7], (size_t)w * h * 8, stream_));
+    NUS_XFER(download(flow_out, slot_[7].get(), (size_t)w * h * 8, stream_));
     NUS_HIP(hipStreamSynchronize(stream_));
     return kOk;
 }

@@ -11,9 +11,11 @@
 #include <string>
 #include <vector>
 
+#include "nus_host_util.hpp"
+
 namespace nus {
 
-class HipFlowEstimator {
+class HipFlowEstimator : public HostErrors {
 public:
     HipFlowEstimator() = default;
     ~HipFlowEstimator();
@@ -24,7 +26,6 @@ public:
     // true (default): derivatives once per level + K Jacobi steps per launch in LDS; false: one
     // plain kernel per step (the shader's structure).  Bit-identical results.
     int set_tiled(int mode); // 0 plain per-step kernel, 1 multi-step kernel chosen by size, 2 LDS tiles, 3 streamed
-    const char *last_error() const { return error_.c_str(); }
 
     // Primitives on host buffers (parity tests, integration).  f32 RGBA images, float2 flows.
     int rgba8_to_f32(const uint8_t *in, uint32_t w, uint32_t h, float *out);
@@ -94,8 +95,6 @@ private:
     int solve_batch(const uint8_t *d_frames, uint32_t pairs, const Pyramid &g, uint32_t coarse_iters, uint32_t refine_iters,
                     float lambda, uint8_t *d_flows, hipStream_t stream, uint8_t *d_mid = nullptr, float t = 0.5f,
                     bool flow_half = false, const MidTimes *mt = nullptr);
-    int fail(int status, const std::string &msg);
-    int fail_hip(hipError_t e, const char *what);
     int ensure_device();
     int reserve(size_t bytes, int slot); // grow-only device scratch slots
     void release();
@@ -110,9 +109,7 @@ private:
     bool scene_ = false; // set_scene_detect
     uint32_t scene_mad_ = 20, scene_hist_ = 400;
     static constexpr int kSlotCount = 12; // 0-5 pyramids / flows / planes, 6-7 the host entry point's frames, 8 the FAST pair, 9 one pair's flow, 10 a chunk's flows as f16, 11 the scene detector's workspace and flags
-    void *slot_[kSlotCount] = {nullptr};
-    size_t slot_cap_[kSlotCount] = {0};
-    std::string error_;
+    DeviceBuffer slot_[kSlotCount];
 };
 
 } // namespace nus

@@ -14,13 +14,6 @@
 
 namespace nus {
 
-namespace {
-thread_local std::string g_thread_error;
-} // namespace
-
-void set_thread_error(const std::string &msg) { g_thread_error = msg; }
-const char *thread_error() { return g_thread_error.c_str(); }
-
 // ---------------------------------------------------------------------------------
 // HipUpscaler
 // ---------------------------------------------------------------------------------
@@ -28,20 +21,6 @@ const char *thread_error() { return g_thread_error.c_str(); }
 HipUpscaler::HipUpscaler(Quality q, Algorithm a) : quality_(q), algorithm_(a) {}
 
 HipUpscaler::~HipUpscaler() { release(); }
-
-int HipUpscaler::fail(int status, const std::string &msg)
-{
-    error_ = msg;
-    set_thread_error(msg);
-    return status;
-}
-
-int HipUpscaler::fail_hip(hipError_t e, const char *what)
-{
-    (void)hipGetLastError();
-    return fail(e == hipErrorOutOfMemory ? kOutOfMemory : kHipError,
-                fmt("HIP error in %s: %s", what, hipGetErrorString(e)));
-}
 
 const char *HipUpscaler::name() const
 {
@@ -233,15 +212,7 @@ float HipUpscaler::rcas_sharpness() const
     }
 }
 
-int HipUpscaler::ensure_device()
-{
-    const int n = device_count();
-    if (n <= 0)
-        return fail(kNoDevice, "no HIP device available (the gfx950 path has no CPU fallback)");
-    if (device_ >= n) return fail(kNoDevice, fmt("HIP device %d requested but only %d present", device_, n));
-    NUS_HIP(hipSetDevice(device_));
-    return kOk;
-}
+int HipUpscaler::ensure_device() { return select_device(device_); }
 
 void HipUpscaler::release()
 {

@@ -23,28 +23,14 @@
 
 #include "nus_kernels.hpp"
 #include "nus_copy.hpp"
+#include "nus_host_util.hpp"
 #include "nus_tables.hpp"
 
 namespace nus {
 
-// nus_status values (kept in sync with include/nuscaler_hip.h).
-enum Status : int {
-    kOk = 0,
-    kInvalidArgument = -1,
-    kNotInitialized = -2,
-    kSizeMismatch = -3,
-    kHipError = -4,
-    kNoDevice = -5,
-    kUnsupported = -6,
-    kOutOfMemory = -7,
-};
-
 enum class Algorithm : int { Nearest = 0, Bilinear = 1, Lanczos3 = 2, Bicubic = 3, Triangle = 4, Fsr1 = 5, FsrEasu = 6, FsrRcas = 7 };
 enum class Quality : int { UltraPerformance = 0, Ultra, Quality, Balanced, Performance, Native };
 enum class Technology : int { None = 0, FSR, DLSS, Wgpu, Fallback };
-
-void set_thread_error(const std::string &msg);
-const char *thread_error();
 
 // trait Upscaler (upscale/mod.rs:67-88).  Result<()> becomes a Status + last_error().
 class Upscaler {
@@ -58,7 +44,7 @@ public:
     virtual const char *last_error() const = 0;
 };
 
-class HipUpscaler final : public Upscaler {
+class HipUpscaler final : public Upscaler, protected HostErrors {
 public:
     HipUpscaler(Quality q, Algorithm a);
     ~HipUpscaler() override;
@@ -174,8 +160,6 @@ private:
     hipEvent_t ev_fork_ = nullptr, ev_join_ = nullptr;
     int edge_stream_ = 1;
 
-    int fail(int status, const std::string &msg);
-    int fail_hip(hipError_t e, const char *what);
     int ensure_device();
     int ensure_streams();
     int ensure_slot(Slot &s, size_t in_bytes, size_t out_bytes);
@@ -269,7 +253,6 @@ private:
     bool profiling_ = false;
     std::vector<hipEvent_t> prof_events_; // begin/end pairs
     size_t prof_used_ = 0;                // events handed out since the last collect
-    std::string error_;
 };
 
 // UpscalerFactory::create_upscaler (upscale/mod.rs:95-117).
@@ -298,7 +281,7 @@ public:
     virtual const char *last_error() const = 0;
 };
 
-class HipFrameInterpolator final : public FrameInterpolator {
+class HipFrameInterpolator final : public FrameInterpolator, protected HostErrors {
 public:
     explicit HipFrameInterpolator(int wg_preset);
     ~HipFrameInterpolator() override;
@@ -340,14 +323,19 @@ public:
     int wg_preset() const { return wg_preset_; }
 
 private:
-    int fail(int status, const std::string &msg);
-    int fail_hip(hipError_t e, const char *what);
     int ensure(size_t frame_bytes, bool with_flow, uint32_t n_out = 1);
     void release();
     // (mu_ held, arguments checked) stage and upload the pair, run one launch of the frames at `t` or at times[0 .. n_times), bring
     // the n frames back into `out`
     int host_pass(const uint8_t *a, const uint8_t *b, const float *flow, uint32_t w, uint32_t h, float t, const float *times,
                   uint32_t n_times, uint8_t *out);
+    // the host entry points: lock, the checks they share (times == nullptr: the single-time form), host_pass
+    int host_call(const char *who, const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, const float *flow, uint32_t w,
+                  uint32_t h, float t, const float *times, uint32_t n_times, bool multi, uint8_t *out, size_t out_cap);
+    // the device entry points: lock, the checks they share, one launch
+    int device_call(const char *who, const void *d_a, size_t a_stride, const void *d_b, size_t b_stride, const void *d_flow, uint32_t w,
+                    uint32_t h, float t, const float *times, uint32_t n_times, bool multi, void *d_out, size_t out_pair_stride,
+                    uint32_t n_pairs, hipStream_t stream);
 
     mutable std::mutex mu_;
     int wg_preset_;
@@ -369,7 +357,6 @@ private:
     hipEvent_t k_begin_ = nullptr, k_end_ = nullptr, half_done_ = nullptr;
     bool have_ms_ = false;
     double last_ms_ = 0.0;
-    std::string error_;
 };
 
 } // namespace nus

@@ -13,6 +13,10 @@ namespace nus {
 // HipFrameInterpolator
 // ---------------------------------------------------------------------------------
 
+namespace {
+constexpr uint64_t kMaxPixels = (1ull << 31) - 1;
+} // namespace
+
 HipFrameInterpolator::HipFrameInterpolator(int wg_preset) : wg_preset_(wg_preset) {}
 
 HipFrameInterpolator::~HipFrameInterpolator()
@@ -24,20 +28,6 @@ HipFrameInterpolator::~HipFrameInterpolator()
         if (half_done_) (void)hipEventDestroy(half_done_);
         if (stream_) (void)hipStreamDestroy(stream_);
     }
-}
-
-int HipFrameInterpolator::fail(int status, const std::string &msg)
-{
-    error_ = msg;
-    set_thread_error(msg);
-    return status;
-}
-
-int HipFrameInterpolator::fail_hip(hipError_t e, const char *what)
-{
-    (void)hipGetLastError();
-    return fail(e == hipErrorOutOfMemory ? kOutOfMemory : kHipError,
-                fmt("HIP error in %s: %s", what, hipGetErrorString(e)));
 }
 
 int HipFrameInterpolator::set_device(int device)
@@ -72,10 +62,8 @@ void HipFrameInterpolator::release()
 int HipFrameInterpolator::ensure(size_t frame_bytes, bool with_flow, uint32_t n_out)
 {
     if (!device_ready_) {
-        const int n = device_count();
-        if (n <= 0) return fail(kNoDevice, "no HIP device available (the gfx950 path has no CPU fallback)");
-        if (device_ >= n) return fail(kNoDevice, fmt("HIP device %d requested but only %d present", device_, n));
-        NUS_HIP(hipSetDevice(device_));
+        const int rc = select_device(device_);
+        if (rc != kOk) return rc;
         NUS_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
         NUS_HIP(hipEventCreate(&k_begin_));
         NUS_HIP(hipEventCreate(&k_end_));
@@ -108,10 +96,10 @@ int HipFrameInterpolator::ensure(size_t frame_bytes, bool with_flow, uint32_t n_
 int HipFrameInterpolator::initialize(uint32_t width, uint32_t height)
 {
     std::lock_guard<std::mutex> lk(mu_);
-    if (width == 0 || height == 0 || (uint64_t)width * height >= (1ull << 31))
-        return fail(kInvalidArgument, "initialize: bad dimensions");
+    int rc = pass(check_dims("initialize", width, height, kMaxPixels));
+    if (rc != kOk) return rc;
     if (init_w_ == width && init_h_ == height) return kOk; // interpolation/mod.rs:306-308
-    const int rc = ensure((size_t)width * height * 4, false);
+    rc = ensure((size_t)width * height * 4, false);
     if (rc != kOk) return rc;
     init_w_ = width;
     init_h_ = height;
@@ -144,34 +132,32 @@ int HipFrameInterpolator::set_quality(InterpolationQuality q)
 int HipFrameInterpolator::interpolate(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, const float *flow,
                                       uint32_t w, uint32_t h, float t, uint8_t *out, size_t out_cap)
 {
-    std::lock_guard<std::mutex> lk(mu_);
-    if (w == 0 || h == 0 || (uint64_t)w * h >= (1ull << 31)) return fail(kInvalidArgument, "interpolate: bad dimensions");
-    const size_t expected = (size_t)w * h * 4;
-    if (a_len != expected || b_len != expected)
-        // wgpu_interpolator.rs:234-237
-        return fail(kSizeMismatch, fmt("Expected %zu bytes per frame for %ux%ux4 RGBA, got frame_a: %zu bytes, frame_b: %zu bytes",
-                                       expected, w, h, a_len, b_len));
-    if (!a || !b || !out) return fail(kInvalidArgument, "interpolate: null frame pointer");
-    if (out_cap < expected) return fail(kInvalidArgument, "interpolate: output capacity too small");
-    return host_pass(a, b, flow, w, h, t, nullptr, 0, out);
+    return host_call("interpolate", a, a_len, b, b_len, flow, w, h, t, nullptr, 0, false, out, out_cap);
 }
 
 int HipFrameInterpolator::interpolate_multi(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, const float *flow,
                                             uint32_t w, uint32_t h, const float *times, uint32_t n_times, uint8_t *out, size_t out_cap)
 {
+    return host_call("nus_interp_interpolate_multi", a, a_len, b, b_len, flow, w, h, 0.0f, times, n_times, true, out, out_cap);
+}
+
+int HipFrameInterpolator::host_call(const char *who, const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, const float *flow,
+                                    uint32_t w, uint32_t h, float t, const float *times, uint32_t n_times, bool multi, uint8_t *out,
+                                    size_t out_cap)
+{
     std::lock_guard<std::mutex> lk(mu_);
-    if (w == 0 || h == 0 || (uint64_t)w * h >= (1ull << 31)) return fail(kInvalidArgument, "nus_interp_interpolate_multi: bad dimensions");
+    int st = pass(check_dims(who, w, h, kMaxPixels));
+    if (st != kOk || (st = pass(check_frame_lengths(a_len, b_len, w, h))) != kOk) return st;
+    if (!a || !b || !out) return fail(kInvalidArgument, fmt("%s: null frame pointer", who));
     const size_t expected = (size_t)w * h * 4;
-    if (a_len != expected || b_len != expected) // the text of nus_interp_interpolate (wgpu_interpolator.rs:234-237)
-        return fail(kSizeMismatch, fmt("Expected %zu bytes per frame for %ux%ux4 RGBA, got frame_a: %zu bytes, frame_b: %zu bytes",
-                                       expected, w, h, a_len, b_len));
-    if (!a || !b || !out) return fail(kInvalidArgument, "nus_interp_interpolate_multi: null frame pointer");
-    const std::string bad = check_interp_times(times, n_times);
-    if (!bad.empty()) return fail(kInvalidArgument, "nus_interp_interpolate_multi: " + bad);
-    if (out_cap / n_times < expected)
-        return fail(kInvalidArgument, fmt("nus_interp_interpolate_multi: output capacity %zu below n_times * w * h * 4 = %zu", out_cap,
-                                          (size_t)n_times * expected));
-    return host_pass(a, b, flow, w, h, 0.0f, times, n_times, out);
+    if (!multi) {
+        if (out_cap < expected) return fail(kInvalidArgument, fmt("%s: output capacity too small", who));
+    } else {
+        if ((st = pass(check_interp_times(who, times, n_times))) != kOk) return st;
+        if (out_cap / n_times < expected)
+            return fail(kInvalidArgument, fmt("%s: output capacity %zu below n_times * w * h * 4 = %zu", who, out_cap, (size_t)n_times * expected));
+    }
+    return host_pass(a, b, flow, w, h, t, times, n_times, out);
 }
 
 int HipFrameInterpolator::host_pass(const uint8_t *a, const uint8_t *b, const float *flow, uint32_t w, uint32_t h, float t,
@@ -241,16 +227,31 @@ int HipFrameInterpolator::interpolate_device(const void *d_a, size_t a_stride, c
                                              const void *d_flow, uint32_t w, uint32_t h, float t, void *d_out,
                                              uint32_t n_pairs, hipStream_t stream)
 {
+    return device_call("interpolate_device", d_a, a_stride, d_b, b_stride, d_flow, w, h, t, nullptr, 0, false, d_out, 0, n_pairs, stream);
+}
+
+int HipFrameInterpolator::interpolate_multi_device(const void *d_a, size_t a_stride, const void *d_b, size_t b_stride,
+                                                   const void *d_flow, uint32_t w, uint32_t h, const float *times, uint32_t n_times,
+                                                   void *d_out, size_t out_pair_stride, uint32_t n_pairs, hipStream_t stream)
+{
+    return device_call("nus_interp_interpolate_multi_device", d_a, a_stride, d_b, b_stride, d_flow, w, h, 0.5f, times, n_times, true, d_out,
+                       out_pair_stride, n_pairs, stream);
+}
+
+int HipFrameInterpolator::device_call(const char *who, const void *d_a, size_t a_stride, const void *d_b, size_t b_stride,
+                                      const void *d_flow, uint32_t w, uint32_t h, float t, const float *times, uint32_t n_times, bool multi,
+                                      void *d_out, size_t out_pair_stride, uint32_t n_pairs, hipStream_t stream)
+{
     std::lock_guard<std::mutex> lk(mu_);
-    if (w == 0 || h == 0 || (uint64_t)w * h >= (1ull << 31)) return fail(kInvalidArgument, "interpolate_device: bad dimensions");
-    if (!d_a || !d_b || !d_out) return fail(kInvalidArgument, "interpolate_device: null device pointer");
+    int st = pass(check_dims(who, w, h, kMaxPixels));
+    if (st != kOk) return st;
+    if (!d_a || !d_b || !d_out) return fail(kInvalidArgument, fmt("%s: null device pointer", who));
+    if (multi && (st = pass(check_interp_times(who, times, n_times))) != kOk) return st;
+    if (!multi && n_pairs == 0) return kOk; // (the single-time form has always answered this before it looks at the alignment)
+    if ((st = pass(check_pixel_aligned(who, d_a, a_stride, d_b, b_stride, d_out, d_flow, flow_half_ ? 4 : 8))) != kOk) return st;
+    if (multi && (st = pass(check_out_pair_stride(who, out_pair_stride, n_times, (size_t)w * h * 4))) != kOk) return st;
     if (n_pairs == 0) return kOk;
-    if ((reinterpret_cast<uintptr_t>(d_a) % 4) || (reinterpret_cast<uintptr_t>(d_b) % 4) ||
-        (reinterpret_cast<uintptr_t>(d_out) % 4) || (a_stride % 4) || (b_stride % 4) ||
-        (d_flow && reinterpret_cast<uintptr_t>(d_flow) % (flow_half_ ? 4 : 8)))
-        return fail(kInvalidArgument, "interpolate_device: pointers/strides must be pixel aligned");
-    const int n = device_count();
-    if (n <= 0) return fail(kNoDevice, "no HIP device available (the gfx950 path has no CPU fallback)");
+    if (device_count() <= 0) return fail(kNoDevice, "no HIP device available (the gfx950 path has no CPU fallback)");
     NUS_HIP(hipSetDevice(device_));
     WarpLaunch L;
     L.a = static_cast<const uint8_t *>(d_a);
@@ -264,55 +265,14 @@ int HipFrameInterpolator::interpolate_device(const void *d_a, size_t a_stride, c
     L.w = w;
     L.h = h;
     L.t = t;
-    L.n_pairs = n_pairs;
-    L.stream = stream;
-    L.in_sel = input_selector(in_format_);
-    hipError_t e = launch_warp_blend(L);
-    if (e != hipSuccess) return fail_hip(e, "warp+blend launch");
-    return kOk;
-}
-
-int HipFrameInterpolator::interpolate_multi_device(const void *d_a, size_t a_stride, const void *d_b, size_t b_stride,
-                                                   const void *d_flow, uint32_t w, uint32_t h, const float *times, uint32_t n_times,
-                                                   void *d_out, size_t out_pair_stride, uint32_t n_pairs, hipStream_t stream)
-{
-    static const char *const who = "nus_interp_interpolate_multi_device";
-    std::lock_guard<std::mutex> lk(mu_);
-    if (w == 0 || h == 0 || (uint64_t)w * h >= (1ull << 31)) return fail(kInvalidArgument, fmt("%s: bad dimensions", who));
-    if (!d_a || !d_b || !d_out) return fail(kInvalidArgument, fmt("%s: null device pointer", who));
-    const std::string bad = check_interp_times(times, n_times);
-    if (!bad.empty()) return fail(kInvalidArgument, fmt("%s: %s", who, bad.c_str()));
-    if ((reinterpret_cast<uintptr_t>(d_a) % 4) || (reinterpret_cast<uintptr_t>(d_b) % 4) ||
-        (reinterpret_cast<uintptr_t>(d_out) % 4) || (a_stride % 4) || (b_stride % 4) ||
-        (d_flow && reinterpret_cast<uintptr_t>(d_flow) % (flow_half_ ? 4 : 8)))
-        return fail(kInvalidArgument, fmt("%s: pointers/strides must be pixel aligned", who));
-    const size_t frame_bytes = (size_t)w * h * 4;
-    if (out_pair_stride != 0 && (out_pair_stride < n_times * frame_bytes || out_pair_stride % 4))
-        return fail(kInvalidArgument, fmt("%s: out_pair_stride %zu must be 0 or a multiple of 4 of at least n_times * w * h * 4 = %zu", who,
-                                          out_pair_stride, n_times * frame_bytes));
-    if (n_pairs == 0) return kOk;
-    const int n = device_count();
-    if (n <= 0) return fail(kNoDevice, "no HIP device available (the gfx950 path has no CPU fallback)");
-    NUS_HIP(hipSetDevice(device_));
-    WarpLaunch L;
-    L.a = static_cast<const uint8_t *>(d_a);
-    L.b = static_cast<const uint8_t *>(d_b);
-    L.flow = static_cast<const float *>(d_flow);
-    L.flow_half = flow_half_;
-    L.fma = fma_;
-    L.out = static_cast<uint8_t *>(d_out);
-    L.a_stride = a_stride;
-    L.b_stride = b_stride;
-    L.w = w;
-    L.h = h;
     L.times = times;
     L.n_times = n_times;
     L.out_pair_stride = out_pair_stride;
     L.n_pairs = n_pairs;
     L.stream = stream;
     L.in_sel = input_selector(in_format_);
-    hipError_t e = launch_warp_blend(L);
-    if (e != hipSuccess) return fail_hip(e, "multi-time warp+blend launch");
+    const hipError_t e = launch_warp_blend(L);
+    if (e != hipSuccess) return fail_hip(e, multi ? "multi-time warp+blend launch" : "warp+blend launch");
     return kOk;
 }
 

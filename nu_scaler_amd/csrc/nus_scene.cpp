@@ -14,26 +14,12 @@ namespace nus {
 
 namespace {
 
-constexpr int kMaxDevices = 64;
-
-int fail(int status, const std::string &msg)
-{
-    set_thread_error(msg);
-    return status;
-}
-
-int fail_hip(hipError_t e, const char *what)
-{
-    (void)hipGetLastError();
-    return fail(e == hipErrorOutOfMemory ? kOutOfMemory : kHipError, fmt("HIP error in %s: %s", what, hipGetErrorString(e)));
-}
-
-bool misaligned(const void *p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) % to) != 0; }
+constexpr uint64_t kMaxPixels = (uint64_t)1 << 30;
 
 int check_shape(const char *who, uint32_t w, uint32_t h, uint32_t n_pairs)
 {
     if (w == 0 || h == 0) return fail(kInvalidArgument, fmt("%s: width and height must be non-zero", who));
-    if ((uint64_t)w * h > ((uint64_t)1 << 30)) return fail(kInvalidArgument, fmt("%s: %ux%u frames are too large", who, w, h));
+    if (check_frame_area(who, w, h, kMaxPixels) != kOk) return kInvalidArgument;
     const std::string bad = check_scene_launch(w, h, n_pairs);
     if (!bad.empty()) return fail(kInvalidArgument, fmt("%s: %s", who, bad.c_str()));
     return kOk;
@@ -43,35 +29,6 @@ int check_format(const char *who, int format)
 {
     if (format < 0 || format > 3) return fail(kInvalidArgument, fmt("%s: unknown pixel format %d", who, format));
     return kOk;
-}
-
-// frame pointers and strides of n_pairs pairs, as nus_interp_interpolate_device addresses them
-int check_pairs(const char *who, const void *d_a, size_t a_stride, const void *d_b, size_t b_stride, uint32_t w, uint32_t h)
-{
-    if (misaligned(d_a, 4) || misaligned(d_b, 4) || a_stride % 4 || b_stride % 4)
-        return fail(kInvalidArgument, fmt("%s: frame pointers and strides must be multiples of 4 bytes", who));
-    const size_t frame_bytes = (size_t)w * h * 4;
-    if (a_stride < frame_bytes || b_stride < frame_bytes)
-        return fail(kInvalidArgument, fmt("%s: strides (%zu, %zu) are smaller than a %ux%u frame (%zu bytes)", who, a_stride, b_stride,
-                                          w, h, frame_bytes));
-    return kOk;
-}
-
-// the host entry point's device buffers, one set per device, kept for reuse (grown when a larger frame arrives)
-struct Slot {
-    std::mutex m;
-    uint8_t *d_a = nullptr, *d_b = nullptr;
-    size_t frame_cap = 0;
-    void *ws = nullptr;
-    size_t ws_cap = 0;
-    uint8_t *d_res = nullptr; // 16 bytes of measures, then the flag
-    hipStream_t stream = nullptr;
-};
-
-Slot &slot_of(int device)
-{
-    static Slot *slots = new Slot[kMaxDevices]; // never destroyed: the runtime may be gone before a static destructor runs
-    return slots[device];
 }
 
 } // namespace
@@ -120,9 +77,8 @@ int scene_detect_device(const void *d_a, size_t a_stride, const void *d_b, size_
     if (!bad.empty()) return fail(kInvalidArgument, fmt("%s: %s", who, bad.c_str()));
     if (misaligned(d_workspace, 8) || misaligned(d_measures, 8))
         return fail(kInvalidArgument, fmt("%s: workspace and measures must be 8-byte aligned", who));
-    const size_t need = scene_shape(w, h, n_pairs ? n_pairs : 1).workspace_bytes;
-    if (workspace_bytes < need)
-        return fail(kInvalidArgument, fmt("%s: workspace of %zu bytes, %zu needed (nus_scene_workspace_size)", who, workspace_bytes, need));
+    if ((st = check_workspace(who, workspace_bytes, scene_shape(w, h, n_pairs ? n_pairs : 1).workspace_bytes, "nus_scene_workspace_size")) != kOk)
+        return st;
     if (n_pairs == 0) return kOk;
     if (device_count() <= 0) return fail(kNoDevice, fmt("%s: no HIP device available", who));
     SceneLaunch L;
@@ -142,13 +98,10 @@ int scene_apply_cuts_device(const void *d_a, size_t a_stride, const void *d_b, s
     if (!d_a || !d_b || !d_cut || !d_out) return fail(kInvalidArgument, fmt("%s: null pointer", who));
     int st = check_shape(who, w, h, n_pairs);
     if (st != kOk || (st = check_format(who, format)) != kOk || (st = check_pairs(who, d_a, a_stride, d_b, b_stride, w, h)) != kOk) return st;
-    const std::string bad = check_interp_times(times, n_times);
-    if (!bad.empty()) return fail(kInvalidArgument, fmt("%s: %s", who, bad.c_str()));
+    if ((st = check_interp_times(who, times, n_times)) != kOk) return st;
     if (misaligned(d_out, 4)) return fail(kInvalidArgument, fmt("%s: d_out must be 4-byte aligned", who));
     const size_t frame_bytes = (size_t)w * h * 4;
-    if (out_pair_stride != 0 && (out_pair_stride < n_times * frame_bytes || out_pair_stride % 4))
-        return fail(kInvalidArgument, fmt("%s: out_pair_stride %zu must be 0 or a multiple of 4 of at least n_times * w * h * 4 = %zu", who,
-                                          out_pair_stride, n_times * frame_bytes));
+    if ((st = check_out_pair_stride(who, out_pair_stride, n_times, frame_bytes)) != kOk) return st;
     if (n_pairs == 0) return kOk;
     if (device_count() <= 0) return fail(kNoDevice, fmt("%s: no HIP device available", who));
     SceneLaunch L;
@@ -175,41 +128,22 @@ int scene_detect(int device, const uint8_t *a, size_t a_len, const uint8_t *b, s
     if (a_len != frame_bytes)
         return fail(kSizeMismatch, fmt("Input data size (%zu) does not match expected input buffer size (%zu for %ux%u)", a_len,
                                        frame_bytes, w, h));
-    const int n = device_count();
-    if (n <= 0) return fail(kNoDevice, fmt("%s: no HIP device available", who));
-    if (device < 0 || device >= n || device >= kMaxDevices) return fail(kNoDevice, fmt("%s: no HIP device %d", who, device));
+    int r = check_device(who, device);
+    if (r != kOk) return r;
 
-    Slot &s = slot_of(device);
+    static PairScratch *const scratch = new PairScratch[kMaxDevices]; // never destroyed: see DeviceBuffer
+    PairScratch &s = scratch[device];
     std::lock_guard<std::mutex> lock(s.m);
-    NUS_HIP(hipSetDevice(device));
-    if (!s.stream) NUS_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
-    if (s.frame_cap < frame_bytes) {
-        if (s.d_a) (void)hipFree(s.d_a);
-        if (s.d_b) (void)hipFree(s.d_b);
-        s.d_a = s.d_b = nullptr;
-        s.frame_cap = 0;
-        NUS_HIP(hipMalloc(reinterpret_cast<void **>(&s.d_a), frame_bytes));
-        NUS_HIP(hipMalloc(reinterpret_cast<void **>(&s.d_b), frame_bytes));
-        s.frame_cap = frame_bytes;
-    }
-    const size_t need = scene_shape(w, h, 1).workspace_bytes;
-    if (s.ws_cap < need) {
-        if (s.ws) (void)hipFree(s.ws);
-        s.ws = nullptr;
-        s.ws_cap = 0;
-        NUS_HIP(hipMalloc(&s.ws, need));
-        s.ws_cap = need;
-    }
-    if (!s.d_res) NUS_HIP(hipMalloc(reinterpret_cast<void **>(&s.d_res), 32));
+    if ((r = s.prepare(device, frame_bytes, scene_shape(w, h, 1).workspace_bytes, 32)) != kOk) return r;
+    uint8_t *const d_res = static_cast<uint8_t *>(s.result.get()); // 16 bytes of measures, then the flag
     // the library's own road for the caller's (possibly pageable) buffers: never handed to the runtime
-    int r;
-    if ((r = upload(s.d_a, a, frame_bytes, s.stream)) != kOk) return r;
-    if ((r = upload(s.d_b, b, frame_bytes, s.stream)) != kOk) return r;
-    if ((r = scene_detect_device(s.d_a, frame_bytes, s.d_b, frame_bytes, w, h, 1, format, mad_threshold, hist_permille, s.ws, s.ws_cap,
-                                 s.d_res, s.d_res + 16, s.stream)) != kOk)
+    if ((r = upload(s.a.get(), a, frame_bytes, s.stream)) != kOk) return r;
+    if ((r = upload(s.b.get(), b, frame_bytes, s.stream)) != kOk) return r;
+    if ((r = scene_detect_device(s.a.get(), frame_bytes, s.b.get(), frame_bytes, w, h, 1, format, mad_threshold, hist_permille,
+                                 s.workspace.get(), s.workspace.capacity(), d_res, d_res + 16, s.stream)) != kOk)
         return r;
     uint8_t res[17];
-    if ((r = download(res, s.d_res, sizeof res, s.stream)) != kOk) return r;
+    if ((r = download(res, d_res, sizeof res, s.stream)) != kOk) return r;
     if (measures_out) memcpy(measures_out, res, 16);
     *cut_out = res[16];
     return kOk;

@@ -12,8 +12,6 @@ namespace nus {
 
 namespace {
 
-constexpr int kMaxDevices = 64;
-
 // One ring per device: the chunks are pinned memory of that device's context and the events that say "the DMA engine is done
 // with chunk k" are recorded on streams of that device.  A transfer holds the ring's mutex from its first chunk to its last, so
 // concurrent callers on one device take turns (they share the two DMA engines anyway).
@@ -29,18 +27,6 @@ Ring &ring_of(int device)
 {
     static Ring *rings = new Ring[kMaxDevices]; // never destroyed: the runtime may be gone before a static destructor runs
     return rings[device];
-}
-
-int fail(int status, const std::string &msg)
-{
-    set_thread_error(msg);
-    return status;
-}
-
-int fail_hip(hipError_t e, const char *what)
-{
-    (void)hipGetLastError();
-    return fail(e == hipErrorOutOfMemory ? kOutOfMemory : kHipError, fmt("HIP error in %s: %s", what, hipGetErrorString(e)));
 }
 
 // the calling thread's current device, put back on every way out

@@ -293,6 +293,48 @@ def test_interpolate_equals_the_oracle_warp_of_the_yardstick_flow(nsc, oracle_mo
             assert bm.interpolate(a, b, w, h, times=[t], mode=mode)[0] == frames[k], (mode, k)
 
 
+REUSE = [("shifted", 16, 12), ("noise", 48, 32), ("shifted", 16, 12)]  # the handle's device arena: small, grown, reused
+
+
+def test_estimate_reuses_its_grown_arena(nsc):
+    """nus_bm_estimate on one handle with a 16x12 pair (2 x 2 blocks of 8), a 48x32 pair and the 16x12 pair again: each result
+    equals the yardstick bit for bit, the third the first."""
+    bm = nsc.BlockMatcher(block_size=8, search_radius=24)
+    got = []
+    for content, w, h in REUSE:
+        a, b = _pair(content, w, h)
+        _, sad, ref, flags, _ = _expected(content, w, h, 8, 24, bmref.CENTER)
+        v, s, f = (np.asarray(x) for x in bm.estimate(a, b, w, h))
+        assert np.array_equal(v.reshape(ref.shape), ref) and np.array_equal(s.reshape(sad.shape), sad), (content, w, h)
+        assert np.array_equal(f.reshape(flags.shape), flags), (content, w, h)
+        got.append(v.tobytes() + s.tobytes() + f.tobytes())
+    assert got[2] == got[0]
+
+
+def test_interpolate_with_scene_detection_reuses_its_grown_arena(nsc, oracle_mod):
+    """nus_bm_interpolate with scene detection on, same handle, same three pairs: a pair the yardstick detector flags gives
+    repeats of the nearer frame, any other the oracle's warp of the yardstick flow (EXACT mode: bit for bit)."""
+    import _scenecut as sc
+
+    bm = nsc.BlockMatcher(block_size=8, search_radius=24)
+    bm.set_scene_detect(True)
+    times = [0.25, 0.75]
+    got = []
+    for content, w, h in REUSE:
+        a, b = _pair(content, w, h)
+        if content == "noise":  # the larger pair is a cut: noise against white
+            b = np.full_like(a, 255)
+            assert sc.is_cut(*sc.measures(a, b), w, h)
+        if sc.is_cut(*sc.measures(a, b), w, h):
+            want = [a.tobytes(), b.tobytes()]
+        else:
+            flow = bmref.dense_flow(_expected(content, w, h, 8, 24, bmref.CENTER)[2], w, h, 8)
+            want = [oracle_mod.warp_blend(a, b, flow, t).tobytes() for t in times]
+        got.append(bm.interpolate(a, b, w, h, times=times, mode="exact"))
+        assert got[-1] == want, (content, w, h)
+    assert got[2] == got[0]
+
+
 def _write_png(path, img):
     from nu_scaler_amd.imagefile import write_png
 

@@ -200,6 +200,20 @@ def test_host_entry_point_equals_device_entry_point(nsc, shape):
     assert (em2.mse(), em2.psnr()) == (em.mse(), em.psnr())
 
 
+def test_host_entry_point_reuses_its_grown_buffers(nsc):
+    """nus_metrics_compare on one device with a 16x12 pair, a 48x32 pair (the kept buffers grow) and the 16x12 pair again (they
+    are reused, larger than needed): each result against the float64 definition, the third the bytes of the first."""
+    from nu_scaler_amd.metrics import ErrorMetrics
+
+    res = []
+    for w, h in ((16, 12), (48, 32), (16, 12)):
+        a, b = _pair("noise", w, h)
+        em = ErrorMetrics.calculate(a, b)
+        res.append(np.array([em.mse(), em.psnr(), em.ssim()]))
+        _check(res[-1], a, b)
+    assert res[2].tobytes() == res[0].tobytes()
+
+
 def test_scores_gpu_lanczos_on_the_same_stream(nsc, oracle_mod):
     """upscale_device, then compare_device on the same non-null stream with no synchronisation between them: the GPU
     Lanczos-3 x2 (FMA mode, within 1 LSB) against the oracle's output."""

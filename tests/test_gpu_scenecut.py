@@ -164,6 +164,19 @@ def test_decisions_on_content_with_wide_margins(nsc):
         assert (got_cut, (sad, hist)) == (want, sc.measures(x, y)), name
 
 
+def test_host_entry_point_reuses_its_grown_buffers(nsc):
+    """nus_scene_detect on one device with a 16x12 pair, a 48x32 pair (the kept buffers grow) and the 16x12 pair again (they are
+    reused, larger than needed): each answer equals the yardstick's, so the third equals the first."""
+    got = []
+    for w, h in ((16, 12), (48, 32), (16, 12)):
+        x, y = _frame(w, h, 0), _frame(w, h, 3)
+        cut, sad, hist = nsc.SceneDetector().detect(x, y, w, h)
+        s, l = sc.measures(x, y)
+        assert (cut, (sad, hist)) == (sc.is_cut(s, l, w, h, 20, 400), (s, l)), (w, h)
+        got.append((cut, sad, hist))
+    assert got[2] == got[0]
+
+
 def test_threshold_extremes(nsc):
     w, h = 64, 32
     n = 5

@@ -475,6 +475,19 @@ def test_host_tables_and_queue_under_address_and_ub_sanitizers(tmp_path):
     assert run.returncode == 0 and "bad 0" in run.stdout and "runtime error" not in run.stderr, run.stdout + run.stderr
 
 
+def test_shared_argument_checks_under_address_and_ub_sanitizers(tmp_path):
+    """nus_checks.cpp -- the argument checks the host entry points share -- swept over their boundary values (null and off-by-1/2/3
+    pointers, strides and out_pair_stride around a frame, n_times and times at and past their ends, dimensions at each caller's
+    limit +- 1) in a stand-alone program built with -fsanitize=address,undefined (tests/c_abi/host_checks_sanitize.cpp); it
+    exits non-zero on a wrong status."""
+    import subprocess
+    src_dir = os.path.join(ROOT, "nu_scaler_amd", "csrc")
+    exe = _sanitizer_build(tmp_path, "host_checks_asan",
+                           [os.path.join(ROOT, "tests", "c_abi", "host_checks_sanitize.cpp"), os.path.join(src_dir, "nus_checks.cpp")])
+    run = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, **_SAN_ENV), timeout=600)
+    assert run.returncode == 0 and " bad 0" in run.stdout and "runtime error" not in run.stderr, run.stdout + run.stderr
+
+
 def test_copy_pool_stress_under_thread_sanitizer(tmp_path):
     """The same program built with -fsanitize=thread (CPU build; GPU sanitizers are not available on this pool): copies, populate
     requests racing with copies into the same fresh mapping, the low-priority queue, worker start-up and shutdown -- no report."""
