@@ -484,7 +484,13 @@ int nus_flow_set_tiled(nus_flow *h, int enabled);
  * Jacobi steps with separable 3x3 sums, a multiply by 1/9, a precomputed reciprocal of lambda + Ix^2 + Iy^2 and FMAs
  * (shaders/horn_schunck.wgsl:24-92 in its cheapest f32 form; every level in the register-pipelined kernel) -- the flow within
  * 1e-3 px of the exact one, the frame interpolated with it within 1 LSB on < 0.1 % of its samples; 2.2x fewer instructions per
- * step.  The reference never runs this front end (wgpu_interpolator.rs:1156-1203 is unwired), so neither mode has a fixture.
+ * step.  The 1e-3 px bound holds for lambda >= 4e-4 (the default) and is checked against a float64 restatement of the shaders
+ * (tests/_flow64.py).  For a smaller lambda it is NOT promised: the problem becomes ill-conditioned (lambda = 1e-6 on noise: flows
+ * beyond 50 px, and the exact f32 arithmetic itself is more than 1e-3 px from the float64 result -- both asserted in
+ * tests/test_flow.py), and FAST then stays within 3.1x the distance of the exact mode's own result from the float64 one
+ * (measured at lambda = 1e-6: 0.56x on noise, 0.78x on a static scene; the test allows four times the larger).
+ * EXACT is bit-identical for every operand, subnormal flows around a local change on a static background included.
+ * The reference never runs this front end (wgpu_interpolator.rs:1156-1203 is unwired), so neither mode has a fixture.
  * The primitives below are always exact. */
 #define NUS_FLOW_EXACT 0
 #define NUS_FLOW_FAST 1

@@ -155,14 +155,43 @@ __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? l
 // r = x - q y (exact in the FMA), result = RN(q + r z).  Equal to the IEEE quotient for every y whose
 // mantissa is not all ones (Markstein's theorem) and, checked exhaustively over every mantissa of x on the
 // CPU (tests/test_div_by_recip.py), also for the all-ones mantissa -- the theorem's exception is not needed
-// for this sequence -- and for y = 9 and y = 255, as long as quotient and remainder stay in the normal range
-// (the sequence is invariant under scaling x or y by powers of two).  Replaces ~11 slow-class instructions
-// per division by 3 fast ones.
+// for this sequence -- and for y = 9 and y = 255.  Replaces ~11 slow-class instructions per division by 3 fast ones.
+//
+// Proven domain.  The argument needs q normal and r = x - q y formed without rounding.  r is a multiple of
+// ulp(q) ulp(y) = 2^(e_q + e_y - 46) with e_q >= e_x - e_y - 1, so it is exact in f32 (>= 2^-149) once e_x >= -102; below that
+// the FMA rounds r, and for a subnormal x or quotient q itself has lost bits: the result is then off by an ulp for some
+// operands (first seen in the Horn-Schunck kernels, whose flow decays through every f32 magnitude around a local change on a
+// static background).  The sequence is invariant under scaling x or y by powers of two only inside
+//     x = +0, or 2^-100 <= |x| <= 2^100,   with   2^-24 <= y <= 2^24
+// (q then lies in [2^-125, 2^125]; +0 gives +0 through every step).  -0, subnormal, tiny, huge, infinite and NaN x are outside it.
+// The callers whose operands can leave the domain go through div_exact below; the others are inside it by construction:
+// u8 / 255 (x = +0 or 1 .. 255), and in nus_k_fsr.hip the colour-difference sums / 3 (+0 or >= 2^-9: distinct u8 / 255 values
+// are >= 1/255 - 2^-24 apart), (vg + 0.0001) / len (both in [1e-4, 2]), the 16-tap sums / max(weight sum, 1e-4) (FsrCubic is >= 1 on
+// d <= 1 and a multiple of 2^-24 beyond, a tap >= 1/255: a non-zero sum is a multiple of 2^-57, the weight sum is in
+// [1e-4, 32]) and RCAS's (max - min luma) / 0.2 (+0 or >= one ulp of a luma >= 0.114 / 255: 2^-35).
 __device__ __forceinline__ float div_by_recip(float x, float y, float z)
 {
     const float q = x * z;
     const float r = __builtin_fmaf(-y, q, x);
     return __builtin_fmaf(r, z, q);
+}
+
+// z for div_exact: RN(1 / y) for a divisor inside div_by_recip's domain, a negative number (never a reciprocal of such a y)
+// for any other -- zero, negative, NaN included -- which sends every division by it down the plain path.
+__device__ __forceinline__ float div_exact_recip(float y)
+{
+    return (y >= 0x1p-24f && y <= 0x1p+24f) ? 1.0f / y : -1.0f;
+}
+
+// x / y, IEEE, for every x and y: div_by_recip where it is proven, the plain division elsewhere (a rarely taken branch: a wave
+// takes it only while one of its lanes holds a non-zero operand below 2^-100 or above 2^100).  z = div_exact_recip(y).
+// tests/helpers/div_by_recip_check.c checks the same three functions on the CPU, across the exponent range.
+__device__ __forceinline__ float div_exact(float x, float y, float z)
+{
+    const float a = fabsf(x);
+    const bool proven = ((a >= 0x1p-100f && a <= 0x1p+100f) || __float_as_uint(x) == 0u) && z > 0.0f;
+    if (__builtin_expect(proven, 1)) return div_by_recip(x, y, z);
+    return x / y;
 }
 
 // u8 -> f32 / 255 (the Rgba8Unorm view of a frame); exact IEEE quotient via the reciprocal + 2 FMAs

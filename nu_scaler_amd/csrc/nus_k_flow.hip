@@ -485,8 +485,10 @@ __global__ __launch_bounds__(256) void k_hs_prepare(const IMG *__restrict__ i1, 
 
 struct HsCell {
     float ix, iy, it, den, zinv;
-    bool plain_div; // mantissa of den all ones: takes the true division.  Not needed for exactness (tests/test_div_by_recip.py),
-                    // but this kernel is 7 % faster with the branch in its step than without (profiles/r02_flow_jacobi_streamed_ab.txt)
+    bool plain_div; // mantissa of den all ones: takes the true division.  The reciprocal sequence is exact for such a den too
+                    // (tests/test_div_by_recip.py); the test stays because this kernel measured 7 % faster with the branch in its step
+                    // than without (profiles/r02_flow_jacobi_streamed_ab.txt).  The guard that IS needed for exactness -- operands
+                    // outside the sequence's proven range -- is div_exact's own, below.
 };
 
 // T x T output tile, K Jacobi steps per launch (temporal blocking).  A thread owns a vertical run
@@ -532,7 +534,7 @@ __global__ __launch_bounds__(NT) void k_hs_tiled(const float *__restrict__ coef_
             cell[i].iy = iy;
             cell[i].it = c[2];
             cell[i].den = den;
-            cell[i].zinv = 1.0f / den; // correctly rounded reciprocal, for div_by_recip
+            cell[i].zinv = div_exact_recip(den); // correctly rounded reciprocal, for div_exact
             cell[i].plain_div = (__float_as_uint(den) & 0x7fffffu) == 0x7fffffu;
             s_flow[0][ly * R + lx] = fin ? fin[g] : make_float2(0.0f, 0.0f); // null = start from zero flow
             if (gx == x0 + lx && gy == y0 + ly) ring[i] = min(min(lx, ly), min(R - 1 - lx, R - 1 - ly));
@@ -572,10 +574,11 @@ __global__ __launch_bounds__(NT) void k_hs_tiled(const float *__restrict__ coef_
                     sv += f[i + dy][d].y;
                 }
             // sum / count with count == 9 (horn_schunck.wgsl:38-41)
-            const float ua = div_by_recip(su, 9.0f, 1.0f / 9.0f), va = div_by_recip(sv, 9.0f, 1.0f / 9.0f);
+            // (div_exact: the sums and the numerator pass through every f32 magnitude where a flow decays into a static region)
+            const float ua = div_exact(su, 9.0f, 1.0f / 9.0f), va = div_exact(sv, 9.0f, 1.0f / 9.0f);
             const HsCell &c = cell[i];
             const float num = c.ix * ua + c.iy * va + c.it;
-            const float common = c.plain_div ? num / c.den : div_by_recip(num, c.den, c.zinv);
+            const float common = c.plain_div ? num / c.den : div_exact(num, c.den, c.zinv);
             if (ring[i] >= j) s_flow[cur ^ 1][(ly0 + i) * R + lx] = make_float2(ua - common * c.ix, va - common * c.iy);
         }
         __syncthreads();
@@ -712,7 +715,7 @@ __global__ __launch_bounds__(256) void k_hs_stream(const float *__restrict__ coe
                 l1_above = l1_row, l1_row = nix;
             }
             const float den = lambda + ix * ix + iy * iy;
-            cf[0] = HsCoef{ix, iy, it, den, 1.0f / den}; // correctly rounded reciprocal, for div_by_recip
+            cf[0] = HsCoef{ix, iy, it, den, div_exact_recip(den)}; // correctly rounded reciprocal, for div_exact
         }
         float2 arr = nf; // level 0's arrival: row t of the input flow
 #pragma unroll
@@ -743,11 +746,12 @@ __global__ __launch_bounds__(256) void k_hs_stream(const float *__restrict__ coe
             float su = pu[j], sv = pv[j];
             su += b.ul, sv += b.vl, su += b.uc, sv += b.vc, su += b.ur, sv += b.vr;
             su += n.ul, sv += n.vl, su += n.uc, sv += n.vc, su += n.ur, sv += n.vr;
-            const float ua = div_by_recip(su, 9.0f, 1.0f / 9.0f), va = div_by_recip(sv, 9.0f, 1.0f / 9.0f);
+            const float ua = div_exact(su, 9.0f, 1.0f / 9.0f), va = div_exact(sv, 9.0f, 1.0f / 9.0f);
             const HsCoef c = cf[j + 1]; // row r-1 entered j+1 passes ago
             const float num = c.ix * ua + c.iy * va + c.it;
-            // == num / den for every den, the all-ones mantissa included (tests/test_div_by_recip.py): no branch in the pass
-            const float common = div_by_recip(num, c.den, c.zinv);
+            // == num / den for every den, the all-ones mantissa included (tests/test_div_by_recip.py); operands outside the
+            // sequence's proven range (a flow decaying into a static region) take the plain division
+            const float common = div_exact(num, c.den, c.zinv);
             arr = make_float2(ua - common * c.ix, va - common * c.iy);
             // the row that was newest becomes the row above
             float qu = 0.0f, qv = 0.0f;

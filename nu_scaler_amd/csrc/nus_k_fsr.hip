@@ -63,6 +63,8 @@ __device__ __forceinline__ uint32_t fsr_pack(float r, float g, float b)
 __device__ __forceinline__ float fsr_dir_wx(const float3 up, const float3 dn, const float3 lf, const float3 rt)
 {
     const float third = 1.0f / 3.0f;
+    // (unguarded div_by_recip: the sums are +0 or >= 2^-9, dxr, dyr and len lie in [1e-4, 2] -- inside the domain stated in nus_device.hpp;
+    // an edit that lets a numerator become tiny or -0 has to switch to div_exact)
     const float vgx = div_by_recip(fabsf(up.x - dn.x) + fabsf(up.y - dn.y) + fabsf(up.z - dn.z), 3.0f, third);
     const float vgy = div_by_recip(fabsf(lf.x - rt.x) + fabsf(lf.y - rt.y) + fabsf(lf.z - rt.z), 3.0f, third);
     const float dxr = vgx + 0.0001f, dyr = vgy + 0.0001f;
@@ -86,6 +88,8 @@ __device__ __forceinline__ void fsr_div3(float &r, float &g, float &b, float den
         g = g / den;
         b = b / den;
     } else {
+        // (unguarded: a 16-tap sum is +0 or a multiple of 2^-57, den is in [1e-4, 32] -- the domain argument in nus_device.hpp rests on
+        // FsrCubic being >= 1 on d <= 1 and a multiple of 2^-24 beyond; change the weights and it has to be made again, or div_exact used)
         const float z = 1.0f / den;
         r = div_by_recip(r, den, z);
         g = div_by_recip(g, den, z);
@@ -311,6 +315,7 @@ __device__ __forceinline__ uint32_t fsr_rcas_px(const float4 c, const float4 t, 
     const float mn = fminf(c.w, fminf(fminf(t.w, b.w), fminf(l.w, r.w)));
     const float mx = fmaxf(c.w, fmaxf(fmaxf(t.w, b.w), fmaxf(l.w, r.w)));
     // (contrast - 0.0) / (0.2 - 0.0): x - 0.0 == x; the quotient by the constant via its reciprocal (exact, see div_by_recip)
+    // (unguarded: mx - mn is +0 or >= one ulp of a luma >= 0.114 / 255, i.e. >= 2^-35 -- inside div_by_recip's domain, nus_device.hpp)
     const float st = clamp01(div_by_recip(mx - mn, 0.2f, 1.0f / 0.2f));
     const float strength = sharp * (1.0f - st * st * (3.0f - 2.0f * st));
     return fsr_pack(c.x + (4.0f * c.x - t.x - b.x - l.x - r.x) * strength,

@@ -1,6 +1,7 @@
 """The kernels divide by a per-cell / constant denominator with one correctly rounded reciprocal, one multiply and two
 FMAs (nus_device.hpp: div_by_recip).  That this equals the IEEE quotient bit for bit -- also for a denominator whose
-mantissa is all ones, the exception of Markstein's theorem -- is checked here exhaustively on the CPU."""
+mantissa is all ones, the exception of Markstein's theorem -- is checked here exhaustively on the CPU, and so is the guarded
+form the Horn-Schunck kernels call (div_exact), for subnormal, tiny, huge and special operands across the exponent range."""
 import os
 import shutil
 import subprocess
@@ -20,4 +21,7 @@ def test_div_by_recip_equals_ieee_division_for_every_mantissa(tmp_path):
     subprocess.run(["gcc", *flags, "-o", exe, src, "-lm"], check=True)
     out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout + out.stderr
-    assert int(out.stdout.split()[1]) > 150_000_000
+    fields = out.stdout.split()  # ok <sequence alone> guarded <guarded form, every exponent> unguarded_bad <misses without the guard>
+    assert int(fields[1]) > 150_000_000
+    assert fields[2] == "guarded" and int(fields[3]) > 500_000_000
+    assert fields[4] == "unguarded_bad" and int(fields[5]) > 0

@@ -20,6 +20,38 @@ def _smooth(w, h, shift=0.0):
     return img
 
 
+def _static_scene(w, h, seed, background="noise", change="patch"):
+    """A pair (a, b) of RGBA8 frames with the same textured background -- "noise" or "smooth" -- that differ only in a small
+    box: "patch" re-randomises 8x8 pixels, "box" moves a 12x12 textured box 3 px to the right, "pixel" changes one pixel.
+    The ordinary video case: the flow is exactly zero far from the box and decays towards it through every f32 magnitude."""
+    rng = np.random.default_rng(seed)
+    if background == "noise":
+        a = rng.integers(0, 256, size=(h, w, 4), dtype=np.uint8)
+        a[..., 3] = 255
+    else:
+        a = _smooth(w, h)
+    b = a.copy()
+    x0, y0 = w // 16, h // 8  # near a corner: the far side of the frame stays out of reach of ~140 steps
+    if change == "patch":
+        b[y0:y0 + 8, x0:x0 + 8, :3] = rng.integers(0, 256, size=(8, 8, 3), dtype=np.uint8)
+    elif change == "box":
+        box = rng.integers(0, 256, size=(12, 12, 4), dtype=np.uint8)
+        box[..., 3] = 255
+        a[y0:y0 + 12, x0:x0 + 12] = box
+        b[y0:y0 + 12, x0 + 3:x0 + 15] = box
+    elif change == "pixel":
+        b[y0, x0, :3] = 255 - b[y0, x0, :3]
+    else:
+        raise ValueError(change)
+    return a, b
+
+
+def _subnormal_count(flow):
+    """Non-zero values below the smallest normal f32: where the EXACT kernels' reciprocal division leaves its fast path."""
+    m = np.abs(flow)
+    return int(((m > 0) & (m < np.finfo(np.float32).tiny)).sum())
+
+
 # ---- CPU: oracle properties -----------------------------------------------------------
 
 def test_oracle_blur_and_downsample_properties(oracle_mod):
@@ -552,3 +584,173 @@ def test_interpolate_device_stream_rg16float_handoff(nsc, oracle_mod, w, h, leve
         assert int(d.max()) <= 1, (mode, tiled)
     with pytest.raises(ValueError):
         fe.interpolate_device_stream(d_frames.data_ptr(), n_frames, w, h, t, mid32.data_ptr(), 0, s, "bf16")
+
+
+# ---- a static background with a small local change: the ordinary video case ----------------------------------------------
+# Around the change the flow spreads one cell per Jacobi step and shrinks ~9x per cell: after ~30 steps it passes through the
+# f32 subnormals on its way to exact zero.  Every case below must get there (the assert on _subnormal_count is the
+# precondition, checked with the oracle on the CPU): that is where a division shortcut leaves the range it was proven for.
+
+# lambda < 4e-4: how far FAST may be from the float64 witness, as a multiple of the exact f32 arithmetic's own distance to it
+# (|oracle - witness|, computed in the test for the very case).  Measured on an MI355X at lambda = 1e-6 (97x45, 3 levels, 9 + 3
+# steps; the figures test_flow_lambda_sweep prints): noise |FAST - witness| = 1.171e-3 px against |oracle - witness| = 2.081e-3 px
+# (ratio 0.56, flows up to 96.7 px), static scene 5.746e-5 against 7.365e-5 px (ratio 0.78).  Asserted: the larger ratio x 4.
+_FAST_TO_EXACT_ERROR_RATIO = 4 * 0.78
+
+
+def _bits_differ(got, want):
+    """Values whose bit patterns differ (np.array_equal would take -0 for +0)."""
+    return int((np.ascontiguousarray(got, np.float32).view(np.uint32) != np.ascontiguousarray(want, np.float32).view(np.uint32)).sum())
+
+
+# 31 steps reach the subnormals only on a noise background (its gradients damp the flow faster); the smooth one needs 40
+_STATIC_HS = [((160, 120), "noise", "box", (31, 40, 64)), ((131, 70), "noise", "pixel", (31, 40, 64)),
+              ((131, 120), "noise", "patch", (31, 40, 64)), ((160, 70), "smooth", "pixel", (40, 64))]
+_STATIC_EST = [((160, 120), "noise", "patch"), ((160, 70), "smooth", "box"), ((131, 120), "noise", "pixel"), ((131, 70), "noise", "pixel")]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("size,background,change,step_counts", _STATIC_HS)
+def test_horn_schunck_exact_on_a_static_scene(nsc, oracle_mod, size, background, change, step_counts):
+    """fe.horn_schunck on unblurred static-scene frames, from zero flow and from a flow that is non-zero in a 5x5 box only:
+    bit for bit the oracle's with every kernel, through the subnormal range."""
+    w, h = size
+    a, b = _static_scene(w, h, 3, background, change)
+    i1, i2 = oracle_mod.rgba8_to_f32(a), oracle_mod.rgba8_to_f32(b)
+    f0 = np.zeros((h, w, 2), np.float32)
+    f0[h // 8:h // 8 + 5, w // 16:w // 16 + 5] = np.random.default_rng(1).standard_normal((5, 5, 2))
+    fe = nsc.FlowEstimator()
+    wrong = []
+    for fin in (None, f0):
+        for it in step_counts:
+            want = oracle_mod.horn_schunck(i1, i2, fin, iterations=it, lam=4e-4)
+            assert _subnormal_count(want) > 0, (size, it, "the case does not reach the subnormal range")
+            for tiled in (1, 2, 3, 0):
+                fe.set_tiled(tiled)
+                n = _bits_differ(fe.horn_schunck(i1, i2, fin, iterations=it, lambda_=4e-4), want)
+                print(f"static {size} {background}/{change}, {it} steps, start {'zero' if fin is None else 'given'}, kernels {tiled}: "
+                      f"{n} values differ ({_subnormal_count(want)} subnormal)")
+                if n:
+                    wrong.append((it, fin is not None, tiled, n))
+    assert not wrong, wrong
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("size,background,change", _STATIC_EST)
+@pytest.mark.parametrize("levels,coarse,refine", [(1, 64, 0), (2, 48, 40)])
+def test_flow_estimate_exact_on_a_static_scene(nsc, oracle_mod, size, background, change, levels, coarse, refine):
+    """The estimator's three entry points in EXACT mode, every kernel choice: the oracle's bits.  The stream holds four frames of
+    which one pair differs (in the box only), at each batch position in turn: that pair's flow is the oracle's wherever it
+    sits, the flows of the identical pairs are exactly zero."""
+    import torch
+
+    w, h = size
+    a, b = _static_scene(w, h, 3, background, change)
+    fe = nsc.FlowEstimator(levels=levels, coarse_iterations=coarse, refine_iterations=refine)
+    want = oracle_mod.flow_estimate(a, b, levels, coarse, refine, fe.lambda_)
+    assert _subnormal_count(want) > 0, (size, levels, "the case does not reach the subnormal range")
+    dev = torch.device("cuda:0")
+    s = torch.cuda.current_stream().cuda_stream
+    streams = [put(np.stack([a] * (k + 1) + [b] * (3 - k))) for k in range(3)]  # the moving pair is pair k
+    d_flows = guarded.full((3, h, w, 2), float("nan"), dtype=torch.float32, device=dev)
+    one = guarded.full((h, w, 2), float("nan"), dtype=torch.float32, device=dev)
+    wrong = []
+    for tiled in (1, 2, 3, 0):
+        fe.set_tiled(tiled)
+        got = {"estimate": fe.estimate(a, b, w, h)}
+        one.fill_(float("nan"))
+        fe.estimate_device(streams[0][0].data_ptr(), streams[0][1].data_ptr(), w, h, one.data_ptr(), s)
+        torch.cuda.synchronize()
+        got["estimate_device"] = fetch(one)
+        for k, d_frames in enumerate(streams):
+            d_flows.fill_(float("nan"))
+            fe.estimate_device_stream(d_frames.data_ptr(), 4, w, h, d_flows.data_ptr(), s)
+            torch.cuda.synchronize()
+            flows = fetch(d_flows)
+            got[f"stream, pair {k}"] = flows[k]
+            for j in range(3):
+                if j != k:
+                    assert _bits_differ(flows[j], np.zeros_like(want)) == 0, (tiled, k, j, "identical frames, non-zero flow")
+        for name, flow in got.items():
+            n = _bits_differ(flow, want)
+            print(f"static {size} {background}/{change}, {levels} levels {coarse}+{refine}, kernels {tiled}, {name}: {n} values differ")
+            if n:
+                wrong.append((tiled, name, n))
+    assert not wrong, wrong
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("size,background,change", _STATIC_EST)
+@pytest.mark.parametrize("levels,coarse,refine", [(1, 64, 0), (2, 48, 40)])
+def test_flow_fast_mode_on_a_static_scene(nsc, oracle_mod, size, background, change, levels, coarse, refine):
+    """FAST mode on the same content: finite, within 1e-3 px of the float64 WITNESS (tests/_flow64.py -- not of the oracle, whose
+    own distance to it is below 2e-5 px here), zero flow between identical frames within the same bound, and the frames
+    interpolate_device_stream makes with it within 1 LSB of the oracle's warp with the oracle's flow."""
+    import torch
+
+    import _flow64 as wit
+
+    w, h = size
+    a, b = _static_scene(w, h, 3, background, change)
+    frames = np.stack([a, a, b, b])
+    fe = nsc.FlowEstimator(levels=levels, coarse_iterations=coarse, refine_iterations=refine)
+    want = wit.estimate(a, b, levels, coarse, refine, fe.lambda_)
+    exact = oracle_mod.flow_estimate(a, b, levels, coarse, refine, fe.lambda_)
+    assert _subnormal_count(exact) > 0
+    zero = np.zeros_like(exact)
+    t = 0.5
+    want_mid = [oracle_mod.warp_blend(frames[k], frames[k + 1], exact if k == 1 else zero, t) for k in range(3)]
+    fe.set_mode("fast")
+    dev = torch.device("cuda:0")
+    s = torch.cuda.current_stream().cuda_stream
+    d_frames = put(frames)
+    d_flows = guarded.full((3, h, w, 2), float("nan"), dtype=torch.float32, device=dev)
+    d_mid = guarded.zeros((3, h, w, 4), dtype=torch.uint8, device=dev)
+    for tiled in (3, 1):  # the FAST kernels themselves; kernels by size
+        fe.set_tiled(tiled)
+        d_flows.fill_(float("nan"))
+        fe.interpolate_device_stream(d_frames.data_ptr(), 4, w, h, t, d_mid.data_ptr(), d_flows.data_ptr(), s)
+        torch.cuda.synchronize()
+        got, mid = fetch(d_flows), fetch(d_mid)
+        assert np.isfinite(got).all()
+        for k in range(3):
+            ok, mx = _flow_close(got[k], want if k == 1 else zero)
+            d = np.abs(mid[k].astype(np.int16) - want_mid[k].astype(np.int16))
+            print(f"static {size} {background}/{change}, {levels} levels, FAST kernels {tiled}, pair {k}: |flow - witness| = {mx:.2e} px, "
+                  f"frame max {int(d.max())} LSB on {float((d > 0).mean()):.1e} of the samples")
+            assert ok, (tiled, k, mx)
+            assert d.max() <= 1, (tiled, k, int(d.max()))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("lam", [1e-6, 4e-4, 1e-2, 1.0])
+@pytest.mark.parametrize("content", ["noise", "static"])
+def test_flow_lambda_sweep(nsc, oracle_mod, lam, content):
+    """The smoothness weight over six decades.  EXACT: the oracle's bits with every kernel.  FAST against the float64 witness:
+    within the 1e-3 px contract for lambda >= 4e-4.  At lambda = 1e-6 the problem itself is ill-conditioned: on the noise pair
+    the test asserts that the flow exceeds 50 px (96.7) and that the f32 ORACLE is more than 1e-3 px from the witness (2.08e-3), so no f32 form can promise 1e-3 px there.  The contract is therefore stated for lambda >= 4e-4 (nuscaler_hip.h,
+    nus_flow_set_mode), and below that FAST is held to a multiple of the exact arithmetic's own error: _FAST_TO_EXACT_ERROR_RATIO."""
+    import _flow64 as wit
+
+    w, h, levels, coarse, refine = 97, 45, 3, 9, 3
+    a, b = (oracle_mod.gen_noise(w, h, 41), oracle_mod.gen_noise(w, h, 42)) if content == "noise" else _static_scene(w, h, 3)
+    fe = nsc.FlowEstimator(levels=levels, coarse_iterations=coarse, refine_iterations=refine, lambda_=lam)
+    exact = oracle_mod.flow_estimate(a, b, levels, coarse, refine, fe.lambda_)
+    want = wit.estimate(a, b, levels, coarse, refine, fe.lambda_)
+    for tiled in (1, 2, 3, 0):
+        fe.set_tiled(tiled)
+        assert _bits_differ(fe.estimate(a, b, w, h), exact) == 0, (lam, content, tiled)
+    fe.set_mode("fast")
+    fe.set_tiled(3)  # the FAST kernels whatever the size
+    got = fe.estimate(a, b, w, h)
+    assert np.isfinite(got).all()
+    _, err_fast = _flow_close(got, want)
+    _, err_exact = _flow_close(exact, want)
+    print(f"lambda {lam:g}, {content}: |FAST - witness| = {err_fast:.3e} px, |oracle - witness| = {err_exact:.3e} px, "
+          f"max |flow| = {float(np.abs(want).max()):.1f} px")
+    if lam >= 4e-4:
+        assert err_fast <= 1e-3, (lam, content, err_fast)
+    else:
+        if content == "noise":  # the reason the contract stops at 4e-4: asserted, not only printed
+            assert float(np.abs(want).max()) > 50.0 and err_exact > 1e-3, (float(np.abs(want).max()), err_exact)
+        assert err_fast <= _FAST_TO_EXACT_ERROR_RATIO * err_exact, (lam, content, err_fast, err_exact)
