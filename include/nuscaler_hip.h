@@ -634,6 +634,38 @@ int nus_bm_estimate(nus_blockmatch *h, const uint8_t *a, size_t a_len, const uin
  * nus_interp_interpolate_multi_device in `mode` (nus_interp_mode_t).  Time-set rules as there; n_times frames back to back in out. */
 int nus_bm_interpolate(nus_blockmatch *h, const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, uint32_t w, uint32_t hgt,
                        const float *times, uint32_t n_times, int mode, uint8_t *out, size_t out_cap);
+/* Warp + blend of n_pairs device pairs straight from their per-block vectors: frame (i, k), at d_out + i * out_pair_stride +
+ * k * w*hgt*4, is the frame the dense route writes for pair i at times[k] -- the vectors expanded to the flow defined above, then
+ * nus_interp_interpolate_multi_device -- without a flow field anywhere.  d_vectors: the layout nus_bm_estimate_device writes, 2 x
+ * int16 per block at the handle's block size, blocks_x * blocks_y per pair, 4-byte aligned.  Every component must lie within
+ * +-NUS_BM_MAX_RADIUS: the caller's contract, not checked on the device (a breach moves no access out of the frames: every sample
+ * position is clamped).  Frames (NUS_FORMAT_RGBA8 only), strides, the time set, `mode` (nus_interp_mode_t) and out_pair_stride (0 =
+ * tightly packed; the gap is never written) exactly as nus_interp_interpolate_multi_device.
+ *   NUS_INTERP_MODE_EXACT  byte for byte the CPU warp + blend of the expanded vectors, and so byte for byte the dense route.
+ *   NUS_INTERP_MODE_FMA    the interpolation path's FMA contract against the CPU warp + blend: no byte off by more than 1, and fewer
+ *                          than 0.1 % of the bytes of a frame of at least 328 x 200 differing.  Not promised to be the dense FMA
+ *                          route's bytes.
+ * Enqueue only on `stream`: no allocation, no synchronisation.  n_pairs == 0: NUS_OK, nothing launched.  Argument errors are
+ * NUS_ERR_INVALID_ARGUMENT, returned before any HIP call, with a text that names the entry point. */
+int nus_bm_warp_device(nus_blockmatch *h, const void *d_a, size_t a_stride, const void *d_b, size_t b_stride, uint32_t w, uint32_t hgt,
+                       uint32_t n_pairs, const void *d_vectors, const float *times, uint32_t n_times, int mode, void *d_out,
+                       size_t out_pair_stride, void *stream);
+/* Block-matched frame generation over a device-resident stream, no host in the loop: n_frames RGBA8 frames frame_stride bytes apart
+ * (a multiple of 4 of at least w*hgt*4; the gaps are never read), pair k = (frame k, frame k + 1), its frames at d_mid +
+ * k * mid_pair_stride + j * w*hgt*4 (mid_pair_stride as out_pair_stride above).  One search launch over all pairs, the confidence
+ * pass as the handle is set, one launch of nus_bm_warp_device's kernel; with nus_bm_set_scene_detect on, the detector and the cut
+ * rule behind it as in nus_bm_interpolate (off: no byte differs).  d_vectors (may be NULL) receives exactly what
+ * nus_bm_estimate_device writes.  In NUS_INTERP_MODE_EXACT pair k's frames are byte for byte what nus_bm_interpolate returns for
+ * (frame k, frame k + 1) under the same settings, at every batch position and for every batch size; NUS_INTERP_MODE_FMA holds the
+ * contract stated at nus_bm_warp_device.  d_workspace: 16-byte aligned, at least nus_bm_stream_workspace_size(h, w, hgt, n_frames)
+ * bytes at the handle's current settings -- the search's workspace, the vectors of every pair (used when d_vectors is NULL) and,
+ * with detection on, the detector's workspace and flags; 0 (and the reason in nus_bm_last_error) for an invalid shape.  At most
+ * 65535 pairs and block rows, as nus_bm_estimate_device.  n_frames < 2: NUS_OK, nothing launched.  Enqueue only; argument errors as
+ * above. */
+size_t nus_bm_stream_workspace_size(nus_blockmatch *h, uint32_t w, uint32_t hgt, uint32_t n_frames);
+int nus_bm_interpolate_multi_device_stream(nus_blockmatch *h, const void *d_frames, size_t frame_stride, uint32_t n_frames, uint32_t w,
+                                           uint32_t hgt, const float *times, uint32_t n_times, int mode, void *d_workspace,
+                                           size_t workspace_bytes, void *d_vectors, void *d_mid, size_t mid_pair_stride, void *stream);
 
 /* ---- Scene-cut detection and the cut-aware output rule ------------------------------------------------------------
  * BUILD-DEFINED: the reference has no such stage; its GUI interpolates every pair of a stream, the one that straddles a cut

@@ -158,6 +158,9 @@ SIGNATURES = [
     ("nus_bm_estimate_device", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _vp, _sz, _vp, _vp, _vp, _vp, _i, _vp]),
     ("nus_bm_estimate", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _vp, _vp, _vp]),
     ("nus_bm_interpolate", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _vp, _u32, _i, _vp, _sz]),
+    ("nus_bm_warp_device", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _vp, _vp, _u32, _i, _vp, _sz, _vp]),
+    ("nus_bm_stream_workspace_size", _sz, [_vp, _u32, _u32, _u32]),
+    ("nus_bm_interpolate_multi_device_stream", _i, [_vp, _vp, _sz, _u32, _u32, _u32, _vp, _u32, _i, _vp, _sz, _vp, _vp, _sz, _vp]),
     ("nus_scene_workspace_size", _sz, [_u32, _u32, _u32]),
     ("nus_scene_detect_device", _i, [_vp, _sz, _vp, _sz, _u32, _u32, _u32, _i, _u32, _u32, _vp, _sz, _vp, _vp, _vp]),
     ("nus_scene_detect", _i, [_i, _vp, _sz, _vp, _sz, _u32, _u32, _i, _u32, _u32, _vp, _vp]),

@@ -110,6 +110,44 @@ class BlockMatcher:
                                                      int(n_pairs), d_workspace or None, int(workspace_bytes), d_vectors or None,
                                                      d_sad or None, d_flags or None, d_flow or None, fmt, stream or None))
 
+    def warp_device(self, d_a: int, a_stride: int, d_b: int, b_stride: int, w: int, h: int, n_pairs: int, d_vectors: int, d_out: int,
+                    *, times: Optional[Sequence[float]] = None, multiplier: Optional[int] = None, mode: str = "exact",
+                    out_pair_stride: int = 0, stream: int = 0) -> None:
+        """Enqueue the warp + blend of `n_pairs` pairs straight from their block vectors (nus_bm_warp_device): `d_vectors` as
+        `estimate_device` writes them at this block size; frame (i, k) at d_out + i * out_pair_stride + k * w*h*4 (0: tightly
+        packed), at `times` or at frame_times(multiplier)."""
+        m = _MODE.get(str(mode).lower())
+        if m is None:
+            raise ValueError("mode must be 'exact' or 'fma'")
+        ts = _time_array(times, multiplier)
+        self._check(self._lib.nus_bm_warp_device(self._h, d_a or None, int(a_stride), d_b or None, int(b_stride), int(w), int(h),
+                                                 int(n_pairs), d_vectors or None, ts, len(ts), m, d_out or None, int(out_pair_stride),
+                                                 stream or None))
+
+    def stream_workspace_size(self, w: int, h: int, n_frames: int) -> int:
+        """Bytes of device workspace `interpolate_stream_device` needs at the current settings (nus_bm_stream_workspace_size);
+        ValueError for an invalid shape."""
+        n = int(self._lib.nus_bm_stream_workspace_size(self._h, int(w), int(h), int(n_frames)))
+        if n == 0:
+            raise ValueError(self._lib.nus_bm_last_error(self._h).decode("utf-8", "replace"))
+        return n
+
+    def interpolate_stream_device(self, d_frames: int, frame_stride: int, n_frames: int, w: int, h: int, d_workspace: int,
+                                  workspace_bytes: int, d_mid: int, *, times: Optional[Sequence[float]] = None,
+                                  multiplier: Optional[int] = None, mode: str = "exact", d_vectors: int = 0,
+                                  mid_pair_stride: int = 0, stream: int = 0) -> None:
+        """Enqueue block-matched frame generation over `n_frames` device frames `frame_stride` bytes apart
+        (nus_bm_interpolate_multi_device_stream): pair k = (frame k, frame k + 1), its frames at d_mid + k * mid_pair_stride +
+        j * w*h*4; the pairs' vectors at d_vectors (0: not wanted).  Scene detection as set_scene_detect left it."""
+        m = _MODE.get(str(mode).lower())
+        if m is None:
+            raise ValueError("mode must be 'exact' or 'fma'")
+        ts = _time_array(times, multiplier)
+        self._check(self._lib.nus_bm_interpolate_multi_device_stream(self._h, d_frames or None, int(frame_stride), int(n_frames), int(w),
+                                                                     int(h), ts, len(ts), m, d_workspace or None, int(workspace_bytes),
+                                                                     d_vectors or None, d_mid or None, int(mid_pair_stride),
+                                                                     stream or None))
+
     def estimate(self, frame_a, frame_b, w: int, h: int):
         """Host frames (bytes or uint8 arrays) -> (vectors int16 (blocks_y, blocks_x, 2) as (dx, dy), sad uint32 (blocks_y,
         blocks_x), flags uint8 (blocks_y, blocks_x))."""

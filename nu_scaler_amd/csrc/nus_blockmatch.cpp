@@ -209,6 +209,128 @@ int BlockMatcher::estimate_device(const void *d_a, size_t a_stride, const void *
     return enqueue(d_a, a_stride, d_b, b_stride, w, h, n_pairs, d_workspace, d_vectors, d_sad, d_flags, d_flow, flow_format, stream);
 }
 
+int BlockMatcher::warp_device(const void *d_a, size_t a_stride, const void *d_b, size_t b_stride, uint32_t w, uint32_t h, uint32_t n_pairs,
+                              const void *d_vectors, const float *times, uint32_t n_times, int mode, void *d_out, size_t out_pair_stride,
+                              hipStream_t stream)
+{
+    static const char *const who = "nus_bm_warp_device";
+    std::lock_guard<std::mutex> lk(mu_);
+    int st = pass(check_dims(who, w, h, kMaxPixels));
+    if (st != kOk) return st;
+    if (!d_a || !d_b || !d_vectors || !d_out) return fail(kInvalidArgument, fmt("%s: null device pointer", who));
+    if ((st = pass(check_interp_times(who, times, n_times))) != kOk) return st;
+    if (mode != 0 && mode != 1) return fail(kInvalidArgument, fmt("%s: mode must be NUS_INTERP_MODE_EXACT or NUS_INTERP_MODE_FMA", who));
+    if ((st = pass(check_pixel_aligned(who, d_a, a_stride, d_b, b_stride, d_out, d_vectors, 4))) != kOk) return st;
+    if ((st = pass(check_out_pair_stride(who, out_pair_stride, n_times, (size_t)w * h * 4))) != kOk) return st;
+    if (n_pairs == 0) return kOk;
+    if ((st = select_device(device_)) != kOk) return st;
+    return enqueue_warp(d_a, a_stride, d_b, b_stride, w, h, n_pairs, d_vectors, times, n_times, mode, d_out, out_pair_stride, stream);
+}
+
+int BlockMatcher::enqueue_warp(const void *d_a, size_t a_stride, const void *d_b, size_t b_stride, uint32_t w, uint32_t h,
+                               uint32_t n_pairs, const void *d_vectors, const float *times, uint32_t n_times, int mode, void *d_out,
+                               size_t out_pair_stride, hipStream_t stream)
+{
+    BmWarpLaunch L;
+    L.a = static_cast<const uint8_t *>(d_a);
+    L.b = static_cast<const uint8_t *>(d_b);
+    L.a_stride = a_stride;
+    L.b_stride = b_stride;
+    L.w = w;
+    L.h = h;
+    L.n_pairs = n_pairs;
+    L.bs = bs_;
+    L.vectors = static_cast<const int16_t *>(d_vectors);
+    L.times = times;
+    L.n_times = n_times;
+    L.fma = mode == 1;
+    L.out = static_cast<uint8_t *>(d_out);
+    L.out_pair_stride = out_pair_stride;
+    L.stream = stream;
+    const hipError_t e = launch_bm_warp(L);
+    if (e != hipSuccess) return fail_hip(e, "block-vector warp+blend launch");
+    return kOk;
+}
+
+// The stream entry point's workspace: the search's, the vectors of every pair (used when the caller keeps none) and, with
+// detection on, the detector's workspace and one flag byte per pair.
+BlockMatcher::StreamLayout BlockMatcher::stream_layout(uint32_t w, uint32_t h, uint32_t n_pairs) const
+{
+    StreamLayout l;
+    const BmShape s = bm_shape(w, h, bs_, n_pairs);
+    l.o_vec = up16(s.workspace_bytes);
+    l.o_scene = l.o_vec + up16((size_t)n_pairs * s.blocks_x * s.blocks_y * 4);
+    l.o_cut = l.o_scene + (scene_ ? up16(scene_shape(w, h, n_pairs).workspace_bytes) : 0);
+    l.total = l.o_cut + (scene_ ? up16(n_pairs) : 0);
+    return l;
+}
+
+size_t BlockMatcher::stream_workspace_size(uint32_t w, uint32_t h, uint32_t n_frames)
+{
+    static const char *const who = "nus_bm_stream_workspace_size";
+    std::lock_guard<std::mutex> lk(mu_);
+    const uint32_t n_pairs = n_frames < 2 ? 1 : n_frames - 1;
+    if (check_shape(who, w, h, n_pairs) != kOk) return 0;
+    if (scene_) {
+        const std::string too_many = check_scene_launch(w, h, n_pairs);
+        if (!too_many.empty()) {
+            fail(kInvalidArgument, fmt("%s: %s", who, too_many.c_str()));
+            return 0;
+        }
+    }
+    return stream_layout(w, h, n_pairs).total;
+}
+
+int BlockMatcher::interpolate_multi_device_stream(const void *d_frames, size_t frame_stride, uint32_t n_frames, uint32_t w, uint32_t h,
+                                                  const float *times, uint32_t n_times, int mode, void *d_workspace,
+                                                  size_t workspace_bytes, void *d_vectors, void *d_mid, size_t mid_pair_stride,
+                                                  hipStream_t stream)
+{
+    static const char *const who = "nus_bm_interpolate_multi_device_stream";
+    std::lock_guard<std::mutex> lk(mu_);
+    const uint32_t n_pairs = n_frames < 2 ? 1 : n_frames - 1;
+    int st = check_shape(who, w, h, n_pairs);
+    if (st != kOk) return st;
+    if (!d_frames || !d_workspace || !d_mid) return fail(kInvalidArgument, fmt("%s: null device pointer", who));
+    if ((st = pass(check_interp_times(who, times, n_times))) != kOk) return st;
+    if (mode != 0 && mode != 1) return fail(kInvalidArgument, fmt("%s: mode must be NUS_INTERP_MODE_EXACT or NUS_INTERP_MODE_FMA", who));
+    const size_t frame_bytes = (size_t)w * h * 4;
+    if ((st = pass(check_pixel_aligned(who, d_frames, frame_stride, d_frames, frame_stride, d_mid, d_vectors, 4))) != kOk) return st;
+    if (frame_stride < frame_bytes)
+        return fail(kInvalidArgument, fmt("%s: frame_stride %zu is smaller than a %ux%u frame (%zu bytes)", who, frame_stride, w, h, frame_bytes));
+    if ((st = pass(check_out_pair_stride(who, mid_pair_stride, n_times, frame_bytes))) != kOk) return st;
+    if (misaligned(d_workspace, 16)) return fail(kInvalidArgument, fmt("%s: workspace must be 16-byte aligned", who));
+    if (scene_) {
+        const std::string too_many = check_scene_launch(w, h, n_pairs);
+        if (!too_many.empty()) return fail(kInvalidArgument, fmt("%s: %s", who, too_many.c_str()));
+    }
+    const StreamLayout l = stream_layout(w, h, n_pairs);
+    if ((st = pass(check_workspace(who, workspace_bytes, l.total, "nus_bm_stream_workspace_size"))) != kOk) return st;
+    if (n_frames < 2) return kOk;
+    const uint8_t *const a = static_cast<const uint8_t *>(d_frames), *const b = a + frame_stride;
+    uint8_t *const ws = static_cast<uint8_t *>(d_workspace);
+    void *const vec = d_vectors ? d_vectors : ws + l.o_vec;
+    // one search over all pairs -> the confidence pass -> one warp from the block vectors -> with detection on, the detector (it
+    // reads the frames only) and the flagged pairs' frames overwritten with repeats, as interpolate() does for its one pair
+    int rc = enqueue(a, frame_stride, b, frame_stride, w, h, n_pairs, ws, vec, nullptr, nullptr, nullptr, 0, stream);
+    if (rc != kOk) return rc;
+    if ((rc = enqueue_warp(a, frame_stride, b, frame_stride, w, h, n_pairs, vec, times, n_times, mode, d_mid, mid_pair_stride, stream)) != kOk)
+        return rc;
+    if (scene_) {
+        SceneLaunch S;
+        S.a = a;
+        S.b = b;
+        S.a_stride = S.b_stride = frame_stride;
+        S.w = w, S.h = h, S.n_pairs = n_pairs, S.stream = stream;
+        hipError_t es = launch_scene_detect(S, scene_mad_, scene_hist_, ws + l.o_scene, nullptr, ws + l.o_cut);
+        if (es != hipSuccess) return fail_hip(es, "scene-detect launch");
+        es = launch_scene_apply(S, n_times, scene_from_a_mask(times, n_times), ws + l.o_cut, static_cast<uint8_t *>(d_mid),
+                                mid_pair_stride ? mid_pair_stride : (size_t)n_times * frame_bytes);
+        if (es != hipSuccess) return fail_hip(es, "scene-apply launch");
+    }
+    return kOk;
+}
+
 int BlockMatcher::check_host_frames(const char *who, const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, uint32_t w,
                                     uint32_t h)
 {

@@ -40,12 +40,30 @@ public:
     int estimate_device(const void *d_a, size_t a_stride, const void *d_b, size_t b_stride, uint32_t w, uint32_t h, uint32_t n_pairs,
                         void *d_workspace, size_t workspace_bytes, void *d_vectors, void *d_sad, void *d_flags, void *d_flow,
                         int flow_format, hipStream_t stream);
+    // warp + blend of n_pairs pairs straight from their block vectors (estimate_device's layout at this handle's block size):
+    // enqueue only.  Frames, strides, time set, mode and out_pair_stride as the dense multi-time warp's.
+    int warp_device(const void *d_a, size_t a_stride, const void *d_b, size_t b_stride, uint32_t w, uint32_t h, uint32_t n_pairs,
+                    const void *d_vectors, const float *times, uint32_t n_times, int mode, void *d_out, size_t out_pair_stride,
+                    hipStream_t stream);
+    // n_frames frames frame_stride apart -> the frames of every pair (k, k + 1): search, confidence pass, warp_device's kernel and,
+    // with detection on, the cut rule.  Enqueue only; the workspace is the caller's.
+    size_t stream_workspace_size(uint32_t w, uint32_t h, uint32_t n_frames); // 0 and the reason for an invalid shape
+    int interpolate_multi_device_stream(const void *d_frames, size_t frame_stride, uint32_t n_frames, uint32_t w, uint32_t h,
+                                        const float *times, uint32_t n_times, int mode, void *d_workspace, size_t workspace_bytes,
+                                        void *d_vectors, void *d_mid, size_t mid_pair_stride, hipStream_t stream);
     int estimate(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, uint32_t w, uint32_t h, int16_t *vectors_out,
                  uint32_t *sad_out, uint8_t *flags_out);
     int interpolate(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, uint32_t w, uint32_t h, const float *times,
                     uint32_t n_times, int mode, uint8_t *out, size_t out_cap);
 
 private:
+    struct StreamLayout { // offsets into the stream entry point's workspace (the search's own part starts it)
+        size_t o_vec = 0, o_scene = 0, o_cut = 0, total = 0;
+    };
+    StreamLayout stream_layout(uint32_t w, uint32_t h, uint32_t n_pairs) const;
+    int enqueue_warp(const void *d_a, size_t a_stride, const void *d_b, size_t b_stride, uint32_t w, uint32_t h, uint32_t n_pairs,
+                     const void *d_vectors, const float *times, uint32_t n_times, int mode, void *d_out, size_t out_pair_stride,
+                     hipStream_t stream);
     int check_shape(const char *who, uint32_t w, uint32_t h, uint32_t n_pairs);
     int check_host_frames(const char *who, const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, uint32_t w, uint32_t h);
     int ensure_tables();                 // first device use: the rank tables of every radius and both orders, once

@@ -862,6 +862,40 @@ int nus_bm_estimate_device(nus_blockmatch *h, const void *d_a, size_t a_stride, 
                  : null_handle();
     });
 }
+int nus_bm_warp_device(nus_blockmatch *h, const void *d_a, size_t a_stride, const void *d_b, size_t b_stride, uint32_t w, uint32_t hgt,
+                       uint32_t n_pairs, const void *d_vectors, const float *times, uint32_t n_times, int mode, void *d_out,
+                       size_t out_pair_stride, void *stream)
+{
+    return guarded<int>("nus_bm_warp_device", [&]() -> int {
+        return h ? h->impl.warp_device(d_a, a_stride, d_b, b_stride, w, hgt, n_pairs, d_vectors, times, n_times, mode, d_out,
+                                       out_pair_stride, static_cast<hipStream_t>(stream))
+                 : null_handle();
+    });
+}
+size_t nus_bm_stream_workspace_size(nus_blockmatch *h, uint32_t w, uint32_t hgt, uint32_t n_frames)
+{
+    try {
+        if (!h) {
+            null_handle();
+            return 0;
+        }
+        return h->impl.stream_workspace_size(w, hgt, n_frames);
+    } catch (...) {
+        nus::set_thread_error("nus_bm_stream_workspace_size: unexpected exception");
+        return 0;
+    }
+}
+int nus_bm_interpolate_multi_device_stream(nus_blockmatch *h, const void *d_frames, size_t frame_stride, uint32_t n_frames, uint32_t w,
+                                           uint32_t hgt, const float *times, uint32_t n_times, int mode, void *d_workspace,
+                                           size_t workspace_bytes, void *d_vectors, void *d_mid, size_t mid_pair_stride, void *stream)
+{
+    return guarded<int>("nus_bm_interpolate_multi_device_stream", [&]() -> int {
+        return h ? h->impl.interpolate_multi_device_stream(d_frames, frame_stride, n_frames, w, hgt, times, n_times, mode, d_workspace,
+                                                           workspace_bytes, d_vectors, d_mid, mid_pair_stride,
+                                                           static_cast<hipStream_t>(stream))
+                 : null_handle();
+    });
+}
 int nus_bm_estimate(nus_blockmatch *h, const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, uint32_t w, uint32_t hgt,
                     void *vectors_out, uint32_t *sad_out, uint8_t *flags_out)
 {

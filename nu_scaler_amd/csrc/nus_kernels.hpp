@@ -310,6 +310,24 @@ struct BmLaunch {
 };
 hipError_t launch_blockmatch(const BmLaunch &L);
 
+// Warp + blend straight from the block vectors (nus_k_bm_warp.hip; nus_bm_warp_device): the frames launch_warp_blend writes from
+// the flow launch_blockmatch expands those vectors to, without that flow.  RGBA8 frames; vectors in launch_blockmatch's layout at
+// block size bs; frame k of pair i at out + i * out_pair_stride + k * w * h * 4.
+struct BmWarpLaunch {
+    const uint8_t *a = nullptr, *b = nullptr;
+    size_t a_stride = 0, b_stride = 0; // bytes between consecutive pairs
+    uint32_t w = 0, h = 0, n_pairs = 1;
+    uint32_t bs = 16;               // 8, 16 or 32
+    const int16_t *vectors = nullptr;
+    const float *times = nullptr;   // 1 .. kInterpMaxTimes
+    uint32_t n_times = 0;
+    bool fma = false;               // as WarpLaunch::fma
+    uint8_t *out = nullptr;
+    size_t out_pair_stride = 0;     // 0: the pair's frames tightly packed
+    hipStream_t stream = nullptr;
+};
+hipError_t launch_bm_warp(const BmWarpLaunch &L);
+
 // Scene-cut detection and the cut-aware output rule (nus_k_scene.hip; nus_scene_* in include/nuscaler_hip.h).  Pair i reads A at
 // a + i * a_stride and B at b + i * b_stride (4-byte aligned).  The workspace holds the measure kernel's per-workgroup partials:
 // u64 SADs at sad_offset, 64 u32 bins (32 of A, 32 of B) at hist_offset.

@@ -42,6 +42,31 @@ __device__ __forceinline__ float4 sample_corner(__amdgpu_buffer_rsrc_t rs, uint3
     return make_float4(r[0], r[1], r[2], r[3]);
 }
 
+// The one-pixel-per-thread kernels' sample (frames narrower or lower than 2 pixels, or of 4 GiB and more: 64-bit addressing, border
+// selects).  interpolation/mod.rs:467-510: clamp, bilinear, truncate to u8 -- returned as the four truncated
+// channel values still in f32 (floor of a value in [0, 255]) so the blend needs no unpack.
+__device__ __forceinline__ float4 sample_trunc(const uint32_t *__restrict__ f, uint32_t w, uint32_t h, float x, float y)
+{
+    x = fminf(fmaxf(x, 0.0f), (float)(w - 1));
+    y = fminf(fmaxf(y, 0.0f), (float)(h - 1));
+    const float xfl = floorf(x), yfl = floorf(y);
+    const uint32_t x0 = (uint32_t)xfl, y0 = (uint32_t)yfl;
+    const uint32_t x1 = umin(x0 + 1, w - 1), y1 = umin(y0 + 1, h - 1);
+    const float xf = x - xfl, yf = y - yfl;
+    const float nxf = 1.0f - xf, nyf = 1.0f - yf;
+    const uint32_t p00 = f[(size_t)y0 * w + x0], p01 = f[(size_t)y0 * w + x1];
+    const uint32_t p10 = f[(size_t)y1 * w + x0], p11 = f[(size_t)y1 * w + x1];
+    float r[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const float top = ch_f32(p00, c) * nxf + ch_f32(p01, c) * xf;
+        const float bottom = ch_f32(p10, c) * nxf + ch_f32(p11, c) * xf;
+        const float value = top * nyf + bottom * yf;
+        r[c] = fminf(floorf(value), 255.0f); // `value as u8`; value >= 0 here
+    }
+    return make_float4(r[0], r[1], r[2], r[3]);
+}
+
 // One output pixel at (xfl, yfl) with flow f (delta A -> B): A sampled at p - t f, B at p + (1 - t) f, each sample truncated to u8 as
 // sample_frame returns it, then the blend of the two truncated samples with the CPU's three roundings in BOTH modes: with integer
 // operands and a t like 0.3 a tenth of the exact results are integers themselves (0.7 * 10 + 0.3 * 20 = 13), and there the truncation

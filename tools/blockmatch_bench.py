@@ -11,7 +11,16 @@ the floor of the search -- candidates x pixels byte-SAD lane-operations at 78.6 
 / 2 per FMA), an estimate from shapes -- and the fraction of it reached.  A last line times the FAST Horn-Schunck flow stream
 (nus_flow_estimate_device_stream, tools/flow_stream_bench.py's mode 9) on 33 frames of 1080p in the same process: the project's
 other estimator.
-usage: python tools/blockmatch_bench.py [--reps R] [--rounds N] [--quick]"""
+--stream: instead, frame generation over a device-resident stream of 65 frames of 1080p (64 distinct pairs, 539 MB), per preset and
+per K in {1, 3, 7} in-between frames per pair, FMA mode, us per pair of
+  stream        nus_bm_interpolate_multi_device_stream: search, confidence pass, the warp straight from the block vectors;
+  dense_route   the same frames from the entry points that were there before: nus_bm_estimate_device with an F16 flow, then
+                nus_interp_interpolate_multi_device reading it;
+  bm_warp       nus_bm_warp_device alone, on the vectors of the stream;
+  dense_warp    nus_interp_interpolate_multi_device alone, on their expanded flow;
+  flow_expand   k_bm_flow's share: nus_bm_estimate_device with the flow minus without.
+The legs of a case alternate in one process, bracket by bracket; each figure is the median of its brackets.
+usage: python tools/blockmatch_bench.py [--reps R] [--rounds N] [--quick] [--stream]"""
 import argparse
 import json
 import os
@@ -51,17 +60,107 @@ def timed(fn, reps, warm_seconds=1.0, rounds=5):
     return got[len(got) // 2]
 
 
+def timed_alternating(fns, reps, warm_seconds=0.5, rounds=5):
+    """The legs of one case side by side: every leg warmed, then `rounds` times one bracket of each in turn -> median ms per call."""
+    import time
+
+    for fn in fns:
+        fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < warm_seconds:
+            for _ in range(reps):
+                fn()
+            torch.cuda.synchronize()
+    got = [[] for _ in fns]
+    for _ in range(max(1, rounds)):
+        for i, fn in enumerate(fns):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(reps):
+                fn()
+            b.record()
+            torch.cuda.synchronize()
+            got[i].append(a.elapsed_time(b) / reps)
+    return [sorted(g)[len(g) // 2] for g in got]
+
+
+def stream_legs(args):
+    dev = torch.device("cuda:0")
+    s = torch.cuda.current_stream().cuda_stream
+    w, h, n_frames = 1920, 1080, 65
+    n, fb = n_frames - 1, 1920 * 1080 * 4
+    # every frame the one before moved by a few pixels: 64 distinct pairs
+    frames = syn.noise_stream_torch(n_frames, w, h, dev)
+    for k in range(n):
+        frames[k + 1] = torch.roll(frames[k], (5 - 2 * (k % 6), 3 * (k % 7) - 9), (0, 1))
+    base = frames.data_ptr()
+    flow = torch.empty((n, h, w, 2), dtype=torch.float16, device=dev)
+    it = nsc.WgpuFrameInterpolator()
+    it.set_flow_format("f16")
+    it.set_mode("fma")
+    for K in (1, 3, 7):
+        times = [0.5] if K == 1 else nsc.frame_times(K + 1)
+        mid = torch.empty((n, K, h, w, 4), dtype=torch.uint8, device=dev)
+        mid_d = torch.empty((n, K, h, w, 4), dtype=torch.uint8, device=dev)
+        for name, bs, radius in PRESETS:
+            bm = nsc.BlockMatcher(name)
+            nbx, nby = bm.block_grid(w, h)
+            ws_n, sws_n = bm.workspace_size(w, h, n), bm.stream_workspace_size(w, h, n_frames)
+            ws = torch.empty(ws_n, dtype=torch.uint8, device=dev)
+            sws = torch.empty(sws_n, dtype=torch.uint8, device=dev)
+            vec = torch.empty((n, nby, nbx, 2), dtype=torch.int16, device=dev)
+
+            def estimate(d_flow=0):
+                bm.estimate_device(base, fb, base + fb, fb, w, h, n, ws.data_ptr(), ws_n, vec.data_ptr(), 0, 0, d_flow, "f16", s)
+
+            def dense_warp():
+                it.interpolate_multi_device(base, fb, base + fb, fb, flow.data_ptr(), w, h, times, mid_d.data_ptr(), 0, n, s)
+
+            def dense_route():
+                estimate(flow.data_ptr())
+                dense_warp()
+
+            def stream():
+                bm.interpolate_stream_device(base, fb, n_frames, w, h, sws.data_ptr(), sws_n, mid.data_ptr(), times=times, mode="fma",
+                                             stream=s)
+
+            def bm_warp():
+                bm.warp_device(base, fb, base + fb, fb, w, h, n, vec.data_ptr(), mid.data_ptr(), times=times, mode="fma", stream=s)
+
+            dense_route()  # vec and flow hold this preset's motion for the warp-alone legs
+            stream()
+            torch.cuda.synchronize()
+            same = bool(torch.equal(mid, mid_d))
+            legs = [stream, dense_route, bm_warp, dense_warp, estimate, lambda: estimate(flow.data_ptr())]
+            ms = timed_alternating(legs, args.reps, args.warm_seconds, args.rounds)
+            us = [round(x * 1e3 / n, 2) for x in ms]
+            row = {"case": f"{w}x{h}x{n}_{name}_K{K}_stream", "width": w, "height": h, "pairs": n, "block_size": bs,
+                   "search_radius": radius, "n_times": K, "mode": "fma", "working_set_bytes": frames.numel(),
+                   "stream_equals_dense_route_bytes": same, "us_per_pair_stream": us[0], "us_per_pair_dense_route": us[1],
+                   "stream_over_dense_route": round(us[0] / us[1], 3), "us_per_pair_bm_warp": us[2], "us_per_pair_dense_warp": us[3],
+                   "us_per_pair_flow_expand": round(us[5] - us[4], 2),
+                   "bm_warp_over_dense_warp_plus_expand": round(us[2] / (us[3] + us[5] - us[4]), 3)}
+            print(json.dumps(row), flush=True)
+            del ws, sws, vec
+        del mid, mid_d
+        torch.cuda.synchronize()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5, help="calls per timed bracket")
     ap.add_argument("--rounds", type=int, default=5, help="timed brackets per case; the median is reported")
     ap.add_argument("--warm-seconds", type=float, default=0.5)
     ap.add_argument("--quick", action="store_true", help="one warm-up call and one bracket of 2 calls per case (profiling runs)")
+    ap.add_argument("--stream", action="store_true", help="the stream legs (see above) instead of the estimator's cases")
     args = ap.parse_args()
     if nsc.device_count() < 1:
         raise SystemExit("blockmatch_bench: no HIP device")
     if args.quick:
         args.reps, args.rounds, args.warm_seconds = 2, 1, 0.0
+    if args.stream:
+        return stream_legs(args)
     dev = torch.device("cuda:0")
     s = torch.cuda.current_stream().cuda_stream
     it = nsc.WgpuFrameInterpolator()
