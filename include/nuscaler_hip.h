@@ -598,11 +598,39 @@ int nus_metrics_compare(int device, const uint8_t *a, size_t a_len, const uint8_
  *            flow nus_interp_interpolate_device defines (A is sampled at p - t v, B at p + (1 - t) v).  The reference's CPU text
  *            (:738-742) has the opposite sign, which under its own matcher moves content the wrong way: B = A shifted by +s
  *            gives v = +s, and the true mid-frame is A sampled at p - s / 2.
+ *   Forward-backward check (nus_bm_set_bidirectional, default off).  BUILD-DEFINED: the reference names it as what its confidence
+ *            pass lacks ("bidirectional motion estimation and consistency checks between forward and backward motion vectors",
+ *            :798-799).  The search runs one way, so content that exists in one frame only -- background about to be covered or
+ *            just uncovered, whatever enters or leaves at the border -- still gets a winner.  With the check on, per pair, at the
+ *            handle's block size bs, radius and tie order:
+ *              1. F, sadF: the search above (A's blocks in B).  G, sadG: the same search with the frames exchanged (B's blocks in
+ *                 A, on the same block grid).
+ *              2. A's block (bx, by) with F = (dx, dy) is consistent iff sadF != NUS_BM_NO_MATCH, sadG[cy][cx] != NUS_BM_NO_MATCH and
+ *                 |dx + gx| + |dy + gy| <= tolerance, where cx = clamp(bx bs + dx + bs / 2, 0, w - 1) / bs, cy = clamp(by bs + dy +
+ *                 bs / 2, 0, h - 1) / bs and (gx, gy) = G[cy][cx]: the block its centre lands in points back at it.  B's block
+ *                 (bx, by) is consistent by the same rule with F and G exchanged.
+ *              3. V = F where A's block is consistent; else V = -G[by][bx] where B's block at the same grid position is consistent
+ *                 (flag bit 2); else the block is unresolved.
+ *              4. One pass over step 3's result (so no order matters): an unresolved block takes, for dx and for dy on their own, the
+ *                 lower median -- element (n - 1) / 2 of the n values in ascending order -- of that component over those of its up
+ *                 to 8 neighbours that step 3 resolved (flag bit 3); with none, the zero vector (flag bit 4).
+ *            d_vectors receives V (every component within +-24), d_sad stays the forward SAD, d_flags carries bits 2 - 4.  THE
+ *            CONFIDENCE PASS IS NOT RUN AND BITS 0 AND 1 STAY CLEAR, WHATEVER nus_bm_set_refine SAYS: run behind V the pass zeroes
+ *            true motion boundaries and takes back most of what the check gains, and on its own it loses to doing nothing as
+ *            soon as the background moves, a cross-fade being the wrong fallback for a pan.  PSNR of the t = 0.5 frame against a
+ *            rendered true mid-frame, on synthetic pairs of a panning background under a moving square (192 x 128 and 200 x 72,
+ *            all presets; DESIGN 8.5 has the table): raw winners 22.6 .. 29.8 dB, confidence pass 19.2 .. 26.6 dB, this check
+ *            28.1 .. 32.0 dB, the smallest gains 2.06 dB over the raw winners and 3.74 dB over the pass.  Everything behind the
+ *            vectors (flow expansion, nus_bm_warp_device, nus_bm_interpolate, the stream entry point, scene detection) is
+ *            unchanged and runs on V.  Cost: the search runs twice; both workspaces grow while the check is on and are their old
+ *            sizes with it off, when every entry point writes the bytes it wrote before.  tolerance 0 .. 96 (default
+ *            NUS_BM_BIDIR_DEFAULT_TOLERANCE: a SETTING, NOT A MEASUREMENT; 0, 2 and 4 moved the numbers above by under 1 dB).
  * Quality presets (:531-542): High 8 / 24, Medium 16 / 16 (default), Low 32 / 8. */
 typedef struct nus_blockmatch nus_blockmatch;
 typedef enum nus_bm_tie_order { NUS_BM_TIES_SCAN = 0, NUS_BM_TIES_CENTER = 1 } nus_bm_tie_order;
 #define NUS_BM_MAX_RADIUS 24
 #define NUS_BM_NO_MATCH 0xFFFFFFFFu
+#define NUS_BM_BIDIR_DEFAULT_TOLERANCE 2
 
 nus_blockmatch *nus_bm_create(void); /* never touches the GPU */
 void nus_bm_destroy(nus_blockmatch *h);
@@ -612,12 +640,16 @@ int nus_bm_set_params(nus_blockmatch *h, uint32_t block_size, uint32_t search_ra
 int nus_bm_set_quality(nus_blockmatch *h, int quality); /* nus_interp_quality_level */
 int nus_bm_set_tie_order(nus_blockmatch *h, int order);
 int nus_bm_set_refine(nus_blockmatch *h, int enabled);
+/* enabled 0 or 1, tolerance 0 .. 96; anything else: NUS_ERR_INVALID_ARGUMENT before any HIP call.  Workspace sizes asked for before
+ * the call no longer hold after it. */
+int nus_bm_set_bidirectional(nus_blockmatch *h, int enabled, uint32_t tolerance);
 /* Workspace bytes nus_bm_estimate_device needs at the handle's block size; 0 (and the reason in nus_bm_last_error) for an invalid
  * shape. */
 size_t nus_bm_workspace_size(nus_blockmatch *h, uint32_t w, uint32_t hgt, uint32_t n_pairs);
 /* n_pairs pairs as nus_interp_interpolate_device (same pointers and strides).  Per block: d_vectors 2 x int16 (dx, dy), after the
  * confidence pass (the raw winners with refine off); d_sad (may be NULL) the raw winner's SAD, u32; d_flags (may be NULL) u8, bit 0
- * = the pass zeroed this block, bit 1 = the pair's motion was not smooth (set on every block of the pair alike).  d_flow (may be
+ * = the pass zeroed this block, bit 1 = the pair's motion was not smooth (set on every block of the pair alike); with the
+ * forward-backward check on, V and bits 2 - 4 as defined above instead.  d_flow (may be
  * NULL): the dense flow, w*h*8 bytes per pair and 8-byte aligned (NUS_FLOW_F32) or w*h*4 and 4-byte aligned (NUS_FLOW_F16; the
  * vectors are integers of magnitude <= 24, exact in f16).  d_workspace 16-byte aligned.  n_pairs == 0: NUS_OK, nothing launched.
  * Enqueue only on `stream`: no allocation, no synchronisation (a handle's first call puts its 163 KiB of rank tables on the

@@ -35,6 +35,7 @@ FLOW_F32, FLOW_F16 = 0, 1  # nus_flow_format
 INTERP_MODE_EXACT, INTERP_MODE_FMA = 0, 1  # nus_interp_mode_t
 BM_TIES_SCAN, BM_TIES_CENTER = 0, 1  # nus_bm_tie_order
 BM_MAX_RADIUS = 24  # NUS_BM_MAX_RADIUS
+BM_BIDIR_DEFAULT_TOLERANCE = 2  # NUS_BM_BIDIR_DEFAULT_TOLERANCE: a setting, not a measurement
 SCENE_DEFAULT_MAD, SCENE_DEFAULT_HIST_PERMILLE = 20, 400  # NUS_SCENE_DEFAULT_*: settings, not measurements
 BM_NO_MATCH = 0xFFFFFFFF  # NUS_BM_NO_MATCH: the SAD of a block with no admitted candidate
 
@@ -154,6 +155,7 @@ SIGNATURES = [
     ("nus_bm_set_quality", _i, [_vp, _i]),
     ("nus_bm_set_tie_order", _i, [_vp, _i]),
     ("nus_bm_set_refine", _i, [_vp, _i]),
+    ("nus_bm_set_bidirectional", _i, [_vp, _i, _u32]),
     ("nus_bm_workspace_size", _sz, [_vp, _u32, _u32, _u32]),
     ("nus_bm_estimate_device", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _vp, _sz, _vp, _vp, _vp, _vp, _i, _vp]),
     ("nus_bm_estimate", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _vp, _vp, _vp]),

@@ -30,10 +30,12 @@ def block_grid(w: int, h: int, block_size: int) -> tuple[int, int]:
 class BlockMatcher:
     """Full-search block matching of RGBA8 frame pairs.  `quality` picks a preset ("high" 8 / 24, "medium" 16 / 16, "low" 32 / 8);
     `block_size` (8, 16, 32) and `search_radius` (1 .. 24) override it.  `tie_order`: "center" (default: the smallest
-    displacement among equal SADs) or "scan" (the reference's first minimum in dy-major order).  `refine`: the confidence pass."""
+    displacement among equal SADs) or "scan" (the reference's first minimum in dy-major order).  `refine`: the confidence pass.
+    `bidirectional`: the forward-backward check with `tolerance` (see set_bidirectional) in place of that pass."""
 
     def __init__(self, quality: str = "medium", *, block_size: Optional[int] = None, search_radius: Optional[int] = None,
-                 tie_order: str = "center", refine: bool = True, device: int = 0):
+                 tie_order: str = "center", refine: bool = True, bidirectional: bool = False,
+                 tolerance: int = C.BM_BIDIR_DEFAULT_TOLERANCE, device: int = 0):
         self._lib = C.lib()
         self._h = self._lib.nus_bm_create()
         if not self._h:
@@ -43,6 +45,7 @@ class BlockMatcher:
         self.set_params(bs if block_size is None else block_size, radius if search_radius is None else search_radius)
         self.set_tie_order(tie_order)
         self.set_refine(refine)
+        self.set_bidirectional(bidirectional, tolerance)
         self.scene_detect, self._scene_thresholds = False, (C.SCENE_DEFAULT_MAD, C.SCENE_DEFAULT_HIST_PERMILLE)
 
     def __del__(self):
@@ -77,6 +80,13 @@ class BlockMatcher:
     def set_refine(self, enabled: bool) -> None:
         self._check(self._lib.nus_bm_set_refine(self._h, 1 if enabled else 0))
         self.refine = bool(enabled)
+
+    def set_bidirectional(self, enabled: bool, tolerance: int = C.BM_BIDIR_DEFAULT_TOLERANCE) -> None:
+        """Forward-backward check (nus_bm_set_bidirectional; off by default): every pair is searched both ways, a block whose
+        two vectors do not answer each other within `tolerance` (0 .. 96, L1) takes the backward vector or the median of its
+        neighbours, and the confidence pass is not run.  The search runs twice and both workspace sizes grow while it is on."""
+        self._check(self._lib.nus_bm_set_bidirectional(self._h, 1 if enabled else 0, int(tolerance)))
+        self.bidirectional, self.tolerance = bool(enabled), int(tolerance)
 
     def set_scene_detect(self, enabled: bool, mad_threshold: int = C.SCENE_DEFAULT_MAD,
                          hist_permille: int = C.SCENE_DEFAULT_HIST_PERMILLE) -> None:
@@ -194,9 +204,11 @@ class PyFrameInterpolator:
     """`PyFrameInterpolator(method="optical_flow", quality="medium")` (interpolation/mod.rs:959-1049).  "block_matching" and
     "simplified" run the block matcher at the quality's preset (name "BlockMatching"); "optical_flow" -- and, as in the reference,
     any unknown method -- is the pyramid + Horn-Schunck estimator followed by the dense-flow warp (name "OpticalFlow"; the quality
-    is kept and reported).  Unknown quality strings in the constructor mean "medium"; the setter raises."""
+    is kept and reported).  Unknown quality strings in the constructor mean "medium"; the setter raises.  `bidirectional` (not
+    in the reference) turns the block matcher's forward-backward check on; the optical-flow method has none and raises."""
 
-    def __init__(self, method: str = "optical_flow", quality: str = "medium", *, device: int = 0, scene_detect: bool = False):
+    def __init__(self, method: str = "optical_flow", quality: str = "medium", *, device: int = 0, scene_detect: bool = False,
+                 bidirectional: bool = False):
         m = str(method).lower()
         self._scene = None  # (not in the reference) a pair flagged as a scene cut gives a repeat of the nearer frame, not a blend
         self._block = m in ("block_matching", "simplified")
@@ -204,8 +216,10 @@ class PyFrameInterpolator:
         self._quality = q if q in _QUALITY else "medium"
         self._size = None
         self._device = int(device)
+        if bidirectional and not self._block:
+            raise ValueError("bidirectional: only the block-matching methods have a forward-backward check")
         if self._block:
-            self._bm = BlockMatcher(self._quality, device=device)
+            self._bm = BlockMatcher(self._quality, device=device, bidirectional=bidirectional)
             if scene_detect:
                 self._bm.set_scene_detect(True)
         else:

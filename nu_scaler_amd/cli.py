@@ -2,7 +2,7 @@
 (SURVEY.md section 8f rank 2): `upscale <in.png> <out.png> --algorithm --scale`, following the
 legacy crate's `upscale_image_file` (Nu_scale/src/upscale/mod.rs:307-338) and the option names of
 its `fullscreen` subcommand (Nu_scale/src/main.rs:36-73: --tech, --quality, --algorithm); `interpolate <a.png> <b.png> <out.png>`
-with zero flow, `--flow` (Horn-Schunck) or `--method block_matching [--quality high|medium|low]`; `compare <a.png> <b.png>`
+with zero flow, `--flow` (Horn-Schunck) or `--method block_matching [--quality high|medium|low] [--bidirectional]`; `compare <a.png> <b.png>`
 prints the `ErrorMetrics` of two images (Nu_scale/src/upscale/common.rs:475-543); `scene <a.png> <b.png>` prints the scene-cut
 detector's verdict on the pair, and `interpolate --multiplier M --scene-detect` writes repeats instead of blends across a cut.
 Everything runs on the HIP device; without one the command fails (no CPU path).
@@ -35,6 +35,10 @@ def build_parser() -> argparse.ArgumentParser:
     it.add_argument("--flow", action="store_true", help="estimate motion (pyramid + Horn-Schunck) instead of zero flow")
     it.add_argument("--method", default=None, help="block_matching: the full-search block matcher supplies the motion field")
     it.add_argument("--quality", default="medium", help="block matching preset: high (8 / 24), medium (16 / 16) or low (32 / 8)")
+    it.add_argument("--bidirectional", action="store_true",
+                    help="with --method block_matching: search both ways and repair the blocks the two searches disagree on")
+    it.add_argument("--bidir-tolerance", type=int, default=None,
+                    help="with --bidirectional: L1 distance (0 .. 96) within which two vectors answer each other (default 2)")
     it.add_argument("--scene-detect", action="store_true",
                     help="with --multiplier: if the scene-cut detector flags the pair, write repeats of the nearer frame, not blends")
     it.add_argument("--device", type=int, default=0)
@@ -181,6 +185,14 @@ def main(argv=None) -> int:
             parser.error(f"--method must be block_matching, got {args.method}")
         if args.quality.lower() not in ("high", "medium", "low"):
             parser.error(f"--quality must be high, medium or low, got {args.quality}")
+    if args.command == "interpolate":
+        if (args.bidirectional or args.bidir_tolerance is not None) and args.method is None:
+            parser.error("--bidirectional needs --method block_matching")
+        if args.bidir_tolerance is not None:
+            if not args.bidirectional:
+                parser.error("--bidir-tolerance needs --bidirectional")
+            if not 0 <= args.bidir_tolerance <= 96:
+                parser.error(f"--bidir-tolerance must be from 0 to 96, got {args.bidir_tolerance}")
     if args.command == "stream":
         try:
             return stream_command(args, list(sys.argv[1:] if argv is None else argv))
@@ -217,7 +229,9 @@ def main(argv=None) -> int:
         elif args.method is not None:
             paths = imagefile.interpolate_image_files_block_matching(args.frame_a, args.frame_b, args.output, args.quality.lower(),
                                                                      0.5 if args.t is None else args.t, args.multiplier,
-                                                                     device=args.device, scene_detect=args.scene_detect)
+                                                                     device=args.device, scene_detect=args.scene_detect,
+                                                                     bidirectional=args.bidirectional,
+                                                                     tolerance=args.bidir_tolerance)
             for path in paths:
                 print(path)
         elif args.multiplier is not None:

@@ -5,7 +5,7 @@
 //
 //   nu_scaler_cli upscale <in.png> <out.png> [--algorithm A] [--scale S] [--tech T] [--quality Q] [--device N]
 //   nu_scaler_cli interpolate <a.png> <b.png> <out.png> [--t X | --multiplier M] [--flow] [--device N]
-//                             [--method block_matching [--quality high|medium|low]]
+//                             [--method block_matching [--quality high|medium|low] [--bidirectional [--bidir-tolerance N]]]
 //   nu_scaler_cli scene <a.png> <b.png> [--mad N] [--hist N] [--device N]   (the scene-cut detector: cut=0|1 mad=.. hist_permille=..)
 //   nu_scaler_cli compare <a.png> <b.png> [--device N]   (MSE / PSNR / SSIM, ErrorMetrics: Nu_scale/src/upscale/common.rs:475-543)
 //   nu_scaler_cli png-copy <in.png> <out.png>        (decode + encode only; no GPU: codec self-check)
@@ -38,6 +38,7 @@ int usage(int rc)
                  "                             [--device N]\n"
                  "       nu_scaler_cli interpolate <a.png> <b.png> <out.png> [--t X | --multiplier 2..8] [--flow] [--device N]\n"
                  "                             [--method block_matching [--quality high|medium|low]] [--scene-detect]\n"
+                 "                             [--bidirectional [--bidir-tolerance 0..96]]   (block matching: forward-backward check)\n"
                  "       nu_scaler_cli scene <a.png> <b.png> [--mad 0..255] [--hist 0..1000] [--device N]\n"
                  "       nu_scaler_cli compare <a.png> <b.png> [--device N]\n"
                  "       nu_scaler_cli png-copy <in.png> <out.png>\n");
@@ -49,6 +50,7 @@ struct Args {
     std::map<std::string, std::string> options;
     bool flow = false;
     bool scene_detect = false;
+    bool bidirectional = false;
 };
 
 bool parse(int argc, char **argv, Args &a, std::string &err)
@@ -59,6 +61,8 @@ bool parse(int argc, char **argv, Args &a, std::string &err)
             a.flow = true;
         } else if (s == "--scene-detect") {
             a.scene_detect = true;
+        } else if (s == "--bidirectional") {
+            a.bidirectional = true;
         } else if (s.rfind("--", 0) == 0) {
             if (i + 1 >= argc) {
                 err = "option " + s + " needs a value";
@@ -192,6 +196,25 @@ int cmd_interpolate(const Args &a)
             return usage(2);
         }
     }
+    const auto tol_it = a.options.find("bidir-tolerance");
+    uint32_t bidir_tolerance = NUS_BM_BIDIR_DEFAULT_TOLERANCE;
+    if ((a.bidirectional || tol_it != a.options.end()) && bm_quality < 0) {
+        std::fprintf(stderr, "nu_scaler_cli: error: --bidirectional needs --method block_matching\n");
+        return usage(2);
+    }
+    if (tol_it != a.options.end()) {
+        if (!a.bidirectional) {
+            std::fprintf(stderr, "nu_scaler_cli: error: --bidir-tolerance needs --bidirectional\n");
+            return usage(2);
+        }
+        char *end = nullptr;
+        const long v = std::strtol(tol_it->second.c_str(), &end, 10);
+        if (end == tol_it->second.c_str() || *end != '\0' || v < 0 || v > 96) {
+            std::fprintf(stderr, "nu_scaler_cli: error: --bidir-tolerance must be from 0 to 96\n");
+            return usage(2);
+        }
+        bidir_tolerance = (uint32_t)v;
+    }
     nus_cli::Image fa, fb;
     std::string err = nus_cli::read_png(a.positional[0], fa);
     if (err.empty()) err = nus_cli::read_png(a.positional[1], fb);
@@ -210,6 +233,7 @@ int cmd_interpolate(const Args &a)
         if (!bm) return fail(nus_last_error());
         int rc = nus_bm_set_device(bm, device);
         if (rc == NUS_OK) rc = nus_bm_set_quality(bm, bm_quality);
+        if (rc == NUS_OK && a.bidirectional) rc = nus_bm_set_bidirectional(bm, 1, bidir_tolerance);
         if (rc == NUS_OK && a.scene_detect) rc = nus_bm_set_scene_detect(bm, 1, NUS_SCENE_DEFAULT_MAD, NUS_SCENE_DEFAULT_HIST_PERMILLE);
         if (rc == NUS_OK)
             rc = nus_bm_interpolate(bm, fa.rgba.data(), fa.rgba.size(), fb.rgba.data(), fb.rgba.size(), fa.width, fa.height, times.data(),

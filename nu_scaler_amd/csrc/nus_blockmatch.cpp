@@ -103,6 +103,17 @@ int BlockMatcher::set_refine(int enabled)
     return kOk;
 }
 
+int BlockMatcher::set_bidirectional(int enabled, uint32_t tolerance)
+{
+    std::lock_guard<std::mutex> lk(mu_);
+    if (enabled != 0 && enabled != 1) return fail(kInvalidArgument, fmt("nus_bm_set_bidirectional: 0 or 1, got %d", enabled));
+    if (tolerance > kBmMaxTolerance)
+        return fail(kInvalidArgument, fmt("nus_bm_set_bidirectional: tolerance must be 0..%u, got %u", kBmMaxTolerance, tolerance));
+    bidir_ = enabled == 1;
+    tolerance_ = tolerance;
+    return kOk;
+}
+
 int BlockMatcher::set_scene_detect(int enabled, uint32_t mad_threshold, uint32_t hist_permille)
 {
     std::lock_guard<std::mutex> lk(mu_);
@@ -130,7 +141,7 @@ size_t BlockMatcher::workspace_size(uint32_t w, uint32_t h, uint32_t n_pairs)
 {
     std::lock_guard<std::mutex> lk(mu_);
     if (check_shape("nus_bm_workspace_size", w, h, n_pairs) != kOk) return 0;
-    return bm_shape(w, h, bs_, n_pairs ? n_pairs : 1).workspace_bytes;
+    return bm_shape(w, h, bs_, n_pairs ? n_pairs : 1, bidir_).workspace_bytes;
 }
 
 int BlockMatcher::ensure_tables()
@@ -179,6 +190,8 @@ int BlockMatcher::enqueue(const void *d_a, size_t a_stride, const void *d_b, siz
     L.cand = L.rank + (size_t)(2 * radius_ + 1) * (2 * radius_ + 1);
     L.workspace = d_workspace;
     L.refine = refine_;
+    L.bidir = bidir_;
+    L.tolerance = tolerance_;
     L.vectors = static_cast<int16_t *>(d_vectors);
     L.sad = static_cast<uint32_t *>(d_sad);
     L.flags = static_cast<uint8_t *>(d_flags);
@@ -203,7 +216,7 @@ int BlockMatcher::estimate_device(const void *d_a, size_t a_stride, const void *
         return fail(kInvalidArgument, fmt("%s: flow_format must be NUS_FLOW_F32 or NUS_FLOW_F16", who));
     if ((st = pass(check_pixel_aligned(who, d_a, a_stride, d_b, b_stride, d_vectors, d_flow, flow_format == 1 ? 4 : 8, d_sad))) != kOk) return st;
     if (misaligned(d_workspace, 16)) return fail(kInvalidArgument, fmt("%s: workspace must be 16-byte aligned", who));
-    const size_t need = bm_shape(w, h, bs_, n_pairs ? n_pairs : 1).workspace_bytes;
+    const size_t need = bm_shape(w, h, bs_, n_pairs ? n_pairs : 1, bidir_).workspace_bytes;
     if ((st = pass(check_workspace(who, workspace_bytes, need, "nus_bm_workspace_size"))) != kOk) return st;
     if (n_pairs == 0) return kOk;
     return enqueue(d_a, a_stride, d_b, b_stride, w, h, n_pairs, d_workspace, d_vectors, d_sad, d_flags, d_flow, flow_format, stream);
@@ -252,12 +265,12 @@ int BlockMatcher::enqueue_warp(const void *d_a, size_t a_stride, const void *d_b
     return kOk;
 }
 
-// The stream entry point's workspace: the search's, the vectors of every pair (used when the caller keeps none) and, with
+// The stream entry point's workspace: the search's (with the forward-backward check's part while that is on), the vectors of every pair (used when the caller keeps none) and, with
 // detection on, the detector's workspace and one flag byte per pair.
 BlockMatcher::StreamLayout BlockMatcher::stream_layout(uint32_t w, uint32_t h, uint32_t n_pairs) const
 {
     StreamLayout l;
-    const BmShape s = bm_shape(w, h, bs_, n_pairs);
+    const BmShape s = bm_shape(w, h, bs_, n_pairs, bidir_);
     l.o_vec = up16(s.workspace_bytes);
     l.o_scene = l.o_vec + up16((size_t)n_pairs * s.blocks_x * s.blocks_y * 4);
     l.o_cut = l.o_scene + (scene_ ? up16(scene_shape(w, h, n_pairs).workspace_bytes) : 0);
@@ -310,8 +323,9 @@ int BlockMatcher::interpolate_multi_device_stream(const void *d_frames, size_t f
     const uint8_t *const a = static_cast<const uint8_t *>(d_frames), *const b = a + frame_stride;
     uint8_t *const ws = static_cast<uint8_t *>(d_workspace);
     void *const vec = d_vectors ? d_vectors : ws + l.o_vec;
-    // one search over all pairs -> the confidence pass -> one warp from the block vectors -> with detection on, the detector (it
-    // reads the frames only) and the flagged pairs' frames overwritten with repeats, as interpolate() does for its one pair
+    // one search over all pairs -> the confidence pass (or the forward-backward check) -> one warp from the block vectors -> with
+    // detection on, the detector (it reads the frames only) and the flagged pairs' frames overwritten with repeats, as
+    // interpolate() does for its one pair
     int rc = enqueue(a, frame_stride, b, frame_stride, w, h, n_pairs, ws, vec, nullptr, nullptr, nullptr, 0, stream);
     if (rc != kOk) return rc;
     if ((rc = enqueue_warp(a, frame_stride, b, frame_stride, w, h, n_pairs, vec, times, n_times, mode, d_mid, mid_pair_stride, stream)) != kOk)
@@ -356,7 +370,7 @@ int BlockMatcher::estimate(const uint8_t *a, size_t a_len, const uint8_t *b, siz
     const int st = check_host_frames(who, a, a_len, b, b_len, w, h);
     if (st != kOk) return st;
     if (!vectors_out) return fail(kInvalidArgument, fmt("%s: vectors_out is null", who));
-    const BmShape s = bm_shape(w, h, bs_, 1);
+    const BmShape s = bm_shape(w, h, bs_, 1, bidir_);
     const size_t frame = up16((size_t)w * h * 4), nb = (size_t)s.blocks_x * s.blocks_y;
     const size_t o_b = frame, o_ws = 2 * frame, o_vec = o_ws + up16(s.workspace_bytes), o_sad = o_vec + up16(nb * 4),
                  o_flags = o_sad + up16(nb * 4), total = o_flags + up16(nb);
@@ -387,7 +401,7 @@ int BlockMatcher::interpolate(const uint8_t *a, size_t a_len, const uint8_t *b, 
     const size_t expected = (size_t)w * h * 4;
     if (out_cap / n_times < expected)
         return fail(kInvalidArgument, fmt("%s: output capacity %zu below n_times * w * h * 4 = %zu", who, out_cap, (size_t)n_times * expected));
-    const BmShape s = bm_shape(w, h, bs_, 1);
+    const BmShape s = bm_shape(w, h, bs_, 1, bidir_);
     const size_t frame = up16(expected), nb = (size_t)s.blocks_x * s.blocks_y;
     const size_t o_b = frame, o_ws = 2 * frame, o_vec = o_ws + up16(s.workspace_bytes), o_flow = o_vec + up16(nb * 4), o_out = o_flow + frame,
                  out_end = o_out + (size_t)n_times * expected,

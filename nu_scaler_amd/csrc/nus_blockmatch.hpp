@@ -33,6 +33,9 @@ public:
     int set_quality(int quality); // nus_interp_quality_level: High 8 / 24, Medium 16 / 16, Low 32 / 8 (interpolation/mod.rs:531-542)
     int set_tie_order(int order);
     int set_refine(int enabled);
+    // Forward-backward check (nus_bm_set_bidirectional): off by default.  On, every pair is searched both ways and the blocks the
+    // two searches disagree on are repaired; the confidence pass is not run, and both workspaces grow.
+    int set_bidirectional(int enabled, uint32_t tolerance);
     // Scene-cut detection in front of interpolate() and the cut-aware output rule behind it (nus_scene_* of the C header): off by
     // default.  On, the frames of a pair the detector flags are repeats of the nearer real frame.
     int set_scene_detect(int enabled, uint32_t mad_threshold, uint32_t hist_permille);
@@ -45,7 +48,7 @@ public:
     int warp_device(const void *d_a, size_t a_stride, const void *d_b, size_t b_stride, uint32_t w, uint32_t h, uint32_t n_pairs,
                     const void *d_vectors, const float *times, uint32_t n_times, int mode, void *d_out, size_t out_pair_stride,
                     hipStream_t stream);
-    // n_frames frames frame_stride apart -> the frames of every pair (k, k + 1): search, confidence pass, warp_device's kernel and,
+    // n_frames frames frame_stride apart -> the frames of every pair (k, k + 1): search, confidence pass or forward-backward check, warp_device's kernel and,
     // with detection on, the cut rule.  Enqueue only; the workspace is the caller's.
     size_t stream_workspace_size(uint32_t w, uint32_t h, uint32_t n_frames); // 0 and the reason for an invalid shape
     int interpolate_multi_device_stream(const void *d_frames, size_t frame_stride, uint32_t n_frames, uint32_t w, uint32_t h,
@@ -76,6 +79,8 @@ private:
     uint32_t bs_ = 16, radius_ = 16; // Medium
     int order_ = kBmTiesCenter;
     bool refine_ = true;
+    bool bidir_ = false;
+    uint32_t tolerance_ = 2;
     bool scene_ = false;
     uint32_t scene_mad_ = 20, scene_hist_ = 400;
     uint16_t *d_tables_ = nullptr;

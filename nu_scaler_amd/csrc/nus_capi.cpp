@@ -839,6 +839,10 @@ int nus_bm_set_refine(nus_blockmatch *h, int enabled)
 {
     return guarded<int>("nus_bm_set_refine", [&]() -> int { return h ? h->impl.set_refine(enabled) : null_handle(); });
 }
+int nus_bm_set_bidirectional(nus_blockmatch *h, int enabled, uint32_t tolerance)
+{
+    return guarded<int>("nus_bm_set_bidirectional", [&]() -> int { return h ? h->impl.set_bidirectional(enabled, tolerance) : null_handle(); });
+}
 size_t nus_bm_workspace_size(nus_blockmatch *h, uint32_t w, uint32_t hgt, uint32_t n_pairs)
 {
     try {

@@ -18,6 +18,8 @@
 //   k_bm_refine      ORs those words (the pair's motion is not smooth), then zeroes every interior block whose L1 differences
 //                    to its 8 neighbours sum to 35 or more, and writes vectors and flags.
 //   k_bm_flow<HALF>  every pixel gets its block's vector as (dx, dy), 2 x f32 or 2 x f16 (|v| <= 24: exact in both).
+// The forward-backward check runs k_bm_search a second time with the frames exchanged; its own two kernels are in
+// nus_k_bm_bidir.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -239,7 +241,7 @@ __global__ __launch_bounds__(256) void k_bm_flow(const short2 *__restrict__ vect
 
 } // namespace
 
-BmShape bm_shape(uint32_t w, uint32_t h, uint32_t bs, uint32_t n_pairs)
+BmShape bm_shape(uint32_t w, uint32_t h, uint32_t bs, uint32_t n_pairs, bool bidir)
 {
     BmShape s;
     s.blocks_x = (w + bs - 1) / bs;
@@ -249,6 +251,15 @@ BmShape bm_shape(uint32_t w, uint32_t h, uint32_t bs, uint32_t n_pairs)
     const size_t raw = (size_t)n_pairs * s.blocks_x * s.blocks_y * 4;
     s.rough_offset = (raw + 15) & ~(size_t)15;
     s.workspace_bytes = s.rough_offset + (size_t)n_pairs * s.rough_groups * 4;
+    if (bidir) {
+        const auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+        s.g_offset = up16(s.workspace_bytes);
+        s.sad_g_offset = s.g_offset + up16(raw);
+        s.sad_f_offset = s.sad_g_offset + up16(raw);
+        s.chosen_offset = s.sad_f_offset + up16(raw);
+        s.state_offset = s.chosen_offset + up16(raw);
+        s.workspace_bytes = s.state_offset + raw / 4;
+    }
     return s;
 }
 
@@ -256,24 +267,46 @@ size_t bm_lds_bytes(uint32_t bs, uint32_t R) { return (size_t)(2 * R + bs) * (2 
 
 hipError_t launch_blockmatch(const BmLaunch &L)
 {
-    const BmShape s = bm_shape(L.w, L.h, L.bs, L.n_pairs);
-    int16_t *raw = L.refine ? static_cast<int16_t *>(L.workspace) : L.vectors;
+    const BmShape s = bm_shape(L.w, L.h, L.bs, L.n_pairs, L.bidir);
+    uint8_t *const ws = static_cast<uint8_t *>(L.workspace);
+    int16_t *raw = (L.refine || L.bidir) ? static_cast<int16_t *>(L.workspace) : L.vectors;
+    uint32_t *sad = L.sad;
+    if (L.bidir && !sad) sad = reinterpret_cast<uint32_t *>(ws + s.sad_f_offset); // the check reads them
     const dim3 grid(s.runs_x, s.blocks_y, L.n_pairs);
     const size_t lds = bm_lds_bytes(L.bs, L.R);
+    // the blocks of `from` searched in `to`
+    const auto search = [&](const uint8_t *from, size_t from_stride, const uint8_t *to, size_t to_stride, int16_t *v, uint32_t *sd) {
 #define NUS_BM_SEARCH(BS)                                                                                                          \
-    hipLaunchKernelGGL(k_bm_search<BS>, grid, dim3(256), lds, L.stream, L.a, L.a_stride, L.b, L.b_stride, L.w, L.h, (int)L.R, L.rank, \
-                       L.cand, s.blocks_x, s.blocks_y, raw, L.sad)
-    if (L.bs == 8)
-        NUS_BM_SEARCH(8);
-    else if (L.bs == 16)
-        NUS_BM_SEARCH(16);
-    else
-        NUS_BM_SEARCH(32);
+    hipLaunchKernelGGL(k_bm_search<BS>, grid, dim3(256), lds, L.stream, from, from_stride, to, to_stride, L.w, L.h, (int)L.R, L.rank, \
+                       L.cand, s.blocks_x, s.blocks_y, v, sd)
+        if (L.bs == 8)
+            NUS_BM_SEARCH(8);
+        else if (L.bs == 16)
+            NUS_BM_SEARCH(16);
+        else
+            NUS_BM_SEARCH(32);
 #undef NUS_BM_SEARCH
-    hipError_t e = hipGetLastError();
+        return hipGetLastError();
+    };
+    hipError_t e = search(L.a, L.a_stride, L.b, L.b_stride, raw, sad);
     if (e != hipSuccess) return e;
     const size_t nblocks = (size_t)L.n_pairs * s.blocks_x * s.blocks_y;
-    if (L.refine) {
+    uint32_t lg = 3;
+    while ((1u << lg) < L.bs) ++lg;
+    if (L.bidir) {
+        // the same search with the frames exchanged: B's blocks in A, on the same grid
+        int16_t *const bwd = reinterpret_cast<int16_t *>(ws + s.g_offset);
+        uint32_t *const sad_b = reinterpret_cast<uint32_t *>(ws + s.sad_g_offset);
+        if ((e = search(L.b, L.b_stride, L.a, L.a_stride, bwd, sad_b)) != hipSuccess) return e;
+        BmBidirLaunch C;
+        C.fwd = raw, C.sad_f = sad, C.bwd = bwd, C.sad_b = sad_b;
+        C.w = L.w, C.h = L.h, C.n_pairs = L.n_pairs, C.bs_log2 = lg, C.blocks_x = s.blocks_x, C.blocks_y = s.blocks_y;
+        C.tolerance = L.tolerance;
+        C.chosen = reinterpret_cast<int16_t *>(ws + s.chosen_offset);
+        C.state = ws + s.state_offset;
+        C.vectors = L.vectors, C.flags = L.flags, C.stream = L.stream;
+        if ((e = launch_bm_bidir(C)) != hipSuccess) return e;
+    } else if (L.refine) {
         uint32_t *rough = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(L.workspace) + s.rough_offset);
         const dim3 g(s.rough_groups, L.n_pairs);
         hipLaunchKernelGGL(k_bm_rough, g, dim3(256), 0, L.stream, reinterpret_cast<const short2 *>(raw), s.blocks_x, s.blocks_y, rough);
@@ -284,8 +317,6 @@ hipError_t launch_blockmatch(const BmLaunch &L)
     }
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (L.flow) {
-        uint32_t lg = 3;
-        while ((1u << lg) < L.bs) ++lg;
         const dim3 g((L.w * L.h + 255) / 256, L.n_pairs);
         if (L.flow_half)
             hipLaunchKernelGGL(k_bm_flow<true>, g, dim3(256), 0, L.stream, reinterpret_cast<const short2 *>(L.vectors), L.w, L.h, lg,

@@ -284,14 +284,18 @@ hipError_t launch_metrics(const uint8_t *a, size_t a_stride, const uint8_t *b, s
 // Block-matching motion estimation (nus_k_blockmatch.hip; nus_bm_* in include/nuscaler_hip.h).  Pair i reads A at
 // a + i * a_stride and B at b + i * b_stride (4-byte aligned); block (bx, by) of pair i is entry (i * blocks_y + by) * blocks_x + bx
 // of vectors (2 x int16: dx, dy), sad and flags.  The workspace holds the raw winners (2 x int16 per block) and, at rough_offset,
-// one word per 256 blocks for the smoothness test.
+// one word per 256 blocks for the smoothness test.  With the forward-backward check (bidir) it also holds, per block and 16-byte
+// aligned each, the backward winners G and their SADs, the forward SADs (used when the caller keeps none), the vectors of the
+// choose step and that step's state bytes.
 constexpr uint32_t kBmRunPixels = 64; // frame-A pixels per search workgroup along x: 64 / bs neighbouring blocks share one LDS window
 constexpr uint32_t kBmMaxRadius = 24;
 struct BmShape {
     uint32_t blocks_x = 0, blocks_y = 0, runs_x = 0, rough_groups = 0;
     size_t rough_offset = 0, workspace_bytes = 0;
+    size_t g_offset = 0, sad_g_offset = 0, sad_f_offset = 0, chosen_offset = 0, state_offset = 0; // bidir only
 };
-BmShape bm_shape(uint32_t w, uint32_t h, uint32_t bs, uint32_t n_pairs); // host only
+constexpr uint32_t kBmMaxTolerance = 96; // 2 components of two vectors of magnitude <= 24 each: a larger one changes nothing
+BmShape bm_shape(uint32_t w, uint32_t h, uint32_t bs, uint32_t n_pairs, bool bidir = false); // host only
 size_t bm_lds_bytes(uint32_t bs, uint32_t R);                            // dynamic LDS of one search workgroup
 struct BmLaunch {
     const uint8_t *a = nullptr, *b = nullptr;
@@ -301,6 +305,8 @@ struct BmLaunch {
     const uint16_t *rank = nullptr, *cand = nullptr; // (2R + 1)^2 entries each: candidate -> place in the tie order, and back
     void *workspace = nullptr;
     bool refine = true;        // confidence pass; off: vectors are the raw winners, flags 0
+    bool bidir = false;        // forward-backward check in place of the confidence pass (refine is then not looked at)
+    uint32_t tolerance = 2;    // of the check, 0 .. kBmMaxTolerance
     int16_t *vectors = nullptr;
     uint32_t *sad = nullptr;   // may be null
     uint8_t *flags = nullptr;  // may be null
@@ -309,6 +315,21 @@ struct BmLaunch {
     hipStream_t stream = nullptr;
 };
 hipError_t launch_blockmatch(const BmLaunch &L);
+
+// The forward-backward check behind the two searches (nus_k_bm_bidir.hip; launch_blockmatch calls it with bidir set).  All fields
+// in launch_blockmatch's per-block layout over n_pairs pairs; chosen (2 x int16) and state (u8) are the workspace's.
+struct BmBidirLaunch {
+    const int16_t *fwd = nullptr, *bwd = nullptr;    // raw winners A -> B and B -> A
+    const uint32_t *sad_f = nullptr, *sad_b = nullptr;
+    uint32_t w = 0, h = 0, n_pairs = 1, bs_log2 = 4, blocks_x = 0, blocks_y = 0;
+    uint32_t tolerance = 2;
+    int16_t *chosen = nullptr;
+    uint8_t *state = nullptr;
+    int16_t *vectors = nullptr;
+    uint8_t *flags = nullptr; // may be null
+    hipStream_t stream = nullptr;
+};
+hipError_t launch_bm_bidir(const BmBidirLaunch &L);
 
 // Warp + blend straight from the block vectors (nus_k_bm_warp.hip; nus_bm_warp_device): the frames launch_warp_blend writes from
 // the flow launch_blockmatch expands those vectors to, without that flow.  RGBA8 frames; vectors in launch_blockmatch's layout at

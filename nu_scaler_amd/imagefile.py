@@ -220,8 +220,10 @@ def interpolate_image_files_multi(path_a: str, path_b: str, output_path: str, mu
 
 def interpolate_image_files_block_matching(path_a: str, path_b: str, output_path: str, quality: str = "medium",
                                            time_t: float = 0.5, multiplier: int | None = None, device: int = 0,
-                                           scene_detect: bool = False) -> list[str]:
-    """`interpolate --method block_matching`: the block matcher's vectors (preset of `quality`) drive the warp.  One frame at
+                                           scene_detect: bool = False, bidirectional: bool = False,
+                                           tolerance: int | None = None) -> list[str]:
+    """`interpolate --method block_matching`: the block matcher's vectors (preset of `quality`; with `bidirectional` after the
+    forward-backward check at `tolerance`, None: the default) drive the warp.  One frame at
     `time_t` written to output_path, or with `multiplier` the M - 1 frames at multi_output_paths(output_path, M).  Returns the
     paths written."""
     from .blockmatch import BlockMatcher
@@ -231,6 +233,8 @@ def interpolate_image_files_block_matching(path_a: str, path_b: str, output_path
     if (w, h) != (wb, hb):
         raise ValueError(f"frame sizes differ: {w}x{h} vs {wb}x{hb}")
     bm = BlockMatcher(quality, device=device)
+    if bidirectional:
+        bm.set_bidirectional(True) if tolerance is None else bm.set_bidirectional(True, tolerance)
     if scene_detect:
         bm.set_scene_detect(True)
     if multiplier is not None:

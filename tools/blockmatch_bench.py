@@ -19,8 +19,13 @@ per K in {1, 3, 7} in-between frames per pair, FMA mode, us per pair of
   bm_warp       nus_bm_warp_device alone, on the vectors of the stream;
   dense_warp    nus_interp_interpolate_multi_device alone, on their expanded flow;
   flow_expand   k_bm_flow's share: nus_bm_estimate_device with the flow minus without.
+--bidirectional: instead, the forward-backward check (nus_bm_set_bidirectional) on and off, per preset, on 32 pairs of 1080p (the
+working set of the estimator's case; content that moves, so that the searches agree on most blocks), us per pair of
+  estimate_off / estimate_on   nus_bm_estimate_device with vectors, SADs and flags out, two handles of one binary;
+  stream_off / stream_on       nus_bm_interpolate_multi_device_stream over the same 33 frames, K = 1, FMA mode;
+and the ratios on / off: the mode's cost is the second search.
 The legs of a case alternate in one process, bracket by bracket; each figure is the median of its brackets.
-usage: python tools/blockmatch_bench.py [--reps R] [--rounds N] [--quick] [--stream]"""
+usage: python tools/blockmatch_bench.py [--reps R] [--rounds N] [--quick] [--stream | --bidirectional]"""
 import argparse
 import json
 import os
@@ -147,6 +152,55 @@ def stream_legs(args):
         torch.cuda.synchronize()
 
 
+def bidirectional_legs(args):
+    dev = torch.device("cuda:0")
+    s = torch.cuda.current_stream().cuda_stream
+    w, h, n_frames = 1920, 1080, 33
+    n, fb = n_frames - 1, 1920 * 1080 * 4
+    frames = syn.noise_stream_torch(n_frames, w, h, dev)
+    for k in range(n):
+        frames[k + 1] = torch.roll(frames[k], (5 - 2 * (k % 6), 3 * (k % 7) - 9), (0, 1))
+    base = frames.data_ptr()
+    mid = torch.empty((n, 1, h, w, 4), dtype=torch.uint8, device=dev)
+    for name, bs, radius in PRESETS:
+        legs, keep, flagged = [], [], 0
+        for on in (False, True):
+            bm = nsc.BlockMatcher(name, bidirectional=on)
+            nbx, nby = bm.block_grid(w, h)
+            ws_n, sws_n = bm.workspace_size(w, h, n), bm.stream_workspace_size(w, h, n_frames)
+            ws = torch.empty(ws_n, dtype=torch.uint8, device=dev)
+            sws = torch.empty(sws_n, dtype=torch.uint8, device=dev)
+            vec = torch.empty((n, nby, nbx, 2), dtype=torch.int16, device=dev)
+            sad = torch.empty((n, nby, nbx), dtype=torch.int32, device=dev)
+            flags = torch.empty((n, nby, nbx), dtype=torch.uint8, device=dev)
+
+            def estimate(bm=bm, ws=ws, ws_n=ws_n, vec=vec, sad=sad, flags=flags):
+                bm.estimate_device(base, fb, base + fb, fb, w, h, n, ws.data_ptr(), ws_n, vec.data_ptr(), sad.data_ptr(), flags.data_ptr(),
+                                   0, "f16", s)
+
+            def stream(bm=bm, sws=sws, sws_n=sws_n):
+                bm.interpolate_stream_device(base, fb, n_frames, w, h, sws.data_ptr(), sws_n, mid.data_ptr(), times=[0.5], mode="fma",
+                                             stream=s)
+
+            legs += [estimate, stream]
+            keep.append((bm, ws, sws, vec, sad, flags))
+            if on:
+                estimate()
+                torch.cuda.synchronize()
+                flagged = int((flags != 0).sum())
+        legs = [legs[0], legs[2], legs[1], legs[3]]  # estimate off, on, stream off, on
+        ms = timed_alternating(legs, args.reps, args.warm_seconds, args.rounds)
+        us = [round(x * 1e3 / n, 2) for x in ms]
+        print(json.dumps({"case": f"{w}x{h}x{n}_{name}_bidirectional", "width": w, "height": h, "pairs": n, "block_size": bs,
+                          "search_radius": radius, "working_set_bytes": frames.numel(), "blocks_repaired": flagged,
+                          "blocks": n * keep[1][3].shape[1] * keep[1][3].shape[2], "us_per_pair_estimate_off": us[0],
+                          "us_per_pair_estimate_on": us[1], "estimate_on_over_off": round(us[1] / us[0], 3),
+                          "us_per_pair_stream_off": us[2], "us_per_pair_stream_on": us[3],
+                          "stream_on_over_off": round(us[3] / us[2], 3)}), flush=True)
+        del keep, legs
+        torch.cuda.synchronize()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5, help="calls per timed bracket")
@@ -154,6 +208,7 @@ def main():
     ap.add_argument("--warm-seconds", type=float, default=0.5)
     ap.add_argument("--quick", action="store_true", help="one warm-up call and one bracket of 2 calls per case (profiling runs)")
     ap.add_argument("--stream", action="store_true", help="the stream legs (see above) instead of the estimator's cases")
+    ap.add_argument("--bidirectional", action="store_true", help="the forward-backward check on and off (see above) instead")
     args = ap.parse_args()
     if nsc.device_count() < 1:
         raise SystemExit("blockmatch_bench: no HIP device")
@@ -161,6 +216,8 @@ def main():
         args.reps, args.rounds, args.warm_seconds = 2, 1, 0.0
     if args.stream:
         return stream_legs(args)
+    if args.bidirectional:
+        return bidirectional_legs(args)
     dev = torch.device("cuda:0")
     s = torch.cuda.current_stream().cuda_stream
     it = nsc.WgpuFrameInterpolator()
