@@ -81,7 +81,8 @@ struct RowRaw<0> {
 #endif
 #ifndef NUS_LZ_ABLATE
 #define NUS_LZ_ABLATE 0 // dev macro, timing only (wrong pixels): 1 no stores, 2 no arithmetic, 3 stores only (no loads either),
-                        // 5 every row request goes to the first 16 rows of frame 0 (cache hits), 6 no lane exchange, 7 no pack
+                        // 5 every row request goes to the first 16 rows of frame 0 (cache hits), 6 no lane exchange (neither the
+                        // LDS form nor the DPP moves), 7 no pack
 #endif
 #if (NUS_LZ_ABLATE != 0 || !NUS_LZ_ASM_LOADS) && !defined(NUS_DEV_BUILD)
 #error "timing-only dev macros of k_lanczos3_x2 (wrong pixels / A-B forms) need -DNUS_DEV_BUILD: never in a product build"
@@ -298,10 +299,34 @@ __device__ __forceinline__ void lanczos_x2_vpass_edge(const float (&win)[6][16],
     }
 }
 
-// Horizontal pass of the lane's 8 output pixels, convert + pack.
+// How the horizontal pass gets the three columns it needs from each neighbouring lane.
+// The FMA-mode six-tap instantiations exchange them through LDS: each wave owns 16 planes of 64 dwords, plane c * 4 + m holding
+// V[m * 4 + c] of every lane at the lane's index (one pad dword at each end of the area).  A lane writes its vertical sums (12
+// dwords on the 3-channel path, 16 with alpha: ds_write2st64_b32), keeps its own four columns of a channel in registers and reads
+// only the six halo values of the channel: planes c*4+1..3 at lane - 1, planes c*4+0..2 at lane + 1 (three ds_read2_b32).  Lane
+// 0's left and lane 63's right neighbour are the last / first dword of the adjacent plane (or the pad): finite or not, those
+// lanes are halo or idle lanes whose pixels the store offsets drop.  The planes are lane-contiguous, so neither the accesses nor
+// the +-1 shift meet a bank conflict; LDS instructions of one wave execute in order, so the compiler-only wave barriers are all
+// the ordering the exchange needs.  This replaces 24 v_mov_b32_dpp per output row (36 per opaque wave-step, 48 with alpha), each
+// ~7.5 issue cycles among FMAs (profiles/r01_probe_valu_instruction_rates.txt) against the kernel's VALU-issue bound; the LDS
+// instructions issue on their own port and their latency hides behind the SIMD's other waves.  Two earlier LDS forms fetched all
+// ten values of a channel back and lost a wave per SIMD to the registers (docs/history_r01-r05.md); this one stays at 165 - 168.
+// EXACT (verification mode) and NARROW (two waves per SIMD already) keep the DPP moves.
+#ifndef NUS_LZ_LDS_XCHG
+#define NUS_LZ_LDS_XCHG 1 // dev macro: 0 = DPP moves in every instantiation, rows through the LDS turn (the form before; A/B timing only)
+#endif
+#if !NUS_LZ_LDS_XCHG && !defined(NUS_DEV_BUILD)
+#error "timing-only dev macros of k_lanczos3_x2 need -DNUS_DEV_BUILD: never in a product build"
+#endif
+constexpr bool lanczos_x2_lds_exchange(bool exact, bool narrow) { return NUS_LZ_LDS_XCHG != 0 && !exact && !narrow; }
+constexpr int kLzXchgDwords = 16 * 64 + 2; // per wave: 16 planes of one dword per lane, a pad dword at each end
+
+// Horizontal pass of the lane's 8 output pixels, convert + pack.  xl: the lane's dword in plane 0 of its wave's exchange area.
 template <bool EXACT, bool ALPHA, bool NARROW = false>
-__device__ __forceinline__ void lanczos_x2_hpass(const float (&V)[16], const PhaseWeights &W, uint32_t (&o)[8], uint32_t flat_alpha = 0u)
+__device__ __forceinline__ void lanczos_x2_hpass(const float (&V)[16], const PhaseWeights &W, uint32_t (&o)[8], float *xl,
+                                                 uint32_t flat_alpha = 0u)
 {
+    constexpr bool LDSX = lanczos_x2_lds_exchange(EXACT, NARROW) && NUS_LZ_ABLATE != 6;
     const uint32_t a0 = ALPHA ? 0u : flat_alpha; // 3-channel path: the window's one alpha (wave-uniform), already in bits 31:24
 #pragma unroll
     for (int q = 0; q < 8; ++q) o[q] = a0;
@@ -310,19 +335,34 @@ __device__ __forceinline__ void lanczos_x2_hpass(const float (&V)[16], const Pha
     for (int q = 0; q < 8; ++q) o[q] = __float_as_uint(V[q]);
     return;
 #endif
+    if constexpr (LDSX) {
+#pragma unroll
+        for (int c = 0; c < (ALPHA ? 4 : 3); ++c)
+#pragma unroll
+            for (int m = 0; m < 4; ++m) xl[(c * 4 + m) * 64] = V[m * 4 + c];
+        __builtin_amdgcn_wave_barrier(); // compiler only: the reads below see other lanes' writes (same wave, in-order LDS)
+    }
 #pragma unroll
     for (int c = 0; c < (ALPHA ? 4 : 3); ++c) {
         float e[10]; // vertical sums of input columns c0-3 .. c0+6 for this channel (NARROW: e[0] and e[9] are not read)
-        e[0] = NARROW ? 0.0f : lane_up(V[1 * 4 + c]);
-        e[1] = lane_up(V[2 * 4 + c]);
-        e[2] = lane_up(V[3 * 4 + c]);
+        if constexpr (LDSX) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                e[k] = xl[(c * 4 + 1 + k) * 64 - 1];
+                e[7 + k] = xl[(c * 4 + k) * 64 + 1];
+            }
+        } else {
+            e[0] = NARROW ? 0.0f : lane_up(V[1 * 4 + c]);
+            e[1] = lane_up(V[2 * 4 + c]);
+            e[2] = lane_up(V[3 * 4 + c]);
+            e[7] = lane_down(V[0 * 4 + c]);
+            e[8] = lane_down(V[1 * 4 + c]);
+            e[9] = NARROW ? 0.0f : lane_down(V[2 * 4 + c]);
+        }
         e[3] = V[0 * 4 + c];
         e[4] = V[1 * 4 + c];
         e[5] = V[2 * 4 + c];
         e[6] = V[3 * 4 + c];
-        e[7] = lane_down(V[0 * 4 + c]);
-        e[8] = lane_down(V[1 * 4 + c]);
-        e[9] = NARROW ? 0.0f : lane_down(V[2 * 4 + c]);
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
             constexpr int J0 = NARROW ? 1 : 0, J1 = NARROW ? 5 : 6;
@@ -342,6 +382,7 @@ __device__ __forceinline__ void lanczos_x2_hpass(const float (&V)[16], const Pha
 #endif
         }
     }
+    if constexpr (LDSX) __builtin_amdgcn_wave_barrier(); // the next row's writes stay behind these reads
 }
 
 // Where a wave's output row goes.  A lane computes 8 consecutive output pixels (32 B), but a store instruction in
@@ -357,6 +398,7 @@ struct RowStore {
                            // belong to halo lanes or to the edge kernel's columns sit at 2^31: the range check drops them
     int idx_a, idx_b;      // which 16-B pieces of the stage this lane reads back
     int lane;
+    float *xchg;           // LDS lane exchange of the horizontal pass: the lane's dword in plane 0 of its wave's area (or null)
 };
 
 #ifndef NUS_LZ_CONTIG_STORES
@@ -372,15 +414,23 @@ struct RowStore {
 // (385 GPU parity cases), and measured against the LDS turn in one process: one-launch step 5.691 against 5.693 ms per 300 units
 // (gradient), 6.751 / 6.787 (noise); the plain kernel 2.667 / 2.647 and 3.310 / 3.310 ms per 300 frames
 // (profiles/r06_x2_row_store_without_lds_ab.txt).  The turn through LDS was not what held the kernel: it sits on its memory and
-// issue floors either way.  The product keeps the LDS turn, whose stores cover whole 128-byte lines per
-// instruction (with 60 storing lanes the swap form splits one line in fifteen between its two stores).
+// issue floors either way.  The instantiations whose horizontal pass exchanges lanes through LDS
+// (lanczos_x2_lds_exchange) take the swap form: it leaves out the turn's two address registers and 8 KiB of LDS per block, which
+// is what keeps them at three waves per SIMD without a spill (with the turn kept they need 169 - 172 registers).  EXACT and
+// NARROW keep the LDS turn, whose stores cover whole 128-byte lines per instruction (with 60 storing lanes the swap form splits
+// one line in fifteen between its two stores).
 #ifndef NUS_LZ_SWAP_STORES
-#define NUS_LZ_SWAP_STORES 0 // 1 = the permlane32_swap form (A/B builds)
+#define NUS_LZ_SWAP_STORES 0 // 1 = the permlane32_swap form in every instantiation (A/B builds)
 #endif
+constexpr bool lanczos_x2_swap_stores(bool exact, bool narrow)
+{
+    return NUS_LZ_CONTIG_STORES != 0 && (NUS_LZ_SWAP_STORES != 0 || lanczos_x2_lds_exchange(exact, narrow));
+}
 
 // The two 16-B stores of an output row.  Buffer stores: lanes that must not write carry an offset beyond
 // num_records and the hardware range check drops them, so the store instructions issue on every path and
 // for every lane -- the hand-counted waits of the row prefetches (wait_vmcnt) rely on exactly two per phase.
+template <bool SWAP>
 __device__ __forceinline__ void lanczos_x2_store(const uint32_t (&o)[8], __amdgpu_buffer_rsrc_t rs, const RowStore &st,
                                                  uint32_t row_off)
 {
@@ -390,21 +440,23 @@ __device__ __forceinline__ void lanczos_x2_store(const uint32_t (&o)[8], __amdgp
     return;
 #endif
     u32x4 lo = {o[0], o[1], o[2], o[3]}, hi = {o[4], o[5], o[6], o[7]};
-#if NUS_LZ_CONTIG_STORES && NUS_LZ_SWAP_STORES
-    typedef uint32_t u32x2_sw __attribute__((ext_vector_type(2)));
+    if constexpr (SWAP) {
+        typedef uint32_t u32x2_sw __attribute__((ext_vector_type(2)));
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const u32x2_sw r = __builtin_amdgcn_permlane32_swap(lo[k], hi[k], false, false); // (the compiler pads the VALU -> swap hazard)
-        lo[k] = r.x, hi[k] = r.y;
-    }
-#elif NUS_LZ_CONTIG_STORES
-    st.stage[2 * st.lane] = lo;
-    st.stage[2 * st.lane + 1] = hi;
-    __builtin_amdgcn_wave_barrier(); // compiler only: the reads below see other lanes' writes (same wave, in-order LDS)
-    lo = st.stage[st.idx_a];
-    hi = st.stage[st.idx_b];
-    __builtin_amdgcn_wave_barrier();
+        for (int k = 0; k < 4; ++k) {
+            const u32x2_sw r = __builtin_amdgcn_permlane32_swap(lo[k], hi[k], false, false); // (the compiler pads the VALU -> swap hazard)
+            lo[k] = r.x, hi[k] = r.y;
+        }
+    } else {
+#if NUS_LZ_CONTIG_STORES
+        st.stage[2 * st.lane] = lo;
+        st.stage[2 * st.lane + 1] = hi;
+        __builtin_amdgcn_wave_barrier(); // compiler only: the reads below see other lanes' writes (same wave, in-order LDS)
+        lo = st.stage[st.idx_a];
+        hi = st.stage[st.idx_b];
+        __builtin_amdgcn_wave_barrier();
 #endif
+    }
     __builtin_amdgcn_raw_buffer_store_b128(lo, rs, row_off + st.off_a, 0, NUS_STORE_AUX);
     __builtin_amdgcn_raw_buffer_store_b128(hi, rs, row_off + st.off_b, 0, NUS_STORE_AUX);
 }
@@ -449,10 +501,11 @@ __device__ __forceinline__ void lanczos_x2_step(float (&win)[6][16], const RowRi
 {
     constexpr int D = kLzDepth, NL = BLEND ? 2 : 1, M = UNIT ? 1 : 0;
     constexpr bool HIDDEN = NUS_LZ_ASM_LOADS != 0, EARLY = HIDDEN && NUS_LZ_WAIT_EARLY != 0;
+    constexpr bool SWAP = lanczos_x2_swap_stores(EXACT, NARROW);
     const uint32_t row_bytes = A.iw * 8; // output row: 2*iw pixels
     const uint32_t off0 = (uint32_t)(2 * r) * row_bytes;
     const bool interior = r >= 4 && r + 5 <= (int)A.ih; // wave-uniform
-    // The 3-channel path is compiled into the FMA-mode kernels (plain and blend variants: 164 - 166 VGPRs, three waves per SIMD
+    // The 3-channel path is compiled into the FMA-mode kernels (plain and blend variants: 165 - 168 VGPRs, three waves per SIMD
     // since the LDS-DMA ring took the in-flight rows out of the registers); EXACT is the register-hungry verification mode.
     constexpr bool OP = !EXACT && NUS_LZ_BLEND_OPAQUE_PATH_OK(BLEND);
     float V[16];
@@ -481,10 +534,10 @@ __device__ __forceinline__ void lanczos_x2_step(float (&win)[6][16], const RowRi
     }
 #endif
     if (path == 1)
-        lanczos_x2_hpass<EXACT, false, NARROW>(V, W, o, alpha_e);
+        lanczos_x2_hpass<EXACT, false, NARROW>(V, W, o, st.xchg, alpha_e);
     else
-        lanczos_x2_hpass<EXACT, true, NARROW>(V, W, o);
-    lanczos_x2_store(o, rs, st, off0); // after the paths have joined: straight-line code holds every memory instruction
+        lanczos_x2_hpass<EXACT, true, NARROW>(V, W, o, st.xchg);
+    lanczos_x2_store<SWAP>(o, rs, st, off0); // after the paths have joined: straight-line code holds every memory instruction
     // row r+3 in, then request row r+3+D into the same slot
     if (HIDDEN && !EARLY) {
         wait_vmcnt<4 * D + (D - 1) * (NL + M), (D - 1) * NL + 1>();
@@ -523,15 +576,15 @@ __device__ __forceinline__ void lanczos_x2_step(float (&win)[6][16], const RowRi
     const uint32_t path_o = !interior ? 0u : ((OP && alpha_run_six(arun)) ? 1u : 2u);
     if (path_o == 0) {
         lanczos_x2_vpass_edge<EXACT, S + 1>(win, A.wy6, 2 * (uint32_t)r + 1, V);
-        lanczos_x2_hpass<EXACT, true, NARROW>(V, W, o);
+        lanczos_x2_hpass<EXACT, true, NARROW>(V, W, o, st.xchg);
     } else if (path_o == 1) {
         lanczos_x2_vpass<EXACT, S + 1, false, NARROW>(win, W.o, V);
-        lanczos_x2_hpass<EXACT, false, NARROW>(V, W, o, arun.alpha);
+        lanczos_x2_hpass<EXACT, false, NARROW>(V, W, o, st.xchg, arun.alpha);
     } else {
         lanczos_x2_vpass<EXACT, S + 1, true, NARROW>(win, W.o, V);
-        lanczos_x2_hpass<EXACT, true, NARROW>(V, W, o);
+        lanczos_x2_hpass<EXACT, true, NARROW>(V, W, o, st.xchg);
     }
-    lanczos_x2_store(o, rs, st, off0 + row_bytes);
+    lanczos_x2_store<SWAP>(o, rs, st, off0 + row_bytes);
 }
 
 // Exact x2 Lanczos-3.  One wave loads a strip of 256 input columns (4 per lane); lanes 1 .. 60 produce the
@@ -540,9 +593,11 @@ __device__ __forceinline__ void lanczos_x2_step(float (&win)[6][16], const RowRi
 // f32 window of its columns in registers:
 //   row prefetch   : LDS-DMA into a per-wave ring, D steps ahead, hand-counted vmcnt waits (see RowRing)
 //   vertical pass  : 6 taps from the register window
-//   horizontal pass: 6 taps over the lane's own 4 columns + 3 columns from each
-//                    neighbouring lane, fetched with wave_shr/wave_shl DPP moves
-//   store          : the row's 2 KiB are turned round in LDS, two stores of one contiguous KiB each (RowStore)
+//   horizontal pass: 6 taps over the lane's own 4 columns + 3 columns from each neighbouring lane: read back from a per-wave
+//                    exchange area in LDS by the FMA-mode six-tap instantiations, fetched with wave_shr/wave_shl DPP moves
+//                    by EXACT and NARROW (lanczos_x2_hpass)
+//   store          : two stores of one contiguous KiB each; the row's 2 KiB are put in store order by v_permlane32_swap where
+//                    the lanes exchange through LDS, by a turn through LDS elsewhere (RowStore, lanczos_x2_store)
 // so every input byte is read once per strip-row-block and no workgroup barrier is needed.  (The 6 halo rows two vertically
 // neighbouring row blocks share are requested a whole block apart in time; letting odd row blocks walk bottom-up through a
 // vertical mirror of the frame, so that both readers of a halo reach it together, was built and measured in round 3: outputs
@@ -564,7 +619,7 @@ __device__ __forceinline__ void lanczos_x2_step(float (&win)[6][16], const RowRi
 // row from HBM about once where three launches (blend, upscale, upscale) read it four times, and writes nothing twice.
 // (NARROW: the compiler gives the four-tap form 215 registers, two waves per SIMD; held to three (168 registers) it spills 49
 // dwords, whose reloads bring vmcnt waits back into the loop: 9.7 against 7.7 - 8.0 us per frame.  Left as the compiler has it.
-// The six-tap instantiations are instruction for instruction what they were before the parameter existed.)
+// Adding the parameter left the six-tap instantiations instruction for instruction what they were.)
 template <bool EXACT, int BLEND, bool UNIT, bool NARROW = false>
 __global__ __launch_bounds__(256) void k_lanczos3_x2(const LanczosX2Args A)
 {
@@ -641,10 +696,11 @@ __global__ __launch_bounds__(256) void k_lanczos3_x2(const LanczosX2Args A)
         return L >= 1 && L <= (int)(kLanczosX2StripCols / 4) && cc >= 4 && cc + 8 <= (int)A.iw;
 #endif
     };
+    constexpr bool SWAP = lanczos_x2_swap_stores(EXACT, NARROW), LDSX = lanczos_x2_lds_exchange(EXACT, NARROW);
     RowStore st;
     st.lane = lane;
-#if NUS_LZ_CONTIG_STORES && NUS_LZ_SWAP_STORES
-    {
+#if NUS_LZ_CONTIG_STORES
+    if constexpr (SWAP) {
         // after the swaps: store A carries lane l's first piece (l < 32) or lane l - 32's second piece; store B lane l + 32's first
         // (l < 32) or lane l's second -- each piece dropped (offset 2^31) when the lane that COMPUTED it stores nothing
         const int span0 = ((int)(strip * kLanczosX2StripCols) - 4) * 8; // byte offset of the span in an output row (may be < 0)
@@ -653,9 +709,7 @@ __global__ __launch_bounds__(256) void k_lanczos3_x2(const LanczosX2Args A)
         st.off_a = computes_stored_pixels(la) ? (uint32_t)(span0 + 32 * la + half) : 0x80000000u;
         st.off_b = computes_stored_pixels(lb) ? (uint32_t)(span0 + 32 * lb + half) : 0x80000000u;
         st.idx_a = st.idx_b = 0;
-    }
-#elif NUS_LZ_CONTIG_STORES
-    {
+    } else {
         // after the turn in LDS this lane holds 16 B of the wave's 512-pixel span for each store: SKIP bytes into the span
         // for the first store, 1024 further for the second; they were computed by lanes (SKIP + 16 lane) / 32 and
         // (SKIP + 1024 + 16 lane) / 32
@@ -690,12 +744,18 @@ __global__ __launch_bounds__(256) void k_lanczos3_x2(const LanczosX2Args A)
         ring.slot = lds_rows[HIDDEN ? w : 0];
         ring.lds = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)&lds_rows[HIDDEN ? w : 0][0][0]);
         ring.lane = lane;
-#if NUS_LZ_CONTIG_STORES && !NUS_LZ_SWAP_STORES
-        __shared__ u32x4 lds_stage[4][128]; // one output row (2 KiB) per wave, turned round between compute and store order
-        st.stage = lds_stage[w];
-#else
         st.stage = nullptr;
+#if NUS_LZ_CONTIG_STORES
+        if constexpr (!SWAP) {
+            __shared__ u32x4 lds_stage[4][128]; // one output row (2 KiB) per wave, turned round between compute and store order
+            st.stage = lds_stage[w];
+        }
 #endif
+        st.xchg = nullptr;
+        if constexpr (LDSX) {
+            __shared__ float lds_xchg[4][kLzXchgDwords]; // lane exchange of the horizontal pass (lanczos_x2_hpass)
+            st.xchg = &lds_xchg[w][1 + lane];
+        }
     }
 
     PhaseWeights W;
