@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import _blockmatch as bmref
+from _warp64 import warp_contract
 from conftest import guarded
 from nu_scaler_amd.transfer import to_device as put, to_numpy as fetch
 
@@ -103,12 +104,13 @@ def _host_frames(bm, a, b, w, h, times, mode, **kw):
     return np.stack([np.frombuffer(x, np.uint8).reshape(h, w, 4) for x in bm.interpolate(a, b, w, h, times=times, mode=mode, **kw)])
 
 
-def _fma_contract(got, want, share):
+def _fma_contract(got, want, share, a, b, flow, t):
     d = np.abs(got.astype(np.int16) - want.astype(np.int16))
     print(f"fma: max |diff| {d.max()}, bytes differing {(d != 0).sum()} of {d.size} ({(d != 0).mean():.5%})")
     assert d.max() <= 1, d.max()
     if share:  # the cap is defined on frames of at least 328 x 200
         assert (d != 0).sum() < 0.001 * d.size, (d != 0).mean()
+    warp_contract(got, a, b, flow, t, 0.5, ("bm stream", a.shape[1::-1], t))  # the float64 contract (tests/_warp64.py)
 
 
 @pytest.mark.parametrize("w,h,bs,R", CASES)
@@ -138,7 +140,7 @@ def test_fma_frames_hold_the_contract_against_the_oracle(nsc, oracle_mod, w, h, 
         for j, t in enumerate(times):
             want = oracle_mod.warp_blend(frames[k], frames[k + 1], flow, t)
             assert np.array_equal(exact[k, j], want), (k, j)
-            _fma_contract(mid[k, j], want, (w, h) == (328, 200))
+            _fma_contract(mid[k, j], want, (w, h) == (328, 200), frames[k], frames[k + 1], flow, t)
 
 
 def test_every_batch_size_and_position_gives_the_same_bytes(nsc):

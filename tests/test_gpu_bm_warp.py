@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import _blockmatch as bmref
+from _warp64 import warp_contract
 from conftest import guarded
 from nu_scaler_amd.transfer import to_device as put, to_numpy as fetch
 
@@ -81,12 +82,14 @@ def _warp(nsc, a, b, vec, bs, times, mode):
     return fetch(out)
 
 
-def _fma_contract(got, want, share):
+def _fma_contract(got, want, share, a, b, flow, t):
     d = np.abs(got.astype(np.int16) - want.astype(np.int16))
     print(f"fma: max |diff| {d.max()}, bytes differing {(d != 0).sum()} of {d.size} ({(d != 0).mean():.5%})")
     assert d.max() <= 1, d.max()
     if share:
         assert (d != 0).sum() < 0.001 * d.size, (d != 0).mean()
+    h, w = a.shape[:2]  # the float64 contract (tests/_warp64.py); frames below 2 x 2 run EXACT arithmetic
+    warp_contract(got, a, b, flow, t, 0.5 if min(w, h) >= 2 else 1.0, ("bm warp", (w, h), t))
 
 
 @pytest.mark.parametrize("bs", BLOCK_SIZES)
@@ -100,7 +103,7 @@ def test_exact_is_the_oracle_and_fma_holds_its_contract(nsc, w, h, bs):
         fma = _warp(nsc, a, b, vec, bs, times, "fma")
         for k, t in enumerate(times):
             assert np.array_equal(exact[k], _want(w, h, bs, t)), (w, h, bs, m, k, "exact")
-            _fma_contract(fma[k], _want(w, h, bs, t), (w, h) == SHARE_SHAPE)
+            _fma_contract(fma[k], _want(w, h, bs, t), (w, h) == SHARE_SHAPE, a, b, bmref.dense_flow(vec, w, h, bs), t)
 
 
 @pytest.mark.parametrize("bs", BLOCK_SIZES)

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from _resample64 import check_fma  # the FMA-mode contract: float64 resample, round to nearest, ties either way
+from _warp64 import warp_contract  # the FMA-mode warp's contract: float64 samples, truncated, a band at integers
 from conftest import GOLDEN, guarded
 from nu_scaler_amd.transfer import to_device as put, to_numpy as fetch  # host <-> HBM through nus_upload / nus_download, never
 # torch's pageable copies (docs/d2h_fault_analysis.md)
@@ -342,6 +343,9 @@ def test_warp_blend_fma_mode_within_one_lsb(nsc, oracle_mod, size):
                         d = np.abs(got[i].astype(np.int16) - want[i].astype(np.int16))
                         assert d.max() <= 1, (size, t, fmt, i, int(d.max()))
                         assert (d > 0).mean() < 1e-3 or d.size < 4000, (size, t, fmt, i, float((d > 0).mean()))
+                        if w * h < 1920 * 1080:  # the float64 contract (tests/_warp64.py); frames below 2 x 2 run EXACT arithmetic
+                            warp_contract(got[i], frames_np[i], frames_np[i + 1], fl_np[i], t, 0.5 if min(w, h) >= 2 else 1.0,
+                                          (size, t, fmt, i))
     # host entry point in FMA mode; zero flow stays the exact blend
     it.set_mode("fma")
     it.set_flow_format("f32")
