@@ -732,14 +732,14 @@ int nus_flow_upsample(nus_flow *h, const float *src, uint32_t sw, uint32_t sh, f
 int nus_flow_estimate(nus_flow *h, const uint8_t *a, const uint8_t *b, uint32_t w, uint32_t hgt, uint32_t levels,
                       uint32_t coarse_iters, uint32_t refine_iters, float lambda, float *flow_out)
 {
-    return guarded<int>("nus_flow_estimate", [&]() -> int { return h ? h->impl.estimate(a, b, w, hgt, levels, coarse_iters, refine_iters, lambda, flow_out) : null_handle(); });
+    return guarded<int>("nus_flow_estimate", [&]() -> int { return h ? h->impl.estimate(a, b, w, hgt, {levels, coarse_iters, refine_iters, lambda}, flow_out) : null_handle(); });
 }
 
 int nus_flow_estimate_device(nus_flow *h, const void *d_a, const void *d_b, uint32_t w, uint32_t hgt, uint32_t levels,
                              uint32_t coarse_iters, uint32_t refine_iters, float lambda, void *d_flow_out, void *stream)
 {
     return guarded<int>("nus_flow_estimate_device", [&]() -> int {
-        return h ? h->impl.estimate_device(d_a, d_b, w, hgt, levels, coarse_iters, refine_iters, lambda, d_flow_out,
+        return h ? h->impl.estimate_device(d_a, d_b, w, hgt, {levels, coarse_iters, refine_iters, lambda}, d_flow_out,
                                            static_cast<hipStream_t>(stream))
                  : null_handle();
     });
@@ -750,8 +750,8 @@ int nus_flow_estimate_device_stream(nus_flow *h, const void *d_frames, uint32_t 
                                     void *d_flows, void *stream)
 {
     return guarded<int>("nus_flow_estimate_device_stream", [&]() -> int {
-        return h ? h->impl.estimate_device_stream(d_frames, n_frames, w, hgt, levels, coarse_iters, refine_iters, lambda,
-                                                  d_flows, static_cast<hipStream_t>(stream))
+        return h ? h->impl.estimate_device_stream(d_frames, n_frames, w, hgt, {levels, coarse_iters, refine_iters, lambda}, d_flows,
+                                                  static_cast<hipStream_t>(stream))
                  : null_handle();
     });
 }
@@ -765,7 +765,7 @@ int nus_flow_interpolate_device_stream(nus_flow *h, const void *d_frames, uint32
             nus::set_thread_error("nus_flow_interpolate_device_stream: flow_format must be NUS_FLOW_F32 or NUS_FLOW_F16");
             return NUS_ERR_INVALID_ARGUMENT;
         }
-        return h ? h->impl.interpolate_device_stream(d_frames, n_frames, w, hgt, levels, coarse_iters, refine_iters, lambda, time_t,
+        return h ? h->impl.interpolate_device_stream(d_frames, n_frames, w, hgt, {levels, coarse_iters, refine_iters, lambda}, time_t,
                                                      d_flows, d_mid, static_cast<hipStream_t>(stream), flow_format == NUS_FLOW_F16)
                  : null_handle();
     });
@@ -782,7 +782,7 @@ int nus_flow_interpolate_multi_device_stream(nus_flow *h, const void *d_frames, 
             nus::set_thread_error("nus_flow_interpolate_multi_device_stream: flow_format must be NUS_FLOW_F32 or NUS_FLOW_F16");
             return NUS_ERR_INVALID_ARGUMENT;
         }
-        return h->impl.interpolate_multi_device_stream(d_frames, n_frames, w, hgt, levels, coarse_iters, refine_iters, lambda, times,
+        return h->impl.interpolate_multi_device_stream(d_frames, n_frames, w, hgt, {levels, coarse_iters, refine_iters, lambda}, times,
                                                        n_times, flow_format == NUS_FLOW_F16, d_flows, d_mid, mid_pair_stride,
                                                        static_cast<hipStream_t>(stream));
     });

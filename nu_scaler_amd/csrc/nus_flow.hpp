@@ -7,13 +7,21 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <functional>
+#include <initializer_list>
 #include <mutex>
 #include <string>
-#include <vector>
+#include <utility>
 
 #include "nus_host_util.hpp"
 
 namespace nus {
+
+// What every estimate takes: pyramid levels (1..12), Jacobi steps on the coarsest level and on each finer one, the smoothness weight.
+struct FlowParams {
+    uint32_t levels = 0, coarse_iters = 0, refine_iters = 0;
+    float lambda = 0.0f;
+};
 
 class HipFlowEstimator : public HostErrors {
 public:
@@ -23,9 +31,10 @@ public:
     HipFlowEstimator &operator=(const HipFlowEstimator &) = delete;
 
     int set_device(int device);
-    // true (default): derivatives once per level + K Jacobi steps per launch in LDS; false: one
-    // plain kernel per step (the shader's structure).  Bit-identical results.
-    int set_tiled(int mode); // 0 plain per-step kernel, 1 multi-step kernel chosen by size, 2 LDS tiles, 3 streamed
+    // 0: one plain kernel per Jacobi step and per pyramid pass (the shader's structure).  1 (default): the fused pyramid kernel,
+    // derivatives once per level and K Jacobi steps per launch, LDS tiles or the streamed (register-pipelined) kernel by the size
+    // of the level's batch.  2: as 1, always LDS tiles.  3: as 1, always streamed.  Bit-identical results.
+    int set_tiled(int mode);
 
     // Primitives on host buffers (parity tests, integration).  f32 RGBA images, float2 flows.
     int rgba8_to_f32(const uint8_t *in, uint32_t w, uint32_t h, float *out);
@@ -36,8 +45,7 @@ public:
     int upsample(const float *src, uint32_t sw, uint32_t sh, float *dst, uint32_t dw, uint32_t dh, float scale);
 
     // Full estimator: RGBA8 frames -> dense flow (w*h*2 floats, pixel delta A -> B).
-    int estimate(const uint8_t *a, const uint8_t *b, uint32_t w, uint32_t h, uint32_t levels, uint32_t coarse_iters,
-                 uint32_t refine_iters, float lambda, float *flow_out);
+    int estimate(const uint8_t *a, const uint8_t *b, uint32_t w, uint32_t h, const FlowParams &p, float *flow_out);
     // 0 EXACT (default): every stage bit-identical to the oracle's restatement of the shaders; 1 FAST: the Jacobi steps of the
     // estimators (estimate, estimate_device, estimate_device_stream) in separable sums / reciprocals / FMAs -- flow within 1e-3 px.
     // The primitives (blur, downsample, horn_schunck, upsample) are always exact.
@@ -46,42 +54,80 @@ public:
     // Scene-cut detection in front of interpolate_multi_device_stream and the cut-aware output rule behind it (nus_scene_* of the C
     // header): off by default.  On, the in-between frames of a pair the detector flags are repeats of the nearer real frame.
     int set_scene_detect(int enabled, uint32_t mad_threshold, uint32_t hist_permille);
-    int estimate_device(const void *d_a, const void *d_b, uint32_t w, uint32_t h, uint32_t levels,
-                        uint32_t coarse_iters, uint32_t refine_iters, float lambda, void *d_flow_out,
+    int estimate_device(const void *d_a, const void *d_b, uint32_t w, uint32_t h, const FlowParams &p, void *d_flow_out,
                         hipStream_t stream);
     // n_frames consecutive RGBA8 frames -> n_frames - 1 flows (k -> k+1), each pyramid built once.
-    int estimate_device_stream(const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t h, uint32_t levels,
-                               uint32_t coarse_iters, uint32_t refine_iters, float lambda, void *d_flows,
+    int estimate_device_stream(const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t h, const FlowParams &p, void *d_flows,
                                hipStream_t stream);
     // The reference's intended interpolate() as ONE pipeline (wgpu_interpolator.rs:881-935: pyramid -> coarse flow -> warp): the
     // flows of estimate_device_stream AND the n_frames - 1 in-between frames at time t warped + blended with them (dense-flow warp
     // in FMA mode) into d_mid: the warp kernel runs behind the estimator on the flow where it is (the caller's buffer, or the
     // workspace when d_flows == nullptr).  (NUS_HS_FUSED_WARP=1: the finest level's last Jacobi launch warps with the flow it has
     // just finished instead -- HsWarp; same bytes, measured slower, off by default; tests/test_flow.py runs both.)
-    int interpolate_device_stream(const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t h, uint32_t levels,
-                                  uint32_t coarse_iters, uint32_t refine_iters, float lambda, float t, void *d_flows, void *d_mid,
-                                  hipStream_t stream, bool flow_half = false);
+    // flow_half: the flows between estimator and warp -- and at d_flows, if given -- as 2 x IEEE half per pixel (Rg16Float, the
+    // reference's live flow layout: wgpu_interpolator.rs:276), each the f32 flow rounded to nearest even; the warp reads them as such.
+    int interpolate_device_stream(const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t h, const FlowParams &p, float t,
+                                  void *d_flows, void *d_mid, hipStream_t stream, bool flow_half = false);
     // As interpolate_device_stream, the frames at n_times times per pair from ONE estimate of each pair's flow: one multi-time
     // warp launch (FMA mode) behind the estimator, never the fused one.  Frame j of pair k at d_mid + k * mid_pair_stride +
     // j * w * h * 4 (0: tightly packed).  The arguments are checked before any HIP call; the flows at d_flows are the same bytes.
-    int interpolate_multi_device_stream(const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t h, uint32_t levels,
-                                        uint32_t coarse_iters, uint32_t refine_iters, float lambda, const float *times, uint32_t n_times,
-                                        bool flow_half, void *d_flows, void *d_mid, size_t mid_pair_stride, hipStream_t stream);
+    int interpolate_multi_device_stream(const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t h, const FlowParams &p,
+                                        const float *times, uint32_t n_times, bool flow_half, void *d_flows, void *d_mid,
+                                        size_t mid_pair_stride, hipStream_t stream);
 
 private:
+    // The grow-only device workspace.  Slots 0, 1, 4 and 5 have two names: the pair path's (plan / build_pyramid / solve, and the
+    // primitives), then -- after the bar -- the batch path's (solve_batch).
+    enum Slot : int {
+        kImage = 0, kLevelInOdd = 0,  // w*h*16: a primitive's input, a pyramid level's input | inputs of the odd levels of all frames
+        kTemp = 1, kLevelInEven = 1,  // w*h*16: a primitive's output, blur temp, then the level's coefficients | ... of the even levels
+        kFlowA = 2, kFlowB = 3,       // flow ping-pong: w*h*8 | [pair][level cells]
+        kPyrA = 4, kLum = 4,          // frame A's pyramid, levels packed (horn_schunck: coefficients) | luminance planes [level][frame][cells]
+        kPyrB = 5, kCoef = 5,         // frame B's pyramid | coefficients [pair][cells][3]
+        kHostA = 6, kHostB = 7,       // estimate(): the host's RGBA8 frames; kHostB then takes the flow on its way back
+        kFastPair = 8,                // estimate_device in FAST mode: the pair as a two-frame stream
+        kPairFlow = 9,                // one pair's f32 flow that no caller's buffer takes
+        kFlowsHalf = 10,              // a chunk's flows as Rg16Float, likewise
+        kScene = 11,                  // the scene detector's workspace and cut flags
+    };
+    static constexpr int kSlotCount = 12;
     struct MidTimes { // the multi-time warp behind the estimator (interpolate_multi_device_stream)
         const float *times = nullptr;
         uint32_t n = 0;
         size_t pair_stride = 0; // bytes between the in-between frames of consecutive pairs
     };
+    struct StreamJob { // n_frames consecutive frames -> flows and / or in-between frames of the n_frames - 1 pairs
+        const uint8_t *frames = nullptr;
+        uint32_t n_frames = 0, w = 0, h = 0;
+        uint8_t *flows = nullptr, *mid = nullptr; // either may be null, not both
+        float t = 0.5f;                           // time of the in-between frame, unless
+        bool flow_half = false;
+        const MidTimes *mt = nullptr;             // ... several per pair
+        hipStream_t stream = nullptr;
+        size_t frame_bytes() const { return (size_t)w * h * 4; }
+        size_t flow_bytes() const { return (size_t)w * h * (flow_half ? 4 : 8); }
+        size_t mid_stride() const { return mt ? mt->pair_stride : frame_bytes(); }
+        StreamJob pairs(uint32_t k0, uint32_t n) const; // the job of pairs [k0, k0 + n)
+    };
     struct Pyramid { // level geometry; levels are packed at `offset` (16 bytes per pixel reserved)
         uint32_t levels = 0, w[12] = {0}, h[12] = {0};
         size_t offset[12] = {0}, total = 0;
     };
+    struct Staged { // a slot a primitive needs, and the host buffer (if any) that fills it
+        Slot slot;
+        size_t bytes;
+        const void *host;
+    };
+    // What the host primitives share: lock, checks (dimensions, then `pointers_ok`), device, `stage` reserved and uploaded, `work`
+    // (the launches; it names the device buffer that holds the result), `out_bytes` of it downloaded, synchronised.
+    int primitive(std::initializer_list<std::pair<uint32_t, uint32_t>> dims, bool pointers_ok, std::initializer_list<Staged> stage,
+                  void *out, size_t out_bytes, const std::function<int(const void *&result)> &work);
+    // (all below: mu_ held)
     int plan(uint32_t w, uint32_t h, uint32_t levels, Pyramid &g); // geometry + workspace
-    int build_pyramid(const void *frame, int pyr_slot, const Pyramid &g, hipStream_t stream);
-    int solve(int slot_a, int slot_b, const Pyramid &g, uint32_t coarse_iters, uint32_t refine_iters, float lambda,
-              void *d_flow_out, hipStream_t stream);
+    int build_pyramid(const void *frame, Slot pyr, const Pyramid &g, hipStream_t stream);
+    int solve(Slot pyr_a, Slot pyr_b, const Pyramid &g, const FlowParams &p, void *d_flow_out, hipStream_t stream);
+    int estimate_pair(const void *d_a, const void *d_b, uint32_t w, uint32_t h, const FlowParams &p, void *d_flow_out,
+                      hipStream_t stream);
     // multi-step kernels, a chunk of consecutive pairs per launch (pairs on the grid's y / z axis): as many as fit the
     // workspace budget (64 MB per 1080p pair, 88 MB with coefficient planes), at most 150 (round 6; 100 and 6 GiB before: with
     // more pairs per launch the levels are cut into fewer row blocks, i.e. fewer halo rows are recomputed -- the motion step with
@@ -89,14 +135,15 @@ private:
     // GPU's 288);  64 -> 100 pairs per chunk had been 76 -> 71 us per pair (profiles/r02_flow_jacobi_streamed_ab.txt)
     static constexpr uint32_t kStreamMaxChunkPairs = 150;
     static constexpr size_t kStreamWorkspaceBytes = (size_t)12 << 30;
-    int stream_impl(const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t h, uint32_t levels, uint32_t coarse_iters,
-                    uint32_t refine_iters, float lambda, void *d_flows, void *d_mid, float t, hipStream_t stream, bool flow_half = false,
-                    const MidTimes *mt = nullptr);
-    int solve_batch(const uint8_t *d_frames, uint32_t pairs, const Pyramid &g, uint32_t coarse_iters, uint32_t refine_iters,
-                    float lambda, uint8_t *d_flows, hipStream_t stream, uint8_t *d_mid = nullptr, float t = 0.5f,
-                    bool flow_half = false, const MidTimes *mt = nullptr);
+    int stream_impl(const StreamJob &J, const FlowParams &p);
+    int solve_batch(const StreamJob &J, const Pyramid &g, const FlowParams &p); // J: one chunk
+    static WarpLaunch warp_behind(const StreamJob &J, const void *flow); // the warp kernel behind the estimator, over J's pairs
     int ensure_device();
-    int reserve(size_t bytes, int slot); // grow-only device scratch slots
+    static constexpr uint64_t kMaxPixels = (1ull << 28) - 1;
+    int check_size(uint32_t w, uint32_t h) { return pass(check_dims("flow", w, h, kMaxPixels, "bad image dimensions")); }
+    int reserve(size_t bytes, Slot slot);
+    float *f32(Slot slot) const { return static_cast<float *>(slot_[slot].get()); }
+    uint8_t *u8(Slot slot) const { return static_cast<uint8_t *>(slot_[slot].get()); }
     void release();
 
     std::mutex mu_;
@@ -108,7 +155,6 @@ private:
     hipStream_t stream_ = nullptr;
     bool scene_ = false; // set_scene_detect
     uint32_t scene_mad_ = 20, scene_hist_ = 400;
-    static constexpr int kSlotCount = 12; // 0-5 pyramids / flows / planes, 6-7 the host entry point's frames, 8 the FAST pair, 9 one pair's flow, 10 a chunk's flows as f16, 11 the scene detector's workspace and flags
     DeviceBuffer slot_[kSlotCount];
 };
 

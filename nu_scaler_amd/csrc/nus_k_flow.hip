@@ -1187,10 +1187,8 @@ hipError_t launch_rgba8_to_f32(const uint8_t *in, float *out, uint32_t w, uint32
 hipError_t launch_blur(const float *in, float *out, uint32_t w, uint32_t h, bool horizontal, hipStream_t stream)
 {
     const dim3 block(kWave, 4), grid(cdiv(w, kWave), cdiv(h, 4));
-    if (horizontal)
-        hipLaunchKernelGGL(k_blur<true>, grid, block, 0, stream, reinterpret_cast<const float4 *>(in), reinterpret_cast<float4 *>(out), (int)w, (int)h);
-    else
-        hipLaunchKernelGGL(k_blur<false>, grid, block, 0, stream, reinterpret_cast<const float4 *>(in), reinterpret_cast<float4 *>(out), (int)w, (int)h);
+    hipLaunchKernelGGL((horizontal ? k_blur<true> : k_blur<false>), grid, block, 0, stream, reinterpret_cast<const float4 *>(in),
+                       reinterpret_cast<float4 *>(out), (int)w, (int)h);
     return hipGetLastError();
 }
 
@@ -1211,9 +1209,7 @@ hipError_t launch_horn_schunck(const float *i1, const float *i2, const float *fl
     return hipGetLastError();
 }
 
-// Batches: every launcher below takes `n` independent images / pairs on the grid's z axis, buffer b of item z at
-// b + z * stride (strides in elements of the buffer's type; bytes for an RGBA8 input).  n = 1 ignores the strides.
-
+// The launchers below take a batch (FlowImages, nus_kernels.hpp).
 // One fused pyramid level: `in` is RGBA8 (u8_input) or f32 RGBA; writes the level's luminance plane
 // (w*h floats) and the f32 RGBA input of the next level; `next` may be null (last level).
 #ifndef NUS_PYR_STREAM_WAVES
@@ -1225,9 +1221,9 @@ hipError_t launch_horn_schunck(const float *i1, const float *i2, const float *fl
 
 // FAST pyramid level (k_pyramid_fast): luminance only.  `in`: RGBA8 frames (level 0; in_stride in bytes) or the previous level's
 // quarter-size luminance output (floats; in_stride in floats); `next`: this level's output for the next one (floats), or null.
-hipError_t launch_pyramid_level_fast(const void *in, bool u8_input, float *level_lum, float *next, uint32_t w, uint32_t h,
-                                     hipStream_t stream, uint32_t n, size_t in_stride, size_t lum_stride, size_t next_stride)
+hipError_t launch_pyramid_level_fast(const PyramidLevelLaunch &L)
 {
+    const uint32_t w = L.img.w, h = L.img.h, n = L.img.n;
 #if defined(NUS_ABLATE_PYR_ALIGNED_STRIPS)
     const uint32_t strips = cdiv(w, 4 * kWave);
 #else
@@ -1239,18 +1235,15 @@ hipError_t launch_pyramid_level_fast(const void *in, bool u8_input, float *level
     const uint32_t rows_per_block = (cdiv(h, want) + 1) & ~1u; // even: a 2x2 block never straddles two row blocks
     const uint32_t row_blocks = cdiv(h, rows_per_block);
     const dim3 block(256), grid(cdiv(strips * row_blocks, 4), n);
-    if (u8_input)
-        hipLaunchKernelGGL(k_pyramid_fast<true>, grid, block, 0, stream, in, in_stride, level_lum, lum_stride, next, next_stride, (int)w,
-                           (int)h, (int)strips, (int)row_blocks, (int)rows_per_block);
-    else
-        hipLaunchKernelGGL(k_pyramid_fast<false>, grid, block, 0, stream, in, in_stride, level_lum, lum_stride, next, next_stride, (int)w,
-                           (int)h, (int)strips, (int)row_blocks, (int)rows_per_block);
+    hipLaunchKernelGGL((L.u8_input ? k_pyramid_fast<true> : k_pyramid_fast<false>), grid, block, 0, L.img.stream, L.in, L.in_stride, L.level_lum,
+                       L.lum_stride, L.next, L.next_stride, (int)w, (int)h, (int)strips, (int)row_blocks, (int)rows_per_block);
     return hipGetLastError();
 }
 
-hipError_t launch_pyramid_level(const void *in, bool u8_input, float *level_lum, float *next, uint32_t w, uint32_t h,
-                                hipStream_t stream, uint32_t n, size_t in_stride, size_t lum_stride, size_t next_stride, int kernel)
+hipError_t launch_pyramid_level(const PyramidLevelLaunch &L, int kernel)
 {
+    const uint32_t w = L.img.w, h = L.img.h, n = L.img.n;
+    float4 *const next = reinterpret_cast<float4 *>(L.next);
     if (kernel != kJacobiTiles) {
         const uint32_t strips = cdiv(w, 2 * kWave - 4);
         const uint64_t columns = (uint64_t)strips * n;
@@ -1260,56 +1253,41 @@ hipError_t launch_pyramid_level(const void *in, bool u8_input, float *level_lum,
         const uint32_t row_blocks = cdiv(h, rows_per_block);
         if (kernel == kJacobiStream || kernel == kJacobiStreamFast || columns * row_blocks >= 2048) {
             const dim3 block(256), grid(cdiv(strips * row_blocks, 4), n);
-            if (u8_input)
-                hipLaunchKernelGGL(k_pyramid_stream<true>, grid, block, 0, stream, in, in_stride, level_lum, lum_stride,
-                                   reinterpret_cast<float4 *>(next), next_stride, (int)w, (int)h, (int)strips, (int)row_blocks,
-                                   (int)rows_per_block);
-            else
-                hipLaunchKernelGGL(k_pyramid_stream<false>, grid, block, 0, stream, in, in_stride, level_lum, lum_stride,
-                                   reinterpret_cast<float4 *>(next), next_stride, (int)w, (int)h, (int)strips, (int)row_blocks,
-                                   (int)rows_per_block);
+            hipLaunchKernelGGL((L.u8_input ? k_pyramid_stream<true> : k_pyramid_stream<false>), grid, block, 0, L.img.stream, L.in, L.in_stride,
+                               L.level_lum, L.lum_stride, next, L.next_stride, (int)w, (int)h, (int)strips, (int)row_blocks, (int)rows_per_block);
             return hipGetLastError();
         }
     }
     const dim3 block(kPyrThreads), grid(cdiv(w, kPyrTW), cdiv(h, kPyrTH), n);
-    if (u8_input)
-        hipLaunchKernelGGL(k_pyramid_level<true>, grid, block, 0, stream, in, in_stride, level_lum, lum_stride,
-                           reinterpret_cast<float4 *>(next), next_stride, (int)w, (int)h);
-    else
-        hipLaunchKernelGGL(k_pyramid_level<false>, grid, block, 0, stream, in, in_stride, level_lum, lum_stride,
-                           reinterpret_cast<float4 *>(next), next_stride, (int)w, (int)h);
+    hipLaunchKernelGGL((L.u8_input ? k_pyramid_level<true> : k_pyramid_level<false>), grid, block, 0, L.img.stream, L.in, L.in_stride, L.level_lum,
+                       L.lum_stride, next, L.next_stride, (int)w, (int)h);
     return hipGetLastError();
 }
 
 // coef: 3 floats (ix, iy, it) per cell -> w*h*12 bytes
-hipError_t launch_hs_prepare(const float *i1, const float *i2, bool luminance_planes, float *coef, uint32_t w, uint32_t h,
-                             hipStream_t stream, uint32_t n, size_t img_stride, size_t coef_stride)
+hipError_t launch_hs_prepare(const HsPrepareLaunch &L)
 {
-    const dim3 block(kWave, 4), grid(cdiv(w, kWave), cdiv(h, 4), n);
-    if (luminance_planes)
-        hipLaunchKernelGGL(k_hs_prepare<float>, grid, block, 0, stream, i1, i2, img_stride, coef, coef_stride, (int)w, (int)h);
+    const dim3 block(kWave, 4), grid(cdiv(L.img.w, kWave), cdiv(L.img.h, 4), L.img.n);
+    if (L.luminance_planes)
+        hipLaunchKernelGGL(k_hs_prepare<float>, grid, block, 0, L.img.stream, L.i1, L.i2, L.img_stride, L.coef, L.coef_stride, (int)L.img.w, (int)L.img.h);
     else
-        hipLaunchKernelGGL(k_hs_prepare<float4>, grid, block, 0, stream, reinterpret_cast<const float4 *>(i1),
-                           reinterpret_cast<const float4 *>(i2), img_stride, coef, coef_stride, (int)w, (int)h);
+        hipLaunchKernelGGL(k_hs_prepare<float4>, grid, block, 0, L.img.stream, reinterpret_cast<const float4 *>(L.i1),
+                           reinterpret_cast<const float4 *>(L.i2), L.img_stride, L.coef, L.coef_stride, (int)L.img.w, (int)L.img.h);
     return hipGetLastError();
 }
 
 // prepare (luminance planes) + upsample of the coarser flow in one launch
-hipError_t launch_hs_level_setup(const float *l1, const float *l2, float *coef, uint32_t w, uint32_t h, const float *coarse,
-                                 uint32_t cw, uint32_t ch, float *flow, float scale, hipStream_t stream, uint32_t n,
-                                 size_t lum_stride, size_t coef_stride, size_t coarse_stride, size_t flow_stride)
+hipError_t launch_hs_level_setup(const HsPrepareLaunch &L, const HsCoarseFlow &coarse, float *flow, size_t flow_stride)
 {
-    const dim3 block(kWave, 4), grid(cdiv(w, kWave), cdiv(h, 4), n);
-    hipLaunchKernelGGL(k_hs_level_setup, grid, block, 0, stream, l1, l2, lum_stride, coef, coef_stride, (int)w, (int)h,
-                       reinterpret_cast<const float2 *>(coarse), coarse_stride, (int)cw, (int)ch,
-                       reinterpret_cast<float2 *>(flow), flow_stride, scale);
+    if (!L.luminance_planes) return hipErrorInvalidValue;
+    const dim3 block(kWave, 4), grid(cdiv(L.img.w, kWave), cdiv(L.img.h, 4), L.img.n);
+    hipLaunchKernelGGL(k_hs_level_setup, grid, block, 0, L.img.stream, L.i1, L.i2, L.img_stride, L.coef, L.coef_stride, (int)L.img.w, (int)L.img.h,
+                       reinterpret_cast<const float2 *>(coarse.flow), coarse.stride, (int)coarse.w, (int)coarse.h,
+                       reinterpret_cast<float2 *>(flow), flow_stride, coarse.scale);
     return hipGetLastError();
 }
 
-// `iterations` Jacobi steps from *flow_a (from zero flow without reading it if zero_start),
-// ping-ponging with *flow_b; on return *flow_a holds the result (the pointers are swapped as
-// needed; with final_out the last launch writes there -- item stride final_stride -- and *flow_a == final_out).
-// Steps are split evenly over the launches.  Tile shape by the number of 32x32 tiles the whole batch has:
+// `iterations` Jacobi steps (HsIterateLaunch, nus_kernels.hpp).  Tile shape by the number of 32x32 tiles the whole batch has:
 //   >= 1024 (1080p, or a batch of smaller levels): 32-wide tiles, 256 threads (7 cells per thread, 5 tiles per CU
 //            by LDS), at most 5 steps per launch (beyond that the tile's registers and LDS cost a wave per SIMD);
 //   >= 256  (one 960x540 level): 32-wide tiles with 1024 threads;
@@ -1381,27 +1359,87 @@ bool hs_iterate_streams(uint32_t w, uint32_t h, uint32_t n, int kernel)
            hs_stream_shape(w, h, n, NUS_HS_STREAM_MAXK, kernel == kJacobiStream || kernel == kJacobiStreamFast).row_blocks != 0;
 }
 
-hipError_t launch_hs_iterate(const float *coef, float lambda, float **flow_a, float **flow_b, uint32_t w, uint32_t h,
-                             uint32_t iterations, bool zero_start, float *final_out, hipStream_t stream, uint32_t n,
-                             size_t coef_stride, size_t flow_stride, size_t final_stride, int kernel, const float *lum1,
-                             size_t lum_stride, const float *coarse, uint32_t cw, uint32_t ch, float coarse_scale, size_t coarse_stride,
-                             const HsWarp *warp, bool *warped, bool *wrote_half)
+hipError_t launch_hs_iterate(const HsIterateLaunch &L, HsIterateResult *result)
 {
-    if (kernel == kJacobiStreamFast) { // FAST arithmetic (k_hs_stream_fast): always streamed, always from the luminance planes
-        if (lum1 == nullptr) return hipErrorInvalidValue;
-        // one launch of k steps over pairs [0, m) of the given bases
-        bool did_warp = false, did_half = false;
-        auto launch_one = [&](uint32_t k, bool ups, const float *lum, const float2 *fi, float2 *fo, size_t out_stride, const HsCoarse &hc,
-                              uint32_t m, const HsWarp *wp, bool half_out, bool half_in) -> hipError_t {
+    const uint32_t w = L.img.w, h = L.img.h, n = L.img.n;
+    const hipStream_t stream = L.img.stream;
+    const float lambda = L.lambda;
+    const size_t flow_stride = L.flow_stride;
+    HsIterateResult res;
+    res.flow = L.flow_a, res.spare = L.flow_b;
+    // The split, for every kernel family: ceil(iterations / maxk) launches of evenly many steps (1..maxk), ping-ponging between the
+    // two buffers; the first reads no flow if zero_start and is the one that sees L.coarse, the last writes final_out if there is one.
+    // launch_steps(k, left, fi, fo, out_stride, hc): one launch of k steps from fi (null: zero flow) into fo, `left` launches of the
+    // level left (this one included); hc.flow set: the level continues the coarser level's flow.
+    auto run = [&](uint32_t maxk, auto &&launch_steps) -> hipError_t {
+        uint32_t iterations = L.iterations, launches = (iterations + maxk - 1) / maxk;
+        bool zero_start = L.zero_start;
+        const float *coarse = L.coarse.flow;
+        while (iterations > 0) {
+            const uint32_t k = (iterations + launches - 1) / launches;
+            size_t out_stride = flow_stride;
+            if (L.final_out && launches == 1) {
+                res.spare = L.final_out;
+                out_stride = L.final_stride;
+            }
+            const float2 *fi = zero_start ? nullptr : reinterpret_cast<const float2 *>(res.flow);
+            const HsCoarse hc{reinterpret_cast<const float2 *>(coarse), L.coarse.stride, (int)L.coarse.w, (int)L.coarse.h, L.coarse.scale};
+            zero_start = false;
+            coarse = nullptr;
+            const hipError_t e = launch_steps(k, launches, fi, reinterpret_cast<float2 *>(res.spare), out_stride, hc);
+            if (e != hipSuccess) return e;
+            iterations -= k;
+            --launches;
+            std::swap(res.flow, res.spare);
+        }
+        if (result) *result = res;
+        return hipSuccess;
+    };
+    if (L.kernel == kJacobiStreamFast) { // FAST arithmetic (k_hs_stream_fast): always streamed, always from the luminance planes
+        const float *const lum = L.lum1;
+        const size_t lum_stride = L.lum_stride;
+        if (lum == nullptr) return hipErrorInvalidValue;
+        const HsWarp *const warp = L.warp;
+        // a level with many steps (the coarsest: 50) takes more of them per launch: its launches are short and memory-bound, and
+        // fewer of them move fewer bytes; the levels with 10 steps stay at 5 (ten per launch costs two waves per SIMD)
+        const uint32_t maxk = L.iterations >= 30 ? NUS_HS_FAST_MAXK_LONG : NUS_HS_FAST_MAXK;
+        const char *hb_env = getenv("NUS_HS_L0_HALF_BETWEEN"); // dev switch: see HsWarp::in_half
+        const bool half_between =
+            hb_env != nullptr && hb_env[0] == '1' && warp != nullptr && (L.iterations + maxk - 1) / maxk == 2 && !L.zero_start;
+        bool prev_stored_half = false;
+        bool &did_warp = res.warped;
+        // (Measured and dropped, round 4: the finest level in sub-chunks of 4-50 pairs, its two launches back to back per sub-chunk so
+        // that the second finds the first's output and the luminance planes in the 256-MiB Infinity Cache -- identical flows,
+        // 61 / 58 / 55 / 54 / 53 / 52 / 50 us per pair at 4 / 6 / 8 / 12 / 16 / 25 / 50 pairs against 50.5 for the whole chunk: launches
+        // of a few thousand waves lose more than the cache gives.)
+        return run(maxk, [&](uint32_t k, uint32_t left, const float2 *fi, float2 *fo, size_t out_stride, const HsCoarse &hc) {
+            const bool ups = hc.flow != nullptr; // the first launch of a level takes the coarser level's flow, upsampled as it loads it
+            // the last launch of the level warps with the flow it finishes, where it can (see HsWarp); then the flow is stored only
+            // for a caller who asked for it
+            // OFF unless NUS_HS_FUSED_WARP=1 is in the environment: built and measured in round 5 -- identical bytes, but the fused launch
+            // takes 23 us per 1080p pair where the plain launch and the warp kernel take 12.2 + 7.9: the Jacobi pass has one pixel per
+            // lane, so the warp's gathers are 8-byte loads at a 4-byte lane stride (every texel pair fetched twice) and its ~140
+            // instructions per pixel run at four waves per SIMD (119 VGPRs) next to a pass that was at the memory rate, not below it
+            // (motion step 21.0 against 20.1 ms per 300 units).  The warp kernel's 2 x 2 pixels per thread is the better shape.
+            const char *fuse_env = getenv("NUS_HS_FUSED_WARP");
+            const bool can_warp = fuse_env != nullptr && fuse_env[0] == '1' &&
+                                  warp != nullptr && warp->frames != nullptr && warp->mid != nullptr && left == 1 && !ups && k <= 5 &&
+                                  NUS_HS_FAST_RING != 0 && w >= 2 && h >= 2 && (uint64_t)w * h * 4 < (1ull << 32) &&
+                                  (uint64_t)w * 4 < (1u << 24) && h < (1u << 24);
+            if (can_warp && L.final_out == nullptr) fo = nullptr;
+            const bool half_out = warp != nullptr && warp->out_half != 0 && left == 1; // the level's final flow as Rg16Float
+            if (half_out) res.wrote_half = true;
+            const bool mid_half = half_between && left == 2; // the first of the two launches stores halves for the second
             HsWarp tail; // what the plain instantiations see of it: only the format of the flow they store (and load)
-            tail.out_half = half_out ? 1u : 0u;
-            tail.in_half = half_in ? 1u : 0u;
-            HsWarp wfull = wp ? *wp : HsWarp{};
+            tail.out_half = half_out || mid_half ? 1u : 0u;
+            tail.in_half = prev_stored_half ? 1u : 0u;
+            prev_stored_half = mid_half;
+            HsWarp wfull = can_warp ? *warp : HsWarp{};
             wfull.out_half = tail.out_half;
             wfull.in_half = tail.in_half;
-            if (wp) wp = &wfull;
-            const HsStreamShape sh = hs_stream_shape(w, h, m, k, true);
-            const dim3 block(256), grid(cdiv(sh.strips * sh.row_blocks, 4), m);
+            const HsWarp *const wp = can_warp ? &wfull : nullptr;
+            const HsStreamShape sh = hs_stream_shape(w, h, n, k, true);
+            const dim3 block(256), grid(cdiv(sh.strips * sh.row_blocks, 4), n);
 #define NUS_HSF_L(KK, UU, RR)                                                                                                        \
     hipLaunchKernelGGL((k_hs_stream_fast<KK, UU, RR>), grid, block, 0, stream, lum, lum_stride, lambda, fi, flow_stride, fo, out_stride, \
                        (int)w, (int)h, (int)sh.strips, (int)sh.row_blocks, (int)sh.rows_per_block, hc, tail)
@@ -1439,80 +1477,17 @@ hipError_t launch_hs_iterate(const float *coef, float lambda, float **flow_a, fl
 #undef NUS_HSF_L
 #undef NUS_HSF_W
             return hipGetLastError();
-        };
-        // a level with many steps (the coarsest: 50) takes more of them per launch: its launches are short and memory-bound, and
-        // fewer of them move fewer bytes; the levels with 10 steps stay at 5 (ten per launch costs two waves per SIMD)
-        const uint32_t maxk = iterations >= 30 ? NUS_HS_FAST_MAXK_LONG : NUS_HS_FAST_MAXK;
-        uint32_t launches = (iterations + maxk - 1) / maxk;
-        const char *hb_env = getenv("NUS_HS_L0_HALF_BETWEEN"); // dev switch: see HsWarp::in_half
-        const bool half_between = hb_env != nullptr && hb_env[0] == '1' && warp != nullptr && launches == 2 && !zero_start;
-        bool prev_stored_half = false;
-        // (Measured and dropped, round 4: the finest level in sub-chunks of 4-50 pairs, its two launches back to back per sub-chunk so
-        // that the second finds the first's output and the luminance planes in the 256-MiB Infinity Cache -- identical flows,
-        // 61 / 58 / 55 / 54 / 53 / 52 / 50 us per pair at 4 / 6 / 8 / 12 / 16 / 25 / 50 pairs against 50.5 for the whole chunk: launches
-        // of a few thousand waves lose more than the cache gives.)
-        while (iterations > 0) {
-            const uint32_t k = (iterations + launches - 1) / launches; // even split, 1..maxk steps per launch
-            size_t out_stride = flow_stride;
-            if (final_out && launches == 1) { // the last launch writes the caller's buffer
-                *flow_b = final_out;
-                out_stride = final_stride;
-            }
-            auto fi = zero_start ? nullptr : reinterpret_cast<const float2 *>(*flow_a);
-            auto fo = reinterpret_cast<float2 *>(*flow_b);
-            zero_start = false;
-            const bool ups = coarse != nullptr; // the first launch of a level takes the coarser level's flow, upsampled as it loads it
-            const HsCoarse hc{reinterpret_cast<const float2 *>(coarse), coarse_stride, (int)cw, (int)ch, coarse_scale};
-            coarse = nullptr;
-            // the last launch of the level warps with the flow it finishes, where it can (see HsWarp); then the flow is stored only
-            // for a caller who asked for it
-            // OFF unless NUS_HS_FUSED_WARP=1 is in the environment: built and measured in round 5 -- identical bytes, but the fused launch
-            // takes 23 us per 1080p pair where the plain launch and the warp kernel take 12.2 + 7.9: the Jacobi pass has one pixel per
-            // lane, so the warp's gathers are 8-byte loads at a 4-byte lane stride (every texel pair fetched twice) and its ~140
-            // instructions per pixel run at four waves per SIMD (119 VGPRs) next to a pass that was at the memory rate, not below it
-            // (motion step 21.0 against 20.1 ms per 300 units).  The warp kernel's 2 x 2 pixels per thread is the better shape.
-            const char *fuse_env = getenv("NUS_HS_FUSED_WARP");
-            const bool can_warp = fuse_env != nullptr && fuse_env[0] == '1' &&
-                                  warp != nullptr && warp->frames != nullptr && warp->mid != nullptr && launches == 1 && !ups && k <= 5 &&
-                                  NUS_HS_FAST_RING != 0 && w >= 2 && h >= 2 && (uint64_t)w * h * 4 < (1ull << 32) &&
-                                  (uint64_t)w * 4 < (1u << 24) && h < (1u << 24);
-            if (can_warp && final_out == nullptr) fo = nullptr;
-            const bool half_out = warp != nullptr && warp->out_half != 0 && launches == 1; // the level's final flow as Rg16Float
-            if (half_out) did_half = true;
-            const bool mid_half = half_between && launches == 2; // the first of the two launches stores halves for the second
-            hipError_t e = launch_one(k, ups, lum1, fi, fo, out_stride, hc, n, can_warp ? warp : nullptr, half_out || mid_half, prev_stored_half);
-            prev_stored_half = mid_half;
-            if (e != hipSuccess) return e;
-            iterations -= k;
-            --launches;
-            float *t = *flow_a;
-            *flow_a = *flow_b;
-            *flow_b = t;
-        }
-        if (warped) *warped = did_warp;
-        if (wrote_half) *wrote_half = did_half;
-        return hipSuccess;
+        });
     }
-    if (warped) *warped = false;
-    if (wrote_half) *wrote_half = false;
-    if (hs_iterate_streams(w, h, n, kernel)) {
-        if (lum1) coef = lum1, coef_stride = lum_stride; // the kernel takes the derivatives from the planes themselves
-        uint32_t launches = (iterations + NUS_HS_STREAM_MAXK - 1) / NUS_HS_STREAM_MAXK;
-        while (iterations > 0) {
-            const uint32_t k = (iterations + launches - 1) / launches; // even split, 1..MAXK steps per launch
-            size_t out_stride = flow_stride;
-            if (final_out && launches == 1) { // the last launch writes the caller's buffer
-                *flow_b = final_out;
-                out_stride = final_stride;
-            }
-            auto fi = zero_start ? nullptr : reinterpret_cast<const float2 *>(*flow_a);
-            auto fo = reinterpret_cast<float2 *>(*flow_b);
-            zero_start = false;
+    if (hs_iterate_streams(w, h, n, L.kernel)) {
+        const float *const lum1 = L.lum1;
+        // with luminance planes the kernel takes the derivatives from the planes themselves
+        const float *const coef = lum1 ? lum1 : L.coef;
+        const size_t coef_stride = lum1 ? L.lum_stride : L.coef_stride;
+        return run(NUS_HS_STREAM_MAXK, [&](uint32_t k, uint32_t, const float2 *fi, float2 *fo, size_t out_stride, const HsCoarse &hc) {
             const HsStreamShape sh = hs_stream_shape(w, h, n, k, true);
             // the first launch of a level that continues a coarser one takes that level's flow, upsampled as it is loaded
-            const bool ups = coarse != nullptr && lum1 != nullptr;
-            const HsCoarse hc{reinterpret_cast<const float2 *>(coarse), coarse_stride, (int)cw, (int)ch, coarse_scale};
-            coarse = nullptr;
+            const bool ups = hc.flow != nullptr && lum1 != nullptr;
             const dim3 block(256), grid(cdiv(sh.strips * sh.row_blocks, 4), n);
 #define NUS_HSS_L(KK, LL, UU)                                                                                               \
     hipLaunchKernelGGL((k_hs_stream<KK, LL, UU>), grid, block, 0, stream, coef, coef_stride, lambda, fi, flow_stride, fo, out_stride, \
@@ -1537,33 +1512,17 @@ hipError_t launch_hs_iterate(const float *coef, float lambda, float **flow_a, fl
             }
 #undef NUS_HSS
 #undef NUS_HSS_L
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return e;
-            iterations -= k;
-            --launches;
-            float *t = *flow_a;
-            *flow_a = *flow_b;
-            *flow_b = t;
-        }
-        return hipSuccess;
+            return hipGetLastError();
+        });
     }
+    const float *const coef = L.coef;
+    const size_t coef_stride = L.coef_stride;
     const uint64_t tiles32 = (uint64_t)cdiv(w, 32) * cdiv(h, 32) * n;
     const int cls = tiles32 >= 1024 ? 2 : (tiles32 >= 256 ? 1 : 0);
     const uint32_t T = cls == 2 ? 32 : (cls == 1 ? NUS_HS_MID_T : NUS_HS_SMALL_T);
     const uint32_t NT = cls == 2 ? NUS_HS_BIG_THREADS : (cls == 1 ? NUS_HS_MID_THREADS : NUS_HS_SMALL_THREADS);
     const dim3 block(NT), grid(cdiv(w, T), cdiv(h, T), n);
-    const uint32_t maxk = cls == 2 ? 5 : 8;
-    uint32_t launches = (iterations + maxk - 1) / maxk;
-    while (iterations > 0) {
-        const uint32_t k = (iterations + launches - 1) / launches; // even split, 1..maxk steps per launch
-        size_t out_stride = flow_stride;
-        if (final_out && launches == 1) { // the last launch writes the caller's buffer
-            *flow_b = final_out;
-            out_stride = final_stride;
-        }
-        auto fi = zero_start ? nullptr : reinterpret_cast<const float2 *>(*flow_a);
-        auto fo = reinterpret_cast<float2 *>(*flow_b);
-        zero_start = false;
+    return run(cls == 2 ? 5 : 8, [&](uint32_t k, uint32_t, const float2 *fi, float2 *fo, size_t out_stride, const HsCoarse &) {
 #define NUS_HS_L(TT, KK, TH)                                                                                                  \
     hipLaunchKernelGGL((k_hs_tiled<TT, KK, TH>), grid, block, 0, stream, coef, coef_stride, lambda, fi, flow_stride, fo, out_stride, \
                        (int)w, (int)h)
@@ -1578,15 +1537,8 @@ hipError_t launch_hs_iterate(const float *coef, float lambda, float **flow_a, fl
         }
 #undef NUS_HS
 #undef NUS_HS_L
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        iterations -= k;
-        --launches;
-        float *t = *flow_a;
-        *flow_a = *flow_b;
-        *flow_b = t;
-    }
-    return hipSuccess;
+        return hipGetLastError();
+    });
 }
 
 namespace {
@@ -1608,12 +1560,11 @@ hipError_t launch_flow_to_half(const float *src, void *dst, size_t n_cells, hipS
     return hipGetLastError();
 }
 
-hipError_t launch_flow_upsample(const float *src, uint32_t sw, uint32_t sh, float *dst, uint32_t dw, uint32_t dh,
-                                float scale, hipStream_t stream, uint32_t n, size_t src_stride, size_t dst_stride)
+hipError_t launch_flow_upsample(const FlowImages &D, const HsCoarseFlow &coarse, float *dst, size_t dst_stride)
 {
-    const dim3 block(kWave, 4), grid(cdiv(dw, kWave), cdiv(dh, 4), n);
-    hipLaunchKernelGGL(k_flow_upsample, grid, block, 0, stream, reinterpret_cast<const float2 *>(src), src_stride, (int)sw, (int)sh,
-                       reinterpret_cast<float2 *>(dst), dst_stride, (int)dw, (int)dh, scale);
+    const dim3 block(kWave, 4), grid(cdiv(D.w, kWave), cdiv(D.h, 4), D.n);
+    hipLaunchKernelGGL(k_flow_upsample, grid, block, 0, D.stream, reinterpret_cast<const float2 *>(coarse.flow), coarse.stride, (int)coarse.w,
+                       (int)coarse.h, reinterpret_cast<float2 *>(dst), dst_stride, (int)D.w, (int)D.h, coarse.scale);
     return hipGetLastError();
 }
 

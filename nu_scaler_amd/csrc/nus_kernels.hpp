@@ -207,33 +207,52 @@ hipError_t launch_blur(const float *in, float *out, uint32_t w, uint32_t h, bool
 hipError_t launch_downsample(const float *in, float *out, uint32_t w, uint32_t h, hipStream_t stream);
 hipError_t launch_horn_schunck(const float *i1, const float *i2, const float *flow_in, float *flow_out, uint32_t w,
                                uint32_t h, float lambda, hipStream_t stream);
-// The launchers below take a batch: `n` independent images / pairs on the grid's z axis, buffer b of item z at
-// b + z * stride (strides in elements of the buffer's type; bytes for an RGBA8 input).  n = 1 ignores the strides.
-// blur H + blur V + downsample of one level in one launch (LDS tile with a 2-pixel halo); the level
-// itself is written as its luminance plane (w*h floats), which is all Horn-Schunck reads of it.
+// What the batch launchers below share: `n` independent images / pairs of w x h on the grid's z (streamed kernels: y) axis.
+struct FlowImages {
+    uint32_t w = 0, h = 0;
+    uint32_t n = 1; // buffer b of item z is at b + z * (b's stride member); n = 1 ignores the strides
+    hipStream_t stream = nullptr;
+};
 // `kernel`: LDS-tile or register-pipelined ("streamed") form of the pyramid and the multi-step Jacobi kernels
 enum JacobiKernel { kJacobiAuto = 0, kJacobiTiles = 1, kJacobiStream = 2, kJacobiStreamFast = 3 }; // Fast: k_hs_stream_fast, every level
-hipError_t launch_pyramid_level(const void *in, bool u8_input, float *level_lum, float *next, uint32_t w, uint32_t h,
-                                hipStream_t stream, uint32_t n = 1, size_t in_stride = 0, size_t lum_stride = 0,
-                                size_t next_stride = 0, int kernel = 0);
-// Fast path of the same iteration: derivatives once per level, then K steps per launch in LDS.
-// i1 / i2: f32 RGBA level images, or their luminance planes (luminance_planes).
-hipError_t launch_pyramid_level_fast(const void *in, bool u8_input, float *level_lum, float *next, uint32_t w, uint32_t h,
-                                     hipStream_t stream, uint32_t n, size_t in_stride, size_t lum_stride, size_t next_stride);
-hipError_t launch_hs_prepare(const float *i1, const float *i2, bool luminance_planes, float *coef, uint32_t w, uint32_t h,
-                             hipStream_t stream, uint32_t n = 1, size_t img_stride = 0, size_t coef_stride = 0);
-// launch_hs_prepare on luminance planes + launch_flow_upsample of the coarser level's flow, one launch.
-hipError_t launch_hs_level_setup(const float *l1, const float *l2, float *coef, uint32_t w, uint32_t h, const float *coarse,
-                                 uint32_t cw, uint32_t ch, float *flow, float scale, hipStream_t stream, uint32_t n = 1,
-                                 size_t lum_stride = 0, size_t coef_stride = 0, size_t coarse_stride = 0,
-                                 size_t flow_stride = 0);
+// blur H + blur V + downsample of one level in one launch; the level itself is written as its luminance plane (w*h floats),
+// which is all Horn-Schunck reads of it.
+struct PyramidLevelLaunch {
+    FlowImages img;
+    const void *in = nullptr; // RGBA8 (u8_input) or f32 RGBA; launch_pyramid_level_fast: RGBA8 or the previous level's `next`
+    bool u8_input = false;
+    float *level_lum = nullptr;
+    float *next = nullptr; // input of the next level, quarter size: f32 RGBA (fast: one float per pixel); null at the last level
+    size_t in_stride = 0;  // in bytes for an RGBA8 input, else in elements of the buffer (float4, or float for the fast kernel)
+    size_t lum_stride = 0, next_stride = 0; // in floats; in float4 for the exact kernels' `next`
+};
+hipError_t launch_pyramid_level(const PyramidLevelLaunch &L, int kernel);
+hipError_t launch_pyramid_level_fast(const PyramidLevelLaunch &L); // k_pyramid_fast: luminance only
+// Derivatives once per level: coef = 3 floats (ix, iy, it) per cell.
+struct HsPrepareLaunch {
+    FlowImages img;
+    const float *i1 = nullptr, *i2 = nullptr; // f32 RGBA level images, or their luminance planes (luminance_planes)
+    bool luminance_planes = false;
+    float *coef = nullptr;
+    size_t img_stride = 0, coef_stride = 0; // in pixels of the images; in floats
+};
+hipError_t launch_hs_prepare(const HsPrepareLaunch &L);
+// The flow of the next coarser level (cw x ch), which a level continues: upsampled to w x h, its vectors times `scale`.
+struct HsCoarseFlow {
+    const float *flow = nullptr; // null: none
+    uint32_t w = 0, h = 0;
+    float scale = 0.0f;
+    size_t stride = 0; // in cells (float2)
+};
+// launch_hs_prepare on luminance planes + launch_flow_upsample of `coarse` into `flow` (item stride in cells), one launch.
+hipError_t launch_hs_level_setup(const HsPrepareLaunch &L, const HsCoarseFlow &coarse, float *flow, size_t flow_stride);
 // HsWarp (round 5; used only with NUS_HS_FUSED_WARP=1 in the environment: measured slower than the warp kernel behind the estimator):
 // the LAST launch of the finest level can warp + blend the pair's two frames with the flow it has just finished
 // (dense-flow warp in FMA mode, nus_warp_device.hpp) and store the in-between frame -- the flow then never has to be written for the
 // warp to read it back.  frames: RGBA8 frame of pair z at frames + z * frame_stride bytes, its partner one frame_stride further;
-// mid: w * h RGBA8 pixels per pair, tightly packed.  *warped tells the caller whether the launch that ran could do it (FAST ring
-// form, not the launch that upsamples the coarser level, frames of at least 2 x 2 pixels and less than 4 GiB); if not, the caller
-// runs the warp kernel itself.  With a warp and final_out == nullptr the flow of the last launch is not stored at all.
+// mid: w * h RGBA8 pixels per pair, tightly packed.  HsIterateResult::warped tells the caller whether the launch that ran could do it
+// (FAST ring form, not the launch that upsamples the coarser level, frames of at least 2 x 2 pixels and less than 4 GiB); if not, the
+// caller runs the warp kernel itself.  With a warp and final_out == nullptr the flow of the last launch is not stored at all.
 struct HsWarp {
     const uint8_t *frames = nullptr;
     size_t frame_stride = 0;
@@ -242,7 +261,7 @@ struct HsWarp {
     uint32_t sel = 0;
     // the level's FINAL flow as 2 x IEEE half per cell (round to nearest even) instead of 2 x f32: the reference's live flow layout,
     // Rg16Float (wgpu_interpolator.rs:276), for a warp that reads it that way.  Honoured by the FAST streamed kernel's last launch
-    // (*wrote_half says so); everything else leaves f32 and the caller converts (launch_flow_to_half).
+    // (HsIterateResult::wrote_half says so); everything else leaves f32 and the caller converts (launch_flow_to_half).
     uint32_t out_half = 0;
     // dev switch NUS_HS_L0_HALF_BETWEEN=1 (round 6, measured: profiles/r06_flow_level0_half_between_launches.txt): the flow BETWEEN the
     // finest level's two launches as Rg16Float as well -- the launch reads 2 x half per cell
@@ -250,15 +269,30 @@ struct HsWarp {
 };
 // n cells of 2 x f32 -> 2 x f16 (round to nearest even)
 hipError_t launch_flow_to_half(const float *src, void *dst, size_t n_cells, hipStream_t stream);
-hipError_t launch_hs_iterate(const float *coef, float lambda, float **flow_a, float **flow_b, uint32_t w, uint32_t h,
-                             uint32_t iterations, bool zero_start, float *final_out, hipStream_t stream, uint32_t n = 1,
-                             size_t coef_stride = 0, size_t flow_stride = 0, size_t final_stride = 0, int kernel = 0,
-                             const float *lum1 = nullptr, size_t lum_stride = 0, const float *coarse = nullptr, uint32_t cw = 0,
-                             uint32_t ch = 0, float coarse_scale = 0.0f, size_t coarse_stride = 0, const HsWarp *warp = nullptr,
-                             bool *warped = nullptr, bool *wrote_half = nullptr);
+// `iterations` Jacobi steps of one level, K per launch (derivatives once per level, the steps in LDS tiles or a register pipeline).
+struct HsIterateLaunch {
+    FlowImages img;
+    const float *coef = nullptr; // launch_hs_prepare's coefficients; or, for the kernel to take the derivatives from as it goes where
+    const float *lum1 = nullptr; // the level streams (hs_iterate_streams): the luminance plane of the pair's first frame, the second's
+    size_t coef_stride = 0, lum_stride = 0; // one lum_stride further
+    float lambda = 0.0f;
+    uint32_t iterations = 0; // split evenly over the launches
+    bool zero_start = false; // from zero flow, without reading flow_a
+    float *flow_a = nullptr, *flow_b = nullptr; // ping-pong, the flow so far in flow_a
+    float *final_out = nullptr;                 // set: the last launch writes here instead
+    size_t flow_stride = 0, final_stride = 0;   // in cells (float2)
+    int kernel = kJacobiAuto;
+    HsCoarseFlow coarse; // streamed kernels on luminance planes: the first launch starts from this flow, upsampled as it loads it
+    const HsWarp *warp = nullptr;
+};
+struct HsIterateResult {
+    float *flow = nullptr, *spare = nullptr; // where the result is (final_out, if given), and the other buffer of the ping-pong
+    bool warped = false, wrote_half = false; // what the last launch did of L.warp
+};
+hipError_t launch_hs_iterate(const HsIterateLaunch &L, HsIterateResult *result);
 bool hs_iterate_streams(uint32_t w, uint32_t h, uint32_t n, int kernel);
-hipError_t launch_flow_upsample(const float *src, uint32_t sw, uint32_t sh, float *dst, uint32_t dw, uint32_t dh,
-                                float scale, hipStream_t stream, uint32_t n = 1, size_t src_stride = 0, size_t dst_stride = 0);
+// bilinear upsample of `coarse` into D.n flows of D.w x D.h at dst (item stride in cells)
+hipError_t launch_flow_upsample(const FlowImages &D, const HsCoarseFlow &coarse, float *dst, size_t dst_stride);
 
 // Box calibration (nus_k_probe.hip; bench.py's denominators, not on the product path): kind 0 hipMemcpyDtoDAsync, 1 stream
 // copy, 2 write-only, 3 read-only (d_dst: 4 bytes of device memory), 4 one read : four writes (d_dst holds 4 * bytes),
