@@ -1,9 +1,15 @@
 """FSR1-style EASU + RCAS ("next" row).
 
-CPU: the C oracle against its independent numpy twin (PARITY UNPINNED: the reference keeps the two
+CPU: the C oracle against its numpy twin (PARITY UNPINNED: the reference keeps the two
 WGSL shaders in nu_scaler_core/src/upscale/fsr.rs:24-260 but never dispatches them, so there is no
-fixture to pin either restatement to).  GPU: the HIP kernels, through the C ABI, bit-exact against
-the C oracle -- each pass alone and the fused pair.
+reference-held vector to pin either restatement to).  GPU: the HIP kernels, through the C ABI, bit-exact
+against the C oracle -- each pass alone and the fused pair.
+
+The twin is an f32, line-by-line restatement by the same hand as the oracle; what holds FSR1 to the
+shaders' definitions is the float64 witness of tests/_fsr64.py, which shares no code with either: the
+oracle meets it on the CPU (tests/test_fsr64_contract.py), and the HIP kernels, EXACT and FAST, are held
+to it directly on the GPU (tests/test_gpu_fsr_witness.py).  The FAST assertions below ("within 1 LSB of
+the oracle") stay; the witness replaces that statement with a per-sample permitted set.
 """
 import numpy as np
 import pytest
