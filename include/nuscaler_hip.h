@@ -501,6 +501,22 @@ int nus_flow_set_tiled(nus_flow *h, int enabled);
 #define NUS_FLOW_FAST 1
 int nus_flow_set_mode(nus_flow *h, int mode);
 int nus_flow_mode(const nus_flow *h);
+/* Re-linearisation of the finer pyramid levels about the flow they start from (off by default: 0).  Without it every level's data
+ * term is linearised about zero flow, It = L2(x) - L1(x), and the upsampled coarser flow is only the Jacobi start value: motion of
+ * more than about a pixel is not followed.  With warps = W (0 .. NUS_FLOW_MAX_WARPS) every level but the coarsest runs W rounds
+ * after its x2 upsample; a round takes the level's current flow f0 = (u0, v0) (round 1: the upsampled one), samples frame B's
+ * luminance plane bilinearly at (x + u0, y + v0) -- coordinates clamped into the plane, pixel centres at integers, the dense warp's
+ * sampler -- forms It' = ((L2w - L1) - Ix*u0) - Iy*v0 and runs `refine_iters` Jacobi steps from f0 on (Ix, Iy, It'), i.e. on
+ * Ix (u - u0) + Iy (v - v0) + (L2w - L1) = 0 (the intent of the reference's flow_refine.wgsl:94-106, which is not valid WGSL and
+ * never runs).  The setting applies to every estimator entry point of the handle (nus_flow_estimate, _estimate_device,
+ * _estimate_device_stream, _interpolate_device_stream, _interpolate_multi_device_stream); it may be changed at any time; with 0
+ * every entry point writes the bytes and reserves the workspace it did before the setting existed.  A warped level costs one gather
+ * launch per round plus the round's Jacobi steps, and 12 B of coefficient planes per cell and pair of workspace; in NUS_FLOW_FAST
+ * its Jacobi steps run in the exact kernels (inside FAST's 1e-3 px contract).  A value above NUS_FLOW_MAX_WARPS:
+ * NUS_ERR_INVALID_ARGUMENT, the setting unchanged. */
+#define NUS_FLOW_MAX_WARPS 4
+int nus_flow_set_warps(nus_flow *h, uint32_t warps);
+int nus_flow_warps(const nus_flow *h);
 const char *nus_flow_last_error(const nus_flow *h);
 
 /* primitives on host buffers */
@@ -512,6 +528,13 @@ int nus_flow_horn_schunck(nus_flow *h, const float *i1, const float *i2, const f
                           uint32_t w, uint32_t hgt, float lambda, uint32_t iterations, float *flow_out);
 int nus_flow_upsample(nus_flow *h, const float *src, uint32_t sw, uint32_t sh,
                       float *dst, uint32_t dw, uint32_t dh, float scale);
+/* The two halves of a re-linearised level (nus_flow_set_warps), always exact.  _warp_coefficients: f32 RGBA images and a w*h*2
+ * flow -> w*h*3 floats (Ix, Iy, It') per cell; flow == NULL is zero flow and gives (Ix, Iy, It = L2 - L1).
+ * _horn_schunck_coef: `iterations` Jacobi steps on such coefficients; flow_in == NULL starts from zero. */
+int nus_flow_warp_coefficients(nus_flow *h, const float *i1, const float *i2, const float *flow, uint32_t w, uint32_t hgt,
+                               float *coef_out);
+int nus_flow_horn_schunck_coef(nus_flow *h, const float *coef, const float *flow_in, uint32_t w, uint32_t hgt, float lambda,
+                               uint32_t iterations, float *flow_out);
 
 /* Full estimator: pyramids of both RGBA8 frames (`levels`), `coarse_iters` steps from zero
  * flow at the coarsest level, then per finer level a x2 upsample (vectors x2) and

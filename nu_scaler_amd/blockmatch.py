@@ -205,10 +205,14 @@ class PyFrameInterpolator:
     "simplified" run the block matcher at the quality's preset (name "BlockMatching"); "optical_flow" -- and, as in the reference,
     any unknown method -- is the pyramid + Horn-Schunck estimator followed by the dense-flow warp (name "OpticalFlow"; the quality
     is kept and reported).  Unknown quality strings in the constructor mean "medium"; the setter raises.  `bidirectional` (not
-    in the reference) turns the block matcher's forward-backward check on; the optical-flow method has none and raises."""
+    in the reference) turns the block matcher's forward-backward check on; the optical-flow method has none and raises.  `flow_warps`
+    (not in the reference either; 0 .. FLOW_MAX_WARPS) is the optical-flow estimator's re-linearisation rounds per finer level
+    (FlowEstimator.set_warps); a block method given a non-zero value raises."""
 
     def __init__(self, method: str = "optical_flow", quality: str = "medium", *, device: int = 0, scene_detect: bool = False,
-                 bidirectional: bool = False):
+                 bidirectional: bool = False, flow_warps: int = 0):
+        from .flow import check_warps
+
         m = str(method).lower()
         self._scene = None  # (not in the reference) a pair flagged as a scene cut gives a repeat of the nearer frame, not a blend
         self._block = m in ("block_matching", "simplified")
@@ -218,6 +222,9 @@ class PyFrameInterpolator:
         self._device = int(device)
         if bidirectional and not self._block:
             raise ValueError("bidirectional: only the block-matching methods have a forward-backward check")
+        flow_warps = check_warps(flow_warps)
+        if flow_warps and self._block:
+            raise ValueError("flow_warps: only the optical-flow method re-linearises its pyramid levels")
         if self._block:
             self._bm = BlockMatcher(self._quality, device=device, bidirectional=bidirectional)
             if scene_detect:
@@ -225,7 +232,7 @@ class PyFrameInterpolator:
         else:
             from .flow import FlowEstimator
 
-            self._flow = FlowEstimator(device=device)
+            self._flow = FlowEstimator(device=device, warps=flow_warps)
             if scene_detect:
                 from .scene import SceneDetector
 

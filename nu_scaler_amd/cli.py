@@ -33,6 +33,8 @@ def build_parser() -> argparse.ArgumentParser:
     it.add_argument("--multiplier", type=int, default=None,
                     help="frame-rate multiplier M (2 .. NUS_INTERP_MAX_TIMES + 1 = 8): the M - 1 frames at t = k / M, written as <stem>_<k><ext>")
     it.add_argument("--flow", action="store_true", help="estimate motion (pyramid + Horn-Schunck) instead of zero flow")
+    it.add_argument("--flow-warps", type=int, default=None,
+                    help="with --flow: rounds per finer pyramid level that re-linearise about the flow so far (0 .. 4; default 0)")
     it.add_argument("--method", default=None, help="block_matching: the full-search block matcher supplies the motion field")
     it.add_argument("--quality", default="medium", help="block matching preset: high (8 / 24), medium (16 / 16) or low (32 / 8)")
     it.add_argument("--bidirectional", action="store_true",
@@ -185,6 +187,13 @@ def main(argv=None) -> int:
             parser.error(f"--method must be block_matching, got {args.method}")
         if args.quality.lower() not in ("high", "medium", "low"):
             parser.error(f"--quality must be high, medium or low, got {args.quality}")
+    if args.command == "interpolate" and args.flow_warps is not None:
+        from ._capi import FLOW_MAX_WARPS
+
+        if not args.flow:
+            parser.error("--flow-warps needs --flow")
+        if not 0 <= args.flow_warps <= FLOW_MAX_WARPS:
+            parser.error(f"--flow-warps must be from 0 to {FLOW_MAX_WARPS}, got {args.flow_warps}")
     if args.command == "interpolate":
         if (args.bidirectional or args.bidir_tolerance is not None) and args.method is None:
             parser.error("--bidirectional needs --method block_matching")
@@ -236,11 +245,13 @@ def main(argv=None) -> int:
                 print(path)
         elif args.multiplier is not None:
             for path in imagefile.interpolate_image_files_multi(args.frame_a, args.frame_b, args.output, args.multiplier, args.flow,
-                                                                device=args.device, scene_detect=args.scene_detect):
+                                                                device=args.device, scene_detect=args.scene_detect,
+                                                                flow_warps=args.flow_warps or 0):
                 print(path)
         else:
             t = 0.5 if args.t is None else args.t
-            w, h = imagefile.interpolate_image_files(args.frame_a, args.frame_b, args.output, t, args.flow, device=args.device)
+            w, h = imagefile.interpolate_image_files(args.frame_a, args.frame_b, args.output, t, args.flow, device=args.device,
+                                                     flow_warps=args.flow_warps or 0)
             print(f"{args.output}: {w}x{h}")
     except (OSError, ValueError, RuntimeError) as e:
         print(f"nu_scaler_cli: error: {e}", file=sys.stderr)

@@ -4,7 +4,7 @@
 // (Nu_scale/src/main.rs:36-73: --tech, --quality, --algorithm).
 //
 //   nu_scaler_cli upscale <in.png> <out.png> [--algorithm A] [--scale S] [--tech T] [--quality Q] [--device N]
-//   nu_scaler_cli interpolate <a.png> <b.png> <out.png> [--t X | --multiplier M] [--flow] [--device N]
+//   nu_scaler_cli interpolate <a.png> <b.png> <out.png> [--t X | --multiplier M] [--flow [--flow-warps N]] [--device N]
 //                             [--method block_matching [--quality high|medium|low] [--bidirectional [--bidir-tolerance N]]]
 //   nu_scaler_cli scene <a.png> <b.png> [--mad N] [--hist N] [--device N]   (the scene-cut detector: cut=0|1 mad=.. hist_permille=..)
 //   nu_scaler_cli compare <a.png> <b.png> [--device N]   (MSE / PSNR / SSIM, ErrorMetrics: Nu_scale/src/upscale/common.rs:475-543)
@@ -36,7 +36,8 @@ int usage(int rc)
                  "usage: nu_scaler_cli upscale <in.png> <out.png> [--algorithm nearest|bilinear|bicubic|lanczos3|triangle|fsr1|easu]\n"
                  "                             [--scale S] [--tech fsr|fallback|none] [--quality ultra|quality|balanced|performance]\n"
                  "                             [--device N]\n"
-                 "       nu_scaler_cli interpolate <a.png> <b.png> <out.png> [--t X | --multiplier 2..8] [--flow] [--device N]\n"
+                 "       nu_scaler_cli interpolate <a.png> <b.png> <out.png> [--t X | --multiplier 2..8] [--flow [--flow-warps 0..4]]\n"
+                 "                             [--device N]\n"
                  "                             [--method block_matching [--quality high|medium|low]] [--scene-detect]\n"
                  "                             [--bidirectional [--bidir-tolerance 0..96]]   (block matching: forward-backward check)\n"
                  "       nu_scaler_cli scene <a.png> <b.png> [--mad 0..255] [--hist 0..1000] [--device N]\n"
@@ -215,6 +216,21 @@ int cmd_interpolate(const Args &a)
         }
         bidir_tolerance = (uint32_t)v;
     }
+    const auto warps_it = a.options.find("flow-warps");
+    uint32_t flow_warps = 0; // the estimator's re-linearisation rounds per finer level (nus_flow_set_warps)
+    if (warps_it != a.options.end()) {
+        if (!a.flow) {
+            std::fprintf(stderr, "nu_scaler_cli: error: --flow-warps needs --flow\n");
+            return usage(2);
+        }
+        char *end = nullptr;
+        const long v = std::strtol(warps_it->second.c_str(), &end, 10);
+        if (end == warps_it->second.c_str() || *end != '\0' || v < 0 || v > NUS_FLOW_MAX_WARPS) {
+            std::fprintf(stderr, "nu_scaler_cli: error: --flow-warps must be from 0 to %d\n", NUS_FLOW_MAX_WARPS);
+            return usage(2);
+        }
+        flow_warps = (uint32_t)v;
+    }
     nus_cli::Image fa, fb;
     std::string err = nus_cli::read_png(a.positional[0], fa);
     if (err.empty()) err = nus_cli::read_png(a.positional[1], fb);
@@ -259,6 +275,7 @@ int cmd_interpolate(const Args &a)
         if (!f) return fail(nus_last_error());
         flow.resize((size_t)fa.width * fa.height * 2);
         int rc = nus_flow_set_device(f, device);
+        if (rc == NUS_OK) rc = nus_flow_set_warps(f, flow_warps);
         // 3 levels, 50 coarse + 10 refining Jacobi steps, lambda as the Python mirror's FlowEstimator defaults
         if (rc == NUS_OK)
             rc = nus_flow_estimate(f, fa.rgba.data(), fb.rgba.data(), fa.width, fa.height, 3, 50, 10, 0.0004f, flow.data());

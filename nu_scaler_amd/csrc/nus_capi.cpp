@@ -87,6 +87,7 @@ static_assert(NUS_BM_MAX_RADIUS == nus::kBmMaxRadius && NUS_BM_TIES_SCAN == nus:
 static_assert(sizeof(nus_scene_measures) == 16 && NUS_SCENE_DEFAULT_MAD == nus::kSceneDefaultMad &&
                   NUS_SCENE_DEFAULT_HIST_PERMILLE == nus::kSceneDefaultHistPermille,
               "the C header's scene-detector layout and defaults are the kernels'");
+static_assert(NUS_FLOW_MAX_WARPS == nus::kFlowMaxWarps, "the C header's NUS_FLOW_MAX_WARPS is the estimator's bound");
 static_assert(NUS_INTERP_MAX_TIMES == nus::kInterpMaxTimes, "the C header's NUS_INTERP_MAX_TIMES is the kernels' time-set size");
 
 extern "C" {
@@ -700,6 +701,11 @@ int nus_flow_set_mode(nus_flow *h, int mode)
     return guarded<int>("nus_flow_set_mode", [&]() -> int { return h ? h->impl.set_mode(mode) : null_handle(); });
 }
 int nus_flow_mode(const nus_flow *h) { return h ? h->impl.mode() : NUS_ERR_INVALID_ARGUMENT; }
+int nus_flow_set_warps(nus_flow *h, uint32_t warps)
+{
+    return guarded<int>("nus_flow_set_warps", [&]() -> int { return h ? h->impl.set_warps(warps) : null_handle(); });
+}
+int nus_flow_warps(const nus_flow *h) { return h ? h->impl.warps() : NUS_ERR_INVALID_ARGUMENT; }
 const char *nus_flow_last_error(const nus_flow *h) { return h ? h->impl.last_error() : "null handle"; }
 
 int nus_flow_rgba8_to_f32(nus_flow *h, const uint8_t *in, uint32_t w, uint32_t hgt, float *out)
@@ -727,6 +733,17 @@ int nus_flow_upsample(nus_flow *h, const float *src, uint32_t sw, uint32_t sh, f
                       float scale)
 {
     return guarded<int>("nus_flow_upsample", [&]() -> int { return h ? h->impl.upsample(src, sw, sh, dst, dw, dh, scale) : null_handle(); });
+}
+
+int nus_flow_warp_coefficients(nus_flow *h, const float *i1, const float *i2, const float *flow, uint32_t w, uint32_t hgt, float *coef_out)
+{
+    return guarded<int>("nus_flow_warp_coefficients", [&]() -> int { return h ? h->impl.warp_coefficients(i1, i2, flow, w, hgt, coef_out) : null_handle(); });
+}
+
+int nus_flow_horn_schunck_coef(nus_flow *h, const float *coef, const float *flow_in, uint32_t w, uint32_t hgt, float lambda,
+                               uint32_t iterations, float *flow_out)
+{
+    return guarded<int>("nus_flow_horn_schunck_coef", [&]() -> int { return h ? h->impl.horn_schunck_coef(coef, flow_in, w, hgt, lambda, iterations, flow_out) : null_handle(); });
 }
 
 int nus_flow_estimate(nus_flow *h, const uint8_t *a, const uint8_t *b, uint32_t w, uint32_t hgt, uint32_t levels,

@@ -30,6 +30,14 @@ int HipFlowEstimator::set_mode(int mode)
     return kOk;
 }
 
+int HipFlowEstimator::set_warps(uint32_t warps)
+{
+    std::lock_guard<std::mutex> lk(mu_);
+    if (warps > kFlowMaxWarps) return fail(kInvalidArgument, fmt("nus_flow_set_warps: 0..%u rounds, got %u", kFlowMaxWarps, warps));
+    warps_ = warps;
+    return kOk;
+}
+
 int HipFlowEstimator::set_device(int device)
 {
     std::lock_guard<std::mutex> lk(mu_);
@@ -147,6 +155,38 @@ int HipFlowEstimator::horn_schunck(const float *i1, const float *i2, const float
     });
 }
 
+int HipFlowEstimator::warp_coefficients(const float *i1, const float *i2, const float *flow, uint32_t w, uint32_t h, float *coef_out)
+{
+    const size_t ib = (size_t)w * h * 16, fb = (size_t)w * h * 8, cb = (size_t)w * h * 12;
+    return primitive({{w, h}}, i1 && i2 && coef_out, {{kImage, ib, i1}, {kTemp, ib, i2}, {kFlowA, fb, flow}, {kPyrA, cb, nullptr}}, coef_out, cb,
+                     [&](const void *&result) -> int {
+        HsPrepareLaunch P;
+        P.img = {w, h, 1, stream_};
+        P.i1 = f32(kImage), P.i2 = f32(kTemp), P.coef = f32(kPyrA);
+        NUS_HIP(launch_hs_warp_setup(P, HsCoarseFlow{}, flow ? f32(kFlowA) : nullptr, 0, nullptr, 0));
+        result = f32(kPyrA);
+        return kOk;
+    });
+}
+
+int HipFlowEstimator::horn_schunck_coef(const float *coef, const float *flow_in, uint32_t w, uint32_t h, float lambda, uint32_t iterations,
+                                        float *flow_out)
+{
+    const size_t fb = (size_t)w * h * 8, cb = (size_t)w * h * 12;
+    return primitive({{w, h}}, coef && flow_out, {{kPyrA, cb, coef}, {kFlowA, fb, flow_in}, {kFlowB, fb, nullptr}}, flow_out, fb,
+                     [&](const void *&result) -> int {
+        if (!flow_in) NUS_HIP(hipMemsetAsync(f32(kFlowA), 0, fb, stream_));
+        HsIterateLaunch I;
+        I.img = {w, h, 1, stream_};
+        I.coef = f32(kPyrA), I.lambda = lambda, I.iterations = iterations, I.flow_a = f32(kFlowA), I.flow_b = f32(kFlowB), I.kernel = jacobi_;
+        HsIterateResult R;
+        R.flow = I.flow_a; // (no step: the start value)
+        NUS_HIP(launch_hs_iterate(I, &R));
+        result = R.flow;
+        return kOk;
+    });
+}
+
 int HipFlowEstimator::upsample(const float *src, uint32_t sw, uint32_t sh, float *dst, uint32_t dw, uint32_t dh, float scale)
 {
     const size_t sb = (size_t)sw * sh * 8, db = (size_t)dw * dh * 8;
@@ -224,7 +264,7 @@ int HipFlowEstimator::solve(Slot pyr_a, Slot pyr_b, const Pyramid &g, const Flow
         HsPrepareLaunch P;
         P.img = {g.w[l], g.h[l], 1, stream};
         P.i1 = reinterpret_cast<const float *>(u8(pyr_a) + g.offset[l]), P.i2 = reinterpret_cast<const float *>(u8(pyr_b) + g.offset[l]);
-        P.luminance_planes = true, P.coef = f32(kTemp);
+        P.luminance_planes = tiled_, P.coef = f32(kTemp); // (the plain kernels' pyramids hold f32 RGBA levels)
         return P;
     };
     // the flow of level l + 1, in f0, as level l takes it up
@@ -232,15 +272,16 @@ int HipFlowEstimator::solve(Slot pyr_a, Slot pyr_b, const Pyramid &g, const Flow
     // compute_coarse_flow starts from zero flow (:1136-1154): the tiled kernel takes that as a null input;
     // the last launch of the finest level writes the caller's buffer directly
     bool zero = true;
-    auto iterate = [&](uint32_t l, uint32_t iters, bool prepared) -> int {
+    // `last`: no further round of the level follows; `on_coef`: the coefficient kernels whatever set_tiled says (a warped round)
+    auto iterate = [&](uint32_t l, uint32_t iters, bool prepared, bool last = true, bool on_coef = false) -> int {
         if (iters == 0) return kOk;
         const HsPrepareLaunch P = prepare(l);
-        if (tiled_) {
+        if (tiled_ || on_coef) {
             if (!prepared) NUS_HIP(launch_hs_prepare(P));
             HsIterateLaunch I;
             I.img = P.img;
             I.coef = P.coef, I.lambda = p.lambda, I.iterations = iters, I.zero_start = zero, I.flow_a = f0, I.flow_b = f1;
-            I.final_out = l == 0 ? static_cast<float *>(d_flow_out) : nullptr, I.kernel = jacobi_;
+            I.final_out = l == 0 && last ? static_cast<float *>(d_flow_out) : nullptr, I.kernel = jacobi_;
             HsIterateResult R;
             NUS_HIP(launch_hs_iterate(I, &R));
             f0 = R.flow, f1 = R.spare;
@@ -257,6 +298,18 @@ int HipFlowEstimator::solve(Slot pyr_a, Slot pyr_b, const Pyramid &g, const Flow
     }
     if ((rc = iterate(L, p.coarse_iters, false)) != kOk) return rc;
     for (int l = (int)L - 1; l >= 0; --l) {
+        if (warped(p)) { // each round: the level's coefficients about the flow it has, then the steps (set_tiled(0) has no plain form of it)
+            for (uint32_t r = 0; r < p.warps; ++r) {
+                if (r == 0) {
+                    NUS_HIP(launch_hs_warp_setup(prepare((uint32_t)l), coarse_of((uint32_t)l), nullptr, 0, f1, 0));
+                    std::swap(f0, f1);
+                } else {
+                    NUS_HIP(launch_hs_warp_setup(prepare((uint32_t)l), HsCoarseFlow{}, f0, 0, nullptr, 0));
+                }
+                if ((rc = iterate((uint32_t)l, p.refine_iters, true, r + 1 == p.warps, true)) != kOk) return rc;
+            }
+            continue;
+        }
         const bool fused_setup = tiled_ && p.refine_iters > 0; // the level's derivatives and the upsampled flow in one launch
         if (fused_setup)
             NUS_HIP(launch_hs_level_setup(prepare((uint32_t)l), coarse_of((uint32_t)l), f1, 0));
@@ -274,7 +327,7 @@ int HipFlowEstimator::estimate_device(const void *d_a, const void *d_b, uint32_t
                                       hipStream_t stream)
 {
     std::lock_guard<std::mutex> lk(mu_);
-    return estimate_pair(d_a, d_b, w, h, p, d_flow_out, stream);
+    return estimate_pair(d_a, d_b, w, h, with_warps(p), d_flow_out, stream);
 }
 
 int HipFlowEstimator::estimate_pair(const void *d_a, const void *d_b, uint32_t w, uint32_t h, const FlowParams &p, void *d_flow_out,
@@ -313,7 +366,7 @@ int HipFlowEstimator::estimate_device_stream(const void *d_frames, uint32_t n_fr
     StreamJob J;
     J.frames = static_cast<const uint8_t *>(d_frames), J.n_frames = n_frames, J.w = w, J.h = h;
     J.flows = static_cast<uint8_t *>(d_flows), J.stream = stream;
-    return stream_impl(J, p);
+    return stream_impl(J, with_warps(p));
 }
 
 int HipFlowEstimator::interpolate_device_stream(const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t h, const FlowParams &p,
@@ -327,7 +380,7 @@ int HipFlowEstimator::interpolate_device_stream(const void *d_frames, uint32_t n
     StreamJob J;
     J.frames = static_cast<const uint8_t *>(d_frames), J.n_frames = n_frames, J.w = w, J.h = h;
     J.flows = static_cast<uint8_t *>(d_flows), J.mid = static_cast<uint8_t *>(d_mid), J.t = t, J.flow_half = flow_half, J.stream = stream;
-    return stream_impl(J, p);
+    return stream_impl(J, with_warps(p));
 }
 
 int HipFlowEstimator::interpolate_multi_device_stream(const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t h, const FlowParams &p,
@@ -356,7 +409,7 @@ int HipFlowEstimator::interpolate_multi_device_stream(const void *d_frames, uint
     J.frames = static_cast<const uint8_t *>(d_frames), J.n_frames = n_frames, J.w = w, J.h = h;
     J.flows = static_cast<uint8_t *>(d_flows), J.mid = static_cast<uint8_t *>(d_mid), J.t = times[0], J.flow_half = flow_half;
     J.mt = &mt, J.stream = stream;
-    if ((rc = stream_impl(J, p)) != kOk || !scene_) return rc;
+    if ((rc = stream_impl(J, with_warps(p))) != kOk || !scene_) return rc;
     // behind estimate + warp, the detector (it reads the frames only, so its place in the order is free) and the flagged pairs'
     // frames overwritten with repeats
     const size_t ws_bytes = scene_shape(w, h, n_pairs).workspace_bytes;
@@ -449,8 +502,9 @@ int HipFlowEstimator::stream_impl(const StreamJob &J, const FlowParams &p)
     };
     uint32_t chunk = chunk_for(31);
     if (chunk > n_pairs) chunk = n_pairs;
-    for (uint32_t l = 0; l < g.levels; ++l)
-        if (!hs_iterate_streams(g.w[l], g.h[l], chunk, fast_ && jacobi_ == kJacobiStream ? kJacobiStreamFast : jacobi_)) {
+    for (uint32_t l = 0; l < g.levels; ++l) // (a warped level -- every one but the coarsest -- always takes coefficient planes)
+        if ((warped(p) && l + 1 < g.levels) ||
+            !hs_iterate_streams(g.w[l], g.h[l], chunk, fast_ && jacobi_ == kJacobiStream ? kJacobiStreamFast : jacobi_)) {
             chunk = chunk_for(43);
             break;
         }
@@ -468,15 +522,19 @@ int HipFlowEstimator::solve_batch(const StreamJob &J, const Pyramid &g, const Fl
     const hipStream_t stream = J.stream;
     // The Jacobi kernel of a level.  FAST: k_hs_stream_fast where the level's batch would stream anyway (or the streamed kernel
     // is forced), the exact LDS-tile kernel -- on the FAST pyramid's planes -- where it would not (a small batch's coarse levels).
-    auto level_kernel = [&](uint32_t l) -> int {
+    auto unwarped_kernel = [&](uint32_t l) -> int {
         if (!fast_ || jacobi_ == kJacobiTiles) return jacobi_;
         if (jacobi_ == kJacobiStream) return kJacobiStreamFast;
         return hs_iterate_streams(g.w[l], g.h[l], pairs, kJacobiAuto) ? kJacobiStreamFast : kJacobiTiles;
     };
+    // A warped level (FlowParams::warps: every level but the coarsest) runs the exact kernels on coefficient planes, FAST or not:
+    // k_hs_stream_fast takes It from the luminance planes itself.  The exact result is inside FAST's contract.
+    auto warped_level = [&](uint32_t l) { return warped(p) && l + 1 < g.levels; };
+    auto level_kernel = [&](uint32_t l) -> int { return warped_level(l) ? jacobi_ : unwarped_kernel(l); };
     // The luminance-only pyramid streams rows per wave as well: where level 0 of the batch is too small for that, the exact
     // LDS-tile pyramid runs instead (its planes serve either Jacobi kernel).
     const bool fast_pyramid = fast_ && !getenv("NUS_FLOW_FAST_EXACT_PYRAMID") &&
-                              (jacobi_ == kJacobiStream || level_kernel(0) == kJacobiStreamFast);
+                              (jacobi_ == kJacobiStream || unwarped_kernel(0) == kJacobiStreamFast); // (the same pyramid with warps as without)
     const int jacobi = fast_ ? (fast_pyramid ? kJacobiStream : kJacobiTiles) : jacobi_; // (for the exact pyramid launcher's choice)
     const uint32_t nf = pairs + 1, nl = g.levels, L = nl - 1;
     size_t cells[13] = {0}, lum_off[12], lum_total = 0; // (0 beyond the last level)
@@ -492,7 +550,7 @@ int HipFlowEstimator::solve_batch(const StreamJob &J, const Pyramid &g, const Fl
         return rc;
     // A level whose Jacobi steps run in the streamed kernel needs no coefficient planes: that kernel takes the
     // derivatives from the luminance planes of the pair's two frames (consecutive planes of the level) as it goes.
-    auto from_planes = [&](uint32_t l) { return hs_iterate_streams(g.w[l], g.h[l], pairs, level_kernel(l)); };
+    auto from_planes = [&](uint32_t l) { return !warped_level(l) && hs_iterate_streams(g.w[l], g.h[l], pairs, level_kernel(l)); };
     size_t coef_cells = 0;
     for (uint32_t l = 0; l < nl; ++l)
         if (!from_planes(l) && cells[l] > coef_cells) coef_cells = cells[l];
@@ -533,14 +591,15 @@ int HipFlowEstimator::solve_batch(const StreamJob &J, const Pyramid &g, const Fl
     // the flow of level l + 1, in f0, as level l takes it up
     auto coarse_of = [&](uint32_t l) { return HsCoarseFlow{f0, g.w[l + 1], g.h[l + 1], 2.0f, cells[l + 1]}; };
     // `coarse`: the level continues the flow of level l + 1 in f0, which the first launch upsamples as it loads it
-    auto iterate = [&](uint32_t l, uint32_t iters, bool zero, bool coarse) -> int {
+    // `last`: no further round of the level follows
+    auto iterate = [&](uint32_t l, uint32_t iters, bool zero, bool coarse, bool last = true) -> int {
         HsIterateLaunch I;
         I.img = {g.w[l], g.h[l], pairs, stream};
         I.coef = f32(kCoef), I.coef_stride = cells[l] * 3;
         I.lum1 = from_planes(l) ? lum + lum_off[l] : nullptr, I.lum_stride = cells[l];
         I.lambda = p.lambda, I.iterations = iters, I.zero_start = zero;
         I.flow_a = f0, I.flow_b = f1, I.flow_stride = cells[l];
-        I.final_out = l == 0 ? solver_out : nullptr, I.final_stride = cells[0];
+        I.final_out = l == 0 && last ? solver_out : nullptr, I.final_stride = cells[0];
         I.kernel = level_kernel(l);
         if (coarse) I.coarse = coarse_of(l);
         I.coarse.scale = 2.0f;
@@ -560,6 +619,18 @@ int HipFlowEstimator::solve_batch(const StreamJob &J, const Pyramid &g, const Fl
     }
     for (int li = (int)L - 1; li >= 0; --li) {
         const uint32_t l = (uint32_t)li;
+        if (warped_level(l)) { // each round: the level's coefficients about the flow it has (round 1: the upsampled one), then the steps
+            for (uint32_t r = 0; r < p.warps; ++r) {
+                if (r == 0) {
+                    NUS_HIP(launch_hs_warp_setup(prepare(l), coarse_of(l), nullptr, 0, f1, cells[l]));
+                    std::swap(f0, f1);
+                } else {
+                    NUS_HIP(launch_hs_warp_setup(prepare(l), HsCoarseFlow{}, f0, cells[l], nullptr, 0));
+                }
+                if ((rc = iterate(l, p.refine_iters, false, false, r + 1 == p.warps)) != kOk) return rc;
+            }
+            continue;
+        }
         if (p.refine_iters > 0 && from_planes(l)) { // derivatives and upsampled flow both computed inside the Jacobi kernel
             if ((rc = iterate(l, p.refine_iters, false, true)) != kOk) return rc;
             continue;
@@ -608,7 +679,7 @@ int HipFlowEstimator::estimate(const uint8_t *a, const uint8_t *b, uint32_t w, u
     if ((rc = pass(upload(u8(kHostA), a, fbytes, stream_))) != kOk || (rc = pass(upload(u8(kHostB), b, fbytes, stream_))) != kOk) return rc;
     // kHostB doubles as the flow output once frame B has been converted (the estimate copies
     // into it last, after every reader of frame B has been enqueued on the same stream)
-    if ((rc = estimate_pair(u8(kHostA), u8(kHostB), w, h, p, u8(kHostB), stream_)) != kOk ||
+    if ((rc = estimate_pair(u8(kHostA), u8(kHostB), w, h, with_warps(p), u8(kHostB), stream_)) != kOk ||
         (rc = pass(download(flow_out, u8(kHostB), (size_t)w * h * 8, stream_))) != kOk)
         return rc;
     NUS_HIP(hipStreamSynchronize(stream_));

@@ -18,9 +18,14 @@
 namespace nus {
 
 // What every estimate takes: pyramid levels (1..12), Jacobi steps on the coarsest level and on each finer one, the smoothness weight.
+// warps (0..kFlowMaxWarps; the handle's setting, set_warps): rounds per finer level, each re-linearising the data term about the
+// level's current flow -- frame B sampled through it -- before its refine_iters steps.  0: linearised about zero flow, the
+// upsampled flow only the Jacobi start value.
+constexpr uint32_t kFlowMaxWarps = 4; // NUS_FLOW_MAX_WARPS
 struct FlowParams {
     uint32_t levels = 0, coarse_iters = 0, refine_iters = 0;
     float lambda = 0.0f;
+    uint32_t warps = 0;
 };
 
 class HipFlowEstimator : public HostErrors {
@@ -43,6 +48,11 @@ public:
     int horn_schunck(const float *i1, const float *i2, const float *flow_in_or_null, uint32_t w, uint32_t h,
                      float lambda, uint32_t iterations, float *flow_out);
     int upsample(const float *src, uint32_t sw, uint32_t sh, float *dst, uint32_t dw, uint32_t dh, float scale);
+    // The two halves of a re-linearised level (set_warps).  warp_coefficients: (Ix, Iy, It') per cell, w*h*3 floats, with frame B's
+    // luminance sampled through `flow` (null: zero flow, i.e. It = L2 - L1).  horn_schunck_coef: Jacobi steps on such coefficients.
+    int warp_coefficients(const float *i1, const float *i2, const float *flow_or_null, uint32_t w, uint32_t h, float *coef_out);
+    int horn_schunck_coef(const float *coef, const float *flow_in_or_null, uint32_t w, uint32_t h, float lambda, uint32_t iterations,
+                          float *flow_out);
 
     // Full estimator: RGBA8 frames -> dense flow (w*h*2 floats, pixel delta A -> B).
     int estimate(const uint8_t *a, const uint8_t *b, uint32_t w, uint32_t h, const FlowParams &p, float *flow_out);
@@ -51,6 +61,10 @@ public:
     // The primitives (blur, downsample, horn_schunck, upsample) are always exact.
     int set_mode(int mode);
     int mode() const { return fast_ ? 1 : 0; }
+    // Re-linearisation rounds per finer level of every estimator entry point (FlowParams::warps), 0 (default) .. kFlowMaxWarps.  A
+    // warped level's Jacobi steps run on coefficient planes in the exact kernels, in FAST mode too (inside FAST's contract).
+    int set_warps(uint32_t warps);
+    int warps() const { return (int)warps_; }
     // Scene-cut detection in front of interpolate_multi_device_stream and the cut-aware output rule behind it (nus_scene_* of the C
     // header): off by default.  On, the in-between frames of a pair the detector flags are repeats of the nearer real frame.
     int set_scene_detect(int enabled, uint32_t mad_threshold, uint32_t hist_permille);
@@ -91,6 +105,9 @@ private:
         kScene = 11,                  // the scene detector's workspace and cut flags
     };
     static constexpr int kSlotCount = 12;
+    FlowParams with_warps(FlowParams p) const { return p.warps = warps_, p; } // (mu_ held) what the entry points hand on
+    // the finer levels of such an estimate take `warps` rounds of launch_hs_warp_setup + Jacobi steps on coefficient planes
+    static bool warped(const FlowParams &p) { return p.warps > 0 && p.refine_iters > 0; }
     struct MidTimes { // the multi-time warp behind the estimator (interpolate_multi_device_stream)
         const float *times = nullptr;
         uint32_t n = 0;
@@ -151,6 +168,7 @@ private:
     bool ready_ = false;
     bool tiled_ = true;
     int jacobi_ = 0; // JacobiKernel
+    uint32_t warps_ = 0; // set_warps
     bool fast_ = false; // set_mode(1): the estimator's Jacobi steps in FAST arithmetic (k_hs_stream_fast), every level streamed
     hipStream_t stream_ = nullptr;
     bool scene_ = false; // set_scene_detect

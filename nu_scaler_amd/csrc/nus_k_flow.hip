@@ -1174,6 +1174,58 @@ __global__ __launch_bounds__(256) void k_hs_level_setup(const float *__restrict_
     flow[z * flow_stride + (size_t)y * w + x] = flow_upsample_cell(coarse + z * coarse_stride, cw, ch, x, y, w, h, scale);
 }
 
+// ---- Re-linearisation of a finer level about the flow it has (FlowParams::warps) --------------------------------------------
+// The level setup of a warped round: frame B's luminance gathered through the level's current flow f0 = (u0, v0) -- bilinear at
+// (x + u0, y + v0), each coordinate clamped into the plane, pixel centres at integers (the dense warp's sampler) -- and the
+// coefficient triple (Ix, Iy, It') with It' = ((L2w - L1) - Ix*u0) - Iy*v0: the Jacobi kernels, unchanged, then solve
+// Ix (u - u0) + Iy (v - v0) + (L2w - L1) = 0.  UPS (round 1): f0 is the coarser level's flow upsampled (k_flow_upsample's cell),
+// and it is stored as the flow the Jacobi steps start from; otherwise f0 is read (null: zero flow, k_hs_prepare's triple as it is).
+// One cell per lane, pairs on z like k_hs_level_setup.  The flow is loaded before anything that depends on it: the four gathers
+// of L2 are the only loads behind an address computed from memory.  Only `coef` and `fout` are written -- in a stream pair k's
+// second luminance plane is pair k + 1's first.
+template <typename IMG, bool UPS>
+__global__ __launch_bounds__(256) void k_hs_warp_setup(const IMG *__restrict__ l1_all, const IMG *__restrict__ l2_all, size_t img_stride,
+                                                       float *__restrict__ coef_all, size_t coef_stride, int w, int h,
+                                                       const float2 *__restrict__ fin_all, size_t fin_stride, int cw, int ch, float scale,
+                                                       float2 *__restrict__ fout_all, size_t fout_stride)
+{
+    const int x = blockIdx.x * kWave + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+    if (x >= w || y >= h) return;
+    const size_t z = blockIdx.z, i = (size_t)y * w + x;
+    const IMG *const l1 = l1_all + z * img_stride, *const l2 = l2_all + z * img_stride;
+    float *const coef = coef_all + z * coef_stride;
+    if (!UPS && fin_all == nullptr) { // wave-uniform
+        hs_prepare_cell(l1, l2, coef, x, y, w, h);
+        return;
+    }
+    float2 f;
+    if (UPS)
+        f = flow_upsample_cell(fin_all + z * fin_stride, cw, ch, x, y, w, h, scale);
+    else
+        f = fin_all[z * fin_stride + i];
+    // frame A's own cells do not wait for the flow
+    const int xp = min(x + 1, w - 1), xm = max(x, 1) - 1, yp = min(y + 1, h - 1), ym = max(y, 1) - 1;
+    const float a_xp = lum_of(l1, (size_t)y * w + xp), a_xm = lum_of(l1, (size_t)y * w + xm);
+    const float a_yp = lum_of(l1, (size_t)yp * w + x), a_ym = lum_of(l1, (size_t)ym * w + x), a_c = lum_of(l1, i);
+    // per-lane copies of the wave-uniform constants: scalar operands halve the VALU issue rate on gfx950
+    float wmax = (float)(w - 1), hmax = (float)(h - 1);
+    asm volatile("" : "+v"(wmax), "+v"(hmax));
+    const float sx = fminf(fmaxf((float)x + f.x, 0.0f), wmax), sy = fminf(fmaxf((float)y + f.y, 0.0f), hmax); // (a NaN lands on 0)
+    const float xfl = floorf(sx), yfl = floorf(sy);
+    const int x0 = min((int)xfl, w - 1), y0 = min((int)yfl, h - 1), x1 = min(x0 + 1, w - 1), y1 = min(y0 + 1, h - 1);
+    const float fx = sx - xfl, fy = sy - yfl;
+    const float p00 = lum_of(l2, (size_t)y0 * w + x0), p10 = lum_of(l2, (size_t)y0 * w + x1);
+    const float p01 = lum_of(l2, (size_t)y1 * w + x0), p11 = lum_of(l2, (size_t)y1 * w + x1);
+    const float ix = (a_xp - a_xm) * 0.5f, iy = (a_yp - a_ym) * 0.5f;
+    const float top = p00 * (1.0f - fx) + p10 * fx, bot = p01 * (1.0f - fx) + p11 * fx;
+    const float l2w = top * (1.0f - fy) + bot * fy;
+    float *c = coef + i * 3;
+    c[0] = ix;
+    c[1] = iy;
+    c[2] = ((l2w - a_c) - ix * f.x) - iy * f.y;
+    if (UPS) fout_all[z * fout_stride + i] = f;
+}
+
 } // namespace
 
 hipError_t launch_rgba8_to_f32(const uint8_t *in, float *out, uint32_t w, uint32_t h, hipStream_t stream)
@@ -1284,6 +1336,28 @@ hipError_t launch_hs_level_setup(const HsPrepareLaunch &L, const HsCoarseFlow &c
     hipLaunchKernelGGL(k_hs_level_setup, grid, block, 0, L.img.stream, L.i1, L.i2, L.img_stride, L.coef, L.coef_stride, (int)L.img.w, (int)L.img.h,
                        reinterpret_cast<const float2 *>(coarse.flow), coarse.stride, (int)coarse.w, (int)coarse.h,
                        reinterpret_cast<float2 *>(flow), flow_stride, coarse.scale);
+    return hipGetLastError();
+}
+
+// the level setup of a warped round (k_hs_warp_setup): on luminance planes or on f32 RGBA level images
+hipError_t launch_hs_warp_setup(const HsPrepareLaunch &L, const HsCoarseFlow &coarse, const float *flow, size_t flow_stride, float *flow_out,
+                                size_t flow_out_stride)
+{
+    const bool ups = coarse.flow != nullptr;
+    if (ups && flow_out == nullptr) return hipErrorInvalidValue;
+    const dim3 block(kWave, 4), grid(cdiv(L.img.w, kWave), cdiv(L.img.h, 4), L.img.n);
+    const float2 *const fin = reinterpret_cast<const float2 *>(ups ? coarse.flow : flow);
+    const size_t fin_stride = ups ? coarse.stride : flow_stride;
+#define NUS_HWS(IMG, UU)                                                                                                              \
+    hipLaunchKernelGGL((k_hs_warp_setup<IMG, UU>), grid, block, 0, L.img.stream, reinterpret_cast<const IMG *>(L.i1),                 \
+                       reinterpret_cast<const IMG *>(L.i2), L.img_stride, L.coef, L.coef_stride, (int)L.img.w, (int)L.img.h, fin, fin_stride, \
+                       (int)coarse.w, (int)coarse.h, coarse.scale, reinterpret_cast<float2 *>(flow_out), flow_out_stride)
+    if (L.luminance_planes) {
+        if (ups) NUS_HWS(float, true); else NUS_HWS(float, false);
+    } else {
+        if (ups) NUS_HWS(float4, true); else NUS_HWS(float4, false);
+    }
+#undef NUS_HWS
     return hipGetLastError();
 }
 

@@ -246,6 +246,11 @@ struct HsCoarseFlow {
 };
 // launch_hs_prepare on luminance planes + launch_flow_upsample of `coarse` into `flow` (item stride in cells), one launch.
 hipError_t launch_hs_level_setup(const HsPrepareLaunch &L, const HsCoarseFlow &coarse, float *flow, size_t flow_stride);
+// The level setup of a re-linearisation round (FlowParams::warps): frame B's luminance sampled bilinearly through the level's current
+// flow f0, and the triple (Ix, Iy, It' = L2w - L1 - Ix u0 - Iy v0) into L.coef.  `coarse` set (round 1): f0 is that flow upsampled, and
+// it is stored at flow_out; else f0 is `flow` (null: zero flow -- launch_hs_prepare's triple).  L.i1 / L.i2 are only read.
+hipError_t launch_hs_warp_setup(const HsPrepareLaunch &L, const HsCoarseFlow &coarse, const float *flow, size_t flow_stride, float *flow_out,
+                                size_t flow_out_stride);
 // HsWarp (round 5; used only with NUS_HS_FUSED_WARP=1 in the environment: measured slower than the warp kernel behind the estimator):
 // the LAST launch of the finest level can warp + blend the pair's two frames with the flow it has just finished
 // (dense-flow warp in FMA mode, nus_warp_device.hpp) and store the in-between frame -- the flow then never has to be written for the

@@ -5,7 +5,8 @@ Mirrors the reference's `WgpuFrameInterpolator::build_pyramid` / `compute_coarse
 downsample) of both frames, Horn-Schunck Jacobi steps at the coarsest level, then -- where the
 reference's refine path is dead code -- a coarse-to-fine warm start: x2 bilinear flow upsample
 and more Jacobi steps per finer level.  The result is the dense (dx, dy) field that
-`WgpuFrameInterpolator.interpolate_py(..., flow=...)` consumes.
+`WgpuFrameInterpolator.interpolate_py(..., flow=...)` consumes.  With `warps=N` (off by default) every finer level is
+re-linearised N times about the flow it has -- frame B sampled through it -- which is what follows motion of more than a pixel.
 """
 from __future__ import annotations
 
@@ -16,9 +17,18 @@ import numpy as np
 from . import _capi as C
 
 
+def check_warps(warps) -> int:
+    """`warps` as an int in 0 .. FLOW_MAX_WARPS, or ValueError (what every Python entry point that takes the setting shares)."""
+    if isinstance(warps, bool) or int(warps) != warps:
+        raise ValueError(f"flow warps must be an integer from 0 to {C.FLOW_MAX_WARPS}, got {warps!r}")
+    if not 0 <= int(warps) <= C.FLOW_MAX_WARPS:
+        raise ValueError(f"flow warps must be from 0 to {C.FLOW_MAX_WARPS}, got {warps}")
+    return int(warps)
+
+
 class FlowEstimator:
     def __init__(self, levels: int = 3, coarse_iterations: int = 50, refine_iterations: int = 10,
-                 lambda_: float = 0.02 ** 2, *, device: int = 0):
+                 lambda_: float = 0.02 ** 2, *, device: int = 0, warps: int = 0):
         # lambda default: the value of the reference's own (ignored) test, wgpu_interpolator.rs:1535
         self._lib = C.lib()
         self._h = self._lib.nus_flow_create()
@@ -27,6 +37,8 @@ class FlowEstimator:
         self.levels, self.coarse_iterations = int(levels), int(coarse_iterations)
         self.refine_iterations, self.lambda_ = int(refine_iterations), float(lambda_)
         self._check(self._lib.nus_flow_set_device(self._h, int(device)))
+        if warps != 0:
+            self.set_warps(warps)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -45,6 +57,17 @@ class FlowEstimator:
         if m is None:
             raise ValueError("mode must be 'exact' or 'fast'")
         self._check(self._lib.nus_flow_set_mode(self._h, m))
+
+    def set_warps(self, warps: int) -> None:
+        """Re-linearisation rounds per finer pyramid level (nus_flow_set_warps; 0, the default, .. FLOW_MAX_WARPS): each round samples
+        frame B through the level's current flow and runs the level's Jacobi steps on the residual equation about that flow, so the
+        estimate follows motion of more than a pixel.  Applies to every estimator entry point of this object."""
+        w = check_warps(warps)
+        self._check(self._lib.nus_flow_set_warps(self._h, w))
+
+    @property
+    def warps(self) -> int:
+        return int(self._lib.nus_flow_warps(self._h))
 
     def set_scene_detect(self, enabled: bool, mad_threshold: int = C.SCENE_DEFAULT_MAD,
                          hist_permille: int = C.SCENE_DEFAULT_HIST_PERMILLE) -> None:
@@ -101,6 +124,30 @@ class FlowEstimator:
                                                     None if fin is None else fin.ctypes.data, w, h,
                                                     self.lambda_ if lambda_ is None else float(lambda_),
                                                     int(iterations), out.ctypes.data))
+        return out
+
+    def warp_coefficients(self, i1: np.ndarray, i2: np.ndarray, flow=None) -> np.ndarray:
+        """(h, w, 3) float32 (Ix, Iy, It') of two f32 RGBA images, frame 2's luminance sampled through `flow` ((h, w, 2); None: zero
+        flow, It = L2 - L1): what a re-linearised level's Jacobi steps run on (nus_flow_warp_coefficients)."""
+        i1, i2 = self._f32(i1), self._f32(i2, np.shape(i1))
+        h, w = i1.shape[:2]
+        fl = None if flow is None else self._f32(flow, (h, w, 2))
+        out = np.empty((h, w, 3), np.float32)
+        self._check(self._lib.nus_flow_warp_coefficients(self._h, i1.ctypes.data, i2.ctypes.data, None if fl is None else fl.ctypes.data,
+                                                         w, h, out.ctypes.data))
+        return out
+
+    def horn_schunck_coef(self, coef: np.ndarray, flow_in=None, iterations: int = 1, lambda_=None) -> np.ndarray:
+        """`iterations` Jacobi steps on (h, w, 3) coefficients (Ix, Iy, It), from `flow_in` (None: zero flow)."""
+        coef = self._f32(coef)
+        if coef.ndim != 3 or coef.shape[2] != 3:
+            raise ValueError(f"expected (h, w, 3) coefficients, got {coef.shape}")
+        h, w = coef.shape[:2]
+        fin = None if flow_in is None else self._f32(flow_in, (h, w, 2))
+        out = np.empty((h, w, 2), np.float32)
+        self._check(self._lib.nus_flow_horn_schunck_coef(self._h, coef.ctypes.data, None if fin is None else fin.ctypes.data, w, h,
+                                                         self.lambda_ if lambda_ is None else float(lambda_), int(iterations),
+                                                         out.ctypes.data))
         return out
 
     def upsample(self, flow: np.ndarray, dw: int, dh: int, scale: float = 1.0) -> np.ndarray:

@@ -170,7 +170,7 @@ class FramePipeline:
 
     def step_motion(self, frames, flows, mid, up_real, up_mid, stream: int = 0, levels: int = 3,
                     coarse_iterations: int = 50, refine_iterations: int = 10, flow_mode: str = "exact", pipelined: bool = False,
-                    chunk: int = 150, fused_warp: bool = False, flow_format: Optional[str] = None) -> None:
+                    chunk: int = 150, fused_warp: bool = False, flow_format: Optional[str] = None, flow_warps: int = 0) -> None:
         """Motion-compensated variant of `step`: a dense flow per pair from the
         pyramid + Horn-Schunck front end into `flows` ((n_units, h, w, 2) float32), then warp + blend with it
         instead of the reference's zero flow.  The flows are estimated pair by pair (several launches per pair,
@@ -186,13 +186,19 @@ class FramePipeline:
         fused_warp (round 5): estimator and warp through ONE entry point (FlowEstimator.interpolate_device_stream); `flows` may then
         be None (they stay in the estimator's workspace).  The warp is the FMA-mode one whatever `self.interp`'s mode is; same bytes
         as the separate FMA-mode warp.  (The in-kernel fusion -- the last Horn-Schunck launch warping with the flow it has just
-        finished -- exists behind NUS_HS_FUSED_WARP=1: identical bytes, measured slower.)"""
-        from .flow import FlowEstimator
+        finished -- exists behind NUS_HS_FUSED_WARP=1: identical bytes, measured slower.)
+
+        flow_warps: the estimator's re-linearisation rounds per finer pyramid level (FlowEstimator.set_warps; 0: none)."""
+        from .flow import FlowEstimator, check_warps
+
+        flow_warps = check_warps(flow_warps)
 
         if getattr(self, "_flow", None) is None:
             self._flow = FlowEstimator(levels, coarse_iterations, refine_iterations, device=self.upscaler._device)
         if self._flow.mode != flow_mode:
             self._flow.set_mode(flow_mode)  # "fast": the Jacobi steps in separable sums / reciprocals / FMAs (flow within 1e-3 px)
+        if self._flow.warps != flow_warps:
+            self._flow.set_warps(flow_warps)
         n = mid.shape[0]
         base = frames.data_ptr()
         fb = self.frame_bytes

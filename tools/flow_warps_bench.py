@@ -1,0 +1,89 @@
+#!/usr/bin/env python
+"""Device-resident timing of the flow estimator's re-linearisation mode (nus_flow_set_warps): nus_flow_estimate_device_stream on a
+stream of 32 frames of 1080p (31 pairs; 265 MB of frames, every frame the one before moved by a few pixels, as the stream of
+tools/blockmatch_bench.py --stream), 3 levels, 50 + 10 steps, for warps = 0, 1, 2 in EXACT and in FAST mode.  hipEvents on the
+launch stream, every leg warmed, then the legs of a mode alternate bracket by bracket in one process; each figure is the median of
+its brackets, and the smallest and largest bracket are printed beside it.  warps = 0 on the same binary in the same call is the
+baseline of the ratios.  One JSON line per case.
+usage: python tools/flow_warps_bench.py [--reps R] [--rounds N] [--frames F] [--quick]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402  (before the package: torch's HIP runtime first)
+
+import nu_scaler_amd as nsc  # noqa: E402
+from nu_scaler_amd import synthetic as syn  # noqa: E402
+
+WARPS = (0, 1, 2)
+
+
+def timed_alternating(fns, reps, warm_seconds, rounds):
+    """Every leg warmed, then `rounds` times one bracket of each in turn -> per leg the sorted ms per call of its brackets."""
+    for fn in fns:
+        fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < warm_seconds:
+            for _ in range(reps):
+                fn()
+            torch.cuda.synchronize()
+    got = [[] for _ in fns]
+    for _ in range(max(1, rounds)):
+        for i, fn in enumerate(fns):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(reps):
+                fn()
+            b.record()
+            torch.cuda.synchronize()
+            got[i].append(a.elapsed_time(b) / reps)
+    return [sorted(g) for g in got]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5, help="calls per timed bracket")
+    ap.add_argument("--rounds", type=int, default=7, help="timed brackets per leg; the median is reported")
+    ap.add_argument("--warm-seconds", type=float, default=0.5)
+    ap.add_argument("--frames", type=int, default=32)
+    ap.add_argument("--quick", action="store_true", help="one warm-up call and one bracket of 2 calls per leg")
+    args = ap.parse_args()
+    if nsc.device_count() < 1:
+        raise SystemExit("flow_warps_bench: no HIP device")
+    if args.quick:
+        args.reps, args.rounds, args.warm_seconds = 2, 1, 0.0
+    dev = torch.device("cuda:0")
+    s = torch.cuda.current_stream().cuda_stream
+    w, h, n_frames = 1920, 1080, args.frames
+    n = n_frames - 1
+    frames = syn.noise_stream_torch(n_frames, w, h, dev)
+    for k in range(n):
+        frames[k + 1] = torch.roll(frames[k], (5 - 2 * (k % 6), 3 * (k % 7) - 9), (0, 1))
+    flows = torch.empty((n, h, w, 2), dtype=torch.float32, device=dev)
+    for mode in ("exact", "fast"):
+        handles = []
+        for warps in WARPS:
+            fe = nsc.FlowEstimator(levels=3, coarse_iterations=50, refine_iterations=10, warps=warps)
+            fe.set_mode(mode)
+            handles.append(fe)
+        legs = [lambda fe=fe: fe.estimate_device_stream(frames.data_ptr(), n_frames, w, h, flows.data_ptr(), s) for fe in handles]
+        brackets = timed_alternating(legs, args.reps, args.warm_seconds, args.rounds)
+        us = [[x * 1e3 / n for x in g] for g in brackets]
+        med = [g[len(g) // 2] for g in us]
+        for warps, g, m in zip(WARPS, us, med):
+            print(json.dumps({"case": f"{w}x{h}x{n}_{mode}_warps{warps}", "width": w, "height": h, "pairs": n, "mode": mode, "warps": warps,
+                              "levels": 3, "coarse_iterations": 50, "refine_iterations": 10, "working_set_bytes": frames.numel(),
+                              "brackets": len(g), "calls_per_bracket": args.reps, "us_per_pair": round(m, 2),
+                              "us_per_pair_min": round(g[0], 2), "us_per_pair_max": round(g[-1], 2),
+                              "over_warps0": round(m / med[0], 3)}), flush=True)
+        del handles, legs
+        torch.cuda.synchronize()
+
+
+if __name__ == "__main__":
+    main()
