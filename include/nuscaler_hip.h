@@ -494,6 +494,14 @@ int nus_flow_set_tiled(nus_flow *h, int enabled);
  * beyond 50 px, and the exact f32 arithmetic itself is more than 1e-3 px from the float64 result -- both asserted in
  * tests/test_flow.py), and FAST then stays within 3.1x the distance of the exact mode's own result from the float64 one
  * (measured at lambda = 1e-6: 0.56x on noise, 0.78x on a static scene; the test allows four times the larger).
+ * With nus_flow_set_warps(W >= 1) the bound is the larger of 1e-3 px and four times that same distance (the exact f32 result's
+ * from the float64 one, on the same pair): the finer levels re-linearise about a flow that carries the coarsest level's FAST
+ * difference, doubled per level, and every further round samples frame B where the round before left it, so the estimate
+ * amplifies a difference of a few ulps as it amplifies the exact arithmetic's own roundings.  Measured against the CPU float32
+ * restatement (tests/test_gpu_flow_warp_lattice.py asserts the bound): W = 1 at most 3.5e-4 px on every case; W = 4 below
+ * 1e-3 px except 1.01e-3 px on a 4-level estimate (exact f32 4.7e-4 px from float64: 2.1x) and 2.7e-3 / 1.6e-3 px on two
+ * pairs with 45 - 59 px flows where exact f32 is itself 1.8e-3 / 1.3e-3 px from float64 (1.5x, 1.2x); the same cases with
+ * W = 0 stay within 1e-3 px.
  * EXACT is bit-identical for every operand, subnormal flows around a local change on a static background included.
  * The reference never runs this front end (wgpu_interpolator.rs:1156-1203 is unwired), so neither mode has a fixture.
  * The primitives below are always exact. */
@@ -512,8 +520,8 @@ int nus_flow_mode(const nus_flow *h);
  * _estimate_device_stream, _interpolate_device_stream, _interpolate_multi_device_stream); it may be changed at any time; with 0
  * every entry point writes the bytes and reserves the workspace it did before the setting existed.  A warped level costs one gather
  * launch per round plus the round's Jacobi steps, and 12 B of coefficient planes per cell and pair of workspace; in NUS_FLOW_FAST
- * its Jacobi steps run in the exact kernels (inside FAST's 1e-3 px contract).  A value above NUS_FLOW_MAX_WARPS:
- * NUS_ERR_INVALID_ARGUMENT, the setting unchanged. */
+ * its Jacobi steps run in the exact kernels; the pyramid and the coarsest level stay FAST (nus_flow_set_mode: FAST's bound
+ * with warps).  A value above NUS_FLOW_MAX_WARPS: NUS_ERR_INVALID_ARGUMENT, the setting unchanged. */
 #define NUS_FLOW_MAX_WARPS 4
 int nus_flow_set_warps(nus_flow *h, uint32_t warps);
 int nus_flow_warps(const nus_flow *h);

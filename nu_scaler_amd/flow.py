@@ -52,7 +52,7 @@ class FlowEstimator:
 
     def set_mode(self, mode: str) -> None:
         """"exact" (default): every stage bit-identical to the oracle; "fast": the estimators' Jacobi steps in separable sums,
-        reciprocals and FMAs (flow within 1e-3 px; nus_flow_set_mode)."""
+        reciprocals and FMAs (flow within 1e-3 px; with warps see nus_flow_set_mode)."""
         m = {"exact": 0, "fast": 1}.get(str(mode).lower())
         if m is None:
             raise ValueError("mode must be 'exact' or 'fast'")

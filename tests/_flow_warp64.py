@@ -37,6 +37,63 @@ F32_MEASURED_MAX = 4.4e-4
 F32_TOLERANCE = 4 * F32_MEASURED_MAX
 
 
+# ---- the lattice of settings tests/test_gpu_flow_warp_lattice.py holds the estimator to ------------------------------------------------
+# (w, h, levels, coarse_iters, refine_iters), lambda LATTICE_LAMBDA.  What each row is there for: the level counts 1 .. 4 (rounds
+# r >= 2 re-read the flow on one, two and three warped levels in a row; one level warps nothing); refine_iters 1, 5, 6, 7, 10, 13 (the
+# launch split of the Jacobi steps, at most 5 a launch, 8 on small tiles, decides which flow buffer a round ends in) and 0 (no round
+# at all); coarse_iters 0 (the coarsest level is the memset flow); heights 129 and 257 (2 and 4 row blocks of the streamed
+# kernel), widths above 162 (more than three 54-column strips); 333 x 262 and 613 x 517 (the middle and the largest LDS-tile
+# class in a batch of a few pairs); sizes below one tile, one lane and one cell.
+LATTICE = [
+    (65, 33, 2, 50, 7),
+    (130, 71, 4, 50, 13),
+    (119, 257, 3, 50, 10),
+    (173, 70, 3, 0, 10),
+    (173, 70, 3, 50, 0),
+    (64, 129, 2, 50, 1),
+    (64, 129, 1, 50, 10),
+    (5, 3, 3, 50, 10),
+    (333, 262, 3, 50, 6),
+    (613, 517, 2, 50, 5),
+    (2, 2, 2, 3, 2),
+    (1, 1, 1, 50, 10),
+]
+LATTICE_LAMBDA = 4e-4
+LATTICE_PERIOD = 8  # lattice_frames: frame k is frame k mod 8
+
+# Largest |estimate_f32 - estimate| over LATTICE and warps 1 .. 4, measured on the CPU (tests/test_flow_warp_yardstick.py prints
+# every figure): 613 x 517, two levels, 50 + 5 steps, warps 4.  Rounded up; F32_TOLERANCE above stays the bound.
+F32_LATTICE_MEASURED_MAX = 6.6e-4
+
+
+def lattice_frames(w, h, n=2):
+    """(n, h, w, 4) RGBA8 frames of a lattice case.  w >= 60 and h >= 30: frame k is the crop [16:16+h, 24:24+w] of
+    _bm_bidir.scene(w + 64, h + 64, (-2, 1), (6, 4), 24) with pan and square advanced by k mod 8 steps, so frames 0 and 1 are
+    that scene's A and B and the sequence is cyclic with 8 distinct consecutive pairs.  Smaller sizes: noise, two frames."""
+    if w >= 60 and h >= 30:
+        W_, H_, M, sq, pan, mv = w + 64, h + 64, 64, 24, (-2, 1), (6, 4)
+        rng = np.random.default_rng(1)
+        bg = scenes.smooth_noise(rng, H_ + 2 * M, W_ + 2 * M)
+        fg = scenes.smooth_noise(rng, sq, sq, 1)
+        distinct = []
+        for k in range(min(n, LATTICE_PERIOD)):
+            ox, oy = M + pan[0] * k, M + pan[1] * k
+            im = bg[oy:oy + H_, ox:ox + W_].copy()
+            x0, y0 = 40 + mv[0] * k, 30 + mv[1] * k
+            im[y0:y0 + sq, x0:x0 + sq] = fg
+            distinct.append(np.dstack([im, np.full((H_, W_), 255, np.uint8)])[16:16 + h, 24:24 + w])
+        return np.ascontiguousarray(np.stack([distinct[k % LATTICE_PERIOD] for k in range(n)]))
+    if n != 2:
+        raise ValueError("the noise cases are pairs")
+    rng = np.random.default_rng(100 * w + h)
+    return rng.integers(0, 256, (2, h, w, 4), dtype=np.uint8)
+
+
+def lattice_id(case):
+    w, h, levels, coarse, refine = case
+    return f"{w}x{h}-L{levels}-{coarse}+{refine}"
+
+
 def scene(row):
     w, h, pan, mv, sq = row
     return scenes.scene(w, h, pan, mv, sq)

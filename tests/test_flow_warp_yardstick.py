@@ -1,7 +1,8 @@
 """The yardstick of the flow estimator's re-linearisation mode, checked on the CPU (tests/_flow_warp64.py): the float64 witness
 with warps = 0 is tests/_flow64.py's estimator; on the scenes with a rendered true mid-frame one round per finer level buys what
 DESIGN section 8.1 says it buys; the float32 restatement of the stage stays within the tolerance the GPU tests use, and a wrong
-sampler or a wrong It' does not."""
+sampler or a wrong It' does not.  The same for the lattice of settings tests/test_gpu_flow_warp_lattice.py runs (W.LATTICE: level
+counts 1 .. 4, step counts that split unevenly, 0 steps, warps 1 .. 4): every figure printed, the largest recorded."""
 import numpy as np
 import pytest
 
@@ -89,3 +90,92 @@ def test_stage_float32_against_float64():
     print(f"stage: |f32 - f64| = {d:.3g}")
     # operands below 1 and 12: It' sums four terms of at most 1 + 1 + 6 + 6, each rounded at 2^-24 relative, a few times over
     assert d <= 14 * 8 * 2.0 ** -24
+
+
+# ---- the lattice of settings (W.LATTICE) ----------------------------------------------------------------------------------------------
+def _lattice_figure(case, warps, **wrong):
+    w, h, levels, coarse, refine = case
+    a, b = W.lattice_frames(w, h)
+    f32 = W.estimate_f32(oracle, a, b, levels, coarse, refine, W.LATTICE_LAMBDA, warps=warps)
+    assert f32.dtype == np.float32 and f32.shape == (h, w, 2)
+    return float(np.abs(f32 - W.estimate(a, b, levels, coarse, refine, W.LATTICE_LAMBDA, warps=warps, **wrong)).max())
+
+
+def test_lattice_holds_what_it_must():
+    """The table may grow, not shrink below this."""
+    cases = W.LATTICE
+    assert len(set(cases)) == len(cases)
+    assert {c[2] for c in cases} >= {1, 2, 3, 4}
+    assert any(c[3] == 0 and c[4] > 0 for c in cases) and any(c[4] == 0 and c[3] > 0 for c in cases)
+    refine = {c[4] for c in cases}
+    assert 1 in refine and 13 in refine and refine & {6, 7}
+    assert {129, 257} <= {c[1] for c in cases}
+    assert any(c[0] > 162 for c in cases)
+    assert any(c[:2] == (613, 517) for c in cases) and any(c[:2] == (2, 2) for c in cases) and any(c[:2] == (1, 1) for c in cases)
+    assert max(c[0] * c[1] for c in cases) == 613 * 517  # no larger shape than that
+    assert W.LATTICE_LAMBDA == 4e-4
+
+
+def test_lattice_frames_are_the_scene_crop_and_cyclic():
+    import _bm_bidir as scenes
+
+    w, h = 67, 45
+    a, b, _ = scenes.scene(w + 64, h + 64, (-2, 1), (6, 4), 24)
+    fr = W.lattice_frames(w, h, 18)
+    assert fr.shape == (18, h, w, 4) and fr.dtype == np.uint8 and fr.flags["C_CONTIGUOUS"]
+    assert np.array_equal(fr[0], a[16:16 + h, 24:24 + w]) and np.array_equal(fr[1], b[16:16 + h, 24:24 + w])
+    assert np.array_equal(fr[:2], W.lattice_frames(w, h))
+    assert np.array_equal(fr[8:16], fr[:8]) and np.array_equal(fr[16:], fr[:2])
+    pairs = {(fr[k].tobytes(), fr[k + 1].tobytes()) for k in range(8)}
+    assert len(pairs) == 8  # 8 distinct consecutive pairs, the wrap from frame 7 to frame 0 among them
+    small = W.lattice_frames(5, 3)
+    rng = np.random.default_rng(503)
+    assert small.shape == (2, 3, 5, 4) and np.array_equal(small, rng.integers(0, 256, (2, 3, 5, 4), dtype=np.uint8))
+    with pytest.raises(ValueError):
+        W.lattice_frames(5, 3, 3)
+
+
+_lattice_worst = {}
+
+
+@pytest.mark.parametrize("warps", [1, 2, 3, 4])
+def test_lattice_float32_restatement_within_tolerance(warps):
+    worst = 0.0
+    for case in W.LATTICE:
+        d = _lattice_figure(case, warps)
+        print(f"{W.lattice_id(case)} warps {warps}: |f32 - f64| = {d:.3g} px")
+        worst = max(worst, d)
+        assert d <= W.F32_TOLERANCE, (case, warps, d)
+    print(f"warps {warps}: largest |f32 - f64| = {worst:.3g} px, recorded maximum {W.F32_LATTICE_MEASURED_MAX:.3g}, tolerance {W.F32_TOLERANCE:.3g}")
+    assert worst <= W.F32_LATTICE_MEASURED_MAX
+    _lattice_worst[warps] = worst
+    if len(_lattice_worst) == 4:  # the recorded figure is the measured maximum, rounded up: at most one unit of its second digit above
+        assert W.F32_LATTICE_MEASURED_MAX - 0.2e-4 <= max(_lattice_worst.values()) <= W.F32_LATTICE_MEASURED_MAX
+
+
+def test_lattice_cases_without_a_round_are_the_warps_zero_witness():
+    """refine_iters = 0 and one level: there is nothing to re-linearise, whatever warps says."""
+    none = [c for c in W.LATTICE if c[4] == 0 or c[2] == 1]
+    assert any(c[4] == 0 and c[2] > 1 for c in none) and any(c[2] == 1 and c[0] > 1 for c in none)
+    for w, h, levels, coarse, refine in none:
+        a, b = W.lattice_frames(w, h)
+        zero = F.estimate(a, b, levels, coarse, refine, W.LATTICE_LAMBDA)
+        want32 = W.estimate_f32(oracle, a, b, levels, coarse, refine, W.LATTICE_LAMBDA, warps=1)
+        assert np.array_equal(want32, oracle.flow_estimate(a, b, levels, coarse, refine, W.LATTICE_LAMBDA))
+        for warps in range(W.MAX_WARPS + 1):
+            assert np.array_equal(W.estimate(a, b, levels, coarse, refine, W.LATTICE_LAMBDA, warps=warps), zero), (w, h, warps)
+            if warps:
+                got = W.estimate_f32(oracle, a, b, levels, coarse, refine, W.LATTICE_LAMBDA, warps=warps)
+                assert np.array_equal(got.view(np.uint32), want32.view(np.uint32)), (w, h, warps)
+
+
+def test_lattice_tolerance_still_tells_a_wrong_sampler():
+    """warps = 4, every scene case in which a round runs (the 3- and 4-level ones among them): nearest sampling is beyond the
+    tolerance.  (The noise cases of a few cells are left out: their flows of tens of pixels clamp every sample to a border texel,
+    where nearest and bilinear sampling are the same value.)"""
+    held = [c for c in W.LATTICE if c[0] >= 60 and c[1] >= 30 and c[2] > 1 and c[4] > 0]
+    assert {c[2] for c in held} >= {2, 3, 4}
+    for case in held:
+        d = _lattice_figure(case, 4, nearest=True)
+        print(f"{W.lattice_id(case)} warps 4, nearest sampling in the witness: {d:.3g} px")
+        assert d > W.F32_TOLERANCE, (case, d)
