@@ -590,7 +590,8 @@ int nus_flow_interpolate_multi_device_stream(nus_flow *h, const void *d_frames, 
  *   PSNR = 20 log10(255 / sqrt(MSE)), +inf at MSE 0 (common.rs:513-519).
  *   SSIM (common.rs:521 keeps a 0.0 placeholder; here Wang et al. 2004) per channel on 0..255: 11 x 11 Gaussian window,
  *          sigma 1.5, weights normalised to 1, population statistics, C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2, averaged over
- *          R, G, B and the (W-10) x (H-10) centres whose window lies inside the frame; within 1e-5 of the float64 definition.
+ *          R, G, B and the (W-10) x (H-10) centres whose window lies inside the frame; within 1e-5 of the float64 definition
+ *          on any content, flat and few-valued frames included (the window statistics and their differences are f64).
  *          Needs W >= 11 and H >= 11 (below: NUS_ERR_INVALID_ARGUMENT).
  * Results are deterministic: the same inputs give the same bytes on every run, at every batch position and whatever else was
  * asked in the same call.  A metric that was not asked is NaN. */

@@ -8,8 +8,10 @@
 // adds them in a fixed order.  No float atomics anywhere: the same inputs give the same bytes on every run.
 //   k_metrics_sse       MSE only: one streaming read of both frames, 16 B per lane where both frame bases allow it.
 //   k_metrics_ssim      SSIM (and the SSE of the same pixels when MSE is asked too): a 64 x 32 tile of valid centres per
-//                       workgroup, staged with its 5-pixel halo in LDS; per channel a horizontal 11-tap pass into LDS, then a
-//                       vertical 11-tap pass in registers, over the five statistics.
+//                       workgroup, staged with its 5-pixel halo in LDS; per channel and for each of the five statistics in turn a
+//                       horizontal 11-tap pass into one f64 plane in LDS, then a vertical 11-tap pass in registers.  The
+//                       statistics and sigma_xx, sigma_yy, sigma_xy are f64: in f32 their cancellation against C2 cost up to
+//                       1.2e-4 of SSIM on flat frames (Precision); the ratio is f32.
 //   k_metrics_finish    one workgroup per frame: [mse, psnr, ssim], NaN for what was not asked.
 #include <hip/hip_runtime.h>
 
@@ -100,14 +102,68 @@ __global__ __launch_bounds__(256) void k_metrics_sse(const uint8_t *__restrict__
     if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
-// keeps a value in a VGPR, so the weight FMAs take VGPR operands only: the repository's instruction-rate probe measured
+// keeps a value in VGPRs, so the weight FMAs take VGPR operands only: the repository's instruction-rate probe measured
 // v_fmac_f32 with an SGPR operand at 4.3 cycles per wave-instruction against 2.3 with VGPRs (profiles/r01_probe_valu_instruction_
-// rates.txt; literal operands were not probed), and v_pk_fma_f32, which hipcc forms from some of these FMAs, needs VGPR
-// operands.  What the pinning changes in this kernel's time was not measured.
-__device__ __forceinline__ float in_vgpr(float x)
+// rates.txt; v_fma_f64 was not probed).  What the pinning changes in this kernel's time was not measured.
+__device__ __forceinline__ double in_vgpr(double x)
 {
     asm volatile("" : "+v"(x));
     return x;
+}
+
+#define NUS_G(tp) g6[(tp) <= 5 ? (tp) : 10 - (tp)]
+
+// One of the five window statistics of one channel over the whole tile, in f64: S = 0..4 is x, y, x^2, y^2, xy of the channel at
+// bit `sh`.  Horizontal 11-tap pass of the staged rows into sH, then the vertical pass of column lx into m[0..kRunV).  The weights
+// are f32 values (24 bits) and the pixel terms integers below 2^16, so every product and every horizontal sum is exact in f64 (a
+// multiple of 2^-33 below 2^16: 49 bits); the vertical FMAs round at 2^-53 relative, eight decimal digits below what the
+// differences E[x^2] - mu^2 need against C2.  Ends with a barrier: sH is free for the next statistic.
+template <int S>
+__device__ __forceinline__ void ssim_stat(const uint32_t (*sA)[kSXP], const uint32_t (*sB)[kSXP], double (*sH)[kTX], uint32_t sh,
+                                          const double (&g6)[6], uint32_t lx, uint32_t run, double (&m)[kRunV])
+{
+    // horizontal: item (r, q) filters staged row r for the centre columns kRunH * q .. kRunH * q + kRunH - 1
+    for (int it = threadIdx.x; it < kItemsH; it += kBlock) {
+        const int r = it / (kTX / kRunH), q = it - r * (kTX / kRunH);
+        const uint4 *ra = reinterpret_cast<const uint4 *>(&sA[r][kRunH * q]);
+        const uint4 *rb = reinterpret_cast<const uint4 *>(&sB[r][kRunH * q]);
+        uint32_t pxa[16], pxb[16];
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const uint4 qa = ra[v], qb = rb[v];
+            pxa[4 * v] = qa.x, pxa[4 * v + 1] = qa.y, pxa[4 * v + 2] = qa.z, pxa[4 * v + 3] = qa.w;
+            pxb[4 * v] = qb.x, pxb[4 * v + 1] = qb.y, pxb[4 * v + 2] = qb.z, pxb[4 * v + 3] = qb.w;
+        }
+        double acc[kRunH];
+#pragma unroll
+        for (int o = 0; o < kRunH; ++o) acc[o] = 0.0;
+#pragma unroll
+        for (int j = 0; j < kRunH + 10; ++j) {
+            const uint32_t x = (pxa[j] >> sh) & 255u, y = (pxb[j] >> sh) & 255u;
+            const double v = (double)(S == 0 ? x : S == 1 ? y : S == 2 ? x * x : S == 3 ? y * y : x * y);
+#pragma unroll
+            for (int o = 0; o < kRunH; ++o) {
+                const int tp = j - o;
+                if (tp >= 0 && tp <= 10) acc[o] = __builtin_fma(NUS_G(tp), v, acc[o]);
+            }
+        }
+        *reinterpret_cast<double2 *>(&sH[r][kRunH * q]) = double2{acc[0], acc[1]};
+        *reinterpret_cast<double2 *>(&sH[r][kRunH * q + 2]) = double2{acc[2], acc[3]};
+    }
+    __syncthreads();
+    // vertical: lane (lx, run) filters column lx for the centre rows kRunV * run .. kRunV * run + kRunV - 1
+#pragma unroll
+    for (int o = 0; o < kRunV; ++o) m[o] = 0.0;
+#pragma unroll
+    for (int j = 0; j < kRunV + 10; ++j) {
+        const double v = sH[kRunV * run + j][lx];
+#pragma unroll
+        for (int o = 0; o < kRunV; ++o) {
+            const int tp = j - o;
+            if (tp >= 0 && tp <= 10) m[o] = __builtin_fma(NUS_G(tp), v, m[o]);
+        }
+    }
+    __syncthreads();
 }
 
 // grid: tiles_x * tiles_y * frames.  Staged pixel (r, c) of tile (tx, ty) is frame pixel (tx * kTX + c, ty * kTY + r); the tile's
@@ -121,7 +177,7 @@ __global__ __launch_bounds__(256, 2) void k_metrics_ssim(const uint8_t *__restri
 {
     __shared__ __attribute__((aligned(16))) uint32_t sA[kSY][kSXP];
     __shared__ __attribute__((aligned(16))) uint32_t sB[kSY][kSXP];
-    __shared__ __attribute__((aligned(16))) float sH[5][kSY][kTX];
+    __shared__ __attribute__((aligned(16))) double sH[kSY][kTX]; // one statistic at a time
     __shared__ double red[kBlock / 64];
     __shared__ u64 red_u[kBlock / 64];
 
@@ -151,93 +207,39 @@ __global__ __launch_bounds__(256, 2) void k_metrics_ssim(const uint8_t *__restri
     }
     __syncthreads();
 
-    float g6[6];
+    double g6[6];
 #pragma unroll
-    for (int k = 0; k < 6; ++k) g6[k] = in_vgpr(kG[k]);
-#define NUS_G(tp) g6[(tp) <= 5 ? (tp) : 10 - (tp)]
+    for (int k = 0; k < 6; ++k) g6[k] = in_vgpr((double)kG[k]);
 
     const uint32_t lx = threadIdx.x & (kTX - 1), run = threadIdx.x / kTX;
     const bool col_ok = x0 + lx + 2 * kHalo < w;
     double ssim_sum = 0.0;
     for (uint32_t ch = 0; ch < 3; ++ch) {
         const uint32_t sh = 8 * ch;
-        // horizontal: item (r, q) filters staged row r for the centre columns kRunH * q .. kRunH * q + kRunH - 1
-        for (int it = threadIdx.x; it < kItemsH; it += kBlock) {
-            const int r = it / (kTX / kRunH), q = it - r * (kTX / kRunH);
-            const uint4 *ra = reinterpret_cast<const uint4 *>(&sA[r][kRunH * q]);
-            const uint4 *rb = reinterpret_cast<const uint4 *>(&sB[r][kRunH * q]);
-            uint32_t pxa[16], pxb[16];
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                const uint4 qa = ra[v], qb = rb[v];
-                pxa[4 * v] = qa.x, pxa[4 * v + 1] = qa.y, pxa[4 * v + 2] = qa.z, pxa[4 * v + 3] = qa.w;
-                pxb[4 * v] = qb.x, pxb[4 * v + 1] = qb.y, pxb[4 * v + 2] = qb.z, pxb[4 * v + 3] = qb.w;
-            }
-            float acc[5][kRunH];
-#pragma unroll
-            for (int s = 0; s < 5; ++s)
-#pragma unroll
-                for (int o = 0; o < kRunH; ++o) acc[s][o] = 0.0f;
-#pragma unroll
-            for (int j = 0; j < kRunH + 10; ++j) {
-                // offset domain: x - 128 keeps every product and square an exact f32 integer
-                const float x = (float)((pxa[j] >> sh) & 255u) - 128.0f, y = (float)((pxb[j] >> sh) & 255u) - 128.0f;
-                const float xx = x * x, yy = y * y, xy = x * y;
-#pragma unroll
-                for (int o = 0; o < kRunH; ++o) {
-                    const int tp = j - o;
-                    if (tp >= 0 && tp <= 10) {
-                        acc[0][o] = __builtin_fmaf(NUS_G(tp), x, acc[0][o]);
-                        acc[1][o] = __builtin_fmaf(NUS_G(tp), y, acc[1][o]);
-                        acc[2][o] = __builtin_fmaf(NUS_G(tp), xx, acc[2][o]);
-                        acc[3][o] = __builtin_fmaf(NUS_G(tp), yy, acc[3][o]);
-                        acc[4][o] = __builtin_fmaf(NUS_G(tp), xy, acc[4][o]);
-                    }
-                }
-            }
-#pragma unroll
-            for (int s = 0; s < 5; ++s)
-                *reinterpret_cast<float4 *>(&sH[s][r][kRunH * q]) = float4{acc[s][0], acc[s][1], acc[s][2], acc[s][3]};
-        }
-        __syncthreads();
-        // vertical: lane (lx, run) filters column lx for the centre rows kRunV * run .. kRunV * run + kRunV - 1
-        float m[5][kRunV];
-#pragma unroll
-        for (int s = 0; s < 5; ++s)
-#pragma unroll
-            for (int o = 0; o < kRunV; ++o) m[s][o] = 0.0f;
-#pragma unroll
-        for (int j = 0; j < kRunV + 10; ++j) {
-            float v[5];
-#pragma unroll
-            for (int s = 0; s < 5; ++s) v[s] = sH[s][kRunV * run + j][lx];
-#pragma unroll
-            for (int o = 0; o < kRunV; ++o) {
-                const int tp = j - o;
-                if (tp >= 0 && tp <= 10) {
-#pragma unroll
-                    for (int s = 0; s < 5; ++s) m[s][o] = __builtin_fmaf(NUS_G(tp), v[s], m[s][o]);
-                }
-            }
-        }
-        __syncthreads(); // sH is rewritten by the next channel
+        double mx[kRunV], my[kRunV], mxx[kRunV], myy[kRunV], mxy[kRunV];
+        ssim_stat<0>(sA, sB, sH, sh, g6, lx, run, mx);
+        ssim_stat<1>(sA, sB, sH, sh, g6, lx, run, my);
+        ssim_stat<2>(sA, sB, sH, sh, g6, lx, run, mxx);
+        ssim_stat<3>(sA, sB, sH, sh, g6, lx, run, myy);
+        ssim_stat<4>(sA, sB, sH, sh, g6, lx, run, mxy);
         if (col_ok) {
             const float C1 = 6.5025f, C2 = 58.5225f;
 #pragma unroll
             for (int o = 0; o < kRunV; ++o) {
                 if (y0 + kRunV * run + o + 2 * kHalo < h) {
-                    const float mxo = m[0][o], myo = m[1][o];
-                    const float sxx = m[2][o] - mxo * mxo, syy = m[3][o] - myo * myo, sxy = m[4][o] - mxo * myo;
-                    const float mx = mxo + 128.0f, my = myo + 128.0f;
-                    // 2*mx*my and mx^2 + my^2 from the same rounded means: identical frames give exactly 1
-                    const float num = (2.0f * mx * my + C1) * (2.0f * sxy + C2);
-                    const float den = (mx * mx + my * my + C1) * (sxx + syy + C2);
+                    // the three differences in f64 (in f32 they miss float64 by up to 1.2e-4 of SSIM on flat frames), then
+                    // rounded once; the ratio itself is f32
+                    const float sxx = (float)(mxx[o] - mx[o] * mx[o]), syy = (float)(myy[o] - my[o] * my[o]);
+                    const float sxy = (float)(mxy[o] - mx[o] * my[o]);
+                    const float ux = (float)mx[o], uy = (float)my[o];
+                    // 2*ux*uy and ux^2 + uy^2 from the same rounded means: identical frames give exactly 1
+                    const float num = (2.0f * ux * uy + C1) * (2.0f * sxy + C2);
+                    const float den = (ux * ux + uy * uy + C1) * (sxx + syy + C2);
                     ssim_sum += (double)(num / den);
                 }
             }
         }
     }
-#undef NUS_G
     const double s = block_sum<double>(ssim_sum, red);
     if (threadIdx.x == 0) ssim_part[blockIdx.x] = s;
     if (WITH_SSE) {
@@ -245,6 +247,7 @@ __global__ __launch_bounds__(256, 2) void k_metrics_ssim(const uint8_t *__restri
         if (threadIdx.x == 0) sse_part[blockIdx.x] = e;
     }
 }
+#undef NUS_G
 
 // one workgroup per frame: the frame's partials in a fixed order (lane-strided, then the block sum)
 __global__ __launch_bounds__(256) void k_metrics_finish(const u64 *__restrict__ sse_part, uint32_t sse_blocks,
