@@ -69,7 +69,7 @@ int HipUpscaler::set_bilinear_variant(int variant)
     std::lock_guard<std::mutex> lk(mu_);
     if (variant != 0 && variant != 1) return fail(kInvalidArgument, "unknown bilinear variant");
     if (initialized_) return fail(kInvalidArgument, "set_bilinear_variant must be called before initialize");
-    wgsl_bilinear_ = variant == 1;
+    plan_opt_.wgsl_bilinear = variant == 1;
     return kOk;
 }
 
@@ -87,17 +87,17 @@ int HipUpscaler::set_option(const char *key, int64_t value)
     if (!key) return fail(kInvalidArgument, "null option key");
     if (!strcmp(key, "force_general")) {
         if (initialized_) return fail(kInvalidArgument, "force_general must be set before initialize");
-        force_general_ = value != 0;
+        plan_opt_.force_general = value != 0;
         return kOk;
     }
     if (!strcmp(key, "force_per_pixel")) {
         if (initialized_) return fail(kInvalidArgument, "force_per_pixel must be set before initialize");
-        force_per_pixel_ = value != 0;
+        plan_opt_.force_per_pixel = value != 0;
         return kOk;
     }
     if (!strcmp(key, "force_rows")) {
         if (initialized_) return fail(kInvalidArgument, "force_rows must be set before initialize");
-        force_rows_ = value != 0;
+        plan_opt_.force_rows = value != 0;
         return kOk;
     }
     if (!strcmp(key, "single_bands")) { // 1: a frame alone in the pipeline goes through it in row bands (default), 0: whole
@@ -118,7 +118,7 @@ int HipUpscaler::set_option(const char *key, int64_t value)
     if (!strcmp(key, "down_seg_width")) { // output columns per wave of the down-scaling kernel; 0 = the host's choice
         if (initialized_) return fail(kInvalidArgument, "down_seg_width must be set before initialize");
         if (value < 0 || value > 64) return fail(kInvalidArgument, "down_seg_width out of range");
-        down_seg_width_ = (uint32_t)value;
+        plan_opt_.down_seg_width = (uint32_t)value;
         return kOk;
     }
     if (!strcmp(key, "rows_per_wave")) {
@@ -139,7 +139,7 @@ int HipUpscaler::set_option(const char *key, int64_t value)
     if (!strcmp(key, "fsr_two_pass")) { // FSR1: EASU -> scratch image -> row-walking RCAS for frames of >= 1 MiB (default 1); 0 = fused tile always
         if (initialized_) return fail(kInvalidArgument, "fsr_two_pass must be set before initialize");
         if (value != 0 && value != 1) return fail(kInvalidArgument, "fsr_two_pass must be 0 or 1");
-        fsr_two_pass_ = value != 0;
+        plan_opt_.fsr_two_pass = value != 0;
         return kOk;
     }
     if (!strcmp(key, "fsr_fast")) { // FSR1-style EASU in FAST arithmetic (nus_k_fsr.hip): 0 = the shaders' own operation order (default)
@@ -168,12 +168,12 @@ int HipUpscaler::get_option(const char *key, int64_t *value)
 {
     std::lock_guard<std::mutex> lk(mu_);
     if (!key || !value) return fail(kInvalidArgument, "null option key or result pointer");
-    const bool pq = initialized_ && variant_ == Variant::LanczosPqRegWin;
-    if (!strcmp(key, "pq_p")) *value = pq ? pq_p_ : 0;
-    else if (!strcmp(key, "pq_q")) *value = pq ? pq_q_ : 0;
-    else if (!strcmp(key, "pq_narrow_active")) *value = pq && pq_narrow_ && pq_narrow_allowed_ ? 1 : 0;
+    const bool pq = initialized_ && plan_.variant == Variant::LanczosPqRegWin;
+    if (!strcmp(key, "pq_p")) *value = pq ? plan_.pq_p : 0;
+    else if (!strcmp(key, "pq_q")) *value = pq ? plan_.pq_q : 0;
+    else if (!strcmp(key, "pq_narrow_active")) *value = pq && plan_.pq_narrow && pq_narrow_allowed_ ? 1 : 0;
     else if (!strcmp(key, "rows_per_wave")) *value = rows_per_wave_;
-    else if (!strcmp(key, "win_outputs_per_lane")) *value = initialized_ && variant_ == Variant::ResizeWin ? win_outputs_per_lane_ : 0;
+    else if (!strcmp(key, "win_outputs_per_lane")) *value = initialized_ && plan_.variant == Variant::ResizeWin ? plan_.win_outputs_per_lane : 0;
     else return fail(kInvalidArgument, fmt("unknown option '%s'", key));
     return kOk;
 }
@@ -248,253 +248,6 @@ void HipUpscaler::release()
     have_ms_ = false;
 }
 
-// widest input-column footprint of a `segw`-column output segment (what one wave's LDS row / register columns must hold)
-uint32_t HipUpscaler::widest_footprint(uint32_t segw) const
-{
-    uint32_t widest = 0;
-    for (uint32_t x0 = 0; x0 < ow_; x0 += segw) {
-        const uint32_t xl = (x0 + segw < ow_ ? x0 + segw : ow_) - 1;
-        const uint32_t span = (uint32_t)(tx_.lz_left[xl] + (int32_t)tx_.lz_ntaps[xl] - tx_.lz_left[x0]);
-        if (span > widest) widest = span;
-    }
-    return widest;
-}
-
-// widest union of the tap windows of `n` adjacent outputs (a lane's outputs in the union-window H pass); ow_ % n == 0.  For two
-// outputs per lane a window is as long as the axis's widest one (7 for Lanczos-3 on an up-scale; the table's slots beyond a window's
-// taps hold zeros), so that their union fits the 8-tap pass; for four the table's 8 slots as before (counted tightly, x1.4 - x1.5 would
-// move from the plain 8-slot pass to the 10-tap union with its weights in LDS, which is slower there: 768p -> 1080p 6.1 -> 7.3 us)
-uint32_t HipUpscaler::widest_union(uint32_t n) const
-{
-    uint32_t widest = 0;
-    const uint32_t taps = n == 2 && tx_.lz_max_taps > 0 && tx_.lz_max_taps < 8 ? (uint32_t)tx_.lz_max_taps : 8u;
-    for (uint32_t x0 = 0; x0 < ow_; x0 += n) {
-        const uint32_t u = (uint32_t)(tx_.lz_left[x0 + n - 1] - tx_.lz_left[x0]) + taps;
-        if (u > widest) widest = u;
-    }
-    return widest;
-}
-
-// Kernel for the resize filters (Lanczos-3 / Catmull-Rom / Triangle), most specialised first.
-void HipUpscaler::choose_resize_variant(bool x2)
-{
-    variant_ = Variant::LanczosGeneral; // per-pixel fallback
-    xs_factor_ = 0;
-    resize_ncols_max_ = resize_union_taps_ = 0;
-    resize_small_taps_ = false;
-    win_outputs_per_lane_ = 4;
-    const bool addressable = (uint64_t)ow_ * oh_ * 4 < (1ull << 31); // buffer-resource addressing of the output frame
-    // exact x2: fixed interior weights; same ratio on both axes, so the two passes share the same 12 numbers
-    if (x2 && iw_ >= 16 && ih_ >= 16 && addressable && lanczos_x2_phase_frame(tx_, wx6_) && lanczos_x2_phase_frame(ty_, wy6_) &&
-        lanczos_x2_interior_uniform(tx_, wx6_) && lanczos_x2_interior_uniform(ty_, wy6_) &&
-        memcmp(&wx6_[(size_t)8 * 6], &wy6_[(size_t)8 * 6], 12 * sizeof(float)) == 0) {
-        variant_ = Variant::LanczosX2RegWin;
-        return;
-    }
-    // integer factors x3 / x4: the same register-window design (nus_k_lanczos_xs.hip).  x4: the interior weights are
-    // uniform (one set per phase, the same numbers on both axes).  x3: they move with the binade of the coordinate
-    // (nus_tables.hpp), so every lane / row takes the set of its class
-    xs_cls_x_.clear(), xs_cls_y_.clear(), xs_wcls_x_.clear(), xs_wcls_y_.clear();
-    for (uint32_t S = 3; S <= 4 && !force_general_; ++S) {
-        if (ow_ != S * iw_ || oh_ != S * ih_ || (iw_ % 4) != 0 || iw_ < 16 || ih_ < 16 || !addressable) continue;
-        if (!lanczos_xs_phase_frame(tx_, S, wx6_) || !lanczos_xs_phase_frame(ty_, S, wy6_)) continue;
-        if (lanczos_xs_interior_uniform(tx_, S, wx6_) && lanczos_xs_interior_uniform(ty_, S, wy6_) &&
-            memcmp(&wx6_[(size_t)8 * S * 6], &wy6_[(size_t)8 * S * 6], (size_t)S * 6 * sizeof(float)) == 0) {
-            xs_factor_ = S;
-            variant_ = Variant::LanczosXsRegWin;
-            return;
-        }
-        if (S == 3 && lanczos_xs_weight_classes(tx_, S, wx6_, true, xs_cls_x_, xs_wcls_x_) &&
-            lanczos_xs_weight_classes(ty_, S, wy6_, false, xs_cls_y_, xs_wcls_y_)) {
-            xs_factor_ = S;
-            variant_ = Variant::LanczosXsRegWin;
-            return;
-        }
-        xs_cls_x_.clear(), xs_cls_y_.clear(), xs_wcls_x_.clear(), xs_wcls_y_.clear();
-    }
-    // x3/2 (720p -> 1080p, 1440p -> 4K): the same design with three output rows per input row pair (nus_k_lanczos_r32.hip);
-    // weights by class of the input pair on both axes, as at x3
-    if (!force_general_ && 2 * (uint64_t)ow_ == 3 * (uint64_t)iw_ && 2 * (uint64_t)oh_ == 3 * (uint64_t)ih_ && (iw_ % 8) == 0 &&
-        (ih_ % 2) == 0 && iw_ >= 32 && ih_ >= 16 && addressable && lanczos_r32_phase_frame(tx_, wx6_) &&
-        lanczos_r32_phase_frame(ty_, wy6_) && lanczos_r32_weight_classes(tx_, wx6_, true, xs_cls_x_, xs_wcls_x_) &&
-        lanczos_r32_weight_classes(ty_, wy6_, false, xs_cls_y_, xs_wcls_y_)) {
-        variant_ = Variant::LanczosR32RegWin;
-        return;
-    }
-    xs_cls_x_.clear(), xs_cls_y_.clear(), xs_wcls_x_.clear(), xs_wcls_y_.clear();
-    // x4/3 (1080p -> 1440p): four output rows per group of three input rows (nus_k_lanczos_r43.hip); the ratio 3/4 is exact in
-    // f32, so the interior weights are uniform (one set per phase, the same numbers on both axes), as at x2 and x4
-    if (!force_general_ && 3 * (uint64_t)ow_ == 4 * (uint64_t)iw_ && 3 * (uint64_t)oh_ == 4 * (uint64_t)ih_ && (iw_ % 12) == 0 &&
-        (ih_ % 3) == 0 && iw_ >= 48 && ih_ >= 18 && addressable && lanczos_r43_phase_frame(tx_, wx6_) &&
-        lanczos_r43_phase_frame(ty_, wy6_) && lanczos_r43_interior_uniform(tx_, wx6_) && lanczos_r43_interior_uniform(ty_, wy6_) &&
-        memcmp(&wx6_[(size_t)8 * 6], &wy6_[(size_t)8 * 6], 24 * sizeof(float)) == 0) {
-        variant_ = Variant::LanczosR43RegWin;
-        return;
-    }
-    // x5/4, x6/5, x5/3, x5/2: P output rows per group of Q input rows, every output's weights from the tables in frame form
-    // (nus_k_lanczos_pq.hip); the ratios are not exact in f32, so nothing about the weights is assumed beyond their frames
-    pq_p_ = pq_q_ = 0;
-    pq_narrow_ = false;
-    if (!force_general_ && ow_ > iw_ && addressable && iw_ >= 32 && ih_ >= 12) {
-        uint64_t a = ow_, b = iw_;
-        while (b) {
-            const uint64_t r = a % b;
-            a = b, b = r;
-        }
-        const uint32_t P = (uint32_t)(ow_ / a), Q = (uint32_t)(iw_ / a);
-        if (lanczos_pq_supported(P, Q) && (uint64_t)oh_ * Q == (uint64_t)ih_ * P && (iw_ % Q) == 0 && (ih_ % Q) == 0 && (ow_ % 4) == 0 &&
-            lanczos_pq_phase_frame(tx_, P, Q, wx6_) && lanczos_pq_phase_frame(ty_, P, Q, wy6_)) {
-            pq_p_ = P, pq_q_ = Q;
-            // a filter of support 2 or less (Catmull-Rom, Triangle): slots 0 and 5 of every output's frame are zero on both axes, and
-            // the kernel may sum slots 1 .. 4 only (checked on the tables themselves, border outputs included)
-            auto edge_slots_zero = [](const std::vector<float> &w6) {
-                for (size_t o = 0; o + 6 <= w6.size(); o += 6)
-                    if (w6[o] != 0.0f || w6[o + 5] != 0.0f) return false;
-                return true;
-            };
-            pq_narrow_ = edge_slots_zero(wx6_) && edge_slots_zero(wy6_);
-        }
-    }
-    if (pq_p_) {
-        // The any-scale kernel's parameters as well: at x6/5, x8/5, x9/5 the kernel's EXACT instantiations hold 250 - 430 registers (one
-        // wave per SIMD) and lose to it (1080p: 11.2 / 25.4 / 30.0 against 8.3 / 19.9 / 28.5 us; x7/5 wins, 11.6 against 17.4), so EXACT
-        // mode -- which can be switched on after initialize() -- takes it there (enqueue)
-        choose_general_resize_variant();
-        pq_exact_fallback_ = variant_ == Variant::ResizeWin && pq_q_ == 5 && pq_p_ != 7;
-        variant_ = Variant::LanczosPqRegWin;
-        return;
-    }
-    choose_general_resize_variant();
-}
-
-// ... and the kernels for every other shape: streamed down-scaling, the register-window / LDS-row any-scale kernels, per pixel
-void HipUpscaler::choose_general_resize_variant()
-{
-    variant_ = Variant::LanczosGeneral;
-    if (force_per_pixel_) return;
-    // vertical down-scaling: stream the input rows through 7 accumulator slots, if the windows allow it and a
-    // 64-column output segment's footprint fits 5 columns per lane
-    if (ih_ > oh_ && tx_.lz_max_taps <= 32 && !force_rows_) {
-        const uint32_t widest64 = widest_footprint(64);
-        if (build_down_stream_tables(ty_, down_rows_, down_done_) && widest64 <= 320) {
-            variant_ = Variant::ResizeDown;
-            // Output columns per wave: every lane carries ceil(footprint / 64) input columns through the vertical pass whether
-            // the segment fills them or not, so a slightly narrower segment whose footprint fits one column per lane fewer is
-            // cheaper (2x down: 58 outputs over 128 columns instead of 64 over 140 = 3 columns per lane, a third of them idle).
-            // Cost per output column ~ (vertical FMAs of a lane per output row + its horizontal pass: an LDS read and 4 FMAs per
-            // tap of the compiled trip count, priced at 10) / width, calibrated on profiles/r03_resize_down_segment_width_ab.txt
-            // (4K -> 1080p: 58 columns 16.9 us against 20.1 at 64; 4K -> 720p, 32-tap passes: 64 stays, 57 is 4 % slower).
-            down_seg_w_ = 64;
-            resize_ncols_max_ = widest64;
-            if (down_seg_width_ == 0) {
-                const double rows_per_out = (double)ih_ / oh_;
-                double best = 0.0;
-                for (uint32_t w = 64; w >= 40; --w) {
-                    const uint32_t fp = widest_footprint(w);
-                    const double cost = (28.0 * ((fp + 63) / 64) * rows_per_out + 10.0 * (tx_.lz_max_taps > 16 ? 32 : 16) + 30.0) / w;
-                    if (w == 64 || cost < best * 0.97) best = cost, down_seg_w_ = w, resize_ncols_max_ = fp;
-                }
-            } else { // option "down_seg_width" (tests, A/B timing)
-                down_seg_w_ = down_seg_width_ > 64 ? 64 : down_seg_width_;
-                resize_ncols_max_ = widest_footprint(down_seg_w_);
-                if (resize_ncols_max_ > 320) down_seg_w_ = 64, resize_ncols_max_ = widest64;
-            }
-            return;
-        }
-    }
-    // LDS row kernel: the widest segment footprint must fit the per-wave LDS row (4 waves x 640 x 16 B = 40 KiB per block)
-    const uint32_t widest = widest_footprint((ow_ % 4) == 0 ? 256 : 64);
-    if (widest > 640) return;
-    variant_ = Variant::ResizeRows;
-    resize_ncols_max_ = widest;
-    resize_small_taps_ = tx_.lz_max_taps <= 8 && ty_.lz_max_taps <= 8;
-    if ((ow_ % 4) != 0 || !resize_small_taps_) return;
-    resize_union_taps_ = widest_union(4); // union-window H pass, 4 outputs per lane
-    // register-window variant: up-scaling shapes whose first tap row moves by at most one per output row
-    bool win_ok = ty_.lz_max_taps <= 7 && !force_rows_;
-    for (uint32_t y = 1; win_ok && y < oh_; ++y) {
-        const int32_t d = ty_.lz_left[y] - ty_.lz_left[y - 1];
-        win_ok = d == 0 || d == 1;
-    }
-    if (!win_ok) return;
-    // Four outputs per lane (segments of 256 output columns) from x2 up.  Below x2 two outputs per lane win wherever their 8-tap union
-    // pass applies (two input columns per lane, union weights in registers, rows through the ring -- the four-output shape there needs
-    // three columns per lane and keeps its union weights in LDS): 768p -> 1080p 7.2 -> 6.5, x1.7 18.6 -> 15.8, x1.9 21.2 -> 19.0 us per
-    // frame; from x2.2 up the four-output shape is the faster one again (profiles/r05_resize_win_rotating_window.txt)
-    const bool two_per_lane = 2 * (uint64_t)iw_ > ow_ && widest_footprint(128) <= 128 && widest_union(2) <= 8;
-    if (widest <= 192 && !two_per_lane) {
-        variant_ = Variant::ResizeWin;
-        return;
-    }
-    // factors x1.0 .. x2: two outputs per lane, segments of 128 output columns
-    const uint32_t widest2 = widest_footprint(128);
-    if (widest2 > 192) return;
-    variant_ = Variant::ResizeWin;
-    win_outputs_per_lane_ = 2;
-    resize_ncols_max_ = widest2;
-    resize_union_taps_ = widest_union(2);
-}
-
-// One of the small rational factors P/Q the fixed-ratio nearest / bilinear kernels are built for, with tables of exactly the
-// shape they assume on both axes: source index Q (o / P) + (o % P) Q / P and, for bilinear, fraction 0 where the phase lands
-// on a pixel ((o % P) Q % P == 0).
-bool HipUpscaler::ratio_shape(bool bilinear) const
-{
-    static const uint32_t kRatios[][2] = {{3, 2}, {4, 3}, {3, 1}, {4, 1}, {2, 1}, {5, 4}, {6, 5}, {5, 3}, {5, 2}, {7, 2}, {7, 5}};
-    for (const auto &r : kRatios) { // (x8/5: the table kernel is the faster one for nearest too, 5.6 against 5.8 us at 1080p)
-        const uint32_t P = r[0], Q = r[1];
-        if ((uint64_t)ow_ * Q != (uint64_t)iw_ * P || (uint64_t)oh_ * Q != (uint64_t)ih_ * P || iw_ % Q != 0 || ih_ % Q != 0) continue;
-        // bilinear at x5/2 and x7/2: five / seven lerped outputs from two input columns per lane leave the fixed-ratio kernel behind the
-        // table kernel (864p -> 4K: 11.7 against 10.6 us per frame, profiles/r05_nearest_bilinear_pq_ratios.txt); nearest gains at every factor
-        if (bilinear && Q == 2 && P >= 5) return false;
-        if (bilinear && Q == 5 && P >= 7) return false; // (nearest only: Q + 1 lerped rows of 4 P values do not fit the registers)
-        bool ok = true;
-        for (const AxisTables *t : {&tx_, &ty_})
-            for (uint32_t o = 0; ok && o < t->out_n; ++o) {
-                const uint32_t want = Q * (o / P) + (o % P) * Q / P;
-                ok = bilinear ? (t->bl_i0[o] == want && (((o % P) * Q) % P != 0 || t->bl_frac[o] == 0.0f)) : t->nn_src[o] == want;
-            }
-        return ok;
-    }
-    return false;
-}
-
-void HipUpscaler::choose_variant()
-{
-    const bool x2 = ow_ == 2 * iw_ && oh_ == 2 * ih_ && (iw_ % 4) == 0 && !force_general_;
-    switch (algorithm_) {
-    case Algorithm::Nearest:
-        variant_ = x2 ? Variant::NearestX2 : Variant::NearestTable;
-        if (!x2 && !force_general_ && ratio_shape(false)) variant_ = Variant::NearestRatio;
-        break;
-    case Algorithm::Bilinear: {
-        // The packed-integer x2 kernel is valid iff the CPU-form tables are exactly
-        // i0 = o>>1, frac = 0 / 0.5 (and frac 0 at the clamped last sample).
-        bool ok = x2 && !wgsl_bilinear_;
-        for (const AxisTables *t : {&tx_, &ty_}) {
-            for (uint32_t o = 0; ok && o < t->out_n; ++o) {
-                const bool last_odd = (o & 1) && (o >> 1) == t->in_n - 1;
-                const float want = (o & 1) && !last_odd ? 0.5f : 0.0f;
-                ok = t->bl_i0[o] == (o >> 1) && t->bl_frac[o] == want;
-            }
-        }
-        variant_ = ok ? Variant::BilinearX2Int : Variant::BilinearTable;
-        if (!ok && !wgsl_bilinear_ && !force_general_ && ratio_shape(true)) variant_ = Variant::BilinearRatio;
-        break;
-    }
-    case Algorithm::Lanczos3:
-    case Algorithm::Bicubic:
-    case Algorithm::Triangle: choose_resize_variant(x2); break;
-    case Algorithm::Fsr1:
-        // two kernels with the EASU image in HBM between them beat the fused LDS tile on real frames (1080p -> 4K: EASU 65.5 + RCAS rows
-        // 21.7 against 98.2 us fused; FAST 43.0 + 21.7 against 80.2): the tile's phases add up, the two launches overlap their own
-        variant_ = fsr_two_pass_ && (size_t)ow_ * oh_ * 4 >= ((size_t)1 << 20) ? Variant::Fsr1TwoPass : Variant::Fsr1Fused;
-        break;
-    case Algorithm::FsrEasu: variant_ = Variant::FsrEasu; break;
-    case Algorithm::FsrRcas: variant_ = Variant::FsrRcas; break;
-    }
-}
-
 int HipUpscaler::upload_tables()
 {
     for (void *p : table_allocs_) (void)hipFree(p);
@@ -511,6 +264,15 @@ int HipUpscaler::upload_tables()
     int rc = kOk;
 #define UP(vec, field)                                                                                   \
     if (rc == kOk) rc = up((vec).data(), (vec).size() * sizeof((vec)[0]), reinterpret_cast<const void **>(&dt_.field))
+    const std::vector<float> &wx6 = plan_.wx6, &wy6 = plan_.wy6;
+    // the horizontal weights of the first / last `n` output columns in frame form: the fixed-ratio kernels' edge-column passes
+    auto edge_frames = [&](uint32_t n) {
+        for (uint32_t q = 0; q < n; ++q)
+            for (int j = 0; j < 6; ++j) {
+                dt_.lz_wxs_left[q][j] = wx6[(size_t)q * 6 + j];
+                dt_.lz_wxs_right[q][j] = wx6[((size_t)ow_ - n + q) * 6 + j];
+            }
+    };
     switch (algorithm_) {
     case Algorithm::Nearest:
         UP(tx_.nn_src, nn_sx);
@@ -532,61 +294,49 @@ int HipUpscaler::upload_tables()
         UP(ty_.lz_ntaps, lz_ny);
         UP(ty_.lz_w, lz_wy);
         dt_.lz_stride = kResizeMaxTaps;
-        if (variant_ == Variant::ResizeDown) {
-            UP(down_rows_, lz_down_rows);
-            UP(down_done_, lz_down_done);
+        if (plan_.variant == Variant::ResizeDown) {
+            UP(plan_.down_rows, lz_down_rows);
+            UP(plan_.down_done, lz_down_done);
         }
-        if (variant_ == Variant::LanczosXsRegWin) {
-            UP(wy6_, lz_wy6);
-            if (!xs_cls_x_.empty()) {
-                UP(xs_cls_x_, lz_xs_cls_x);
-                UP(xs_cls_y_, lz_xs_cls_y);
-                UP(xs_wcls_x_, lz_xs_wcls_x);
-                UP(xs_wcls_y_, lz_xs_wcls_y);
+        if (plan_.variant == Variant::LanczosXsRegWin) {
+            UP(wy6, lz_wy6);
+            if (!plan_.xs_cls_x.empty()) {
+                UP(plan_.xs_cls_x, lz_xs_cls_x);
+                UP(plan_.xs_cls_y, lz_xs_cls_y);
+                UP(plan_.xs_wcls_x, lz_xs_wcls_x);
+                UP(plan_.xs_wcls_y, lz_xs_wcls_y);
             }
-            for (uint32_t p = 0; p < xs_factor_; ++p)
-                for (int j = 0; j < 6; ++j) dt_.lz_wxs[p][j] = wx6_[((size_t)8 * xs_factor_ + p) * 6 + j];
-            for (uint32_t q = 0; q < 4 * xs_factor_; ++q)
-                for (int j = 0; j < 6; ++j) {
-                    dt_.lz_wxs_left[q][j] = wx6_[(size_t)q * 6 + j];
-                    dt_.lz_wxs_right[q][j] = wx6_[((size_t)ow_ - 4 * xs_factor_ + q) * 6 + j];
-                }
+            for (uint32_t p = 0; p < plan_.xs_factor; ++p)
+                for (int j = 0; j < 6; ++j) dt_.lz_wxs[p][j] = wx6[((size_t)8 * plan_.xs_factor + p) * 6 + j];
+            edge_frames(4 * plan_.xs_factor);
         }
-        if (variant_ == Variant::LanczosR43RegWin) {
+        if (plan_.variant == Variant::LanczosR43RegWin) {
             for (uint32_t p = 0; p < 4; ++p)
-                for (int j = 0; j < 6; ++j) dt_.lz_wxs[p][j] = wx6_[((size_t)8 + p) * 6 + j];
-            for (uint32_t q = 0; q < 8; ++q)
-                for (int j = 0; j < 6; ++j) {
-                    dt_.lz_wxs_left[q][j] = wx6_[(size_t)q * 6 + j];
-                    dt_.lz_wxs_right[q][j] = wx6_[((size_t)ow_ - 8 + q) * 6 + j];
-                }
-            UP(wy6_, lz_wy6);
+                for (int j = 0; j < 6; ++j) dt_.lz_wxs[p][j] = wx6[((size_t)8 + p) * 6 + j];
+            edge_frames(8);
+            UP(wy6, lz_wy6);
         }
-        if (variant_ == Variant::LanczosPqRegWin) {
-            UP(wx6_, lz_wx6);
-            UP(wy6_, lz_wy6);
+        if (plan_.variant == Variant::LanczosPqRegWin) {
+            UP(wx6, lz_wx6);
+            UP(wy6, lz_wy6);
         }
-        if (variant_ == Variant::LanczosR32RegWin) {
-            for (uint32_t q = 0; q < 12; ++q)
-                for (int j = 0; j < 6; ++j) {
-                    dt_.lz_wxs_left[q][j] = wx6_[(size_t)q * 6 + j];
-                    dt_.lz_wxs_right[q][j] = wx6_[((size_t)ow_ - 12 + q) * 6 + j];
-                }
-            UP(wy6_, lz_wy6);
-            UP(xs_cls_x_, lz_xs_cls_x);
-            UP(xs_cls_y_, lz_xs_cls_y);
-            UP(xs_wcls_x_, lz_xs_wcls_x);
-            UP(xs_wcls_y_, lz_xs_wcls_y);
+        if (plan_.variant == Variant::LanczosR32RegWin) {
+            edge_frames(12);
+            UP(wy6, lz_wy6);
+            UP(plan_.xs_cls_x, lz_xs_cls_x);
+            UP(plan_.xs_cls_y, lz_xs_cls_y);
+            UP(plan_.xs_wcls_x, lz_xs_wcls_x);
+            UP(plan_.xs_wcls_y, lz_xs_wcls_y);
         }
-        if (variant_ == Variant::LanczosX2RegWin) {
-            UP(wy6_, lz_wy6);
+        if (plan_.variant == Variant::LanczosX2RegWin) {
+            UP(wy6, lz_wy6);
             for (int j = 0; j < 6; ++j) {
-                dt_.lz_wxe[j] = wx6_[(size_t)8 * 6 + j];
-                dt_.lz_wxo[j] = wx6_[(size_t)9 * 6 + j];
+                dt_.lz_wxe[j] = wx6[(size_t)8 * 6 + j];
+                dt_.lz_wxo[j] = wx6[(size_t)9 * 6 + j];
             }
             for (int i = 0; i < 48; ++i) {
-                dt_.lz_wx_left[i] = wx6_[i];
-                dt_.lz_wx_right[i] = wx6_[(size_t)(ow_ - 8) * 6 + i];
+                dt_.lz_wx_left[i] = wx6[i];
+                dt_.lz_wx_right[i] = wx6[(size_t)(ow_ - 8) * 6 + i];
             }
         }
         break;
@@ -612,21 +362,21 @@ int HipUpscaler::initialize(uint32_t in_w, uint32_t in_h, uint32_t out_w, uint32
     ih_ = in_h;
     ow_ = out_w;
     oh_ = out_h;
-    build_axis_tables(iw_, ow_, wgsl_bilinear_, tx_, resize_filter());
-    build_axis_tables(ih_, oh_, wgsl_bilinear_, ty_, resize_filter());
+    build_axis_tables(iw_, ow_, plan_opt_.wgsl_bilinear, tx_, resize_filter());
+    build_axis_tables(ih_, oh_, plan_opt_.wgsl_bilinear, ty_, resize_filter());
     if (is_resize() && (tx_.lz_max_taps < 0 || ty_.lz_max_taps < 0))
         return fail(kUnsupported, fmt("Lanczos-3 window exceeds %u taps for %ux%u -> %ux%u", kResizeMaxTaps, iw_, ih_, ow_, oh_));
     if (algorithm_ == Algorithm::FsrRcas && (iw_ != ow_ || ih_ != oh_))
         return fail(kInvalidArgument, "initialize: RCAS alone is a same-size pass (output size must equal input size)");
-    choose_variant();
+    plan_ = plan_kernels(algorithm_, plan_opt_, tx_, ty_);
     rc = upload_tables();
     if (rc != kOk) return rc;
-    if (variant_ == Variant::Fsr1TwoPass) { // the EASU images between the two passes: allocated here so that enqueue allocates nothing
+    if (plan_.variant == Variant::Fsr1TwoPass) { // the EASU images between the two passes: allocated here so that enqueue allocates nothing
         NUS_HIP(hipMalloc(reinterpret_cast<void **>(&fsr_scratch_), (size_t)kFsrScratchFrames * ow_ * oh_ * 4));
         NUS_HIP(hipEventCreateWithFlags(&ev_fsr_, hipEventDisableTiming));
         fsr_pending_ = false;
     }
-    if (variant_ == Variant::LanczosX2RegWin) { // the edge stream of enqueue(): made here so that enqueue allocates nothing
+    if (plan_.variant == Variant::LanczosX2RegWin) { // the edge stream of enqueue(): made here so that enqueue allocates nothing
         NUS_HIP(hipStreamCreateWithFlags(&s_edge_, hipStreamNonBlocking));
         NUS_HIP(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
         NUS_HIP(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming));
@@ -654,7 +404,7 @@ uint32_t HipUpscaler::lanczos_x2_rows_per_wave(uint32_t n_frames, bool unit) con
 
 uint32_t HipUpscaler::band_alignment(uint32_t n_frames) const
 {
-    switch (variant_) {
+    switch (plan_.variant) {
     case Variant::LanczosX2RegWin: return lanczos_x2_rows_per_wave(n_frames, false);
     case Variant::NearestX2:
     case Variant::BilinearX2Int: return 4;
@@ -665,6 +415,7 @@ uint32_t HipUpscaler::band_alignment(uint32_t n_frames) const
 int HipUpscaler::enqueue(const uint8_t *d_in, uint8_t *d_out, uint32_t n_frames, hipStream_t stream, const BlendSrc *blend,
                          const UnitDst *unit, uint32_t row0, uint32_t rows)
 {
+    const KernelPlan &P = plan_;
     UpscaleLaunch L;
     L.in = d_in;
     L.out = d_out;
@@ -701,28 +452,29 @@ int HipUpscaler::enqueue(const uint8_t *d_in, uint8_t *d_out, uint32_t n_frames,
     // (see below: the x2 resize kernels' edge-column pass of a batch runs beside the main kernel; the fork point is here, in
     // front of the main kernel's launch)
     constexpr uint32_t kEdgeBesideMinFrames = 8; // below that the event operations cost more than the pass
-    const bool beside = variant_ == Variant::LanczosX2RegWin && edge_stream_ && s_edge_ && ev_fork_ && ev_join_ &&
+    const bool beside = P.variant == Variant::LanczosX2RegWin && edge_stream_ && s_edge_ && ev_fork_ && ev_join_ &&
                         n_frames >= kEdgeBesideMinFrames;
     if (beside) {
         NUS_HIP(hipEventRecord(ev_fork_, stream));
         NUS_HIP(hipStreamWaitEvent(s_edge_, ev_fork_, 0));
     }
     hipError_t e = hipSuccess;
-    switch (variant_) {
+    const auto strips = [&](uint32_t cols) { return (iw_ + cols - 1) / cols; }; // of `cols` input columns, one wave each
+    switch (P.variant) {
     case Variant::NearestTable: e = launch_nearest_table(L, dt_); break;
     case Variant::NearestX2: e = launch_nearest_x2(L); break;
     case Variant::NearestRatio: e = launch_nearest_ratio(L); break;
-    case Variant::BilinearTable: e = launch_bilinear_table(L, dt_, wgsl_bilinear_); break;
+    case Variant::BilinearTable: e = launch_bilinear_table(L, dt_, plan_opt_.wgsl_bilinear); break;
     case Variant::BilinearX2Int: e = launch_bilinear_x2_int(L); break;
     case Variant::BilinearRatio: e = launch_bilinear_ratio(L, dt_); break;
     case Variant::LanczosGeneral: e = launch_lanczos_general(L, dt_, lanczos_exact_, 0); break;
     case Variant::ResizeWin:
-        e = launch_resize_win(L, dt_, lanczos_exact_, resize_ncols_max_, resize_union_taps_, win_outputs_per_lane_);
+        e = launch_resize_win(L, dt_, lanczos_exact_, P.ncols_max, P.union_taps, P.win_outputs_per_lane);
         break;
     case Variant::ResizeRows:
-        e = launch_resize_rows(L, dt_, lanczos_exact_, resize_ncols_max_, resize_small_taps_, resize_union_taps_);
+        e = launch_resize_rows(L, dt_, lanczos_exact_, P.ncols_max, P.small_taps, P.union_taps);
         break;
-    case Variant::ResizeDown: e = launch_resize_down(L, dt_, lanczos_exact_, resize_ncols_max_, tx_.lz_max_taps, down_seg_w_); break;
+    case Variant::ResizeDown: e = launch_resize_down(L, dt_, lanczos_exact_, P.ncols_max, tx_.lz_max_taps, P.down_seg_w); break;
     case Variant::FsrEasu: e = launch_fsr1(L, 0, easu_sharpness(), rcas_sharpness(), fsr_fast_); break;
     case Variant::FsrRcas: e = launch_fsr1(L, 1, easu_sharpness(), rcas_sharpness()); break;
     case Variant::Fsr1Fused: e = launch_fsr1(L, 2, easu_sharpness(), rcas_sharpness(), fsr_fast_); break;
@@ -752,62 +504,36 @@ int HipUpscaler::enqueue(const uint8_t *d_in, uint8_t *d_out, uint32_t n_frames,
         break;
     }
     case Variant::LanczosR43RegWin: {
-        uint32_t th = rows_per_wave_;
-        if (th == 0) { // as at x3/2: 24 - 36 rows per wave on a batch, equal row blocks (taller blocks: + 5 - 10 %)
-            const uint64_t rows_total = (uint64_t)ih_ * ((iw_ + 185) / 186) * n_frames;
-            uint64_t t = rows_total / 12288;
-            t = t < 12 ? 12 : (t > 36 ? 36 : t);
-            const uint64_t blocks = (ih_ + t - 1) / t;
-            th = (uint32_t)(((ih_ + blocks - 1) / blocks + 2) / 3 * 3);
-        }
+        // as at x3/2: 24 - 36 rows per wave on a batch, equal row blocks (taller blocks: + 5 - 10 %)
+        const uint32_t th = rows_per_wave_ ? rows_per_wave_ : equal_row_blocks(ih_, strips(186), n_frames, 12288, 12, 36, 3);
         e = launch_lanczos_r43(L, dt_, lanczos_exact_, th);
         if (e == hipSuccess) e = launch_lanczos_r43_edges(L, dt_, lanczos_exact_); // border columns
         break;
     }
     case Variant::LanczosPqRegWin: {
-        uint32_t th = rows_per_wave_;
-        if (th == 0) { // as at x4/3: 12 - 36 rows per wave on a batch, equal row blocks
-            const uint32_t cols = lanczos_pq_strip_cols(pq_p_, pq_q_);
-            const uint64_t rows_total = (uint64_t)ih_ * ((iw_ + cols - 1) / cols) * n_frames;
-            uint64_t t = rows_total / 12288;
-            t = t < 12 ? 12 : (t > 36 ? 36 : t);
-            const uint64_t blocks = (ih_ + t - 1) / t;
-            th = (uint32_t)(((ih_ + blocks - 1) / blocks + pq_q_ - 1) / pq_q_ * pq_q_);
-        }
-        if (lanczos_exact_ && pq_exact_fallback_) // (see choose_resize_variant)
-            e = launch_resize_win(L, dt_, true, resize_ncols_max_, resize_union_taps_, win_outputs_per_lane_);
+        // as at x4/3: 12 - 36 rows per wave on a batch, equal row blocks
+        const uint32_t th = rows_per_wave_ ? rows_per_wave_
+                                           : equal_row_blocks(ih_, strips(lanczos_pq_strip_cols(P.pq_p, P.pq_q)), n_frames, 12288, 12, 36, P.pq_q);
+        if (lanczos_exact_ && P.pq_exact_fallback) // (see plan_kernels)
+            e = launch_resize_win(L, dt_, true, P.ncols_max, P.union_taps, P.win_outputs_per_lane);
         else
-            e = launch_lanczos_pq(L, dt_, lanczos_exact_, pq_p_, pq_q_, th, pq_narrow_ && pq_narrow_allowed_);
+            e = launch_lanczos_pq(L, dt_, lanczos_exact_, P.pq_p, P.pq_q, th, P.pq_narrow && pq_narrow_allowed_);
         break;
     }
     case Variant::LanczosR32RegWin: {
-        uint32_t th = rows_per_wave_;
-        if (th == 0) {
-            // as at x2: enough waves to fill the chip (3 per SIMD) a few times over, tall enough to amortise the 8 halo rows; the
-            // kernel's time is flat from 24 to 96 rows per wave on a batch, so the row blocks are made equal rather than tall
-            // (a last block of a few rows costs more than anything else here: profiles/r03_lanczos_r32_rework_ab.txt)
-            const uint64_t rows_total = (uint64_t)ih_ * ((iw_ + 239) / 240) * n_frames;
-            uint64_t t = rows_total / 12288;
-            t = t < 12 ? 12 : (t > 48 ? 48 : t);
-            const uint64_t blocks = (ih_ + t - 1) / t;
-            th = (uint32_t)((ih_ + blocks - 1) / blocks + 1) & ~1u;
-        }
+        // as at x2: enough waves to fill the chip (3 per SIMD) a few times over, tall enough to amortise the 8 halo rows; the
+        // kernel's time is flat from 24 to 96 rows per wave on a batch, so the row blocks are made equal rather than tall
+        // (a last block of a few rows costs more than anything else here: profiles/r03_lanczos_r32_rework_ab.txt)
+        const uint32_t th = rows_per_wave_ ? rows_per_wave_ : equal_row_blocks(ih_, strips(240), n_frames, 12288, 12, 48, 2);
         e = launch_lanczos_r32(L, dt_, lanczos_exact_, th);
         if (e == hipSuccess) e = launch_lanczos_r32_edges(L, dt_, lanczos_exact_); // border columns
         break;
     }
-    case Variant::LanczosXsRegWin:
-    {
-        uint32_t th = rows_per_wave_;
-        if (th == 0) { // short, equal row blocks: 12 - 16 rows per wave measured best at x3 and x4 on batches (24 - 36: + 4 %)
-            const uint64_t rows_total = (uint64_t)ih_ * ((iw_ + kLanczosX2StripCols - 1) / kLanczosX2StripCols) * n_frames;
-            uint64_t t = rows_total / 16384;
-            t = t < 8 ? 8 : (t > 16 ? 16 : t);
-            const uint64_t blocks = (ih_ + t - 1) / t;
-            th = (uint32_t)((ih_ + blocks - 1) / blocks);
-        }
-        e = launch_lanczos_xs(L, dt_, lanczos_exact_, xs_factor_, th);
-        if (e == hipSuccess) e = launch_lanczos_xs_edges(L, dt_, lanczos_exact_, xs_factor_); // border columns
+    case Variant::LanczosXsRegWin: {
+        // short, equal row blocks: 12 - 16 rows per wave measured best at x3 and x4 on batches (24 - 36: + 4 %)
+        const uint32_t th = rows_per_wave_ ? rows_per_wave_ : equal_row_blocks(ih_, strips(kLanczosX2StripCols), n_frames, 16384, 8, 16, 1);
+        e = launch_lanczos_xs(L, dt_, lanczos_exact_, P.xs_factor, th);
+        if (e == hipSuccess) e = launch_lanczos_xs_edges(L, dt_, lanczos_exact_, P.xs_factor); // border columns
         break;
     }
     case Variant::LanczosX2RegWin: {
@@ -897,7 +623,7 @@ int HipUpscaler::upscale_blend_device(const void *d_a, size_t a_stride, const vo
 {
     std::lock_guard<std::mutex> lk(mu_);
     if (!initialized_) return fail(kNotInitialized, "Upscaler not initialized. Call initialize() first.");
-    if (variant_ != Variant::LanczosX2RegWin)
+    if (plan_.variant != Variant::LanczosX2RegWin)
         return fail(kUnsupported, "upscale_blend_device: only the exact-x2 resize kernels fuse the blend; "
                                   "run interpolate + upscale separately for this configuration");
     if (!d_a || !d_b || !d_out) return fail(kInvalidArgument, "upscale_blend_device: null device pointer");
@@ -920,7 +646,7 @@ int HipUpscaler::upscale_unit_device(const void *d_a, size_t a_stride, const voi
 {
     std::lock_guard<std::mutex> lk(mu_);
     if (!initialized_) return fail(kNotInitialized, "Upscaler not initialized. Call initialize() first.");
-    if (variant_ != Variant::LanczosX2RegWin)
+    if (plan_.variant != Variant::LanczosX2RegWin)
         return fail(kUnsupported, "upscale_unit_device: only the exact-x2 resize kernels run the whole step in one launch; "
                                   "run interpolate + upscale separately for this configuration");
     if (!d_a || !d_b || !d_out_real || !d_out_mid) return fail(kInvalidArgument, "upscale_unit_device: null device pointer");
@@ -1512,7 +1238,7 @@ int HipUpscaler::import_tables(const void *buf, size_t len)
     // every check has passed: only now replace the tables this upscaler runs on
     tx_ = std::move(x);
     ty_ = std::move(y);
-    choose_variant();
+    plan_ = plan_kernels(algorithm_, plan_opt_, tx_, ty_);
     const int rc = upload_tables();
     if (rc != kOk) initialized_ = false; // the device tables are gone: the upscaler must be initialised again
     return rc;

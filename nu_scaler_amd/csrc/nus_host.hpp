@@ -28,7 +28,7 @@
 
 namespace nus {
 
-enum class Algorithm : int { Nearest = 0, Bilinear = 1, Lanczos3 = 2, Bicubic = 3, Triangle = 4, Fsr1 = 5, FsrEasu = 6, FsrRcas = 7 };
+// (enum class Algorithm: nus_plan.hpp)
 enum class Quality : int { UltraPerformance = 0, Ultra, Quality, Balanced, Performance, Native };
 enum class Technology : int { None = 0, FSR, DLSS, Wgpu, Fallback };
 
@@ -100,7 +100,7 @@ public:
     size_t input_size() const { return initialized_ ? (size_t)iw_ * ih_ * 4 : 0; }
     size_t output_size() const { return initialized_ ? (size_t)ow_ * oh_ * 4 : 0; }
     bool last_gpu_ms(double *ms) const;
-    const char *kernel_variant() const { return variant_name(variant_); }
+    const char *kernel_variant() const { return variant_name(plan_.variant); }
 
     // Device-path kernel timing: with profiling on, every upscale_device() call brackets
     // its main kernel launch with a hipEvent pair on the caller's stream;
@@ -187,12 +187,6 @@ private:
     bool is_fsr() const { return algorithm_ == Algorithm::Fsr1 || algorithm_ == Algorithm::FsrEasu || algorithm_ == Algorithm::FsrRcas; }
     bool is_resize() const { return algorithm_ == Algorithm::Lanczos3 || algorithm_ == Algorithm::Bicubic || algorithm_ == Algorithm::Triangle; }
     ResizeFilter resize_filter() const;
-    void choose_variant();
-    bool ratio_shape(bool bilinear) const; // tables have the shape of the fixed-ratio nearest / bilinear kernels
-    void choose_resize_variant(bool x2);
-    void choose_general_resize_variant();
-    uint32_t widest_footprint(uint32_t segw) const;
-    uint32_t widest_union(uint32_t n) const;
     struct BlendSrc {
         const uint8_t *b = nullptr;
         size_t a_stride = 0, b_stride = 0;
@@ -208,43 +202,24 @@ private:
     Quality quality_;
     Algorithm algorithm_;
     int device_ = 0;
-    bool wgsl_bilinear_ = false;
+    PlanOptions plan_opt_; // what set_option / set_bilinear_variant ask of the kernel selection ...
+    KernelPlan plan_;      // ... and its answer for the tables below (plan_kernels: initialize, import_tables)
     bool lanczos_exact_ = false;
     bool fsr_fast_ = false;        // option "fsr_fast"
-    bool fsr_two_pass_ = true;     // option "fsr_two_pass": 0 keeps the fused LDS tile at every size
     // Fsr1TwoPass: kFsrScratchFrames EASU images (RGBA8, output size) between the two passes, and the event that keeps a second
     // batch of this handle (on whatever stream) from writing them before the first batch's RCAS has read them
     static constexpr uint32_t kFsrScratchFrames = 4;
     uint8_t *fsr_scratch_ = nullptr;
     hipEvent_t ev_fsr_ = nullptr;
     bool fsr_pending_ = false;
-    bool force_general_ = false;
-    bool force_per_pixel_ = false; // resize: never use the LDS row kernel
-    bool force_rows_ = false;      // resize: never use the register-window variant of it
-    uint32_t resize_ncols_max_ = 0; // LDS row length of the ResizeRows variant
-    uint32_t down_seg_w_ = 64;      // ResizeDown: output columns per wave (choose_resize_variant)
-    uint32_t down_seg_width_ = 0;   // option "down_seg_width": 0 = chosen by cost
-    std::vector<uint32_t> down_rows_; // ResizeDown: per-input-row slot weights + completion (build_down_stream_tables)
-    std::vector<int32_t> down_done_;
-    bool resize_small_taps_ = false;
-    uint32_t xs_factor_ = 0;         // 3 / 4 when the integer-factor register-window kernel is selected
-    uint32_t win_outputs_per_lane_ = 4; // register-window resize: 4, or 2 for factors below ~x1.4
-    uint32_t resize_union_taps_ = 0; // widest union of the tap windows of 4 adjacent outputs (0: unused)
     uint32_t rows_per_wave_ = 0; // 0: pick from the batch size
     uint32_t unit_order_ = 1;    // wave order of the unit launch: 0 frame-major, 1 row-block-major (option "unit_order")
     float easu_sharp_ = -1.0f, rcas_sharp_ = -1.0f; // < 0: derive from quality_
     int in_format_ = 0; // nus_pixel_format
     bool initialized_ = false;
     uint32_t iw_ = 0, ih_ = 0, ow_ = 0, oh_ = 0;
-    Variant variant_ = Variant::NearestTable;
     AxisTables tx_, ty_;
-    std::vector<float> wy6_, wx6_;
-    uint32_t pq_p_ = 0, pq_q_ = 0; // Variant::LanczosPqRegWin: the factor P / Q
-    bool pq_exact_fallback_ = false; // ... and whether its EXACT mode runs on the any-scale kernel instead (Q = 5)
-    bool pq_narrow_ = false;         // ... and whether every output's frame slots 0 and 5 are zero (a support-2 filter: 4-tap sums)
-    bool pq_narrow_allowed_ = true;  // option "pq_narrow"
-    std::vector<uint32_t> xs_cls_x_, xs_cls_y_; // x3: weight class per input index, and the classes' weights
-    std::vector<float> xs_wcls_x_, xs_wcls_y_;
+    bool pq_narrow_allowed_ = true; // option "pq_narrow"
     DeviceTables dt_;
     std::vector<void *> table_allocs_;
     Slot slots_[kSlots];

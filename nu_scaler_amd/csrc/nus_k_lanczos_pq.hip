@@ -3,12 +3,6 @@
 
 namespace nus {
 
-bool lanczos_pq_supported(uint32_t P, uint32_t Q)
-{
-    return (P == 5 && Q == 4) || (P == 6 && Q == 5) || (P == 5 && Q == 3) || (P == 5 && Q == 2) || (P == 7 && Q == 2) ||
-           (P == 7 && Q == 5) || (P == 8 && Q == 5) || (P == 9 && Q == 5);
-}
-
 uint32_t lanczos_pq_strip_cols(uint32_t P, uint32_t Q)
 {
     if (P == 5 && Q == 4) return PqGeom<5, 4>::kStripCols;

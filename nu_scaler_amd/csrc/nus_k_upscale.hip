@@ -494,31 +494,6 @@ __global__ __launch_bounds__(256) void k_bilinear_ratio(
     }
 }
 
-const char *variant_name(Variant v){
-    switch (v) {
-    case Variant::NearestTable: return "nearest_table";
-    case Variant::NearestX2: return "nearest_x2_vec16";
-    case Variant::NearestRatio: return "nearest_ratio";
-    case Variant::BilinearTable: return "bilinear_table_f32";
-    case Variant::BilinearX2Int: return "bilinear_x2_packed_u8";
-    case Variant::BilinearRatio: return "bilinear_ratio_f32";
-    case Variant::LanczosGeneral: return "lanczos3_general";
-    case Variant::ResizeRows: return "resize_rows_lds";
-    case Variant::ResizeWin: return "resize_regwin_lds";
-    case Variant::ResizeDown: return "resize_down_stream";
-    case Variant::LanczosX2RegWin: return "lanczos3_x2_regwin";
-    case Variant::LanczosXsRegWin: return "lanczos3_xs_regwin";
-    case Variant::LanczosR32RegWin: return "lanczos3_r32_regwin";
-    case Variant::LanczosR43RegWin: return "lanczos3_r43_regwin";
-    case Variant::LanczosPqRegWin: return "lanczos3_pq_regwin";
-    case Variant::FsrEasu: return "fsr1_easu_tile";
-    case Variant::FsrRcas: return "fsr1_rcas_rows";
-    case Variant::Fsr1Fused: return "fsr1_easu_rcas_fused_lds";
-    case Variant::Fsr1TwoPass: return "fsr1_easu_then_rcas_rows";
-    }
-    return "?";
-}
-
 namespace {
 // Output rows per wave of the row-walking table kernels: tall enough that the lerped / gathered source
 // rows get reused, small enough that the launch still has a few thousand waves.

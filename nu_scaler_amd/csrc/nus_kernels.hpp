@@ -7,6 +7,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "nus_plan.hpp" // Variant, variant_name(), lanczos_pq_supported(): the kernel selection, HIP-free
+
 namespace nus {
 
 // Device-side tables of one initialised upscaler (built on the host by nus_tables.cpp).
@@ -72,31 +74,6 @@ struct UpscaleLaunch {
     uint32_t row0 = 0, rows = 0;
 };
 
-// Kernel variants (chosen once at initialize).
-enum class Variant : int {
-    NearestTable = 0, // any scale, index tables
-    NearestX2,        // exact x2, 16-B loads/stores
-    NearestRatio,     // exact x3/2, x4/3, x3, x4: an input group per lane copied into P outputs, a row group into P rows
-    BilinearTable,    // any scale, f32, CPU or WGSL arithmetic
-    BilinearX2Int,    // exact x2, CPU arithmetic done in packed-u8 integer ops
-    BilinearRatio,    // exact x3/2, x4/3, x3, x4, CPU form: one input group per lane, P outputs, row groups
-    LanczosGeneral,   // any scale, direct separable evaluation per output pixel (fallback)
-    ResizeRows,       // any scale, separable: V pass into an LDS row, H pass out of it
-    ResizeWin,        // up-scaling: V pass from a register row window (as the x2 kernel), H pass through the LDS row
-    ResizeDown,       // down-scaling: input rows streamed once into the vertical sums of the 7 output rows in flight
-    LanczosX2RegWin,  // exact x2, register sliding window + wave shifts
-    LanczosXsRegWin,  // exact x3 / x4, same design with S output rows per input row
-    LanczosR32RegWin, // exact x3/2, same design: three output rows per pair of input rows
-    LanczosR43RegWin, // exact x4/3, same design: four output rows per group of three input rows
-    LanczosPqRegWin,  // x5/4, x6/5, x5/3, x5/2, same design: P output rows per group of Q input rows, weights from the tables
-    FsrEasu,          // FSR1-style EASU alone (any scale)
-    FsrRcas,          // FSR1-style RCAS alone (same size in and out)
-    Fsr1Fused,        // EASU tile (+1 px halo) in LDS, RCAS out of it
-    Fsr1TwoPass,      // EASU into a scratch image in HBM, the row-walking RCAS out of it (frames of >= 1 MiB: faster than the fused tile)
-};
-
-const char *variant_name(Variant v);
-
 hipError_t launch_nearest_table(const UpscaleLaunch &L, const DeviceTables &T);
 hipError_t launch_nearest_x2(const UpscaleLaunch &L);
 hipError_t launch_nearest_ratio(const UpscaleLaunch &L); // exact x3/2, x4/3, x3, x4 (host-checked table shape: source index Q (o / P) + (o % P) Q / P)
@@ -154,7 +131,6 @@ hipError_t launch_lanczos_r43(const UpscaleLaunch &L, const DeviceTables &T, boo
 hipError_t launch_lanczos_r43_edges(const UpscaleLaunch &L, const DeviceTables &T, bool exact);
 // x5/4, x6/5, x7/5, x8/5, x5/3, x5/2, x7/2 (Q ow == P iw, Q oh == P ih, iw % Q == 0, ih % Q == 0, ow % 4 == 0; T.lz_wx6 / T.lz_wy6: the tables in frame form,
 // nus_tables.hpp: lanczos_pq_phase_frame).  Writes every output column: no edge pass.
-bool lanczos_pq_supported(uint32_t P, uint32_t Q);
 uint32_t lanczos_pq_strip_cols(uint32_t P, uint32_t Q); // input columns per wave
 hipError_t launch_lanczos_pq(const UpscaleLaunch &L, const DeviceTables &T, bool exact, uint32_t P, uint32_t Q, uint32_t rows_per_wave,
                              bool narrow);

@@ -84,7 +84,7 @@ CASES = {
            ((372, 18), (620, 30), {}, "lanczos3_pq_regwin"), ((240, 30), (600, 75), {}, "lanczos3_pq_regwin"),
            ((248, 30), (868, 105), {}, "lanczos3_pq_regwin"), ((300, 20), (420, 28), {}, "lanczos3_pq_regwin"),
            ((315, 25), (504, 40), {}, "lanczos3_pq_regwin"), ((300, 20), (540, 36), {"rows_per_wave": 7}, "lanczos3_pq_regwin")],
-    # four output columns per lane at x4 and x10, two at x1.4 and x1.006 (widest_footprint / widest_union in nus_host.cpp)
+    # four output columns per lane at x4 and x10, two at x1.4 and x1.006 (widest_footprint / widest_union in nus_plan.cpp)
     "regwin_lds": [((250, 135), (1000, 540), {}, "resize_regwin_lds"), ((100, 37), (1000, 99), {}, "resize_regwin_lds"),
                    ((480, 270), (680, 384), {}, "resize_regwin_lds"), ((517, 40), (520, 41), {}, "resize_regwin_lds")],
     "rows_lds": [((50, 31), (127, 64), {}, "resize_rows_lds"), ((97, 13), (101, 29), {}, "resize_rows_lds"),

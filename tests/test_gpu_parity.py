@@ -628,6 +628,46 @@ def test_table_export_import_roundtrip(nsc, oracle_mod):
         u2.import_tables(nsc.build_tables_blob(64, 36, 96, 54))
 
 
+_PLAN_CASES = [  # one smallest-size case per variant family: (algorithm, (iw, ih), (ow, oh), the option of the fixture's option set)
+    ("lanczos3", (16, 16), (32, 32), None), ("lanczos3", (16, 16), (48, 48), None), ("lanczos3", (16, 16), (64, 64), None),
+    ("lanczos3", (32, 16), (48, 24), None), ("lanczos3", (48, 18), (64, 24), None), ("lanczos3", (32, 12), (40, 15), None),
+    ("bicubic", (32, 12), (40, 15), None),  # the same factor with a support-2 filter: pq_narrow_active
+    ("lanczos3", (100, 60), (237, 141), "force_general"), ("lanczos3", (100, 60), (237, 141), "force_rows"),
+    ("lanczos3", (32, 12), (48, 18), None),  # the register-window any-scale kernel, two outputs per lane
+    ("lanczos3", (64, 64), (32, 32), None), ("lanczos3", (100, 60), (237, 141), "force_per_pixel"),
+    ("nearest", (32, 12), (48, 18), None), ("bilinear", (32, 12), (48, 18), None)]
+
+
+@pytest.fixture(scope="module")
+def kernel_plan_fixture():
+    import json
+    with open(os.path.join(GOLDEN, "kernel_plan_parent.json")) as f:
+        doc = json.load(f)
+    return {c["id"]: dict(zip(doc["scalars"], c["s"]), variant=c["variant"]) for c in doc["cases"]}
+
+
+@pytest.mark.parametrize("alg,size,out,option", _PLAN_CASES)
+def test_handle_runs_the_recorded_kernel_plan(nsc, oracle_mod, kernel_plan_fixture, alg, size, out, option):
+    """The handle runs what plan_kernels() decides: after initialize() the kernel variant and the plan fields get_option reports are
+    those of tests/golden/kernel_plan_parent.json (the CPU test holds every field of every case to that file), and after
+    import_tables(export_tables()) -- the second selection on a live handle -- they are the same again and one seeded frame
+    comes out byte for byte as before."""
+    (w, h), (ow, oh) = size, out
+    want = kernel_plan_fixture[f"{alg} {w}x{h}->{ow}x{oh} {option or 'defaults'}"]
+    pq, win = want["variant"] == "lanczos3_pq_regwin", want["variant"] == "resize_regwin_lds"
+    want_options = {"pq_p": want["pq_p"] if pq else 0, "pq_q": want["pq_q"] if pq else 0,
+                    "pq_narrow_active": want["pq_narrow"] if pq else 0,
+                    "win_outputs_per_lane": want["win_outputs_per_lane"] if win else 0}
+    img = oracle_mod.gen_noise(w, h, 31)
+    before, u = _up(nsc, alg, img, ow, oh, options={option: 1} if option else {})
+    assert u.kernel_variant == want["variant"]
+    assert {k: u.get_option(k) for k in want_options} == want_options
+    u.import_tables(u.export_tables())
+    assert u.kernel_variant == want["variant"]
+    assert {k: u.get_option(k) for k in want_options} == want_options
+    assert u.upscale(img.tobytes()) == before.tobytes()
+
+
 # ---- device-resident batched path (what the bench times) -------------------------------
 
 def test_device_batch_path_matches_host_path(nsc, oracle_mod):

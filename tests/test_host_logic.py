@@ -475,6 +475,57 @@ def test_host_tables_and_queue_under_address_and_ub_sanitizers(tmp_path):
     assert run.returncode == 0 and "bad 0" in run.stdout and "runtime error" not in run.stderr, run.stdout + run.stderr
 
 
+def _kernel_plan_sources():
+    src_dir = os.path.join(ROOT, "nu_scaler_amd", "csrc")
+    return [os.path.join(ROOT, "tests", "c_abi", "kernel_plan_dump.cpp"), os.path.join(src_dir, "nus_plan.cpp"), os.path.join(src_dir, "nus_tables.cpp")]
+
+
+def test_kernel_plan_equals_the_recorded_selection(tmp_path):
+    """plan_kernels() (nus_plan.cpp: HIP-free, plain g++) gives, for every case of tests/c_abi/kernel_plan_dump.cpp -- six algorithms
+    x the workload's, the smallest-accepted, one-step-below and odd shapes x six option sets -- the decision recorded in
+    tests/golden/kernel_plan_parent.json from the HipUpscaler member functions it replaced: the variant, every scalar field, and the
+    length and CRC-32 of every vector, case by case and field by field, no case on either side left out.  The program itself
+    requires a plan to be the same on a second call and behind a call for another shape ("fresh bad 0"), and equal_row_blocks()
+    to equal the four computations it replaced in enqueue() over their shapes, batch sizes and every P/Q ("row_blocks ... bad 0")."""
+    import json
+    import shutil
+    import subprocess
+    if shutil.which("g++") is None:
+        pytest.skip("g++ not available")
+    exe = str(tmp_path / "kernel_plan_dump")
+    res = subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "nu_scaler_amd", "csrc"),
+                          *_kernel_plan_sources(), "-o", exe], capture_output=True, text=True)
+    assert res.returncode == 0 and "warning" not in res.stderr, res.stderr
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert run.returncode == 0 and "fresh bad 0" in run.stderr and "row_blocks compared 2772 bad 0" in run.stderr, run.stderr
+    got = json.loads(run.stdout)
+    with open(os.path.join(ROOT, "tests", "golden", "kernel_plan_parent.json")) as f:
+        want = json.load(f)
+    assert got["scalars"] == want["scalars"] and got["vectors"] == want["vectors"]
+    got_cases = {c["id"]: c for c in got["cases"]}
+    want_cases = {c["id"]: c for c in want["cases"]}
+    assert len(got_cases) == len(got["cases"]) == len(want["cases"]) == len(want_cases) == 6 * 6 * 45
+    assert sorted(got_cases) == sorted(want_cases)
+    for cid, w in want_cases.items():
+        g = got_cases[cid]
+        assert g["variant"] == w["variant"], cid
+        for name, a, b in zip(want["scalars"], g["s"], w["s"]):
+            assert a == b, (cid, name, a, b)
+        for name, a, b in zip(want["vectors"], g["v"], w["v"]):
+            assert a == b, (cid, name, "[length, crc32]", a, b)
+        assert len(g["s"]) == len(w["s"]) == len(want["scalars"]) and len(g["v"]) == len(w["v"]) == len(want["vectors"]), cid
+
+
+def test_kernel_plan_under_address_and_ub_sanitizers(tmp_path):
+    """The same program built with -fsanitize=address,undefined: every index the selection forms into the axis tables and the frame
+    weights, over all its cases, and a clean exit."""
+    import subprocess
+    exe = _sanitizer_build(tmp_path, "kernel_plan_asan", _kernel_plan_sources())
+    run = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, **_SAN_ENV), timeout=600)
+    assert run.returncode == 0 and "fresh bad 0" in run.stderr and "row_blocks compared 2772 bad 0" in run.stderr \
+        and "ERROR: AddressSanitizer" not in run.stderr and "runtime error" not in run.stderr, run.stderr
+
+
 def test_shared_argument_checks_under_address_and_ub_sanitizers(tmp_path):
     """nus_checks.cpp -- the argument checks the host entry points share -- swept over their boundary values (null and off-by-1/2/3
     pointers, strides and out_pair_stride around a frame, n_times and times at and past their ends, dimensions at each caller's
