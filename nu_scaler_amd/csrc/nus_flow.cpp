@@ -570,11 +570,6 @@ int HipFlowEstimator::solve_batch(const StreamJob &J, const Pyramid &g, const Fl
         NUS_HIP(fast_pyramid ? launch_pyramid_level_fast(P) : launch_pyramid_level(P, jacobi));
     }
     float *const out = reinterpret_cast<float *>(J.flows);
-    // the finest level's last launch warps the pairs itself where it can (HsWarp); R.warped says whether it did
-    // (not with several times, J.mt: the in-between frames then come from one multi-time warp launch behind the estimator)
-    HsWarp hw;
-    hw.frames = J.frames, hw.frame_stride = cells[0] * 4, hw.mid = J.mt ? nullptr : J.mid, hw.t = J.t, hw.sel = kSelRGBA;
-    hw.out_half = J.flow_half ? 1u : 0u;
     HsIterateResult R; // of the finest level
     // Rg16Float hand-off: only the FAST streamed kernel's last launch stores halves itself.  The caller's buffer (4 bytes per cell
     // then) may be handed to the solver only if that launch is what finishes level 0 -- every other kernel writes 2 x f32 per cell
@@ -603,7 +598,7 @@ int HipFlowEstimator::solve_batch(const StreamJob &J, const Pyramid &g, const Fl
         I.kernel = level_kernel(l);
         if (coarse) I.coarse = coarse_of(l);
         I.coarse.scale = 2.0f;
-        I.warp = l == 0 && (J.mid || J.flow_half) ? &hw : nullptr;
+        I.final_half = l == 0 && J.flow_half;
         HsIterateResult r;
         NUS_HIP(launch_hs_iterate(I, &r));
         f0 = r.flow, f1 = r.spare;
@@ -642,17 +637,15 @@ int HipFlowEstimator::solve_batch(const StreamJob &J, const Pyramid &g, const Fl
         std::swap(f0, f1);
         if (p.refine_iters > 0 && (rc = iterate(l, p.refine_iters, false, false)) != kOk) return rc;
     }
-    // Where the level's final flow is now, and in which format.  (After a launch that warped without storing its flow, f0 names a
-    // buffer nothing was written to: nobody reads it.)
+    // Where the level's final flow is now, and in which format
     const void *final_flow = f0;
-    const bool unstored = R.warped && J.mid && !out;
     if (!J.flow_half) {
-        if (out && f0 != out && !unstored) NUS_HIP(hipMemcpyAsync(out, f0, cells[0] * pairs * 8, hipMemcpyDeviceToDevice, stream));
+        if (out && f0 != out) NUS_HIP(hipMemcpyAsync(out, f0, cells[0] * pairs * 8, hipMemcpyDeviceToDevice, stream));
         if (out) final_flow = out;
     } else if (R.wrote_half) { // halves, in the caller's buffer if there is one (the launch wrote there), else in the workspace
-        if (out && f0 != out && !unstored) NUS_HIP(hipMemcpyAsync(out, f0, cells[0] * pairs * 4, hipMemcpyDeviceToDevice, stream));
+        if (out && f0 != out) NUS_HIP(hipMemcpyAsync(out, f0, cells[0] * pairs * 4, hipMemcpyDeviceToDevice, stream));
         if (out) final_flow = out;
-    } else if (!unstored) { // 2 x f32 per cell in the workspace (solver_out was null): converted into the caller's buffer, or beside it
+    } else { // 2 x f32 per cell in the workspace (solver_out was null): converted into the caller's buffer, or beside it
         void *dst = out;
         if (!dst) {
             if ((rc = reserve(cells[0] * pairs * 4, kFlowsHalf)) != kOk) return rc;
@@ -662,7 +655,7 @@ int HipFlowEstimator::solve_batch(const StreamJob &J, const Pyramid &g, const Fl
         final_flow = dst;
     }
     // the warp kernel behind the estimator, on the flow where it is (the caller's buffer, or the workspace)
-    if (J.mid && !R.warped) NUS_HIP(launch_warp_blend(warp_behind(J, final_flow)));
+    if (J.mid) NUS_HIP(launch_warp_blend(warp_behind(J, final_flow)));
     return kOk;
 }
 

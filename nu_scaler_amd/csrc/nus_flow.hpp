@@ -76,8 +76,8 @@ public:
     // The reference's intended interpolate() as ONE pipeline (wgpu_interpolator.rs:881-935: pyramid -> coarse flow -> warp): the
     // flows of estimate_device_stream AND the n_frames - 1 in-between frames at time t warped + blended with them (dense-flow warp
     // in FMA mode) into d_mid: the warp kernel runs behind the estimator on the flow where it is (the caller's buffer, or the
-    // workspace when d_flows == nullptr).  (NUS_HS_FUSED_WARP=1: the finest level's last Jacobi launch warps with the flow it has
-    // just finished instead -- HsWarp; same bytes, measured slower, off by default; tests/test_flow.py runs both.)
+    // workspace when d_flows == nullptr).  (The warp inside the finest level's last Jacobi launch, on the flow it has just finished,
+    // was built, measured and removed -- same bytes, slower; the code is in git at d74dcbc.)
     // flow_half: the flows between estimator and warp -- and at d_flows, if given -- as 2 x IEEE half per pixel (Rg16Float, the
     // reference's live flow layout: wgpu_interpolator.rs:276), each the f32 flow rounded to nearest even; the warp reads them as such.
     int interpolate_device_stream(const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t h, const FlowParams &p, float t,

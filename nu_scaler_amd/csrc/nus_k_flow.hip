@@ -1,6 +1,5 @@
 // nus_k_flow.hip -- optical-flow front end: Gaussian pyramid + Horn-Schunck.
 #include "nus_device.hpp"
-#include "nus_warp_device.hpp"
 #include <hip/hip_fp16.h>
 #include <algorithm>
 #include <cstdlib>
@@ -107,10 +106,7 @@ __global__ __launch_bounds__(256) void k_horn_schunck(const float4 *__restrict__
 // goes through exactly the arithmetic of k_blur<true>, k_blur<false> and k_downsample, so the
 // result is bit-identical to the three separate kernels while HBM sees the input once.
 constexpr int kPyrTW = 64, kPyrTH = 16;
-#ifndef NUS_PYR_THREADS
-#define NUS_PYR_THREADS 512
-#endif
-constexpr int kPyrThreads = NUS_PYR_THREADS; // 3 tiles per CU by LDS: twice the waves hide the LDS round trips of its phases
+constexpr int kPyrThreads = 512; // 3 tiles per CU by LDS: twice the waves hide the LDS round trips of its phases
 
 template <bool U8IN>
 __global__ __launch_bounds__(kPyrThreads) void k_pyramid_level(const void *__restrict__ in_all, size_t in_stride,
@@ -288,27 +284,22 @@ __device__ __forceinline__ float blur5_fast(float m2, float m1, float c0, float 
     return __builtin_fmaf(p2, W0, __builtin_fmaf(p1, W1, __builtin_fmaf(c0, W2, __builtin_fmaf(m1, W1, m2 * W0))));
 }
 
-#ifndef NUS_PYR_FAST_AHEAD
-#define NUS_PYR_FAST_AHEAD 2
-#endif
-#ifndef NUS_PYR_FAST_NT
-#define NUS_PYR_FAST_NT 0 // 1: the luminance plane leaves with non-temporal stores (measured, round 6: see the comment at the store)
-#endif
-#ifndef NUS_HS_FAST_NT
-#define NUS_HS_FAST_NT 0 // bit 0: the flow a launch writes leaves non-temporal; bit 1: the luminance rows and the input flow come in non-temporal
-#endif
+constexpr int kPyrFastAhead = 2; // rows in flight per lane
+// (Measured and dropped, round 6, all three as timing-only builds:
+//  * non-temporal stores of the luminance plane here, of the flow in k_hs_stream_fast, and non-temporal loads of that kernel's rows
+//    (profiles/r06_flow_nontemporal_ab.txt): the stores within the spread, -0.5 ... +0.4 us per 1080p pair; the loads cost 3 - 4 us;
+//  * this pass without level 0's luminance store, and k_hs_stream_fast with the instructions an in-kernel level-0 luminance costs at
+//    least (profiles/r06_flow_level0_luminance_in_jacobi_ablation.txt): the store costs 2.7 - 4.5 us per pair, the arithmetic that
+//    would replace it 4.4 - 5.8;
+//  * every lane writing, so that a wave's row segment is one aligned KiB -- wrong halo columns in lanes 0 and 63 (same file):
+//    -0.7 ... -1.5 us per pair before the two extra halo loads per row that a correct form needs.)
 template <bool U8IN>
 __global__ __launch_bounds__(256) void k_pyramid_fast(const void *__restrict__ in_all, size_t in_stride,
                                                       float *__restrict__ lum_all, size_t lum_stride,
                                                       float *__restrict__ next_all, size_t next_stride, int w, int h, int strips,
                                                       int row_blocks, int rows_per_block)
 {
-#if defined(NUS_ABLATE_PYR_ALIGNED_STRIPS) // timing-only dev build: every lane writes, a wave's row segment is one aligned KiB (the halo
-    // columns of lanes 0 and 63 are WRONG: they take their own values) -- what whole-line stores would be worth to this pass
-    constexpr int U = 4 * kWave, XOFF = 0;
-#else
-    constexpr int U = 4 * kWave - 8, XOFF = -4; // columns a wave writes
-#endif
+    constexpr int U = 4 * kWave - 8, XOFF = -4; // columns a wave writes; its first lane's columns are halo
     const int lane = threadIdx.x & (kWave - 1);
     const int g = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
     if (g >= strips * row_blocks) return;
@@ -318,7 +309,7 @@ __global__ __launch_bounds__(256) void k_pyramid_fast(const void *__restrict__ i
     float *level_lum = lum_all + blockIdx.y * lum_stride;
     float *next = next_all ? next_all + blockIdx.y * next_stride : nullptr;
     const int xa = strip * U + XOFF + 4 * lane; // this lane's first column (a multiple of 4)
-    const bool writer = XOFF == 0 || (lane >= 1 && lane <= kWave - 2);
+    const bool writer = lane >= 1 && lane <= kWave - 2;
     // vector-wide rows need all four columns inside the image (and the wave's other lanes too: wave-uniform choice)
     const bool plain = __builtin_amdgcn_readfirstlane((int)(strip * U + XOFF >= 0 && strip * U + XOFF + 4 * kWave <= w)) != 0;
     int cx[4];
@@ -363,7 +354,7 @@ __global__ __launch_bounds__(256) void k_pyramid_fast(const void *__restrict__ i
     };
     float hb[5][4];  // H-blurred rows r-4 .. r of the lane's four columns (slots rotate with the row)
     float keep[4] = {0.0f, 0.0f, 0.0f, 0.0f}; // the blurred even row of a 2x2 block, until its odd row is there
-    constexpr int AH = NUS_PYR_FAST_AHEAD; // rows in flight per lane
+    constexpr int AH = kPyrFastAhead;
     Raw nx[AH];
 #pragma unroll
     for (int d = 0; d < AH; ++d) nx[d] = fetch(y0 - 2 + d);
@@ -391,22 +382,10 @@ __global__ __launch_bounds__(256) void k_pyramid_fast(const void *__restrict__ i
 #pragma unroll
         for (int i = 0; i < 4; ++i)
             v[i] = blur5_fast(hb[(P + 1) % 5][i], hb[(P + 2) % 5][i], hb[(P + 3) % 5][i], hb[(P + 4) % 5][i], hb[P][i]);
-#if defined(NUS_ABLATE_PYR_NO_LUM0_STORE) // timing-only dev build (profiles/r06_flow_level0_luminance_in_jacobi_ablation.txt): the level-0
-        // pass without its luminance-plane store -- the most a Jacobi kernel that forms level 0's luminance itself could save here
-        if (writer && !U8IN) {
-#else
         if (writer) {
-#endif
             float *dst = level_lum + (size_t)y * w;
             if (plain) {
-#if NUS_PYR_FAST_NT // the plane is read again only after the coarser levels have been solved: nothing to keep in the caches
-                typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
-                f32x4_a4 q;
-                q.x = v[0], q.y = v[1], q.z = v[2], q.w = v[3];
-                __builtin_nontemporal_store(q, reinterpret_cast<f32x4_a4 *>(dst + xa));
-#else
                 dst[xa] = v[0], dst[xa + 1] = v[1], dst[xa + 2] = v[2], dst[xa + 3] = v[3]; // (merged into one 16-byte store where aligned)
-#endif
             } else {
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
@@ -786,21 +765,7 @@ __global__ __launch_bounds__(256) void k_hs_stream(const float *__restrict__ coe
 // ~22 f32 operations + 9 register moves per cell and step where the exact kernel has ~60.  Contract (tests/test_flow.py): the
 // flow of the full estimator within 1e-3 px of orc_flow_estimate's at 1080p, the frame interpolated with it within 1 LSB and
 // on < 0.1 % of the samples different.  Always takes the derivatives from the luminance planes (LUM of k_hs_stream).
-#ifndef NUS_HS_FAST_AHEAD
-#define NUS_HS_FAST_AHEAD 2 // passes between a row's request and its use in k_hs_stream_fast
-#endif
-typedef float f32x2_nt __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void nt_store_f2(float2 v, float2 *p)
-{
-    f32x2_nt q;
-    q.x = v.x, q.y = v.y;
-    __builtin_nontemporal_store(q, reinterpret_cast<f32x2_nt *>(p));
-}
-__device__ __forceinline__ float2 nt_load_f2(const float2 *p)
-{
-    const f32x2_nt q = __builtin_nontemporal_load(reinterpret_cast<const f32x2_nt *>(p));
-    return make_float2(q.x, q.y);
-}
+constexpr int kHsFastAhead = 2; // passes between a row's request and its use in k_hs_stream_fast
 struct HsFastCoef {
     float ix, iy, it, gx, gy;
 };
@@ -812,28 +777,29 @@ struct HsFastCoef {
 // of 3 for the three-row rings, >= K + 1 for the delay line, >= 5 for the luminance rows t-1 .. t+3) and 9 rows for K = 6 .. 8, so the
 // pass is instantiated R times (x 2: steady / fill-and-drain) as one straight-line turn of the rings: no value ever changes
 // register.  Same operations on the same operands in the same order: bit-identical flows (tests/test_flow.py runs both forms).
-// K > 8 keeps the shifting form (12 copies of a ten-step pass would not fit the instruction cache).
-#ifndef NUS_HS_FAST_RING
-#define NUS_HS_FAST_RING 1
-#endif
-#ifndef NUS_HS_FAST_INNER_STRIPS
-#define NUS_HS_FAST_INNER_STRIPS 0 // dev macro: 1 = strips that touch no image border run a copy of the pass without the clamp's selects
-                                   // (22 of ~100 VALU instructions of a 5-step pass).  Measured, round 5: identical flows, 110 / 126 / 140 VGPRs
-                                   // instead of 95 / 108 / 122 (one wave per SIMD fewer), 42.1 - 42.8 us per 1080p pair against 41.7 - 42.3: not kept
-#endif
-#ifndef NUS_HS_FAST_RING_MAXK
-#define NUS_HS_FAST_RING_MAXK 8 // launches of up to this many steps take the ring form
-#endif
-// WARP (round 5, ring form only): the launch that finishes the finest level's flow also warps + blends the pair's two frames with it
-// (warp_blend_pixel<kWarpFma>, the very code of k_warp_blend_flow) and stores the in-between pixel; the flow itself is stored only
-// if the caller wants it (fout_all != nullptr).  Saves the flow's way through HBM to a separate warp launch (33 MB per 1080p pair).
-template <int K, bool UPS, bool RING = false, bool WARP = false>
+// The product runs the ring form alone; the shifting form stays as what the test holds it to.
+//
+// out_half (wave-uniform): the launch stores its flow as 2 x IEEE half per cell (round to nearest even) instead of 2 x f32 -- the
+// level's final flow as Rg16Float (HsIterateLaunch::final_half).
+//
+// (Measured and dropped; the code is in git at d74dcbc:
+//  * round 5, the warp fused into the finest level's last launch -- warp_blend_pixel<kWarpFma> on the flow a pass has just finished,
+//    the flow stored only for a caller who asks: identical bytes, but 23 us per 1080p pair where the plain launch and the warp kernel
+//    take 12.2 + 7.9.  The pass has one pixel per lane, so the warp's gathers are 8-byte loads at a 4-byte lane stride, and its ~140
+//    instructions per pixel run at four waves per SIMD (119 VGPRs) next to a pass that was at the memory rate; motion step 21.0
+//    against 20.1 ms per 300 units (profiles/r05_motion_step_warp_in_last_jacobi_launch_ab.txt).
+//  * round 5, a copy of the pass without the clamp's selects for strips that touch no image border (22 of ~100 VALU instructions of a
+//    5-step pass): identical flows, 110 / 126 / 140 VGPRs instead of 95 / 108 / 122 (one wave per SIMD fewer), 42.1 - 42.8 us per
+//    1080p pair against 41.7 - 42.3 (docs/flow_front_end.md, round 5).
+//  * round 6, the flow BETWEEN the finest level's two launches as halves: -0.1 ... -0.3 ms per 300-unit step, but the error injected
+//    half-way through the level's steps grows with the flow (profiles/r06_flow_level0_half_between_launches.txt).)
+constexpr int kHsFastRingMaxK = 8; // launches of up to this many steps have a ring form (R = 6 or 9)
+template <int K, bool UPS, bool RING>
 __global__ __launch_bounds__(256) void k_hs_stream_fast(const float *__restrict__ lum_all, size_t lum_stride, float lambda,
                                                         const float2 *__restrict__ fin_all, size_t fin_stride,
                                                         float2 *__restrict__ fout_all, size_t fout_stride, int w, int h, int strips,
-                                                        int row_blocks, int rows_per_block, HsCoarse coarse, HsWarp warp)
+                                                        int row_blocks, int rows_per_block, HsCoarse coarse, uint32_t out_half)
 {
-    static_assert(!WARP || (RING && !UPS), "WARP: the ring form of a launch that continues a full-resolution flow");
     constexpr int U = kWave - 2 * K; // columns a wave writes
     const int lane = threadIdx.x & (kWave - 1);
     const int g = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)); // wave-uniform, in an SGPR
@@ -842,23 +808,13 @@ __global__ __launch_bounds__(256) void k_hs_stream_fast(const float *__restrict_
     const float *lum1 = lum_all + blockIdx.y * lum_stride; // frame 1's plane; frame 2's follows lum_stride floats further on
     const float2 *fin = fin_all ? fin_all + blockIdx.y * fin_stride : nullptr; // null = start from zero flow
     float2 *fout = fout_all + blockIdx.y * fout_stride;
-    // WARP: the pair's frames through buffer resources (32-bit offsets: frames < 4 GiB, host-checked), per-lane copies of the constants
-    const uint32_t wframe_bytes = (uint32_t)w * (uint32_t)h * 4u;
-    const uint8_t *wfa = WARP ? warp.frames + (size_t)blockIdx.y * warp.frame_stride : nullptr;
-    const __amdgpu_buffer_rsrc_t wra = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(wfa), 0, WARP ? wframe_bytes : 0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wrb = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint8_t *>(WARP ? wfa + warp.frame_stride : nullptr), 0, WARP ? wframe_bytes : 0u, 0x00020000);
-    uint32_t *wmid = WARP ? reinterpret_cast<uint32_t *>(warp.mid) + (size_t)blockIdx.y * (size_t)w * h : nullptr;
-    float wtv = warp.t, wwmax = (float)(w - 1), whmax = (float)(h - 1);
-    if constexpr (WARP) asm volatile("" : "+v"(wtv), "+v"(wwmax), "+v"(whmax));
-    const float wnt = 1.0f - wtv;
     const int x = strip * U - K + lane, xc = clampi(x, 0, w - 1);
     const bool self_l = x <= 0, self_r = x >= w - 1;
     const bool writer = lane >= K && lane < kWave - K && x < w;
     const int y0 = rb * rows_per_block, y1 = min(y0 + rows_per_block, h);
     const int lo = max(y0 - K, 0), hi = min(y1 + K, h);
 
-    static_assert(!RING || K <= 8, "the ring form is instantiated for K <= 8 (R = 6 or 9)");
+    static_assert(!RING || K <= kHsFastRingMaxK, "the ring form is instantiated for K <= 8 (R = 6 or 9)");
     constexpr int R = K <= 5 ? 6 : 9; // RING: passes per turn of every ring
     float2 a1[RING ? 1 : K], a2[RING ? 1 : K]; // level j: its rows r-1 and r-2 (this lane's column)
     HsFastCoef cf[RING ? 1 : K + 1];           // cf[d]: coefficients of row t - d (cf[0] is only the way in)
@@ -867,11 +823,6 @@ __global__ __launch_bounds__(256) void k_hs_stream_fast(const float *__restrict_
     float l1r[RING ? R : 1];                   // RING: frame 1's rows t-1 .. t+3 in slots (row - lo) mod R
     float q2r[3];                              // RING: frame 2's rows t .. t+2
     float2 qfr[3];                             // RING: the input flow's rows t .. t+2 (not UPS)
-#if defined(NUS_ABLATE_HS_LUM0_COST)
-    float abl_ring[2][R];
-#pragma unroll
-    for (int i = 0; i < R; ++i) abl_ring[0][i] = abl_ring[1][i] = 0.0f;
-#endif
 
     // UPS: the level starts from the coarser level's flow, sampled as flow_upsample.wgsl:27-36 samples it (linear, clamp to edge,
     // texel space) while it is loaded.  The column part of the sample position is this lane's for the whole launch (the shader's own
@@ -926,24 +877,12 @@ __global__ __launch_bounds__(256) void k_hs_stream_fast(const float *__restrict_
         return make_float2(__builtin_fmaf(fy, hb.x - top.x, top.x) * coarse.scale, __builtin_fmaf(fy, hb.y - top.y, top.y) * coarse.scale);
     };
     auto load_flow = [&](int r) -> float2 {
-        if constexpr (UPS) {
-#if defined(NUS_HS_FAST_UPS_EXACT) // dev macro: the shader's own expressions (bisecting)
-            return flow_upsample_cell(csrc, coarse.w, coarse.h, xc, min(r, hi - 1), w, h, coarse.scale);
-#else
-            return upsampled_row(r);
-#endif
-        } else {
-            if (warp.in_half) { // (wave-uniform) the previous launch of this level stored halves
-                const __half2 hv = reinterpret_cast<const __half2 *>(fin_all)[blockIdx.y * fin_stride + (size_t)min(r, hi - 1) * w + xc];
-                return __half22float2(hv);
-            }
-            if (NUS_HS_FAST_NT & 2) return fin ? nt_load_f2(&fin[(size_t)min(r, hi - 1) * w + xc]) : make_float2(0.0f, 0.0f);
-            return fin ? fin[(size_t)min(r, hi - 1) * w + xc] : make_float2(0.0f, 0.0f);
-        }
+        if constexpr (UPS) return upsampled_row(r);
+        else return fin ? fin[(size_t)min(r, hi - 1) * w + xc] : make_float2(0.0f, 0.0f);
     };
-    // rows are requested NUS_HS_FAST_AHEAD passes before they are used: a FAST pass is short (~120 instructions), and with one row
+    // rows are requested kHsFastAhead passes before they are used: a FAST pass is short (~120 instructions), and with one row
     // in flight per wave the launch was bound by memory latency, not by bandwidth or instruction issue
-    constexpr int AH = NUS_HS_FAST_AHEAD;
+    constexpr int AH = kHsFastAhead;
     float2 qf[AH]; // (UPS: unused -- the upsampled row comes out of registers when it is due, see upsampled_row)
     float q1[AH], q2[AH]; // q*[d]: row t + d's flow, frame 1's row t + d + 1, frame 2's row t + d (d = 0: this pass's)
 #pragma unroll
@@ -955,18 +894,14 @@ __global__ __launch_bounds__(256) void k_hs_stream_fast(const float *__restrict_
     float l1_above = lum1[(size_t)clampi(lo - 1, 0, h - 1) * w + xc], l1_row = lum1[(size_t)lo * w + xc]; // frame 1, rows t - 1, t
     const float ninth = 1.0f / 9.0f;
     if constexpr (RING) {
-        static_assert(!RING || NUS_HS_FAST_AHEAD == 2, "the ring form keeps rows t .. t+2 in three-slot rings");
+        static_assert(AH == 2, "the ring form keeps rows t .. t+2 in three-slot rings");
         l1r[R - 1] = l1_above, l1r[0] = l1_row, l1r[1] = q1[0], l1r[2] = q1[1];
         q2r[0] = q2[0], q2r[1] = q2[1];
         if constexpr (!UPS) qfr[0] = qf[0], qfr[1] = qf[1];
     }
     // One pass in ring form, phase P = (t - lo) mod R (compile time)
-    auto ring_pass = [&](int t, auto steady_tag, auto phase_tag, auto border_tag) __attribute__((always_inline)) {
+    auto ring_pass = [&](int t, auto steady_tag, auto phase_tag) __attribute__((always_inline)) {
         constexpr bool STEADY = decltype(steady_tag)::value;
-        // BORDER = false: a strip all of whose 64 columns lie strictly inside the image (every strip but the first and the last) --
-        // no lane's neighbour is the lane itself, the selects that implement the shader's clamp drop out of the pass
-        constexpr bool BORDER = decltype(border_tag)::value;
-        const bool sl = BORDER && self_l, sr = BORDER && self_r;
         constexpr int P = decltype(phase_tag)::value;
         float2 nf;
         if constexpr (UPS) nf = load_flow(t);
@@ -974,38 +909,12 @@ __global__ __launch_bounds__(256) void k_hs_stream_fast(const float *__restrict_
             nf = qfr[P % 3];
             qfr[(P + 2) % 3] = load_flow(t + 2); // in flight during this pass and the next
         }
-#if defined(NUS_ABLATE_HS_LUM0_COST) // timing-only dev build (same file): per pass and frame, the instructions an in-kernel level-0
-        // luminance costs at least -- RGBA8 -> luminance (3 converts, 2 adds, 1 multiply), the two halo columns per side from the
-        // neighbouring lanes (4 DPP moves), the 5-tap row blur, a ring of blurred rows and the 5-tap column blur -- run on values
-        // that have already arrived and folded into them as + 0 * result (IEEE: not removable; the flows stay the same).  Not
-        // counted: the 4 extra halo lanes per wave such a kernel needs (U = 50 instead of 54 columns at K = 5).
-        float row = l1r[P % R];
-        const float above = l1r[(P + R - 1) % R], n1 = l1r[(P + 1) % R];
-        float n2 = q2r[P % 3];
-        if (w > 1000) { // (wave-uniform: level 0 of a 1080p stream only)
-            auto cost = [&](float v, float (&ring)[R]) {
-                const uint32_t p = __float_as_uint(v);
-                const float l = ((ch_f32(p, 0) + ch_f32(p, 1)) + ch_f32(p, 2)) * (0.33333f / 255.0f);
-                const float m1 = wave_up(l), p1 = wave_down(l), m2 = wave_up(m1), p2 = wave_down(p1);
-                ring[P % R] = blur5_fast(m2, m1, l, p1, p2);
-                return blur5_fast(ring[(P + 1) % R], ring[(P + 2) % R], ring[(P + 3) % R], ring[(P + 4) % R], ring[P % R]);
-            };
-            row = __builtin_fmaf(0.0f, cost(row, abl_ring[0]), row);
-            n2 = __builtin_fmaf(0.0f, cost(n2, abl_ring[1]), n2);
-        }
-#else
         const float row = l1r[P % R], above = l1r[(P + R - 1) % R], n1 = l1r[(P + 1) % R], n2 = q2r[P % 3];
-#endif
-        if (NUS_HS_FAST_NT & 2) {
-            l1r[(P + 3) % R] = __builtin_nontemporal_load(&lum1[(size_t)clampi(t + 3, 0, h - 1) * w + xc]);
-            q2r[(P + 2) % 3] = __builtin_nontemporal_load(&lum1[lum_stride + (size_t)clampi(t + 2, 0, h - 1) * w + xc]);
-        } else {
-            l1r[(P + 3) % R] = lum1[(size_t)clampi(t + 3, 0, h - 1) * w + xc];
-            q2r[(P + 2) % 3] = lum1[lum_stride + (size_t)clampi(t + 2, 0, h - 1) * w + xc];
-        }
+        l1r[(P + 3) % R] = lum1[(size_t)clampi(t + 3, 0, h - 1) * w + xc];
+        q2r[(P + 2) % 3] = lum1[lum_stride + (size_t)clampi(t + 2, 0, h - 1) * w + xc];
         {
             const float left = wave_up(row), right = wave_down(row);
-            const float ix = ((sr ? row : right) - (sl ? row : left)) * 0.5f;
+            const float ix = ((self_r ? row : right) - (self_l ? row : left)) * 0.5f;
             const float iy = (n1 - above) * 0.5f;
             const float it = n2 - row;
             const float rinv = __builtin_amdgcn_rcpf(__builtin_fmaf(iy, iy, __builtin_fmaf(ix, ix, lambda)));
@@ -1028,8 +937,8 @@ __global__ __launch_bounds__(256) void k_hs_stream_fast(const float *__restrict_
             }
             const float su = (ar[j][s2].x + ar[j][s1].x) + arr.x, sv = (ar[j][s2].y + ar[j][s1].y) + arr.y;
             const float lu = wave_up(su), ru = wave_down(su), lv = wave_up(sv), rv = wave_down(sv);
-            const float ua = (((sl ? su : lu) + su) + (sr ? su : ru)) * ninth;
-            const float va = (((sl ? sv : lv) + sv) + (sr ? sv : rv)) * ninth;
+            const float ua = (((self_l ? su : lu) + su) + (self_r ? su : ru)) * ninth;
+            const float va = (((self_l ? sv : lv) + sv) + (self_r ? sv : rv)) * ninth;
             const HsFastCoef c = cfr[(P - j - 1 + kBig) % R]; // row r-1 entered j+1 passes ago
             const float num = __builtin_fmaf(c.ix, ua, __builtin_fmaf(c.iy, va, c.it));
             ar[j][s0] = arr; // the arriving row takes the slot of row r-3, which nothing reads any more
@@ -1037,53 +946,36 @@ __global__ __launch_bounds__(256) void k_hs_stream_fast(const float *__restrict_
             if (j == K - 1) {
                 const int y = r - 1;
                 if (y >= y0 && y < y1 && writer) {
-                    if (!WARP || fout_all != nullptr) {
-                        if (warp.out_half) // (wave-uniform) the level's final flow as Rg16Float
-                            reinterpret_cast<__half2 *>(fout_all)[blockIdx.y * fout_stride + (size_t)y * w + x] = __floats2half2_rn(arr.x, arr.y);
-                        else if (NUS_HS_FAST_NT & 1)
-                            nt_store_f2(arr, &fout[(size_t)y * w + x]);
-                        else
-                            fout[(size_t)y * w + x] = arr;
-                    }
-                    if constexpr (WARP) {
-                        const uint32_t p = warp_blend_pixel<kWarpFma>(wra, wrb, (uint32_t)w * 4u, wwmax, whmax, (uint32_t)w - 2u, (uint32_t)h - 2u,
-                                                                      (float)x, (float)y, arr, wtv, wnt);
-                        wmid[(size_t)y * w + x] = swz(p, warp.sel);
-                    }
+                    if (out_half)
+                        reinterpret_cast<__half2 *>(fout_all)[blockIdx.y * fout_stride + (size_t)y * w + x] = __floats2half2_rn(arr.x, arr.y);
+                    else
+                        fout[(size_t)y * w + x] = arr;
                 }
             }
         }
     };
     // A whole turn of the rings (R passes) as straight-line code: every value keeps its register across the loop's back edge.
-    auto ring_turn = [&](int t, auto steady_tag, auto border_tag) __attribute__((always_inline)) {
-        ring_pass(t, steady_tag, std::integral_constant<int, 0>{}, border_tag);
-        ring_pass(t + 1, steady_tag, std::integral_constant<int, 1>{}, border_tag);
-        ring_pass(t + 2, steady_tag, std::integral_constant<int, 2>{}, border_tag);
-        ring_pass(t + 3, steady_tag, std::integral_constant<int, 3>{}, border_tag);
-        ring_pass(t + 4, steady_tag, std::integral_constant<int, 4>{}, border_tag);
-        ring_pass(t + 5, steady_tag, std::integral_constant<int, 5>{}, border_tag);
+    auto ring_turn = [&](int t, auto steady_tag) __attribute__((always_inline)) {
+        ring_pass(t, steady_tag, std::integral_constant<int, 0>{});
+        ring_pass(t + 1, steady_tag, std::integral_constant<int, 1>{});
+        ring_pass(t + 2, steady_tag, std::integral_constant<int, 2>{});
+        ring_pass(t + 3, steady_tag, std::integral_constant<int, 3>{});
+        ring_pass(t + 4, steady_tag, std::integral_constant<int, 4>{});
+        ring_pass(t + 5, steady_tag, std::integral_constant<int, 5>{});
         if constexpr (R == 9) {
-            ring_pass(t + 6, steady_tag, std::integral_constant<int, 6>{}, border_tag);
-            ring_pass(t + 7, steady_tag, std::integral_constant<int, 7>{}, border_tag);
-            ring_pass(t + 8, steady_tag, std::integral_constant<int, 8>{}, border_tag);
+            ring_pass(t + 6, steady_tag, std::integral_constant<int, 6>{});
+            ring_pass(t + 7, steady_tag, std::integral_constant<int, 7>{});
+            ring_pass(t + 8, steady_tag, std::integral_constant<int, 8>{});
         }
     };
     if constexpr (RING) {
         // the first turn fills the pipeline (K <= R - 1 passes of it) and the turns from the first one that reaches row hi on drain it:
         // the general form of the pass, whose levels look at their row number (passes past hi + K find nothing to do); all turns in
         // between are steady
-        auto walk = [&](auto border_tag) __attribute__((always_inline)) {
-            int t = lo;
-            ring_turn(t, std::false_type{}, border_tag);
-            for (t += R; t + R <= hi; t += R) ring_turn(t, std::true_type{}, border_tag);
-            for (; t < hi + K; t += R) ring_turn(t, std::false_type{}, border_tag);
-        };
-#if NUS_HS_FAST_INNER_STRIPS
-        const bool inner = strip * U - K > 0 && strip * U - K + (kWave - 1) < w - 1; // wave-uniform
-        if (inner) walk(std::false_type{});
-        else
-#endif
-            walk(std::true_type{});
+        int t = lo;
+        ring_turn(t, std::false_type{});
+        for (t += R; t + R <= hi; t += R) ring_turn(t, std::true_type{});
+        for (; t < hi + K; t += R) ring_turn(t, std::false_type{});
         return;
     }
 
@@ -1129,7 +1021,7 @@ __global__ __launch_bounds__(256) void k_hs_stream_fast(const float *__restrict_
             if (j == K - 1) {
                 const int y = r - 1;
                 if (y >= y0 && y < y1 && writer) {
-                    if (warp.out_half)
+                    if (out_half)
                         reinterpret_cast<__half2 *>(fout_all)[blockIdx.y * fout_stride + (size_t)y * w + x] = __floats2half2_rn(arr.x, arr.y);
                     else
                         fout[(size_t)y * w + x] = arr;
@@ -1264,26 +1156,17 @@ hipError_t launch_horn_schunck(const float *i1, const float *i2, const float *fl
 // The launchers below take a batch (FlowImages, nus_kernels.hpp).
 // One fused pyramid level: `in` is RGBA8 (u8_input) or f32 RGBA; writes the level's luminance plane
 // (w*h floats) and the f32 RGBA input of the next level; `next` may be null (last level).
-#ifndef NUS_PYR_STREAM_WAVES
-#define NUS_PYR_STREAM_WAVES 8192 // waves a launch of the streamed pyramid kernel aims for
-#endif
-#ifndef NUS_PYR_STREAM_MIN_ROWS
-#define NUS_PYR_STREAM_MIN_ROWS 32 // shortest row block (4 halo rows are blurred horizontally per block)
-#endif
+constexpr uint32_t kPyrStreamWaves = 8192;  // waves a launch of the streamed pyramid kernels aims for
+constexpr uint32_t kPyrStreamMinRows = 32;  // shortest row block (4 halo rows are blurred horizontally per block)
 
 // FAST pyramid level (k_pyramid_fast): luminance only.  `in`: RGBA8 frames (level 0; in_stride in bytes) or the previous level's
 // quarter-size luminance output (floats; in_stride in floats); `next`: this level's output for the next one (floats), or null.
 hipError_t launch_pyramid_level_fast(const PyramidLevelLaunch &L)
 {
     const uint32_t w = L.img.w, h = L.img.h, n = L.img.n;
-#if defined(NUS_ABLATE_PYR_ALIGNED_STRIPS)
-    const uint32_t strips = cdiv(w, 4 * kWave);
-#else
     const uint32_t strips = cdiv(w, 4 * kWave - 8);
-#endif
     const uint64_t columns = (uint64_t)strips * n;
-    const uint32_t want = (uint32_t)std::min<uint64_t>((NUS_PYR_STREAM_WAVES + columns - 1) / columns,
-                                                       std::max<uint32_t>(h / NUS_PYR_STREAM_MIN_ROWS, 1));
+    const uint32_t want = (uint32_t)std::min<uint64_t>((kPyrStreamWaves + columns - 1) / columns, std::max<uint32_t>(h / kPyrStreamMinRows, 1));
     const uint32_t rows_per_block = (cdiv(h, want) + 1) & ~1u; // even: a 2x2 block never straddles two row blocks
     const uint32_t row_blocks = cdiv(h, rows_per_block);
     const dim3 block(256), grid(cdiv(strips * row_blocks, 4), n);
@@ -1299,8 +1182,7 @@ hipError_t launch_pyramid_level(const PyramidLevelLaunch &L, int kernel)
     if (kernel != kJacobiTiles) {
         const uint32_t strips = cdiv(w, 2 * kWave - 4);
         const uint64_t columns = (uint64_t)strips * n;
-        const uint32_t want = (uint32_t)std::min<uint64_t>((NUS_PYR_STREAM_WAVES + columns - 1) / columns,
-                                                           std::max<uint32_t>(h / NUS_PYR_STREAM_MIN_ROWS, 1));
+        const uint32_t want = (uint32_t)std::min<uint64_t>((kPyrStreamWaves + columns - 1) / columns, std::max<uint32_t>(h / kPyrStreamMinRows, 1));
         const uint32_t rows_per_block = (cdiv(h, want) + 1) & ~1u; // even: a 2x2 block never straddles two row blocks
         const uint32_t row_blocks = cdiv(h, rows_per_block);
         if (kernel == kJacobiStream || kernel == kJacobiStreamFast || columns * row_blocks >= 2048) {
@@ -1367,36 +1249,29 @@ hipError_t launch_hs_warp_setup(const HsPrepareLaunch &L, const HsCoarseFlow &co
 //   >= 256  (one 960x540 level): 32-wide tiles with 1024 threads;
 //   < 256   (one 480x270 level): 16-wide tiles, so that the grid still covers the 256 CUs, with 1024 threads of one
 //            cell each: two tiles per CU leave the step's LDS round trip exposed unless the waves are many.
-#ifndef NUS_HS_BIG_THREADS
-#define NUS_HS_BIG_THREADS 256
-#endif
-#ifndef NUS_HS_MID_T
-#define NUS_HS_MID_T 32
-#endif
-#ifndef NUS_HS_MID_THREADS
-#define NUS_HS_MID_THREADS 1024
-#endif
-#ifndef NUS_HS_SMALL_T
-#define NUS_HS_SMALL_T 16
-#endif
-#ifndef NUS_HS_SMALL_THREADS
-#define NUS_HS_SMALL_THREADS 1024
-#endif
-#ifndef NUS_HS_STREAM_MAXK
-#define NUS_HS_STREAM_MAXK 5 // steps per launch of the streamed kernel (registers: 8 per level + 5 per delay-line row)
-#endif
-#ifndef NUS_HS_FAST_MAXK_LONG
-#define NUS_HS_FAST_MAXK_LONG 8 // ... of a level with >= 30 steps (50 steps: 7 launches instead of 10; -0.8 us per 1080p pair)
-#endif
-#ifndef NUS_HS_FAST_MAXK
-#define NUS_HS_FAST_MAXK 5 // steps per launch of k_hs_stream_fast (registers: 4 per level + 5 per delay-line row)
-#endif
-#ifndef NUS_HS_STREAM_MIN_ROWS
-#define NUS_HS_STREAM_MIN_ROWS 64 // shortest row block: 2K halo rows and the K passes of pipeline fill are paid per block
-#endif
-#ifndef NUS_HS_STREAM_MIN_WAVES
-#define NUS_HS_STREAM_MIN_WAVES 1024 // below this the LDS tiles fill the chip better
-#endif
+constexpr int kHsBigT = 32, kHsBigThreads = 256, kHsBigMaxK = 5;
+constexpr int kHsMidT = 32, kHsMidThreads = 1024;
+constexpr int kHsSmallT = 16, kHsSmallThreads = 1024;
+constexpr int kHsTiledMaxK = 8;        // steps per launch of the 1024-thread tiles (the 256-thread class is instantiated up to it too)
+constexpr int kHsStreamMaxK = 5;       // steps per launch of the streamed kernel (registers: 8 per level + 5 per delay-line row)
+constexpr int kHsFastMaxK = 5;         // steps per launch of k_hs_stream_fast (registers: 4 per level + 5 per delay-line row)
+constexpr int kHsFastMaxKLong = 8;     // ... of a level with >= 30 steps (50 steps: 7 launches instead of 10; -0.8 us per 1080p pair)
+constexpr uint32_t kHsStreamMinRows = 64;    // shortest row block: 2K halo rows and the K passes of pipeline fill are paid per block
+constexpr uint32_t kHsStreamMinWaves = 1024; // below this the LDS tiles fill the chip better
+static_assert(kHsFastMaxK <= kHsFastMaxKLong && kHsFastMaxKLong <= kHsFastRingMaxK, "every FAST launch has a ring form");
+static_assert(kHsBigMaxK <= kHsTiledMaxK && 2 * kHsStreamMaxK < kWave, "steps per launch: a tile's halo, a strip's halo lanes");
+
+// f(std::integral_constant<int, k>) for a run-time k in 1 .. MaxK: the kernels take their steps per launch as a template argument
+template <int MaxK, typename F>
+hipError_t with_steps(uint32_t k, F &&f)
+{
+    if constexpr (MaxK >= 1) {
+        if (k == MaxK) return f(std::integral_constant<int, MaxK>{});
+        return with_steps<MaxK - 1>(k, f);
+    } else {
+        return hipErrorInvalidValue;
+    }
+}
 
 // The streamed kernel's launch shape for a level: strips of 64 - 2K columns, cut into row blocks.  The kernel is bound
 // by instruction issue and all its waves take the same time, so a launch costs (waves per SIMD, rounded up) x (passes
@@ -1411,7 +1286,7 @@ static HsStreamShape hs_stream_shape(uint32_t w, uint32_t h, uint32_t n, uint32_
     constexpr uint64_t kSimds = 1024; // 256 CUs x 4
     HsStreamShape s{cdiv(w, kWave - 2 * k), 1, h};
     const uint64_t columns = (uint64_t)s.strips * n;
-    const uint32_t max_blocks = std::max<uint32_t>(h / NUS_HS_STREAM_MIN_ROWS, 1);
+    const uint32_t max_blocks = std::max<uint32_t>(h / kHsStreamMinRows, 1);
     uint64_t best = ~0ull;
     for (uint32_t rb = 1; rb <= max_blocks; ++rb) {
         const uint32_t rows = cdiv(h, rb);
@@ -1421,7 +1296,7 @@ static HsStreamShape hs_stream_shape(uint32_t w, uint32_t h, uint32_t n, uint32_
         const uint64_t cost = ((waves + kSimds - 1) / kSimds) * (rows + 3 * k);
         if (cost < best) best = cost, s.row_blocks = rb, s.rows_per_block = rows;
     }
-    if (!force && columns * s.row_blocks < NUS_HS_STREAM_MIN_WAVES) s.row_blocks = 0;
+    if (!force && columns * s.row_blocks < kHsStreamMinWaves) s.row_blocks = 0;
     return s;
 }
 
@@ -1430,7 +1305,7 @@ static HsStreamShape hs_stream_shape(uint32_t w, uint32_t h, uint32_t n, uint32_
 bool hs_iterate_streams(uint32_t w, uint32_t h, uint32_t n, int kernel)
 {
     return kernel != kJacobiTiles &&
-           hs_stream_shape(w, h, n, NUS_HS_STREAM_MAXK, kernel == kJacobiStream || kernel == kJacobiStreamFast).row_blocks != 0;
+           hs_stream_shape(w, h, n, kHsStreamMaxK, kernel == kJacobiStream || kernel == kJacobiStreamFast).row_blocks != 0;
 }
 
 hipError_t launch_hs_iterate(const HsIterateLaunch &L, HsIterateResult *result)
@@ -1473,84 +1348,31 @@ hipError_t launch_hs_iterate(const HsIterateLaunch &L, HsIterateResult *result)
         const float *const lum = L.lum1;
         const size_t lum_stride = L.lum_stride;
         if (lum == nullptr) return hipErrorInvalidValue;
-        const HsWarp *const warp = L.warp;
         // a level with many steps (the coarsest: 50) takes more of them per launch: its launches are short and memory-bound, and
         // fewer of them move fewer bytes; the levels with 10 steps stay at 5 (ten per launch costs two waves per SIMD)
-        const uint32_t maxk = L.iterations >= 30 ? NUS_HS_FAST_MAXK_LONG : NUS_HS_FAST_MAXK;
-        const char *hb_env = getenv("NUS_HS_L0_HALF_BETWEEN"); // dev switch: see HsWarp::in_half
-        const bool half_between =
-            hb_env != nullptr && hb_env[0] == '1' && warp != nullptr && (L.iterations + maxk - 1) / maxk == 2 && !L.zero_start;
-        bool prev_stored_half = false;
-        bool &did_warp = res.warped;
+        const uint32_t maxk = L.iterations >= 30 ? kHsFastMaxKLong : kHsFastMaxK;
+        // (test hook: NUS_HS_FAST_SHIFT=1 in the environment runs the shifting form of the pass where the ring form is the
+        // product's -- tests/test_flow.py compares the two bit for bit, flipping it between calls: read per call, never cached)
+        const char *shift_env = getenv("NUS_HS_FAST_SHIFT");
+        const bool shifting = shift_env != nullptr && shift_env[0] == '1';
         // (Measured and dropped, round 4: the finest level in sub-chunks of 4-50 pairs, its two launches back to back per sub-chunk so
         // that the second finds the first's output and the luminance planes in the 256-MiB Infinity Cache -- identical flows,
         // 61 / 58 / 55 / 54 / 53 / 52 / 50 us per pair at 4 / 6 / 8 / 12 / 16 / 25 / 50 pairs against 50.5 for the whole chunk: launches
         // of a few thousand waves lose more than the cache gives.)
         return run(maxk, [&](uint32_t k, uint32_t left, const float2 *fi, float2 *fo, size_t out_stride, const HsCoarse &hc) {
             const bool ups = hc.flow != nullptr; // the first launch of a level takes the coarser level's flow, upsampled as it loads it
-            // the last launch of the level warps with the flow it finishes, where it can (see HsWarp); then the flow is stored only
-            // for a caller who asked for it
-            // OFF unless NUS_HS_FUSED_WARP=1 is in the environment: built and measured in round 5 -- identical bytes, but the fused launch
-            // takes 23 us per 1080p pair where the plain launch and the warp kernel take 12.2 + 7.9: the Jacobi pass has one pixel per
-            // lane, so the warp's gathers are 8-byte loads at a 4-byte lane stride (every texel pair fetched twice) and its ~140
-            // instructions per pixel run at four waves per SIMD (119 VGPRs) next to a pass that was at the memory rate, not below it
-            // (motion step 21.0 against 20.1 ms per 300 units).  The warp kernel's 2 x 2 pixels per thread is the better shape.
-            const char *fuse_env = getenv("NUS_HS_FUSED_WARP");
-            const bool can_warp = fuse_env != nullptr && fuse_env[0] == '1' &&
-                                  warp != nullptr && warp->frames != nullptr && warp->mid != nullptr && left == 1 && !ups && k <= 5 &&
-                                  NUS_HS_FAST_RING != 0 && w >= 2 && h >= 2 && (uint64_t)w * h * 4 < (1ull << 32) &&
-                                  (uint64_t)w * 4 < (1u << 24) && h < (1u << 24);
-            if (can_warp && L.final_out == nullptr) fo = nullptr;
-            const bool half_out = warp != nullptr && warp->out_half != 0 && left == 1; // the level's final flow as Rg16Float
+            const bool half_out = L.final_half && left == 1; // the level's final flow as Rg16Float
             if (half_out) res.wrote_half = true;
-            const bool mid_half = half_between && left == 2; // the first of the two launches stores halves for the second
-            HsWarp tail; // what the plain instantiations see of it: only the format of the flow they store (and load)
-            tail.out_half = half_out || mid_half ? 1u : 0u;
-            tail.in_half = prev_stored_half ? 1u : 0u;
-            prev_stored_half = mid_half;
-            HsWarp wfull = can_warp ? *warp : HsWarp{};
-            wfull.out_half = tail.out_half;
-            wfull.in_half = tail.in_half;
-            const HsWarp *const wp = can_warp ? &wfull : nullptr;
             const HsStreamShape sh = hs_stream_shape(w, h, n, k, true);
             const dim3 block(256), grid(cdiv(sh.strips * sh.row_blocks, 4), n);
-#define NUS_HSF_L(KK, UU, RR)                                                                                                        \
-    hipLaunchKernelGGL((k_hs_stream_fast<KK, UU, RR>), grid, block, 0, stream, lum, lum_stride, lambda, fi, flow_stride, fo, out_stride, \
-                       (int)w, (int)h, (int)sh.strips, (int)sh.row_blocks, (int)sh.rows_per_block, hc, tail)
-#define NUS_HSF_W(KK)                                                                                                                \
-    hipLaunchKernelGGL((k_hs_stream_fast<KK, false, true, true>), grid, block, 0, stream, lum, lum_stride, lambda, fi, flow_stride, fo, \
-                       out_stride, (int)w, (int)h, (int)sh.strips, (int)sh.row_blocks, (int)sh.rows_per_block, hc, *wp)
-#define NUS_HSF(KK)                                                                                                                  \
-    case KK:                                                                                                                         \
-        if constexpr (NUS_HS_FAST_RING != 0 && KK <= 5) {                                                                            \
-            if (wp != nullptr && !shifting && !ups) {                                                                                \
-                NUS_HSF_W(KK);                                                                                                       \
-                did_warp = true;                                                                                                     \
-                break;                                                                                                               \
-            }                                                                                                                        \
-        }                                                                                                                            \
-        if constexpr (NUS_HS_FAST_RING != 0 && KK <= NUS_HS_FAST_RING_MAXK) {                                                                            \
-            if (!shifting) {                                                                                                         \
-                if (ups) NUS_HSF_L(KK, true, true); else NUS_HSF_L(KK, false, true);                                                 \
-                break;                                                                                                               \
-            }                                                                                                                        \
-        }                                                                                                                            \
-        if (ups) NUS_HSF_L(KK, true, false); else NUS_HSF_L(KK, false, false);                                                       \
-        break;
-            // (test hook: NUS_HS_FAST_SHIFT=1 in the environment runs the shifting form of the pass where the ring form is the
-            // product's -- tests/test_flow.py compares the two bit for bit)
-            const char *shift_env = getenv("NUS_HS_FAST_SHIFT");
-            const bool shifting = shift_env != nullptr && shift_env[0] == '1';
-            switch (k) {
-                NUS_HSF(1) NUS_HSF(2) NUS_HSF(3) NUS_HSF(4) NUS_HSF(5)
-#if NUS_HS_FAST_MAXK > 5 || NUS_HS_FAST_MAXK_LONG > 5
-                NUS_HSF(6) NUS_HSF(7) NUS_HSF(8) NUS_HSF(9) NUS_HSF(10)
-#endif
-            }
-#undef NUS_HSF
-#undef NUS_HSF_L
-#undef NUS_HSF_W
-            return hipGetLastError();
+            return with_steps<kHsFastMaxKLong>(k, [&](auto steps) {
+                constexpr int K = decltype(steps)::value;
+                const auto kernel = shifting ? (ups ? k_hs_stream_fast<K, true, false> : k_hs_stream_fast<K, false, false>)
+                                             : (ups ? k_hs_stream_fast<K, true, true> : k_hs_stream_fast<K, false, true>);
+                hipLaunchKernelGGL(kernel, grid, block, 0, stream, lum, lum_stride, lambda, fi, flow_stride, fo, out_stride, (int)w, (int)h,
+                                   (int)sh.strips, (int)sh.row_blocks, (int)sh.rows_per_block, hc, half_out ? 1u : 0u);
+                return hipGetLastError();
+            });
         });
     }
     if (hs_iterate_streams(w, h, n, L.kernel)) {
@@ -1558,60 +1380,35 @@ hipError_t launch_hs_iterate(const HsIterateLaunch &L, HsIterateResult *result)
         // with luminance planes the kernel takes the derivatives from the planes themselves
         const float *const coef = lum1 ? lum1 : L.coef;
         const size_t coef_stride = lum1 ? L.lum_stride : L.coef_stride;
-        return run(NUS_HS_STREAM_MAXK, [&](uint32_t k, uint32_t, const float2 *fi, float2 *fo, size_t out_stride, const HsCoarse &hc) {
+        return run(kHsStreamMaxK, [&](uint32_t k, uint32_t, const float2 *fi, float2 *fo, size_t out_stride, const HsCoarse &hc) {
             const HsStreamShape sh = hs_stream_shape(w, h, n, k, true);
             // the first launch of a level that continues a coarser one takes that level's flow, upsampled as it is loaded
             const bool ups = hc.flow != nullptr && lum1 != nullptr;
             const dim3 block(256), grid(cdiv(sh.strips * sh.row_blocks, 4), n);
-#define NUS_HSS_L(KK, LL, UU)                                                                                               \
-    hipLaunchKernelGGL((k_hs_stream<KK, LL, UU>), grid, block, 0, stream, coef, coef_stride, lambda, fi, flow_stride, fo, out_stride, \
-                       (int)w, (int)h, (int)sh.strips, (int)sh.row_blocks, (int)sh.rows_per_block, hc)
-#define NUS_HSS(KK)                                                                                                             \
-    case KK:                                                                                                                    \
-        if (lum1 && ups)                                                                                                        \
-            NUS_HSS_L(KK, true, true);                                                                                          \
-        else if (lum1)                                                                                                          \
-            NUS_HSS_L(KK, true, false);                                                                                         \
-        else                                                                                                                    \
-            NUS_HSS_L(KK, false, false);                                                                                        \
-        break;
-            switch (k) {
-                NUS_HSS(1) NUS_HSS(2) NUS_HSS(3) NUS_HSS(4) NUS_HSS(5)
-#if NUS_HS_STREAM_MAXK > 5
-                NUS_HSS(6) NUS_HSS(7) NUS_HSS(8)
-#endif
-#if NUS_HS_STREAM_MAXK > 8
-                NUS_HSS(9) NUS_HSS(10)
-#endif
-            }
-#undef NUS_HSS
-#undef NUS_HSS_L
-            return hipGetLastError();
+            return with_steps<kHsStreamMaxK>(k, [&](auto steps) {
+                constexpr int K = decltype(steps)::value;
+                const auto kernel = ups ? k_hs_stream<K, true, true> : (lum1 ? k_hs_stream<K, true, false> : k_hs_stream<K, false, false>);
+                hipLaunchKernelGGL(kernel, grid, block, 0, stream, coef, coef_stride, lambda, fi, flow_stride, fo, out_stride, (int)w, (int)h,
+                                   (int)sh.strips, (int)sh.row_blocks, (int)sh.rows_per_block, hc);
+                return hipGetLastError();
+            });
         });
     }
     const float *const coef = L.coef;
     const size_t coef_stride = L.coef_stride;
     const uint64_t tiles32 = (uint64_t)cdiv(w, 32) * cdiv(h, 32) * n;
     const int cls = tiles32 >= 1024 ? 2 : (tiles32 >= 256 ? 1 : 0);
-    const uint32_t T = cls == 2 ? 32 : (cls == 1 ? NUS_HS_MID_T : NUS_HS_SMALL_T);
-    const uint32_t NT = cls == 2 ? NUS_HS_BIG_THREADS : (cls == 1 ? NUS_HS_MID_THREADS : NUS_HS_SMALL_THREADS);
+    const uint32_t T = cls == 2 ? kHsBigT : (cls == 1 ? kHsMidT : kHsSmallT);
+    const uint32_t NT = cls == 2 ? kHsBigThreads : (cls == 1 ? kHsMidThreads : kHsSmallThreads);
     const dim3 block(NT), grid(cdiv(w, T), cdiv(h, T), n);
-    return run(cls == 2 ? 5 : 8, [&](uint32_t k, uint32_t, const float2 *fi, float2 *fo, size_t out_stride, const HsCoarse &) {
-#define NUS_HS_L(TT, KK, TH)                                                                                                  \
-    hipLaunchKernelGGL((k_hs_tiled<TT, KK, TH>), grid, block, 0, stream, coef, coef_stride, lambda, fi, flow_stride, fo, out_stride, \
-                       (int)w, (int)h)
-#define NUS_HS(KK)                                                    \
-    case KK:                                                          \
-        if (cls == 2) NUS_HS_L(32, KK, NUS_HS_BIG_THREADS);           \
-        else if (cls == 1) NUS_HS_L(NUS_HS_MID_T, KK, NUS_HS_MID_THREADS); \
-        else NUS_HS_L(NUS_HS_SMALL_T, KK, NUS_HS_SMALL_THREADS);      \
-        break;
-        switch (k) {
-            NUS_HS(1) NUS_HS(2) NUS_HS(3) NUS_HS(4) NUS_HS(5) NUS_HS(6) NUS_HS(7) NUS_HS(8)
-        }
-#undef NUS_HS
-#undef NUS_HS_L
-        return hipGetLastError();
+    return run(cls == 2 ? kHsBigMaxK : kHsTiledMaxK, [&](uint32_t k, uint32_t, const float2 *fi, float2 *fo, size_t out_stride, const HsCoarse &) {
+        return with_steps<kHsTiledMaxK>(k, [&](auto steps) {
+            constexpr int K = decltype(steps)::value;
+            const auto kernel = cls == 2 ? k_hs_tiled<kHsBigT, K, kHsBigThreads>
+                                         : (cls == 1 ? k_hs_tiled<kHsMidT, K, kHsMidThreads> : k_hs_tiled<kHsSmallT, K, kHsSmallThreads>);
+            hipLaunchKernelGGL(kernel, grid, block, 0, stream, coef, coef_stride, lambda, fi, flow_stride, fo, out_stride, (int)w, (int)h);
+            return hipGetLastError();
+        });
     });
 }
 

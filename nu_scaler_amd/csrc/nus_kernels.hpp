@@ -227,27 +227,6 @@ hipError_t launch_hs_level_setup(const HsPrepareLaunch &L, const HsCoarseFlow &c
 // it is stored at flow_out; else f0 is `flow` (null: zero flow -- launch_hs_prepare's triple).  L.i1 / L.i2 are only read.
 hipError_t launch_hs_warp_setup(const HsPrepareLaunch &L, const HsCoarseFlow &coarse, const float *flow, size_t flow_stride, float *flow_out,
                                 size_t flow_out_stride);
-// HsWarp (round 5; used only with NUS_HS_FUSED_WARP=1 in the environment: measured slower than the warp kernel behind the estimator):
-// the LAST launch of the finest level can warp + blend the pair's two frames with the flow it has just finished
-// (dense-flow warp in FMA mode, nus_warp_device.hpp) and store the in-between frame -- the flow then never has to be written for the
-// warp to read it back.  frames: RGBA8 frame of pair z at frames + z * frame_stride bytes, its partner one frame_stride further;
-// mid: w * h RGBA8 pixels per pair, tightly packed.  HsIterateResult::warped tells the caller whether the launch that ran could do it
-// (FAST ring form, not the launch that upsamples the coarser level, frames of at least 2 x 2 pixels and less than 4 GiB); if not, the
-// caller runs the warp kernel itself.  With a warp and final_out == nullptr the flow of the last launch is not stored at all.
-struct HsWarp {
-    const uint8_t *frames = nullptr;
-    size_t frame_stride = 0;
-    uint8_t *mid = nullptr;
-    float t = 0.5f;
-    uint32_t sel = 0;
-    // the level's FINAL flow as 2 x IEEE half per cell (round to nearest even) instead of 2 x f32: the reference's live flow layout,
-    // Rg16Float (wgpu_interpolator.rs:276), for a warp that reads it that way.  Honoured by the FAST streamed kernel's last launch
-    // (HsIterateResult::wrote_half says so); everything else leaves f32 and the caller converts (launch_flow_to_half).
-    uint32_t out_half = 0;
-    // dev switch NUS_HS_L0_HALF_BETWEEN=1 (round 6, measured: profiles/r06_flow_level0_half_between_launches.txt): the flow BETWEEN the
-    // finest level's two launches as Rg16Float as well -- the launch reads 2 x half per cell
-    uint32_t in_half = 0;
-};
 // n cells of 2 x f32 -> 2 x f16 (round to nearest even)
 hipError_t launch_flow_to_half(const float *src, void *dst, size_t n_cells, hipStream_t stream);
 // `iterations` Jacobi steps of one level, K per launch (derivatives once per level, the steps in LDS tiles or a register pipeline).
@@ -264,11 +243,14 @@ struct HsIterateLaunch {
     size_t flow_stride = 0, final_stride = 0;   // in cells (float2)
     int kernel = kJacobiAuto;
     HsCoarseFlow coarse; // streamed kernels on luminance planes: the first launch starts from this flow, upsampled as it loads it
-    const HsWarp *warp = nullptr;
+    // the level's FINAL flow as 2 x IEEE half per cell (round to nearest even) instead of 2 x f32: the reference's live flow layout,
+    // Rg16Float (wgpu_interpolator.rs:276), for a warp that reads it that way.  Honoured if the last launch is the FAST streamed
+    // kernel (HsIterateResult::wrote_half says so); everything else leaves f32 and the caller converts (launch_flow_to_half).
+    bool final_half = false;
 };
 struct HsIterateResult {
     float *flow = nullptr, *spare = nullptr; // where the result is (final_out, if given), and the other buffer of the ping-pong
-    bool warped = false, wrote_half = false; // what the last launch did of L.warp
+    bool wrote_half = false;                 // the last launch stored halves (L.final_half)
 };
 hipError_t launch_hs_iterate(const HsIterateLaunch &L, HsIterateResult *result);
 bool hs_iterate_streams(uint32_t w, uint32_t h, uint32_t n, int kernel);

@@ -186,7 +186,7 @@ class FramePipeline:
         fused_warp (round 5): estimator and warp through ONE entry point (FlowEstimator.interpolate_device_stream); `flows` may then
         be None (they stay in the estimator's workspace).  The warp is the FMA-mode one whatever `self.interp`'s mode is; same bytes
         as the separate FMA-mode warp.  (The in-kernel fusion -- the last Horn-Schunck launch warping with the flow it has just
-        finished -- exists behind NUS_HS_FUSED_WARP=1: identical bytes, measured slower.)
+        finished -- was built, measured and removed: identical bytes, slower; the code is in git at d74dcbc.)
 
         flow_warps: the estimator's re-linearisation rounds per finer pyramid level (FlowEstimator.set_warps; 0: none)."""
         from .flow import FlowEstimator, check_warps

@@ -423,21 +423,14 @@ def test_flow_fast_ring_form_equals_the_shifting_form(nsc, oracle_mod, w, h, lev
 @pytest.mark.gpu
 @pytest.mark.parametrize("w,h,levels,coarse,refine", [(160, 96, 3, 20, 10), (333, 262, 3, 7, 7), (97, 45, 2, 9, 5), (64, 64, 1, 13, 0),
                                                        (130, 70, 2, 4, 0), (1030, 6, 2, 2, 2), (2, 2, 1, 3, 0), (960, 540, 3, 10, 10)])
-@pytest.mark.parametrize("in_kernel", [False, True])
-def test_interpolate_device_stream_equals_estimate_then_warp(nsc, oracle_mod, w, h, levels, coarse, refine, in_kernel, monkeypatch):
+def test_interpolate_device_stream_equals_estimate_then_warp(nsc, oracle_mod, w, h, levels, coarse, refine):
     """nus_flow_interpolate_device_stream (round 5: pyramid -> flow -> warp as ONE pipeline, wgpu_interpolator.rs:881-935): in every
-    kernel mode -- EXACT by size, EXACT pair by pair, FAST with the streamed kernels forced (the last Horn-Schunck launch of the finest
-    level warps with the flow it has just finished; also with 7 = 4 + 3 steps, with no refinement step at all, with one level) -- the
+    kernel mode -- EXACT by size, EXACT pair by pair, FAST with the streamed kernels forced (also with 7 = 4 + 3 steps, with no refinement step at all, with one level) -- the
     in-between frames are bit for bit those of nus_flow_estimate_device_stream followed by the FMA-mode warp kernel, with the flows
     stored or not; the flows, when asked for, are the estimator's; and in EXACT mode everything equals the oracle within the warp's
     FMA contract (<= 1 LSB)."""
     import torch
 
-    # in_kernel: NUS_HS_FUSED_WARP=1 -- the finest level's last FAST launch warps with the flow it has just finished (HsWarp)
-    if in_kernel:
-        monkeypatch.setenv("NUS_HS_FUSED_WARP", "1")
-    else:
-        monkeypatch.delenv("NUS_HS_FUSED_WARP", raising=False)
     dev = torch.device("cuda:0")
     n_frames, t = 4, 0.3
     frames = np.stack([_smooth(w, h, 1.2 * k) if k % 2 else oracle_mod.gen_noise(w, h, 50 + k) // 2 + _smooth(w, h, 0.7 * k) // 2
@@ -468,7 +461,7 @@ def test_interpolate_device_stream_equals_estimate_then_warp(nsc, oracle_mod, w,
                 assert torch.equal(got_flows, flows), (mode, tiled)
             else:
                 assert bool(torch.isnan(got_flows).all())
-        if mode == "exact" and tiled == 1 and not in_kernel:
+        if mode == "exact" and tiled == 1:
             for k in range(n_frames - 1):
                 fl = oracle_mod.flow_estimate(frames[k], frames[k + 1], levels, coarse, refine, fe.lambda_)
                 assert np.array_equal(fetch(flows[k]), fl)
@@ -482,16 +475,11 @@ def test_interpolate_device_stream_equals_estimate_then_warp(nsc, oracle_mod, w,
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("in_kernel", [False, True])
-def test_step_motion_fused_warp_equals_separate_stages(nsc, oracle_mod, in_kernel, monkeypatch):
+def test_step_motion_fused_warp_equals_separate_stages(nsc, oracle_mod):
     """FramePipeline.step_motion(fused_warp=True), stage after stage and as the two-stream pipeline, with the flows stored and not:
     the in-between frames and both 4K outputs bit-identical to the step with the separate FMA-mode warp."""
     import torch
 
-    if in_kernel:
-        monkeypatch.setenv("NUS_HS_FUSED_WARP", "1")
-    else:
-        monkeypatch.delenv("NUS_HS_FUSED_WARP", raising=False)
     w, h, n = 480, 270, 7
     dev = torch.device("cuda:0")
     frames = put(np.stack([_smooth(w, h, 1.1 * k) for k in range(n + 1)]))

@@ -7,7 +7,7 @@ with warps = 0; with warps the larger of 1e-3 px and four times the distance of 
 that pair -- measured on an MI355X: 1e-3 px holds everywhere but at warps = 4 on the 4-level case, 1.01e-3, and on stream pairs 5
 and 7, 2.7e-3 and 1.6e-3, where the restatement itself is 1.8e-3 and 1.3e-3 px from float64; DESIGN section 8.1 has the table).  Streams cut into chunks
 (NUS_FLOW_MAX_CHUNK_PAIRS, and the product's own bound of 150 pairs), a batch whose level 0 streams while level 1 runs on tiles,
-interpolate_device_stream in EXACT, with f32 and f16 flows, with and without a flow buffer and with NUS_HS_FUSED_WARP=1, and one
+interpolate_device_stream in EXACT, with f32 and f16 flows, with and without a flow buffer, and one
 handle taken through warps 0 -> 2 -> 4 -> 0.  The CPU references are computed once per module run and never written to; every
 device output lives in a conftest.guarded tensor and comes down through nu_scaler_amd.transfer."""
 import functools
@@ -29,7 +29,7 @@ FAST_CONDITIONING = 4.0  # with warps: or within this many times |exact f32 - fl
 MIN_DECIDED = 0.9  # the decided-share floor of tests/test_gpu_warp_fma_contract.py
 TABLE = (3, 50, 10)  # levels, coarse and refining steps of the stream tests at 67 x 45, 173 x 70 and 192 x 128 (FlowEstimator's defaults)
 CHEAP = 40000  # cells: below it the EXACT lattice runs warps = 2 as well
-ENV = ("NUS_FLOW_MAX_CHUNK_PAIRS", "NUS_HS_FUSED_WARP")
+ENV = ("NUS_FLOW_MAX_CHUNK_PAIRS",)
 
 
 def _stream():
@@ -212,7 +212,6 @@ def _hold_stream(nsc, w, h, n, params, warps, settings, tag):
 def test_stream_cut_into_small_chunks(nsc, monkeypatch, w, h, warps, chunk):
     """9 frames = 8 pairs in chunks of 3, 3, 2 (and of 1): coefficient planes, flow buffers and luminance planes are indexed by the
     pair's place in its chunk, the caller's buffers by its place in the stream."""
-    monkeypatch.delenv("NUS_HS_FUSED_WARP", raising=False)
     monkeypatch.setenv("NUS_FLOW_MAX_CHUNK_PAIRS", chunk)
     _hold_stream(nsc, w, h, 9, TABLE, warps, [("exact", 0), ("exact", 1), ("exact", 2), ("exact", 3), ("fast", 1), ("fast", 3)],
                  f"chunks of {chunk}")
@@ -295,32 +294,6 @@ def test_interpolate_device_stream(nsc, monkeypatch, w, h, warps, mode, tiled):
         mid_only, _ = _interpolate(nsc, d, n, w, h, t, warps, mode, tiled, ffmt, False)
         assert np.array_equal(mid_only, mid), tag
     assert np.array_equal(fetch(d), frames)
-
-
-@pytest.mark.parametrize("ffmt", ["f32", "f16"])
-def test_fused_warp_switch_falls_back_behind_a_warped_level(nsc, monkeypatch, ffmt):
-    """NUS_HS_FUSED_WARP=1, FAST, warps = 1: level 0 runs the exact kernels, there is no FAST last launch to warp in, and the call
-    gives the frames and flows it gives without the variable."""
-    w, h, n, t = 173, 70, 5, 0.3
-    d = put(_frames(w, h, n), "cuda:0")
-    monkeypatch.delenv("NUS_FLOW_MAX_CHUNK_PAIRS", raising=False)
-    res = {}
-    for fused in (False, True):
-        if fused:
-            monkeypatch.setenv("NUS_HS_FUSED_WARP", "1")
-        else:
-            monkeypatch.delenv("NUS_HS_FUSED_WARP", raising=False)
-        for tiled in (1, 3):
-            for with_flows in (True, False):
-                res[fused, tiled, with_flows] = _interpolate(nsc, d, n, w, h, t, 1, "fast", tiled, ffmt, with_flows)
-    for tiled in (1, 3):
-        for with_flows in (True, False):
-            (mid, flows), (mid_f, flows_f) = res[False, tiled, with_flows], res[True, tiled, with_flows]
-            assert np.array_equal(mid, mid_f), (ffmt, tiled, with_flows)
-            if with_flows:
-                assert np.array_equal(flows.view(np.uint8), flows_f.view(np.uint8)), (ffmt, tiled)
-        assert np.array_equal(res[True, tiled, False][0], res[True, tiled, True][0])
-    _hold_frames(res[True, 3, True][0], _frames(w, h, n), res[True, 3, True][1], t, ("NUS_HS_FUSED_WARP=1", ffmt))
 
 
 # ---- section 6: one handle, changing warps ------------------------------------------------------------------------------------------------

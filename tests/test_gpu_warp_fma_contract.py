@@ -31,8 +31,7 @@ _STATS = {}  # entry -> [samples, decided, bytes differing from the all-floor re
 ENTRIES = ({f"{e} {k} {f}" for e in ("interpolate_device", "interpolate_multi_device") for k in ("2px/lane", "1px/lane") for f in ("f32", "f16")}
            | {f"{e} 1px/lane (flow pointer not 16-byte aligned) {f}" for e in ("interpolate_device", "interpolate_multi_device") for f in ("f32", "f16")}
            | {f"interpolate_multi_device {fmt}" for fmt in ("bgra", "rgbx", "bgrx")}
-           | {"bm warp_device 2px/lane", "bm warp_device 1px/lane", "bm interpolate_stream_device", "flow interpolate_device_stream",
-              "flow interpolate_device_stream (warp in the last Jacobi launch)"})
+           | {"bm warp_device 2px/lane", "bm warp_device 1px/lane", "bm interpolate_stream_device", "flow interpolate_device_stream"})
 
 
 def _f32(ts):
@@ -267,31 +266,21 @@ def test_block_matching_stream_frames_meet_the_contract_with_the_vectors_it_retu
     _hold("bm interpolate_stream_device", fetch(mid), frames[:-1], frames[1:], flow, times, ((w, h), bs, times[0]))
 
 
-@pytest.mark.parametrize("in_kernel", [False, True])
-def test_flow_stream_frames_meet_the_contract_with_the_flows_it_returns(nsc, in_kernel, monkeypatch):
-    """FlowEstimator.interpolate_device_stream, f32 hand-off: the warp kernel behind the estimator (EXACT estimator), and -- FAST
-    estimator with the streamed kernels, NUS_HS_FUSED_WARP=1 -- the warp inside the finest level's last Jacobi launch
-    (k_hs_stream_fast<..., WARP>).  The witness takes the flows the same call stored."""
+def test_flow_stream_frames_meet_the_contract_with_the_flows_it_returns(nsc):
+    """FlowEstimator.interpolate_device_stream, f32 hand-off: the warp kernel behind the estimator (EXACT estimator).  The witness
+    takes the flows the same call stored."""
     import torch
 
-    if in_kernel:
-        monkeypatch.setenv("NUS_HS_FUSED_WARP", "1")
-    else:
-        monkeypatch.delenv("NUS_HS_FUSED_WARP", raising=False)
     w, h, n, t = 160, 96, 4, 0.3
     frames = _moving(n, w, h)
     d_frames = put(frames)
     fe = nsc.FlowEstimator(levels=3, coarse_iterations=20, refine_iterations=10)
-    if in_kernel:
-        fe.set_mode("fast")
-        fe.set_tiled(3)
     mid = guarded.empty((n - 1, h, w, 4), dtype=torch.uint8, device="cuda:0")
     flows = guarded.full((n - 1, h, w, 2), float("nan"), dtype=torch.float32, device="cuda:0")
     fe.interpolate_device_stream(d_frames.data_ptr(), n, w, h, t, mid.data_ptr(), flows.data_ptr(), _stream())
     got, flow = fetch(mid), fetch(flows)
     assert np.isfinite(flow).all() and np.abs(flow).max() > 0.25
-    entry = "flow interpolate_device_stream" + (" (warp in the last Jacobi launch)" if in_kernel else "")
-    _hold(entry, got, frames[:-1], frames[1:], flow, t, ((w, h), t))
+    _hold("flow interpolate_device_stream", got, frames[:-1], frames[1:], flow, t, ((w, h), t))
 
 
 def test_every_fma_warp_entry_was_held_to_the_contract():

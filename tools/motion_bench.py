@@ -24,7 +24,7 @@ s = torch.cuda.current_stream().cuda_stream
 
 
 def timed(**kw):
-    fl = None if kw.get("fused_warp") else flows  # fused: the flow never goes to HBM
+    fl = None if kw.get("fused_warp") else flows  # one entry point: the flow stays in the estimator's workspace
     return _timed(fl, **kw)
 
 
@@ -45,13 +45,10 @@ for rnd in range(2):
         print(f"motion step, {n} units, pipelined, chunks of {c:3d}, real frames per chunk: {timed(pipelined=True, chunk=c):7.2f} ms", flush=True)
         pipe._motion_real_first = True
         print(f"motion step, {n} units, pipelined, chunks of {c:3d}: {timed(pipelined=True, chunk=c):7.2f} ms", flush=True)
-    for env in ("0", "1"):  # one entry point (estimator, then the warp kernel behind it) / the warp inside the last Jacobi launch
-        os.environ["NUS_HS_FUSED_WARP"] = env
-        what = "warp inside the last Jacobi launch" if env == "1" else "one call, warp kernel behind the estimator"
-        print(f"motion step, {n} units, {what}, stage after stage: {timed(fused_warp=True, flow_format='f32'):7.2f} ms", flush=True)
-        for c in chunks:
-            print(f"motion step, {n} units, {what}, pipelined, chunks of {c:3d}: {timed(fused_warp=True, pipelined=True, chunk=c, flow_format='f32'):7.2f} ms", flush=True)
-    os.environ.pop("NUS_HS_FUSED_WARP", None)
+    what = "one call, warp kernel behind the estimator"
+    print(f"motion step, {n} units, {what}, stage after stage: {timed(fused_warp=True, flow_format='f32'):7.2f} ms", flush=True)
+    for c in chunks:
+        print(f"motion step, {n} units, {what}, pipelined, chunks of {c:3d}: {timed(fused_warp=True, pipelined=True, chunk=c, flow_format='f32'):7.2f} ms", flush=True)
     for c in chunks:
         print(f"motion step, {n} units, one call, Rg16Float between estimator and warp, pipelined, chunks of {c:3d}: "
               f"{timed(fused_warp=True, pipelined=True, chunk=c, flow_format='f16'):7.2f} ms", flush=True)
