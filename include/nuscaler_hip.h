@@ -525,6 +525,32 @@ int nus_flow_mode(const nus_flow *h);
 #define NUS_FLOW_MAX_WARPS 4
 int nus_flow_set_warps(nus_flow *h, uint32_t warps);
 int nus_flow_warps(const nus_flow *h);
+/* Median filter of the flow behind every Jacobi run (off by default: 0; Sun, Roth and Black, "Secrets of optical flow estimation",
+ * CVPR 2010).  The quadratic smoothness term turns a motion boundary into a ramp several cells wide, and every re-linearisation
+ * round then samples frame B through that ramp and keeps it; a median removes the ramp and the outliers and keeps the edge.  With
+ * size = 3 or 5, after every Jacobi run of an estimate -- the coarsest level's `coarse_iters` steps, a finer level's
+ * `refine_iters` steps, with nus_flow_set_warps each of a finer level's rounds -- the level's flow is replaced by its component-wise
+ * size x size median: u and v separately, the window centred on the cell, coordinates clamped into the level (replicated border).
+ * A run of zero steps is followed by no median.  What the next stage reads -- the x2 upsample, the next round's gather, the caller
+ * or the warp -- is the filtered flow.  The median is a selection (the 5th of 9, the 13th of 25 values): it rounds nothing and is the
+ * same kernel in NUS_FLOW_EXACT and NUS_FLOW_FAST (FAST's bound is the one nus_flow_set_mode states for warps); where +0 and -0
+ * tie either may be returned, and NaNs are out of contract.
+ * The mode is meant for warps >= 1: there, on the float64 witness of tests/_flow_median.py, it gains the t = 0.5 frame
+ * +0.3 .. +1.5 dB PSNR (3 x 3) and +0.5 .. +2.1 dB (5 x 5) on frames of 192 px and more; with warps = 0 the result is mixed
+ * (-0.2 .. +0.8 dB).  A 5 x 5 window on a small frame's coarsest level covers much of a small object (96 x 64, 3 levels: 3 x 3 is
+ * the better choice), which is why the size is a setting.  The setting applies to every estimator entry point of the handle
+ * (nus_flow_estimate, _estimate_device, _estimate_device_stream, _interpolate_device_stream, _interpolate_multi_device_stream); it
+ * may be changed at any time; with 0 every entry point writes the bytes and reserves the workspace it did before the setting
+ * existed.  Cost: one launch per Jacobi run that moves 16 B per cell (8 read, 8 written) through the flow ping-pong -- no new
+ * workspace, except that a FAST stream with the Rg16Float hand-off and no d_flows keeps its halves beside the flows, 4 B per cell
+ * and pair -- and, with the median on, the finest level's last Jacobi launch no longer writes the caller's buffer or Rg16Float
+ * halves itself (the median writes the caller's f32 buffer; halves are converted afterwards).  Time per pair: DESIGN.md 8.1.
+ * Any other size: NUS_ERR_INVALID_ARGUMENT, the text beginning "nus_flow_set_median:", the setting unchanged. */
+#define NUS_FLOW_MEDIAN_MAX 5
+int nus_flow_set_median(nus_flow *h, uint32_t size);
+int nus_flow_median_size(const nus_flow *h);
+/* Bytes of device workspace the handle holds now (grow-only; 0 for a null handle or before the first call that needs a device). */
+size_t nus_flow_workspace_bytes(nus_flow *h);
 const char *nus_flow_last_error(const nus_flow *h);
 
 /* primitives on host buffers */
@@ -536,6 +562,9 @@ int nus_flow_horn_schunck(nus_flow *h, const float *i1, const float *i2, const f
                           uint32_t w, uint32_t hgt, float lambda, uint32_t iterations, float *flow_out);
 int nus_flow_upsample(nus_flow *h, const float *src, uint32_t sw, uint32_t sh,
                       float *dst, uint32_t dw, uint32_t dh, float scale);
+/* The stage nus_flow_set_median adds, on its own: the component-wise size x size median (3 or 5) of a w*h*2 flow, border
+ * replicated.  size and pointers are checked before any HIP call. */
+int nus_flow_median(nus_flow *h, const float *flow_in, uint32_t w, uint32_t hgt, uint32_t size, float *flow_out);
 /* The two halves of a re-linearised level (nus_flow_set_warps), always exact.  _warp_coefficients: f32 RGBA images and a w*h*2
  * flow -> w*h*3 floats (Ix, Iy, It') per cell; flow == NULL is zero flow and gives (Ix, Iy, It = L2 - L1).
  * _horn_schunck_coef: `iterations` Jacobi steps on such coefficients; flow_in == NULL starts from zero. */

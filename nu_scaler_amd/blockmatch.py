@@ -207,11 +207,12 @@ class PyFrameInterpolator:
     is kept and reported).  Unknown quality strings in the constructor mean "medium"; the setter raises.  `bidirectional` (not
     in the reference) turns the block matcher's forward-backward check on; the optical-flow method has none and raises.  `flow_warps`
     (not in the reference either; 0 .. FLOW_MAX_WARPS) is the optical-flow estimator's re-linearisation rounds per finer level
-    (FlowEstimator.set_warps); a block method given a non-zero value raises."""
+    (FlowEstimator.set_warps); a block method given a non-zero value raises.  `flow_median` (0, 3 or 5; likewise) is that estimator's
+    median filter behind every Jacobi run (FlowEstimator.set_median)."""
 
     def __init__(self, method: str = "optical_flow", quality: str = "medium", *, device: int = 0, scene_detect: bool = False,
-                 bidirectional: bool = False, flow_warps: int = 0):
-        from .flow import check_warps
+                 bidirectional: bool = False, flow_warps: int = 0, flow_median: int = 0):
+        from .flow import check_median, check_warps
 
         m = str(method).lower()
         self._scene = None  # (not in the reference) a pair flagged as a scene cut gives a repeat of the nearer frame, not a blend
@@ -225,6 +226,9 @@ class PyFrameInterpolator:
         flow_warps = check_warps(flow_warps)
         if flow_warps and self._block:
             raise ValueError("flow_warps: only the optical-flow method re-linearises its pyramid levels")
+        flow_median = check_median(flow_median)
+        if flow_median and self._block:
+            raise ValueError("flow_median: only the optical-flow method has a flow to median-filter between its Jacobi runs")
         if self._block:
             self._bm = BlockMatcher(self._quality, device=device, bidirectional=bidirectional)
             if scene_detect:
@@ -232,7 +236,7 @@ class PyFrameInterpolator:
         else:
             from .flow import FlowEstimator
 
-            self._flow = FlowEstimator(device=device, warps=flow_warps)
+            self._flow = FlowEstimator(device=device, warps=flow_warps, median=flow_median)
             if scene_detect:
                 from .scene import SceneDetector
 

@@ -4,7 +4,7 @@
 // (Nu_scale/src/main.rs:36-73: --tech, --quality, --algorithm).
 //
 //   nu_scaler_cli upscale <in.png> <out.png> [--algorithm A] [--scale S] [--tech T] [--quality Q] [--device N]
-//   nu_scaler_cli interpolate <a.png> <b.png> <out.png> [--t X | --multiplier M] [--flow [--flow-warps N]] [--device N]
+//   nu_scaler_cli interpolate <a.png> <b.png> <out.png> [--t X | --multiplier M] [--flow [--flow-warps N] [--flow-median 0|3|5]] [--device N]
 //                             [--method block_matching [--quality high|medium|low] [--bidirectional [--bidir-tolerance N]]]
 //   nu_scaler_cli scene <a.png> <b.png> [--mad N] [--hist N] [--device N]   (the scene-cut detector: cut=0|1 mad=.. hist_permille=..)
 //   nu_scaler_cli compare <a.png> <b.png> [--device N]   (MSE / PSNR / SSIM, ErrorMetrics: Nu_scale/src/upscale/common.rs:475-543)
@@ -36,8 +36,8 @@ int usage(int rc)
                  "usage: nu_scaler_cli upscale <in.png> <out.png> [--algorithm nearest|bilinear|bicubic|lanczos3|triangle|fsr1|easu]\n"
                  "                             [--scale S] [--tech fsr|fallback|none] [--quality ultra|quality|balanced|performance]\n"
                  "                             [--device N]\n"
-                 "       nu_scaler_cli interpolate <a.png> <b.png> <out.png> [--t X | --multiplier 2..8] [--flow [--flow-warps 0..4]]\n"
-                 "                             [--device N]\n"
+                 "       nu_scaler_cli interpolate <a.png> <b.png> <out.png> [--t X | --multiplier 2..8] [--flow [--flow-warps 0..4]\n"
+                 "                             [--flow-median 0|3|5]] [--device N]\n"
                  "                             [--method block_matching [--quality high|medium|low]] [--scene-detect]\n"
                  "                             [--bidirectional [--bidir-tolerance 0..96]]   (block matching: forward-backward check)\n"
                  "       nu_scaler_cli scene <a.png> <b.png> [--mad 0..255] [--hist 0..1000] [--device N]\n"
@@ -231,6 +231,21 @@ int cmd_interpolate(const Args &a)
         }
         flow_warps = (uint32_t)v;
     }
+    const auto median_it = a.options.find("flow-median");
+    uint32_t flow_median = 0; // the estimator's median filter behind every Jacobi run (nus_flow_set_median)
+    if (median_it != a.options.end()) {
+        if (!a.flow) {
+            std::fprintf(stderr, "nu_scaler_cli: error: --flow-median needs --flow\n");
+            return usage(2);
+        }
+        char *end = nullptr;
+        const long v = std::strtol(median_it->second.c_str(), &end, 10);
+        if (end == median_it->second.c_str() || *end != '\0' || (v != 0 && v != 3 && v != 5)) {
+            std::fprintf(stderr, "nu_scaler_cli: error: --flow-median must be 0, 3 or 5\n");
+            return usage(2);
+        }
+        flow_median = (uint32_t)v;
+    }
     nus_cli::Image fa, fb;
     std::string err = nus_cli::read_png(a.positional[0], fa);
     if (err.empty()) err = nus_cli::read_png(a.positional[1], fb);
@@ -276,6 +291,7 @@ int cmd_interpolate(const Args &a)
         flow.resize((size_t)fa.width * fa.height * 2);
         int rc = nus_flow_set_device(f, device);
         if (rc == NUS_OK) rc = nus_flow_set_warps(f, flow_warps);
+        if (rc == NUS_OK) rc = nus_flow_set_median(f, flow_median);
         // 3 levels, 50 coarse + 10 refining Jacobi steps, lambda as the Python mirror's FlowEstimator defaults
         if (rc == NUS_OK)
             rc = nus_flow_estimate(f, fa.rgba.data(), fb.rgba.data(), fa.width, fa.height, 3, 50, 10, 0.0004f, flow.data());

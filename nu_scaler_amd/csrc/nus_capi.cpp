@@ -88,6 +88,7 @@ static_assert(sizeof(nus_scene_measures) == 16 && NUS_SCENE_DEFAULT_MAD == nus::
                   NUS_SCENE_DEFAULT_HIST_PERMILLE == nus::kSceneDefaultHistPermille,
               "the C header's scene-detector layout and defaults are the kernels'");
 static_assert(NUS_FLOW_MAX_WARPS == nus::kFlowMaxWarps, "the C header's NUS_FLOW_MAX_WARPS is the estimator's bound");
+static_assert(NUS_FLOW_MEDIAN_MAX == nus::kFlowMedianMax, "the C header's NUS_FLOW_MEDIAN_MAX is the estimator's largest window");
 static_assert(NUS_INTERP_MAX_TIMES == nus::kInterpMaxTimes, "the C header's NUS_INTERP_MAX_TIMES is the kernels' time-set size");
 
 extern "C" {
@@ -706,6 +707,12 @@ int nus_flow_set_warps(nus_flow *h, uint32_t warps)
     return guarded<int>("nus_flow_set_warps", [&]() -> int { return h ? h->impl.set_warps(warps) : null_handle(); });
 }
 int nus_flow_warps(const nus_flow *h) { return h ? h->impl.warps() : NUS_ERR_INVALID_ARGUMENT; }
+int nus_flow_set_median(nus_flow *h, uint32_t size)
+{
+    return guarded<int>("nus_flow_set_median", [&]() -> int { return h ? h->impl.set_median(size) : null_handle(); });
+}
+int nus_flow_median_size(const nus_flow *h) { return h ? h->impl.median_size() : NUS_ERR_INVALID_ARGUMENT; }
+size_t nus_flow_workspace_bytes(nus_flow *h) { return h ? h->impl.workspace_bytes() : 0; }
 const char *nus_flow_last_error(const nus_flow *h) { return h ? h->impl.last_error() : "null handle"; }
 
 int nus_flow_rgba8_to_f32(nus_flow *h, const uint8_t *in, uint32_t w, uint32_t hgt, float *out)
@@ -733,6 +740,11 @@ int nus_flow_upsample(nus_flow *h, const float *src, uint32_t sw, uint32_t sh, f
                       float scale)
 {
     return guarded<int>("nus_flow_upsample", [&]() -> int { return h ? h->impl.upsample(src, sw, sh, dst, dw, dh, scale) : null_handle(); });
+}
+
+int nus_flow_median(nus_flow *h, const float *flow_in, uint32_t w, uint32_t hgt, uint32_t size, float *flow_out)
+{
+    return guarded<int>("nus_flow_median", [&]() -> int { return h ? h->impl.median(flow_in, w, hgt, size, flow_out) : null_handle(); });
 }
 
 int nus_flow_warp_coefficients(nus_flow *h, const float *i1, const float *i2, const float *flow, uint32_t w, uint32_t hgt, float *coef_out)

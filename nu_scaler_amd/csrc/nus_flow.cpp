@@ -38,6 +38,22 @@ int HipFlowEstimator::set_warps(uint32_t warps)
     return kOk;
 }
 
+int HipFlowEstimator::set_median(uint32_t size)
+{
+    std::lock_guard<std::mutex> lk(mu_);
+    if (size != 0 && size != 3 && size != 5) return fail(kInvalidArgument, fmt("nus_flow_set_median: 0 (off), 3 or 5, got %u", size));
+    median_ = size;
+    return kOk;
+}
+
+size_t HipFlowEstimator::workspace_bytes()
+{
+    std::lock_guard<std::mutex> lk(mu_);
+    size_t total = 0;
+    for (const DeviceBuffer &s : slot_) total += s.capacity();
+    return total;
+}
+
 int HipFlowEstimator::set_device(int device)
 {
     std::lock_guard<std::mutex> lk(mu_);
@@ -197,6 +213,23 @@ int HipFlowEstimator::upsample(const float *src, uint32_t sw, uint32_t sh, float
     });
 }
 
+int HipFlowEstimator::median(const float *flow_in, uint32_t w, uint32_t h, uint32_t size, float *flow_out)
+{
+    if (size != 3 && size != 5) {
+        std::lock_guard<std::mutex> lk(mu_);
+        return fail(kInvalidArgument, fmt("nus_flow_median: size 3 or 5, got %u", size));
+    }
+    const size_t fb = (size_t)w * h * 8;
+    return primitive({{w, h}}, flow_in && flow_out, {{kFlowA, fb, flow_in}, {kFlowB, fb, nullptr}}, flow_out, fb, [&](const void *&result) -> int {
+        FlowMedianLaunch M;
+        M.img = {w, h, 1, stream_};
+        M.size = size, M.in = f32(kFlowA), M.out = f32(kFlowB);
+        NUS_HIP(launch_flow_median(M));
+        result = f32(kFlowB);
+        return kOk;
+    });
+}
+
 int HipFlowEstimator::plan(uint32_t w, uint32_t h, uint32_t levels, Pyramid &g)
 {
     if (levels == 0 || levels > 12) return fail(kInvalidArgument, "flow: levels must be 1..12");
@@ -273,6 +306,17 @@ int HipFlowEstimator::solve(Slot pyr_a, Slot pyr_b, const Pyramid &g, const Flow
     // the last launch of the finest level writes the caller's buffer directly
     bool zero = true;
     // `last`: no further round of the level follows; `on_coef`: the coefficient kernels whatever set_tiled says (a warped round)
+    // the median behind a Jacobi run (FlowParams::median): from the buffer the run left into the other one -- the caller's, if this
+    // was the finest level's last run -- and the two names swapped
+    auto median_behind = [&](uint32_t l, bool last) -> int {
+        FlowMedianLaunch M;
+        M.img = {g.w[l], g.h[l], 1, stream};
+        M.size = p.median, M.in = f0, M.out = l == 0 && last ? static_cast<float *>(d_flow_out) : f1;
+        NUS_HIP(launch_flow_median(M));
+        if (M.out == f1) f1 = f0;
+        f0 = M.out;
+        return kOk;
+    };
     auto iterate = [&](uint32_t l, uint32_t iters, bool prepared, bool last = true, bool on_coef = false) -> int {
         if (iters == 0) return kOk;
         const HsPrepareLaunch P = prepare(l);
@@ -281,16 +325,16 @@ int HipFlowEstimator::solve(Slot pyr_a, Slot pyr_b, const Pyramid &g, const Flow
             HsIterateLaunch I;
             I.img = P.img;
             I.coef = P.coef, I.lambda = p.lambda, I.iterations = iters, I.zero_start = zero, I.flow_a = f0, I.flow_b = f1;
-            I.final_out = l == 0 && last ? static_cast<float *>(d_flow_out) : nullptr, I.kernel = jacobi_;
+            I.final_out = l == 0 && last && !p.median ? static_cast<float *>(d_flow_out) : nullptr, I.kernel = jacobi_;
             HsIterateResult R;
             NUS_HIP(launch_hs_iterate(I, &R));
             f0 = R.flow, f1 = R.spare;
             zero = false;
-            return kOk;
+            return p.median ? median_behind(l, last) : kOk;
         }
         for (uint32_t i = 0; i < iters; ++i, std::swap(f0, f1))
             NUS_HIP(launch_horn_schunck(P.i1, P.i2, f0, f1, g.w[l], g.h[l], p.lambda, stream));
-        return kOk;
+        return p.median ? median_behind(l, last) : kOk;
     };
     if (!tiled_ || p.coarse_iters == 0) {
         NUS_HIP(hipMemsetAsync(f0, 0, (size_t)g.w[L] * g.h[L] * 8, stream));
@@ -575,7 +619,9 @@ int HipFlowEstimator::solve_batch(const StreamJob &J, const Pyramid &g, const Fl
     // then) may be handed to the solver only if that launch is what finishes level 0 -- every other kernel writes 2 x f32 per cell
     // and must be kept in the workspace, its flow converted afterwards.
     const bool fast_last = level_kernel(0) == kJacobiStreamFast && (nl > 1 ? p.refine_iters > 0 : p.coarse_iters > 0);
-    float *const solver_out = J.flow_half && !fast_last ? nullptr : out;
+    // With the median (FlowParams::median) no Jacobi launch finishes level 0: each writes the workspace, f32, and the median behind
+    // the last one writes the caller's f32 buffer if there is one (halves: converted afterwards, wrote_half is never set).
+    float *const solver_out = p.median || (J.flow_half && !fast_last) ? nullptr : out;
     auto prepare = [&](uint32_t l) { // the derivatives of level l from the luminance planes of each pair's two frames
         HsPrepareLaunch P;
         P.img = {g.w[l], g.h[l], pairs, stream};
@@ -598,11 +644,20 @@ int HipFlowEstimator::solve_batch(const StreamJob &J, const Pyramid &g, const Fl
         I.kernel = level_kernel(l);
         if (coarse) I.coarse = coarse_of(l);
         I.coarse.scale = 2.0f;
-        I.final_half = l == 0 && J.flow_half;
+        I.final_half = l == 0 && J.flow_half && !p.median;
         HsIterateResult r;
         NUS_HIP(launch_hs_iterate(I, &r));
         f0 = r.flow, f1 = r.spare;
         if (l == 0) R = r;
+        if (p.median) { // from the buffer the run left into the other one, the two names swapped
+            FlowMedianLaunch M;
+            M.img = I.img;
+            M.size = p.median, M.in = f0, M.in_stride = cells[l];
+            M.out = l == 0 && last && out && !J.flow_half ? out : f1, M.out_stride = cells[l];
+            NUS_HIP(launch_flow_median(M));
+            if (M.out == f1) f1 = f0;
+            f0 = M.out;
+        }
         return kOk;
     };
     // coarsest level: from zero flow (compute_coarse_flow, :1136-1154)

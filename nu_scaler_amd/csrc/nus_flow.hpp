@@ -21,11 +21,16 @@ namespace nus {
 // warps (0..kFlowMaxWarps; the handle's setting, set_warps): rounds per finer level, each re-linearising the data term about the
 // level's current flow -- frame B sampled through it -- before its refine_iters steps.  0: linearised about zero flow, the
 // upsampled flow only the Jacobi start value.
-constexpr uint32_t kFlowMaxWarps = 4; // NUS_FLOW_MAX_WARPS
+// median (0, 3 or 5; the handle's setting, set_median): after every Jacobi run of a level -- the coarsest level's steps, a finer
+// level's, each round's of a warped level -- the level's flow is replaced by its component-wise median x median median (window
+// centred, border replicated) before the next stage reads it.  A run of zero steps is followed by none.  0: no such stage.
+constexpr uint32_t kFlowMaxWarps = 4;  // NUS_FLOW_MAX_WARPS
+constexpr uint32_t kFlowMedianMax = 5; // NUS_FLOW_MEDIAN_MAX
 struct FlowParams {
     uint32_t levels = 0, coarse_iters = 0, refine_iters = 0;
     float lambda = 0.0f;
     uint32_t warps = 0;
+    uint32_t median = 0;
 };
 
 class HipFlowEstimator : public HostErrors {
@@ -48,6 +53,8 @@ public:
     int horn_schunck(const float *i1, const float *i2, const float *flow_in_or_null, uint32_t w, uint32_t h,
                      float lambda, uint32_t iterations, float *flow_out);
     int upsample(const float *src, uint32_t sw, uint32_t sh, float *dst, uint32_t dw, uint32_t dh, float scale);
+    // The stage set_median adds behind every Jacobi run, on its own: the component-wise size x size median (3 or 5) of a flow.
+    int median(const float *flow_in, uint32_t w, uint32_t h, uint32_t size, float *flow_out);
     // The two halves of a re-linearised level (set_warps).  warp_coefficients: (Ix, Iy, It') per cell, w*h*3 floats, with frame B's
     // luminance sampled through `flow` (null: zero flow, i.e. It = L2 - L1).  horn_schunck_coef: Jacobi steps on such coefficients.
     int warp_coefficients(const float *i1, const float *i2, const float *flow_or_null, uint32_t w, uint32_t h, float *coef_out);
@@ -65,6 +72,13 @@ public:
     // warped level's Jacobi steps run on coefficient planes in the exact kernels, in FAST mode too (inside FAST's contract).
     int set_warps(uint32_t warps);
     int warps() const { return (int)warps_; }
+    // Median filter of the level's flow behind every Jacobi run of every estimator entry point (FlowParams::median): 0 (default,
+    // off), 3 or 5.  A selection, so EXACT and FAST run the same kernel; the Jacobi launch that would have written the caller's
+    // buffer (or Rg16Float halves) writes the workspace instead, and the median writes the caller's f32 buffer.
+    int set_median(uint32_t size);
+    int median_size() const { return (int)median_; }
+    // Bytes of device workspace the handle holds (the sum of its grow-only slots): what "reserves the workspace it did" is checked with.
+    size_t workspace_bytes();
     // Scene-cut detection in front of interpolate_multi_device_stream and the cut-aware output rule behind it (nus_scene_* of the C
     // header): off by default.  On, the in-between frames of a pair the detector flags are repeats of the nearer real frame.
     int set_scene_detect(int enabled, uint32_t mad_threshold, uint32_t hist_permille);
@@ -105,7 +119,7 @@ private:
         kScene = 11,                  // the scene detector's workspace and cut flags
     };
     static constexpr int kSlotCount = 12;
-    FlowParams with_warps(FlowParams p) const { return p.warps = warps_, p; } // (mu_ held) what the entry points hand on
+    FlowParams with_warps(FlowParams p) const { return p.warps = warps_, p.median = median_, p; } // (mu_ held) what the entry points hand on: the handle's settings
     // the finer levels of such an estimate take `warps` rounds of launch_hs_warp_setup + Jacobi steps on coefficient planes
     static bool warped(const FlowParams &p) { return p.warps > 0 && p.refine_iters > 0; }
     struct MidTimes { // the multi-time warp behind the estimator (interpolate_multi_device_stream)
@@ -169,6 +183,7 @@ private:
     bool tiled_ = true;
     int jacobi_ = 0; // JacobiKernel
     uint32_t warps_ = 0; // set_warps
+    uint32_t median_ = 0; // set_median
     bool fast_ = false; // set_mode(1): the estimator's Jacobi steps in FAST arithmetic (k_hs_stream_fast), every level streamed
     hipStream_t stream_ = nullptr;
     bool scene_ = false; // set_scene_detect

@@ -256,6 +256,17 @@ hipError_t launch_hs_iterate(const HsIterateLaunch &L, HsIterateResult *result);
 bool hs_iterate_streams(uint32_t w, uint32_t h, uint32_t n, int kernel);
 // bilinear upsample of `coarse` into D.n flows of D.w x D.h at dst (item stride in cells)
 hipError_t launch_flow_upsample(const FlowImages &D, const HsCoarseFlow &coarse, float *dst, size_t dst_stride);
+// Component-wise size x size median (3 or 5) of img.n flows of img.w x img.h (nus_k_flow_median.hip; FlowParams::median): the
+// window centred on the cell, coordinates clamped into the flow.  `in` and `out` must not overlap (one tile's halo is another's
+// output); strides in cells (float2).
+struct FlowMedianLaunch {
+    FlowImages img;
+    uint32_t size = 3;
+    const float *in = nullptr;
+    float *out = nullptr;
+    size_t in_stride = 0, out_stride = 0;
+};
+hipError_t launch_flow_median(const FlowMedianLaunch &L);
 
 // Box calibration (nus_k_probe.hip; bench.py's denominators, not on the product path): kind 0 hipMemcpyDtoDAsync, 1 stream
 // copy, 2 write-only, 3 read-only (d_dst: 4 bytes of device memory), 4 one read : four writes (d_dst holds 4 * bytes),

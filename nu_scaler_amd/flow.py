@@ -7,6 +7,8 @@ reference's refine path is dead code -- a coarse-to-fine warm start: x2 bilinear
 and more Jacobi steps per finer level.  The result is the dense (dx, dy) field that
 `WgpuFrameInterpolator.interpolate_py(..., flow=...)` consumes.  With `warps=N` (off by default) every finer level is
 re-linearised N times about the flow it has -- frame B sampled through it -- which is what follows motion of more than a pixel.
+With `median=3` or `5` (off by default; meant for `warps >= 1`) the level's flow is median-filtered after every Jacobi run, which
+keeps motion boundaries from turning into ramps.
 """
 from __future__ import annotations
 
@@ -26,9 +28,19 @@ def check_warps(warps) -> int:
     return int(warps)
 
 
+MEDIAN_SIZES = (0, 3, 5)  # what nus_flow_set_median takes (0: off)
+
+
+def check_median(size) -> int:
+    """`size` as one of MEDIAN_SIZES, or ValueError (what every Python entry point that takes the setting shares)."""
+    if isinstance(size, bool) or not isinstance(size, (int, np.integer)) or int(size) not in MEDIAN_SIZES:
+        raise ValueError(f"flow median must be 0 (off), 3 or 5, got {size!r}")
+    return int(size)
+
+
 class FlowEstimator:
     def __init__(self, levels: int = 3, coarse_iterations: int = 50, refine_iterations: int = 10,
-                 lambda_: float = 0.02 ** 2, *, device: int = 0, warps: int = 0):
+                 lambda_: float = 0.02 ** 2, *, device: int = 0, warps: int = 0, median: int = 0):
         # lambda default: the value of the reference's own (ignored) test, wgpu_interpolator.rs:1535
         self._lib = C.lib()
         self._h = self._lib.nus_flow_create()
@@ -39,6 +51,8 @@ class FlowEstimator:
         self._check(self._lib.nus_flow_set_device(self._h, int(device)))
         if warps != 0:
             self.set_warps(warps)
+        if median != 0:
+            self.set_median(median)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -68,6 +82,23 @@ class FlowEstimator:
     @property
     def warps(self) -> int:
         return int(self._lib.nus_flow_warps(self._h))
+
+    def set_median(self, size: int) -> None:
+        """Median filter of the flow behind every Jacobi run (nus_flow_set_median; 0, the default, is off; 3 or 5 is the window):
+        after the coarsest level's steps, a finer level's steps and each re-linearisation round the level's flow is replaced by its
+        component-wise size x size median (border replicated).  Meant for `warps >= 1` (with warps = 0 the result is mixed); small
+        frames want 3.  Applies to every estimator entry point of this object."""
+        s = check_median(size)
+        self._check(self._lib.nus_flow_set_median(self._h, s))
+
+    @property
+    def median_size(self) -> int:
+        return int(self._lib.nus_flow_median_size(self._h))
+
+    @property
+    def workspace_bytes(self) -> int:
+        """Bytes of device workspace the handle holds now (nus_flow_workspace_bytes; grow-only)."""
+        return int(self._lib.nus_flow_workspace_bytes(self._h))
 
     def set_scene_detect(self, enabled: bool, mad_threshold: int = C.SCENE_DEFAULT_MAD,
                          hist_permille: int = C.SCENE_DEFAULT_HIST_PERMILLE) -> None:
@@ -155,6 +186,19 @@ class FlowEstimator:
         sh, sw = flow.shape[:2]
         out = np.empty((dh, dw, 2), np.float32)
         self._check(self._lib.nus_flow_upsample(self._h, flow.ctypes.data, sw, sh, out.ctypes.data, dw, dh, float(scale)))
+        return out
+
+    def median(self, flow: np.ndarray, size: int) -> np.ndarray:
+        """The component-wise size x size median (3 or 5) of an (h, w, 2) flow, border replicated: the stage `set_median` adds
+        behind every Jacobi run, on its own (nus_flow_median)."""
+        flow = self._f32(flow)
+        if flow.ndim != 3 or flow.shape[2] != 2:
+            raise ValueError(f"expected an (h, w, 2) flow, got {flow.shape}")
+        if isinstance(size, bool) or size not in (3, 5):
+            raise ValueError(f"median size must be 3 or 5, got {size!r}")
+        h, w = flow.shape[:2]
+        out = np.empty((h, w, 2), np.float32)
+        self._check(self._lib.nus_flow_median(self._h, flow.ctypes.data, w, h, int(size), out.ctypes.data))
         return out
 
     # ---- full estimator ------------------------------------------------------------

@@ -178,12 +178,23 @@ def _check_flow_warps(flow_warps, estimate_flow: bool) -> int:
     return flow_warps
 
 
+def _check_flow_median(flow_median, estimate_flow: bool) -> int:
+    from .flow import check_median
+
+    flow_median = check_median(flow_median)
+    if flow_median and not estimate_flow:
+        raise ValueError("flow_median needs estimate_flow (--flow-median needs --flow)")
+    return flow_median
+
+
 def interpolate_image_files(path_a: str, path_b: str, output_path: str, time_t: float = 0.5, estimate_flow: bool = False,
-                            device: int = 0, flow_warps: int = 0) -> tuple[int, int]:
+                            device: int = 0, flow_warps: int = 0, flow_median: int = 0) -> tuple[int, int]:
     """The in-between frame of two equally sized images (wgpu_interpolator.rs:215-491); with
     `estimate_flow` the Horn-Schunck front end supplies the motion field (`flow_warps`: its re-linearisation rounds per finer
-    level, FlowEstimator.set_warps), otherwise zero flow as the reference's live path."""
+    level, FlowEstimator.set_warps; `flow_median`: its median filter behind every Jacobi run, 0, 3 or 5, FlowEstimator.set_median),
+    otherwise zero flow as the reference's live path."""
     flow_warps = _check_flow_warps(flow_warps, estimate_flow)
+    flow_median = _check_flow_median(flow_median, estimate_flow)
     w, h, a = read_png(path_a)
     wb, hb, b = read_png(path_b)
     if (w, h) != (wb, hb):
@@ -192,7 +203,7 @@ def interpolate_image_files(path_a: str, path_b: str, output_path: str, time_t: 
     flow = None
     if estimate_flow:
         from .flow import FlowEstimator
-        flow = FlowEstimator(device=device, warps=flow_warps).estimate(a, b, w, h)
+        flow = FlowEstimator(device=device, warps=flow_warps, median=flow_median).estimate(a, b, w, h)
     out = it.interpolate_py(a, b, w, h, time_t=time_t, flow=flow) if flow is not None else it.interpolate_py(a, b, w, h, time_t=time_t)
     write_png(output_path, w, h, out)
     return w, h
@@ -205,13 +216,14 @@ def multi_output_paths(output_path: str, multiplier: int) -> list[str]:
 
 
 def interpolate_image_files_multi(path_a: str, path_b: str, output_path: str, multiplier: int, estimate_flow: bool = False,
-                                  device: int = 0, scene_detect: bool = False, flow_warps: int = 0) -> list[str]:
+                                  device: int = 0, scene_detect: bool = False, flow_warps: int = 0, flow_median: int = 0) -> list[str]:
     """The M - 1 in-between frames of a frame-rate multiplier M (t = k / M) from one multi-time call, written to
     multi_output_paths(output_path, M); with `estimate_flow` the flow is estimated once for all of them.  `scene_detect`: a
     pair the scene-cut detector flags gives repeats of the nearer frame instead of blends."""
     from .interpolator import frame_times
 
     flow_warps = _check_flow_warps(flow_warps, estimate_flow)
+    flow_median = _check_flow_median(flow_median, estimate_flow)
     times = frame_times(multiplier)
     w, h, a = read_png(path_a)
     wb, hb, b = read_png(path_b)
@@ -221,7 +233,7 @@ def interpolate_image_files_multi(path_a: str, path_b: str, output_path: str, mu
     flow = None
     if estimate_flow:
         from .flow import FlowEstimator
-        flow = FlowEstimator(device=device, warps=flow_warps).estimate(a, b, w, h)
+        flow = FlowEstimator(device=device, warps=flow_warps, median=flow_median).estimate(a, b, w, h)
     frames = it.interpolate_multi_py(a, b, w, h, times=times, flow=flow, scene_detect=scene_detect)
     paths = multi_output_paths(output_path, multiplier)
     for path, out in zip(paths, frames):

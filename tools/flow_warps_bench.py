@@ -5,7 +5,9 @@ tools/blockmatch_bench.py --stream), 3 levels, 50 + 10 steps, for warps = 0, 1, 
 launch stream, every leg warmed, then the legs of a mode alternate bracket by bracket in one process; each figure is the median of
 its brackets, and the smallest and largest bracket are printed beside it.  warps = 0 on the same binary in the same call is the
 baseline of the ratios.  One JSON line per case.
-usage: python tools/flow_warps_bench.py [--reps R] [--rounds N] [--frames F] [--quick]"""
+--median: the median mode instead (nus_flow_set_median): for EXACT and FAST at warps 1 and 2 the legs median 0 / 3 / 5 alternate the
+same way, and median 0 at the same warps is the baseline of the ratios.
+usage: python tools/flow_warps_bench.py [--median] [--reps R] [--rounds N] [--frames F] [--quick]"""
 import argparse
 import json
 import os
@@ -20,6 +22,8 @@ import nu_scaler_amd as nsc  # noqa: E402
 from nu_scaler_amd import synthetic as syn  # noqa: E402
 
 WARPS = (0, 1, 2)
+MEDIAN_WARPS = (1, 2)  # --median: the settings the mode is meant for
+MEDIANS = (0, 3, 5)
 
 
 def timed_alternating(fns, reps, warm_seconds, rounds):
@@ -52,6 +56,7 @@ def main():
     ap.add_argument("--warm-seconds", type=float, default=0.5)
     ap.add_argument("--frames", type=int, default=32)
     ap.add_argument("--quick", action="store_true", help="one warm-up call and one bracket of 2 calls per leg")
+    ap.add_argument("--median", action="store_true", help="time median 0 / 3 / 5 at warps 1 and 2 instead of warps 0 / 1 / 2")
     args = ap.parse_args()
     if nsc.device_count() < 1:
         raise SystemExit("flow_warps_bench: no HIP device")
@@ -65,7 +70,25 @@ def main():
     for k in range(n):
         frames[k + 1] = torch.roll(frames[k], (5 - 2 * (k % 6), 3 * (k % 7) - 9), (0, 1))
     flows = torch.empty((n, h, w, 2), dtype=torch.float32, device=dev)
-    for mode in ("exact", "fast"):
+    for mode, warps in [(m, wn) for m in ("exact", "fast") for wn in MEDIAN_WARPS] if args.median else []:
+        handles = []
+        for median in MEDIANS:
+            fe = nsc.FlowEstimator(levels=3, coarse_iterations=50, refine_iterations=10, warps=warps, median=median)
+            fe.set_mode(mode)
+            handles.append(fe)
+        legs = [lambda fe=fe: fe.estimate_device_stream(frames.data_ptr(), n_frames, w, h, flows.data_ptr(), s) for fe in handles]
+        brackets = timed_alternating(legs, args.reps, args.warm_seconds, args.rounds)
+        us = [[x * 1e3 / n for x in g] for g in brackets]
+        med = [g[len(g) // 2] for g in us]
+        for median, g, m in zip(MEDIANS, us, med):
+            print(json.dumps({"case": f"{w}x{h}x{n}_{mode}_warps{warps}_median{median}", "width": w, "height": h, "pairs": n, "mode": mode,
+                              "warps": warps, "median": median, "levels": 3, "coarse_iterations": 50, "refine_iterations": 10,
+                              "working_set_bytes": frames.numel(), "brackets": len(g), "calls_per_bracket": args.reps,
+                              "us_per_pair": round(m, 2), "us_per_pair_min": round(g[0], 2), "us_per_pair_max": round(g[-1], 2),
+                              "over_median0": round(m / med[0], 3)}), flush=True)
+        del handles, legs
+        torch.cuda.synchronize()
+    for mode in () if args.median else ("exact", "fast"):
         handles = []
         for warps in WARPS:
             fe = nsc.FlowEstimator(levels=3, coarse_iterations=50, refine_iterations=10, warps=warps)
