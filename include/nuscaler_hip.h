@@ -377,6 +377,31 @@ int nus_interp_set_flow_format(nus_interp *h, int format);
 typedef enum nus_interp_mode_t { NUS_INTERP_MODE_EXACT = 0, NUS_INTERP_MODE_FMA = 1 } nus_interp_mode_t;
 int nus_interp_set_mode(nus_interp *h, int mode);
 int nus_interp_mode(const nus_interp *h);
+/* Projection rounds of the dense-flow warp: the flow evaluated at the in-between time (off by default: 0).  BUILD-DEFINED -- the
+ * reference has nothing like it.  A flow f lives on frame A's grid: f(q) says where A's pixel q goes.  The warp reads it at the
+ * OUTPUT pixel p of the in-between frame, but the content that is at p at time t came from the A-pixel q with q + t f(q) = p, and
+ * its vector is f(q); within t |f| pixels of a motion boundary the two differ by the whole motion difference.  With rounds = N > 0
+ * the warp of one pair of w x h with flow f (f32, or Rg16Float widened exactly) computes for output pixel p = (x, y) and time t
+ *     g = f[y][x]
+ *     repeat N times:
+ *         qx = clamp(x - t g.x, 0, w-1);  qy = clamp(y - t g.y, 0, h-1)      (f32; t g.x one product, then one subtraction)
+ *         x0 = floor(qx); x1 = min(x0+1, w-1); fx = qx - x0                  (the same in y)
+ *         top = f[y0][x0] (1-fx) + f[y0][x1] fx;  bot = f[y1][x0] (1-fx) + f[y1][x1] fx
+ *         g   = top (1-fy) + bot fy          (per component; every product and sum rounded separately)
+ * and then samples and blends exactly as without the setting, with g in place of f[y][x].  The projection arithmetic is the same in
+ * NUS_INTERP_MODE_EXACT and NUS_INTERP_MODE_FMA (separate roundings, no contraction); only the two frame samples that follow differ
+ * by mode: an EXACT frame is the oracle's warp + blend with the flow g byte for byte, an FMA frame is held by the FMA contract above
+ * with g as the flow.  g stays f32 (never re-rounded to half).  At the right / bottom border the kernels may read the cell pair
+ * (w-2, w-1) with fraction 1 instead of (w-1, w-1) with fraction 0: the same value (flows compare as values, -0 equals +0; NaN and
+ * Inf flows are out of contract).  t = 0 gives g = f[y][x]; odd and even N oscillate at boundary cells, which is why N is a setting
+ * (measured gains: DESIGN.md 8.1).  Every gather stays inside its own pair's flow plane.  The setting applies to every
+ * nus_interp_interpolate* entry point given a flow (the multi-time ones project per time); flow == NULL runs the unchanged zero-flow
+ * kernel, and with rounds = 0 every entry point launches the kernels and writes the bytes it did before the setting existed.  No
+ * workspace.  rounds > NUS_FLOW_MAX_PROJECT: NUS_ERR_INVALID_ARGUMENT before any HIP call, the text beginning
+ * "nus_interp_set_flow_project:", the setting unchanged. */
+#define NUS_FLOW_MAX_PROJECT 4
+int nus_interp_set_flow_project(nus_interp *h, uint32_t rounds);
+int nus_interp_flow_project(const nus_interp *h);
 
 /* trait FrameInterpolator (nu_scaler_core/src/interpolation/mod.rs:29-44) -- the shape the dead-code trait gives an
  * interpolator, next to the live pyclass's per-call form below:
@@ -551,6 +576,14 @@ int nus_flow_set_median(nus_flow *h, uint32_t size);
 int nus_flow_median_size(const nus_flow *h);
 /* Bytes of device workspace the handle holds now (grow-only; 0 for a null handle or before the first call that needs a device). */
 size_t nus_flow_workspace_bytes(nus_flow *h);
+/* Projection rounds (BUILD-DEFINED; the rule is stated at nus_interp_set_flow_project) of the warp behind the estimator:
+ * nus_flow_interpolate_device_stream and nus_flow_interpolate_multi_device_stream (per time) warp with the projected vector g
+ * instead of the flow at the output pixel.  0 (default) .. NUS_FLOW_MAX_PROJECT.  The flows written to d_flows are unchanged, the
+ * estimate entry points are untouched, no workspace is added; the frames equal nus_flow_estimate_device_stream followed by
+ * nus_interp_interpolate_multi_device in FMA mode with the same rounds.  With 0: the kernels and bytes from before the setting.
+ * rounds > NUS_FLOW_MAX_PROJECT: NUS_ERR_INVALID_ARGUMENT before any HIP call, the text beginning "nus_flow_set_project:". */
+int nus_flow_set_project(nus_flow *h, uint32_t rounds);
+int nus_flow_project_rounds(const nus_flow *h);
 const char *nus_flow_last_error(const nus_flow *h);
 
 /* primitives on host buffers */
@@ -565,6 +598,11 @@ int nus_flow_upsample(nus_flow *h, const float *src, uint32_t sw, uint32_t sh,
 /* The stage nus_flow_set_median adds, on its own: the component-wise size x size median (3 or 5) of a w*h*2 flow, border
  * replicated.  size and pointers are checked before any HIP call. */
 int nus_flow_median(nus_flow *h, const float *flow_in, uint32_t w, uint32_t hgt, uint32_t size, float *flow_out);
+/* The projection of nus_interp_set_flow_project on its own (BUILD-DEFINED): flow_out = the vector g of every cell of a w*h*2 f32
+ * flow after `rounds` rounds (0 .. NUS_FLOW_MAX_PROJECT; 0 copies) at time t -- the device function of the projecting warp
+ * kernels.  rounds above the bound, a NaN t and null pointers are refused before any HIP call, the text beginning
+ * "nus_flow_project:". */
+int nus_flow_project(nus_flow *h, const float *flow_in, uint32_t w, uint32_t hgt, float t, uint32_t rounds, float *flow_out);
 /* The two halves of a re-linearised level (nus_flow_set_warps), always exact.  _warp_coefficients: f32 RGBA images and a w*h*2
  * flow -> w*h*3 floats (Ix, Iy, It') per cell; flow == NULL is zero flow and gives (Ix, Iy, It = L2 - L1).
  * _horn_schunck_coef: `iterations` Jacobi steps on such coefficients; flow_in == NULL starts from zero. */

@@ -33,6 +33,7 @@ METRIC_MSE, METRIC_SSIM = 1, 2  # nus_metric (bit mask; PSNR comes with MSE)
 INTERP_QUALITY_HIGH, INTERP_QUALITY_MEDIUM, INTERP_QUALITY_LOW = 0, 1, 2  # nus_interp_quality_level
 FLOW_F32, FLOW_F16 = 0, 1  # nus_flow_format
 FLOW_MAX_WARPS = 4  # NUS_FLOW_MAX_WARPS
+FLOW_MAX_PROJECT = 4  # NUS_FLOW_MAX_PROJECT: projection rounds of the dense-flow warp (nus_interp_set_flow_project, nus_flow_set_project)
 FLOW_MEDIAN_MAX = 5  # NUS_FLOW_MEDIAN_MAX: nus_flow_set_median takes 0 (off), 3 or 5
 INTERP_MODE_EXACT, INTERP_MODE_FMA = 0, 1  # nus_interp_mode_t
 BM_TIES_SCAN, BM_TIES_CENTER = 0, 1  # nus_bm_tie_order
@@ -106,6 +107,8 @@ SIGNATURES = [
     ("nus_interp_set_flow_format", _i, [_vp, _i]),
     ("nus_interp_set_mode", _i, [_vp, _i]),
     ("nus_interp_mode", _i, [_vp]),
+    ("nus_interp_set_flow_project", _i, [_vp, _u32]),
+    ("nus_interp_flow_project", _i, [_vp]),
     ("nus_interp_initialize", _i, [_vp, _u32, _u32]),
     ("nus_interp_interpolate_frames", _i, [_vp, _vp, _sz, _vp, _sz, _f, _vp, _sz]),
     ("nus_interp_name", _cp, [_vp]),
@@ -139,6 +142,8 @@ SIGNATURES = [
     ("nus_flow_set_median", _i, [_vp, _u32]),
     ("nus_flow_median_size", _i, [_vp]),
     ("nus_flow_workspace_bytes", _sz, [_vp]),
+    ("nus_flow_set_project", _i, [_vp, _u32]),
+    ("nus_flow_project_rounds", _i, [_vp]),
     ("nus_flow_last_error", _cp, [_vp]),
     ("nus_flow_rgba8_to_f32", _i, [_vp, _vp, _u32, _u32, _vp]),
     ("nus_flow_blur", _i, [_vp, _vp, _u32, _u32, _vp]),
@@ -146,6 +151,7 @@ SIGNATURES = [
     ("nus_flow_horn_schunck", _i, [_vp, _vp, _vp, _vp, _u32, _u32, _f, _u32, _vp]),
     ("nus_flow_upsample", _i, [_vp, _vp, _u32, _u32, _vp, _u32, _u32, _f]),
     ("nus_flow_median", _i, [_vp, _vp, _u32, _u32, _u32, _vp]),
+    ("nus_flow_project", _i, [_vp, _vp, _u32, _u32, _f, _u32, _vp]),
     ("nus_flow_warp_coefficients", _i, [_vp, _vp, _vp, _vp, _u32, _u32, _vp]),
     ("nus_flow_horn_schunck_coef", _i, [_vp, _vp, _vp, _u32, _u32, _f, _u32, _vp]),
     ("nus_flow_estimate", _i, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _f, _vp]),

@@ -208,11 +208,12 @@ class PyFrameInterpolator:
     in the reference) turns the block matcher's forward-backward check on; the optical-flow method has none and raises.  `flow_warps`
     (not in the reference either; 0 .. FLOW_MAX_WARPS) is the optical-flow estimator's re-linearisation rounds per finer level
     (FlowEstimator.set_warps); a block method given a non-zero value raises.  `flow_median` (0, 3 or 5; likewise) is that estimator's
-    median filter behind every Jacobi run (FlowEstimator.set_median)."""
+    median filter behind every Jacobi run (FlowEstimator.set_median).  `flow_project` (0 .. FLOW_MAX_PROJECT; likewise) is the
+    projection rounds of the optical-flow method's dense-flow warp (WgpuFrameInterpolator.set_flow_project)."""
 
     def __init__(self, method: str = "optical_flow", quality: str = "medium", *, device: int = 0, scene_detect: bool = False,
-                 bidirectional: bool = False, flow_warps: int = 0, flow_median: int = 0):
-        from .flow import check_median, check_warps
+                 bidirectional: bool = False, flow_warps: int = 0, flow_median: int = 0, flow_project: int = 0):
+        from .flow import check_median, check_project, check_warps
 
         m = str(method).lower()
         self._scene = None  # (not in the reference) a pair flagged as a scene cut gives a repeat of the nearer frame, not a blend
@@ -229,6 +230,9 @@ class PyFrameInterpolator:
         flow_median = check_median(flow_median)
         if flow_median and self._block:
             raise ValueError("flow_median: only the optical-flow method has a flow to median-filter between its Jacobi runs")
+        flow_project = check_project(flow_project)
+        if flow_project and self._block:
+            raise ValueError("flow_project: only the optical-flow method warps with a dense flow of its own to project")
         if self._block:
             self._bm = BlockMatcher(self._quality, device=device, bidirectional=bidirectional)
             if scene_detect:
@@ -242,6 +246,8 @@ class PyFrameInterpolator:
 
                 self._scene = SceneDetector(device=device)
             self._warp = WgpuFrameInterpolator(device=device)
+            if flow_project:
+                self._warp.set_flow_project(flow_project)
 
     @staticmethod
     def create_best_interpolator(quality: str = "medium") -> "PyFrameInterpolator":

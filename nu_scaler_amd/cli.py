@@ -38,6 +38,9 @@ def build_parser() -> argparse.ArgumentParser:
     it.add_argument("--flow-median", type=int, default=None,
                     help="with --flow: median-filter the flow after every Jacobi run, window 3 or 5 (0, the default: off; meant for "
                          "--flow-warps >= 1)")
+    it.add_argument("--flow-project", type=int, default=None,
+                    help="with --flow: projection rounds of the warp -- the flow looked up where each output pixel's content came "
+                         "from (0 .. 4; default 0)")
     it.add_argument("--method", default=None, help="block_matching: the full-search block matcher supplies the motion field")
     it.add_argument("--quality", default="medium", help="block matching preset: high (8 / 24), medium (16 / 16) or low (32 / 8)")
     it.add_argument("--bidirectional", action="store_true",
@@ -202,6 +205,13 @@ def main(argv=None) -> int:
             parser.error("--flow-median needs --flow")
         if args.flow_median not in (0, 3, 5):
             parser.error(f"--flow-median must be 0, 3 or 5, got {args.flow_median}")
+    if args.command == "interpolate" and args.flow_project is not None:
+        if not args.flow:
+            parser.error("--flow-project needs --flow")
+        from ._capi import FLOW_MAX_PROJECT
+
+        if not 0 <= args.flow_project <= FLOW_MAX_PROJECT:
+            parser.error(f"--flow-project must be from 0 to {FLOW_MAX_PROJECT}, got {args.flow_project}")
     if args.command == "interpolate":
         if (args.bidirectional or args.bidir_tolerance is not None) and args.method is None:
             parser.error("--bidirectional needs --method block_matching")
@@ -254,12 +264,14 @@ def main(argv=None) -> int:
         elif args.multiplier is not None:
             for path in imagefile.interpolate_image_files_multi(args.frame_a, args.frame_b, args.output, args.multiplier, args.flow,
                                                                 device=args.device, scene_detect=args.scene_detect,
-                                                                flow_warps=args.flow_warps or 0, flow_median=args.flow_median or 0):
+                                                                flow_warps=args.flow_warps or 0, flow_median=args.flow_median or 0,
+                                                                flow_project=args.flow_project or 0):
                 print(path)
         else:
             t = 0.5 if args.t is None else args.t
             w, h = imagefile.interpolate_image_files(args.frame_a, args.frame_b, args.output, t, args.flow, device=args.device,
-                                                     flow_warps=args.flow_warps or 0, flow_median=args.flow_median or 0)
+                                                     flow_warps=args.flow_warps or 0, flow_median=args.flow_median or 0,
+                                                     flow_project=args.flow_project or 0)
             print(f"{args.output}: {w}x{h}")
     except (OSError, ValueError, RuntimeError) as e:
         print(f"nu_scaler_cli: error: {e}", file=sys.stderr)

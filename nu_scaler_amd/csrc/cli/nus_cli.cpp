@@ -4,7 +4,7 @@
 // (Nu_scale/src/main.rs:36-73: --tech, --quality, --algorithm).
 //
 //   nu_scaler_cli upscale <in.png> <out.png> [--algorithm A] [--scale S] [--tech T] [--quality Q] [--device N]
-//   nu_scaler_cli interpolate <a.png> <b.png> <out.png> [--t X | --multiplier M] [--flow [--flow-warps N] [--flow-median 0|3|5]] [--device N]
+//   nu_scaler_cli interpolate <a.png> <b.png> <out.png> [--t X | --multiplier M] [--flow [--flow-warps N] [--flow-median 0|3|5] [--flow-project N]] [--device N]
 //                             [--method block_matching [--quality high|medium|low] [--bidirectional [--bidir-tolerance N]]]
 //   nu_scaler_cli scene <a.png> <b.png> [--mad N] [--hist N] [--device N]   (the scene-cut detector: cut=0|1 mad=.. hist_permille=..)
 //   nu_scaler_cli compare <a.png> <b.png> [--device N]   (MSE / PSNR / SSIM, ErrorMetrics: Nu_scale/src/upscale/common.rs:475-543)
@@ -37,7 +37,8 @@ int usage(int rc)
                  "                             [--scale S] [--tech fsr|fallback|none] [--quality ultra|quality|balanced|performance]\n"
                  "                             [--device N]\n"
                  "       nu_scaler_cli interpolate <a.png> <b.png> <out.png> [--t X | --multiplier 2..8] [--flow [--flow-warps 0..4]\n"
-                 "                             [--flow-median 0|3|5]] [--device N]\n"
+                 "                             [--flow-median 0|3|5] [--flow-project 0..4]] [--device N]\n"
+                 "                             (--flow-project: rounds that look the flow up where each output pixel's content came from)\n"
                  "                             [--method block_matching [--quality high|medium|low]] [--scene-detect]\n"
                  "                             [--bidirectional [--bidir-tolerance 0..96]]   (block matching: forward-backward check)\n"
                  "       nu_scaler_cli scene <a.png> <b.png> [--mad 0..255] [--hist 0..1000] [--device N]\n"
@@ -246,6 +247,21 @@ int cmd_interpolate(const Args &a)
         }
         flow_median = (uint32_t)v;
     }
+    const auto project_it = a.options.find("flow-project");
+    uint32_t flow_project = 0; // projection rounds of the warp with the estimated flow (nus_interp_set_flow_project)
+    if (project_it != a.options.end()) {
+        if (!a.flow) {
+            std::fprintf(stderr, "nu_scaler_cli: error: --flow-project needs --flow\n");
+            return usage(2);
+        }
+        char *end = nullptr;
+        const long v = std::strtol(project_it->second.c_str(), &end, 10);
+        if (end == project_it->second.c_str() || *end != '\0' || v < 0 || v > NUS_FLOW_MAX_PROJECT) {
+            std::fprintf(stderr, "nu_scaler_cli: error: --flow-project must be from 0 to %d\n", NUS_FLOW_MAX_PROJECT);
+            return usage(2);
+        }
+        flow_project = (uint32_t)v;
+    }
     nus_cli::Image fa, fb;
     std::string err = nus_cli::read_png(a.positional[0], fa);
     if (err.empty()) err = nus_cli::read_png(a.positional[1], fb);
@@ -316,6 +332,7 @@ int cmd_interpolate(const Args &a)
         if (cut) // a scene cut: repeats of the nearer frame -- the zero-flow launch at t = 0 / 1 (nus_scene_apply_cuts_device's copy)
             for (float &tk : times) tk = tk < 0.5f ? 0.0f : 1.0f;
         int rc = nus_interp_set_device(it, device);
+        if (rc == NUS_OK) rc = nus_interp_set_flow_project(it, flow_project);
         if (rc == NUS_OK)
             rc = nus_interp_interpolate_multi(it, fa.rgba.data(), fa.rgba.size(), fb.rgba.data(), fb.rgba.size(),
                                               a.flow && !cut ? flow.data() : nullptr, fa.width, fa.height, times.data(), n, frames.data(),
@@ -340,6 +357,7 @@ int cmd_interpolate(const Args &a)
     out.height = fa.height;
     out.rgba.resize(fa.rgba.size());
     int rc = nus_interp_set_device(it, device);
+    if (rc == NUS_OK) rc = nus_interp_set_flow_project(it, flow_project);
     if (rc == NUS_OK)
         rc = nus_interp_interpolate(it, fa.rgba.data(), fa.rgba.size(), fb.rgba.data(), fb.rgba.size(),
                                     a.flow ? flow.data() : nullptr, fa.width, fa.height, t, out.rgba.data(), out.rgba.size());

@@ -89,6 +89,7 @@ static_assert(sizeof(nus_scene_measures) == 16 && NUS_SCENE_DEFAULT_MAD == nus::
               "the C header's scene-detector layout and defaults are the kernels'");
 static_assert(NUS_FLOW_MAX_WARPS == nus::kFlowMaxWarps, "the C header's NUS_FLOW_MAX_WARPS is the estimator's bound");
 static_assert(NUS_FLOW_MEDIAN_MAX == nus::kFlowMedianMax, "the C header's NUS_FLOW_MEDIAN_MAX is the estimator's largest window");
+static_assert(NUS_FLOW_MAX_PROJECT == nus::kFlowMaxProject, "the C header's NUS_FLOW_MAX_PROJECT is the warp kernels' bound");
 static_assert(NUS_INTERP_MAX_TIMES == nus::kInterpMaxTimes, "the C header's NUS_INTERP_MAX_TIMES is the kernels' time-set size");
 
 extern "C" {
@@ -509,6 +510,12 @@ int nus_interp_set_mode(nus_interp *h, int mode)
 
 int nus_interp_mode(const nus_interp *h) { return h ? h->impl.mode() : null_handle(); }
 
+int nus_interp_set_flow_project(nus_interp *h, uint32_t rounds)
+{
+    return guarded<int>("nus_interp_set_flow_project", [&]() -> int { return h ? h->impl.set_flow_project(rounds) : null_handle(); });
+}
+int nus_interp_flow_project(const nus_interp *h) { return h ? h->impl.flow_project() : null_handle(); }
+
 int nus_interp_set_flow_format(nus_interp *h, int format)
 {
     return guarded<int>("nus_interp_set_flow_format", [&]() -> int { return h ? h->impl.set_flow_format(format) : null_handle(); });
@@ -713,6 +720,11 @@ int nus_flow_set_median(nus_flow *h, uint32_t size)
 }
 int nus_flow_median_size(const nus_flow *h) { return h ? h->impl.median_size() : NUS_ERR_INVALID_ARGUMENT; }
 size_t nus_flow_workspace_bytes(nus_flow *h) { return h ? h->impl.workspace_bytes() : 0; }
+int nus_flow_set_project(nus_flow *h, uint32_t rounds)
+{
+    return guarded<int>("nus_flow_set_project", [&]() -> int { return h ? h->impl.set_project(rounds) : null_handle(); });
+}
+int nus_flow_project_rounds(const nus_flow *h) { return h ? h->impl.project_rounds() : NUS_ERR_INVALID_ARGUMENT; }
 const char *nus_flow_last_error(const nus_flow *h) { return h ? h->impl.last_error() : "null handle"; }
 
 int nus_flow_rgba8_to_f32(nus_flow *h, const uint8_t *in, uint32_t w, uint32_t hgt, float *out)
@@ -745,6 +757,11 @@ int nus_flow_upsample(nus_flow *h, const float *src, uint32_t sw, uint32_t sh, f
 int nus_flow_median(nus_flow *h, const float *flow_in, uint32_t w, uint32_t hgt, uint32_t size, float *flow_out)
 {
     return guarded<int>("nus_flow_median", [&]() -> int { return h ? h->impl.median(flow_in, w, hgt, size, flow_out) : null_handle(); });
+}
+
+int nus_flow_project(nus_flow *h, const float *flow_in, uint32_t w, uint32_t hgt, float t, uint32_t rounds, float *flow_out)
+{
+    return guarded<int>("nus_flow_project", [&]() -> int { return h ? h->impl.project(flow_in, w, hgt, t, rounds, flow_out) : null_handle(); });
 }
 
 int nus_flow_warp_coefficients(nus_flow *h, const float *i1, const float *i2, const float *flow, uint32_t w, uint32_t hgt, float *coef_out)

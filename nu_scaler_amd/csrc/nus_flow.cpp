@@ -46,6 +46,15 @@ int HipFlowEstimator::set_median(uint32_t size)
     return kOk;
 }
 
+int HipFlowEstimator::set_project(uint32_t rounds)
+{
+    std::lock_guard<std::mutex> lk(mu_);
+    if (rounds > kFlowMaxProject)
+        return fail(kInvalidArgument, fmt("nus_flow_set_project: 0 .. %u projection rounds, got %u", kFlowMaxProject, rounds));
+    project_ = rounds;
+    return kOk;
+}
+
 size_t HipFlowEstimator::workspace_bytes()
 {
     std::lock_guard<std::mutex> lk(mu_);
@@ -225,6 +234,28 @@ int HipFlowEstimator::median(const float *flow_in, uint32_t w, uint32_t h, uint3
         M.img = {w, h, 1, stream_};
         M.size = size, M.in = f32(kFlowA), M.out = f32(kFlowB);
         NUS_HIP(launch_flow_median(M));
+        result = f32(kFlowB);
+        return kOk;
+    });
+}
+
+int HipFlowEstimator::project(const float *flow_in, uint32_t w, uint32_t h, float t, uint32_t rounds, float *flow_out)
+{
+    if (rounds > kFlowMaxProject || t != t) {
+        std::lock_guard<std::mutex> lk(mu_);
+        if (t != t) return fail(kInvalidArgument, "nus_flow_project: t is NaN");
+        return fail(kInvalidArgument, fmt("nus_flow_project: 0 .. %u projection rounds, got %u", kFlowMaxProject, rounds));
+    }
+    if (!flow_in || !flow_out) {
+        std::lock_guard<std::mutex> lk(mu_);
+        return fail(kInvalidArgument, "nus_flow_project: null pointer");
+    }
+    const size_t fb = (size_t)w * h * 8;
+    return primitive({{w, h}}, true, {{kFlowA, fb, flow_in}, {kFlowB, fb, nullptr}}, flow_out, fb, [&](const void *&result) -> int {
+        FlowProjectLaunch P;
+        P.img = {w, h, 1, stream_};
+        P.t = t, P.rounds = rounds, P.in = f32(kFlowA), P.out = f32(kFlowB);
+        NUS_HIP(launch_flow_project(P));
         result = f32(kFlowB);
         return kOk;
     });
@@ -424,6 +455,7 @@ int HipFlowEstimator::interpolate_device_stream(const void *d_frames, uint32_t n
     StreamJob J;
     J.frames = static_cast<const uint8_t *>(d_frames), J.n_frames = n_frames, J.w = w, J.h = h;
     J.flows = static_cast<uint8_t *>(d_flows), J.mid = static_cast<uint8_t *>(d_mid), J.t = t, J.flow_half = flow_half, J.stream = stream;
+    J.project = project_;
     return stream_impl(J, with_warps(p));
 }
 
@@ -452,7 +484,7 @@ int HipFlowEstimator::interpolate_multi_device_stream(const void *d_frames, uint
     StreamJob J;
     J.frames = static_cast<const uint8_t *>(d_frames), J.n_frames = n_frames, J.w = w, J.h = h;
     J.flows = static_cast<uint8_t *>(d_flows), J.mid = static_cast<uint8_t *>(d_mid), J.t = times[0], J.flow_half = flow_half;
-    J.mt = &mt, J.stream = stream;
+    J.mt = &mt, J.stream = stream, J.project = project_;
     if ((rc = stream_impl(J, with_warps(p))) != kOk || !scene_) return rc;
     // behind estimate + warp, the detector (it reads the frames only, so its place in the order is free) and the flagged pairs'
     // frames overwritten with repeats
@@ -497,6 +529,7 @@ WarpLaunch HipFlowEstimator::warp_behind(const StreamJob &J, const void *flow)
     L.out = J.mid;
     L.w = J.w, L.h = J.h, L.t = J.t, L.n_pairs = J.n_frames - 1, L.stream = J.stream;
     if (J.mt) L.times = J.mt->times, L.n_times = J.mt->n, L.out_pair_stride = J.mt->pair_stride;
+    L.project = J.project;
     return L;
 }
 

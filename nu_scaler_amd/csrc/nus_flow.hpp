@@ -55,6 +55,8 @@ public:
     int upsample(const float *src, uint32_t sw, uint32_t sh, float *dst, uint32_t dw, uint32_t dh, float scale);
     // The stage set_median adds behind every Jacobi run, on its own: the component-wise size x size median (3 or 5) of a flow.
     int median(const float *flow_in, uint32_t w, uint32_t h, uint32_t size, float *flow_out);
+    // The projection set_project puts in front of the warp, on its own: g of every cell after `rounds` rounds at time t (launch_flow_project).
+    int project(const float *flow_in, uint32_t w, uint32_t h, float t, uint32_t rounds, float *flow_out);
     // The two halves of a re-linearised level (set_warps).  warp_coefficients: (Ix, Iy, It') per cell, w*h*3 floats, with frame B's
     // luminance sampled through `flow` (null: zero flow, i.e. It = L2 - L1).  horn_schunck_coef: Jacobi steps on such coefficients.
     int warp_coefficients(const float *i1, const float *i2, const float *flow_or_null, uint32_t w, uint32_t h, float *coef_out);
@@ -77,6 +79,10 @@ public:
     // buffer (or Rg16Float halves) writes the workspace instead, and the median writes the caller's f32 buffer.
     int set_median(uint32_t size);
     int median_size() const { return (int)median_; }
+    // Projection rounds of the warp behind the estimator (WarpLaunch::project; interpolate_device_stream and
+    // interpolate_multi_device_stream), 0 (default) .. kFlowMaxProject.  The estimate and the flows handed out are untouched.
+    int set_project(uint32_t rounds);
+    int project_rounds() const { return (int)project_; }
     // Bytes of device workspace the handle holds (the sum of its grow-only slots): what "reserves the workspace it did" is checked with.
     size_t workspace_bytes();
     // Scene-cut detection in front of interpolate_multi_device_stream and the cut-aware output rule behind it (nus_scene_* of the C
@@ -134,6 +140,7 @@ private:
         float t = 0.5f;                           // time of the in-between frame, unless
         bool flow_half = false;
         const MidTimes *mt = nullptr;             // ... several per pair
+        uint32_t project = 0;                     // the warp's projection rounds (set_project)
         hipStream_t stream = nullptr;
         size_t frame_bytes() const { return (size_t)w * h * 4; }
         size_t flow_bytes() const { return (size_t)w * h * (flow_half ? 4 : 8); }
@@ -184,6 +191,7 @@ private:
     int jacobi_ = 0; // JacobiKernel
     uint32_t warps_ = 0; // set_warps
     uint32_t median_ = 0; // set_median
+    uint32_t project_ = 0; // set_project
     bool fast_ = false; // set_mode(1): the estimator's Jacobi steps in FAST arithmetic (k_hs_stream_fast), every level streamed
     hipStream_t stream_ = nullptr;
     bool scene_ = false; // set_scene_detect

@@ -294,6 +294,10 @@ public:
     // 1 FMA (fused lerps, +-1 LSB: the interpolation path's contract).  The zero-flow blend is exact in both.
     int set_mode(int mode);
     int mode() const { return fma_ ? 1 : 0; }
+    // Projection rounds of the dense-flow warp (WarpLaunch::project; nus_interp_set_flow_project), 0 (default) .. kFlowMaxProject:
+    // every entry point given a flow evaluates it at the in-between time first.  0: the kernels and bytes from before the setting.
+    int set_flow_project(uint32_t rounds);
+    int flow_project() const { return (int)project_; }
     bool last_gpu_ms(double *ms) const;
     int wg_preset() const { return wg_preset_; }
 
@@ -325,6 +329,7 @@ private:
     uint8_t *d_a_ = nullptr, *d_b_ = nullptr, *d_out_ = nullptr;
     bool flow_half_ = false; // interpolate_device reads 2 x f16 per pixel
     bool fma_ = false;       // dense-flow warp in FMA mode
+    uint32_t project_ = 0;   // set_flow_project
     float *d_flow_ = nullptr;
     uint8_t *h_stage_ = nullptr; // pinned: a | b | cap_out_ frames out
     float *h_flow_ = nullptr;    // pinned

@@ -198,6 +198,7 @@ int HipFrameInterpolator::host_pass(const uint8_t *a, const uint8_t *b, const fl
     L.n_pairs = 1;
     L.stream = stream_;
     L.fma = fma_;
+    L.project = project_;
     L.in_sel = input_selector(in_format_);
     NUS_HIP(hipEventRecord(k_begin_, stream_));
     hipError_t e = launch_warp_blend(L);
@@ -271,6 +272,7 @@ int HipFrameInterpolator::device_call(const char *who, const void *d_a, size_t a
     L.n_pairs = n_pairs;
     L.stream = stream;
     L.in_sel = input_selector(in_format_);
+    L.project = project_;
     const hipError_t e = launch_warp_blend(L);
     if (e != hipSuccess) return fail_hip(e, multi ? "multi-time warp+blend launch" : "warp+blend launch");
     return kOk;
@@ -281,6 +283,15 @@ int HipFrameInterpolator::set_mode(int mode)
     std::lock_guard<std::mutex> lk(mu_);
     if (mode != 0 && mode != 1) return fail(kInvalidArgument, "unknown interpolation mode");
     fma_ = mode == 1;
+    return kOk;
+}
+
+int HipFrameInterpolator::set_flow_project(uint32_t rounds)
+{
+    std::lock_guard<std::mutex> lk(mu_);
+    if (rounds > kFlowMaxProject)
+        return fail(kInvalidArgument, fmt("nus_interp_set_flow_project: 0 .. %u projection rounds, got %u", kFlowMaxProject, rounds));
+    project_ = rounds;
     return kOk;
 }
 

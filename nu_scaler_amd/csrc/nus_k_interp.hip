@@ -255,6 +255,7 @@ hipError_t launch_swizzle_bgra(const uint8_t *in, uint8_t *out, size_t npx, hipS
 
 hipError_t launch_warp_blend(const WarpLaunch &L)
 {
+    if (L.project > 0 && L.flow != nullptr) return launch_warp_blend_project(L); // nus_k_warp_project.hip; off: everything below, as before
     const size_t npx = (size_t)L.w * L.h;
     TimeSet ts{};
     if (L.n_times == 0) {

@@ -168,11 +168,19 @@ struct WarpLaunch {
     uint32_t n_pairs = 1;
     hipStream_t stream = nullptr;
     uint32_t in_sel = kSelRGBA; // channel order of both input frames (the output is RGBA)
+    uint32_t project = 0;       // projection rounds (0 .. kFlowMaxProject) of the dense-flow warp: see launch_warp_blend_project
 };
 
 // Frame k of pair i goes to out + i * out_pair_stride + k * w * h * 4.  One time runs the single-time kernels; more, their
-// multi-time instantiations (the same per-pixel arithmetic, looped over the times after the loads).
+// multi-time instantiations (the same per-pixel arithmetic, looped over the times after the loads).  With project > 0 and a flow
+// it hands the launch to launch_warp_blend_project.
 hipError_t launch_warp_blend(const WarpLaunch &L);
+
+// The flow evaluated at the in-between time (nus_k_warp_project.hip; BUILD-DEFINED).  Per output pixel p and time t: g = f(p), then
+// `project` rounds of g = bilinear f at clamp(p - t g) -- separate roundings in both warp modes -- then the warp + blend of
+// launch_warp_blend with g in place of f(p).  Every gather stays inside its own pair's flow plane.  L.flow != nullptr, 1 <= L.project.
+constexpr uint32_t kFlowMaxProject = 4; // NUS_FLOW_MAX_PROJECT
+hipError_t launch_warp_blend_project(const WarpLaunch &L);
 
 // BGRA -> RGBA (in place allowed: in == out).
 hipError_t launch_swizzle_bgra(const uint8_t *in, uint8_t *out, size_t npx, hipStream_t stream);
@@ -267,6 +275,16 @@ struct FlowMedianLaunch {
     size_t in_stride = 0, out_stride = 0;
 };
 hipError_t launch_flow_median(const FlowMedianLaunch &L);
+// The projection alone: out = g after `rounds` rounds (0 .. kFlowMaxProject) at time t, for img.n tightly packed f32 flows of
+// img.w x img.h; the device function of the projecting warp kernels.  `in` and `out` must not overlap (a cell gathers its neighbours).
+struct FlowProjectLaunch {
+    FlowImages img;
+    float t = 0.5f;
+    uint32_t rounds = 1;
+    const float *in = nullptr;
+    float *out = nullptr;
+};
+hipError_t launch_flow_project(const FlowProjectLaunch &L);
 
 // Box calibration (nus_k_probe.hip; bench.py's denominators, not on the product path): kind 0 hipMemcpyDtoDAsync, 1 stream
 // copy, 2 write-only, 3 read-only (d_dst: 4 bytes of device memory), 4 one read : four writes (d_dst holds 4 * bytes),

@@ -8,7 +8,8 @@ and more Jacobi steps per finer level.  The result is the dense (dx, dy) field t
 `WgpuFrameInterpolator.interpolate_py(..., flow=...)` consumes.  With `warps=N` (off by default) every finer level is
 re-linearised N times about the flow it has -- frame B sampled through it -- which is what follows motion of more than a pixel.
 With `median=3` or `5` (off by default; meant for `warps >= 1`) the level's flow is median-filtered after every Jacobi run, which
-keeps motion boundaries from turning into ramps.
+keeps motion boundaries from turning into ramps.  With `project=N` (off by default) the warp behind the estimator evaluates the
+flow at the in-between time: every output pixel looks its vector up where its content came from before it is warped.
 """
 from __future__ import annotations
 
@@ -38,9 +39,17 @@ def check_median(size) -> int:
     return int(size)
 
 
+def check_project(rounds) -> int:
+    """`rounds` (projection rounds of the dense-flow warp) as an int in 0 .. FLOW_MAX_PROJECT, or ValueError (what every Python
+    entry point that takes the setting shares)."""
+    if isinstance(rounds, bool) or not isinstance(rounds, (int, np.integer)) or not 0 <= int(rounds) <= C.FLOW_MAX_PROJECT:
+        raise ValueError(f"flow projection rounds must be an integer from 0 to {C.FLOW_MAX_PROJECT}, got {rounds!r}")
+    return int(rounds)
+
+
 class FlowEstimator:
     def __init__(self, levels: int = 3, coarse_iterations: int = 50, refine_iterations: int = 10,
-                 lambda_: float = 0.02 ** 2, *, device: int = 0, warps: int = 0, median: int = 0):
+                 lambda_: float = 0.02 ** 2, *, device: int = 0, warps: int = 0, median: int = 0, project: int = 0):
         # lambda default: the value of the reference's own (ignored) test, wgpu_interpolator.rs:1535
         self._lib = C.lib()
         self._h = self._lib.nus_flow_create()
@@ -53,6 +62,8 @@ class FlowEstimator:
             self.set_warps(warps)
         if median != 0:
             self.set_median(median)
+        if project != 0:
+            self.set_project(project)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -94,6 +105,17 @@ class FlowEstimator:
     @property
     def median_size(self) -> int:
         return int(self._lib.nus_flow_median_size(self._h))
+
+    def set_project(self, rounds: int) -> None:
+        """Projection rounds of the warp behind the estimator (nus_flow_set_project; 0, the default, is off; at most
+        FLOW_MAX_PROJECT): `interpolate_device_stream` and `interpolate_multi_device_stream` evaluate the flow at the in-between
+        time -- N rounds of g = bilinear flow at (p - t g) per output pixel and time -- before they warp.  The flows handed out
+        and the estimate entry points are unchanged."""
+        self._check(self._lib.nus_flow_set_project(self._h, check_project(rounds)))
+
+    @property
+    def project(self) -> int:
+        return int(self._lib.nus_flow_project_rounds(self._h))
 
     @property
     def workspace_bytes(self) -> int:
@@ -199,6 +221,22 @@ class FlowEstimator:
         h, w = flow.shape[:2]
         out = np.empty((h, w, 2), np.float32)
         self._check(self._lib.nus_flow_median(self._h, flow.ctypes.data, w, h, int(size), out.ctypes.data))
+        return out
+
+    def project_flow(self, flow: np.ndarray, t: float, rounds: int) -> np.ndarray:
+        """The vector every output pixel of the in-between frame at time t is warped with after `rounds` projection rounds of an
+        (h, w, 2) flow: the stage `set_project` / `WgpuFrameInterpolator.set_flow_project` put in front of the warp, on its own
+        (nus_flow_project)."""
+        flow = self._f32(flow)
+        if flow.ndim != 3 or flow.shape[2] != 2:
+            raise ValueError(f"expected an (h, w, 2) flow, got {flow.shape}")
+        rounds = check_project(rounds)
+        t = float(t)
+        if t != t:
+            raise ValueError("project_flow: t is NaN")
+        h, w = flow.shape[:2]
+        out = np.empty((h, w, 2), np.float32)
+        self._check(self._lib.nus_flow_project(self._h, flow.ctypes.data, w, h, t, rounds, out.ctypes.data))
         return out
 
     # ---- full estimator ------------------------------------------------------------

@@ -187,19 +187,32 @@ def _check_flow_median(flow_median, estimate_flow: bool) -> int:
     return flow_median
 
 
+def _check_flow_project(flow_project, estimate_flow: bool) -> int:
+    from .flow import check_project
+
+    flow_project = check_project(flow_project)
+    if flow_project and not estimate_flow:
+        raise ValueError("flow_project needs estimate_flow (--flow-project needs --flow)")
+    return flow_project
+
+
 def interpolate_image_files(path_a: str, path_b: str, output_path: str, time_t: float = 0.5, estimate_flow: bool = False,
-                            device: int = 0, flow_warps: int = 0, flow_median: int = 0) -> tuple[int, int]:
+                            device: int = 0, flow_warps: int = 0, flow_median: int = 0, flow_project: int = 0) -> tuple[int, int]:
     """The in-between frame of two equally sized images (wgpu_interpolator.rs:215-491); with
     `estimate_flow` the Horn-Schunck front end supplies the motion field (`flow_warps`: its re-linearisation rounds per finer
-    level, FlowEstimator.set_warps; `flow_median`: its median filter behind every Jacobi run, 0, 3 or 5, FlowEstimator.set_median),
-    otherwise zero flow as the reference's live path."""
+    level, FlowEstimator.set_warps; `flow_median`: its median filter behind every Jacobi run, 0, 3 or 5, FlowEstimator.set_median;
+    `flow_project`: projection rounds of the warp with that field, WgpuFrameInterpolator.set_flow_project), otherwise zero flow as
+    the reference's live path."""
     flow_warps = _check_flow_warps(flow_warps, estimate_flow)
     flow_median = _check_flow_median(flow_median, estimate_flow)
+    flow_project = _check_flow_project(flow_project, estimate_flow)
     w, h, a = read_png(path_a)
     wb, hb, b = read_png(path_b)
     if (w, h) != (wb, hb):
         raise ValueError(f"frame sizes differ: {w}x{h} vs {wb}x{hb}")
     it = WgpuFrameInterpolator(device=device)
+    if flow_project:
+        it.set_flow_project(flow_project)
     flow = None
     if estimate_flow:
         from .flow import FlowEstimator
@@ -216,7 +229,8 @@ def multi_output_paths(output_path: str, multiplier: int) -> list[str]:
 
 
 def interpolate_image_files_multi(path_a: str, path_b: str, output_path: str, multiplier: int, estimate_flow: bool = False,
-                                  device: int = 0, scene_detect: bool = False, flow_warps: int = 0, flow_median: int = 0) -> list[str]:
+                                  device: int = 0, scene_detect: bool = False, flow_warps: int = 0, flow_median: int = 0,
+                                  flow_project: int = 0) -> list[str]:
     """The M - 1 in-between frames of a frame-rate multiplier M (t = k / M) from one multi-time call, written to
     multi_output_paths(output_path, M); with `estimate_flow` the flow is estimated once for all of them.  `scene_detect`: a
     pair the scene-cut detector flags gives repeats of the nearer frame instead of blends."""
@@ -224,12 +238,15 @@ def interpolate_image_files_multi(path_a: str, path_b: str, output_path: str, mu
 
     flow_warps = _check_flow_warps(flow_warps, estimate_flow)
     flow_median = _check_flow_median(flow_median, estimate_flow)
+    flow_project = _check_flow_project(flow_project, estimate_flow)
     times = frame_times(multiplier)
     w, h, a = read_png(path_a)
     wb, hb, b = read_png(path_b)
     if (w, h) != (wb, hb):
         raise ValueError(f"frame sizes differ: {w}x{h} vs {wb}x{hb}")
     it = WgpuFrameInterpolator(device=device)
+    if flow_project:
+        it.set_flow_project(flow_project)
     flow = None
     if estimate_flow:
         from .flow import FlowEstimator

@@ -189,6 +189,19 @@ class WgpuFrameInterpolator:
     def mode(self) -> str:
         return "fma" if self._lib.nus_interp_mode(self._h) == 1 else "exact"
 
+    def set_flow_project(self, rounds: int) -> None:
+        """Projection rounds of the dense-flow warp (nus_interp_set_flow_project; 0, the default, is off; at most
+        FLOW_MAX_PROJECT): the flow lives on frame A's grid, so each output pixel first looks its vector up where its content came
+        from -- N rounds of g = bilinear flow at (p - t g) -- and is then warped with g.  Removes the wrong ring around moving
+        objects; 2 never loses on the float64 witness, 3 gains most.  Applies to every call given a flow."""
+        from .flow import check_project
+
+        self._raise(self._lib.nus_interp_set_flow_project(self._h, check_project(rounds)))
+
+    @property
+    def flow_project(self) -> int:
+        return int(self._lib.nus_interp_flow_project(self._h))
+
     def set_flow_format(self, fmt: str) -> None:
         """Element type of the device flow field `interpolate_device` reads: "f32" (default, 2 x f32 per pixel) or
         "f16" (2 x half per pixel: the Rg16Float texture of wgpu_interpolator.rs:276, half the bytes)."""

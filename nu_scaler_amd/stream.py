@@ -171,7 +171,7 @@ class FramePipeline:
     def step_motion(self, frames, flows, mid, up_real, up_mid, stream: int = 0, levels: int = 3,
                     coarse_iterations: int = 50, refine_iterations: int = 10, flow_mode: str = "exact", pipelined: bool = False,
                     chunk: int = 150, fused_warp: bool = False, flow_format: Optional[str] = None, flow_warps: int = 0,
-                    flow_median: int = 0) -> None:
+                    flow_median: int = 0, flow_project: int = 0) -> None:
         """Motion-compensated variant of `step`: a dense flow per pair from the
         pyramid + Horn-Schunck front end into `flows` ((n_units, h, w, 2) float32), then warp + blend with it
         instead of the reference's zero flow.  The flows are estimated pair by pair (several launches per pair,
@@ -190,11 +190,14 @@ class FramePipeline:
         finished -- was built, measured and removed: identical bytes, slower; the code is in git at d74dcbc.)
 
         flow_warps: the estimator's re-linearisation rounds per finer pyramid level (FlowEstimator.set_warps; 0: none).
-        flow_median: the estimator's median filter behind every Jacobi run (FlowEstimator.set_median; 0: off, 3 or 5)."""
-        from .flow import FlowEstimator, check_median, check_warps
+        flow_median: the estimator's median filter behind every Jacobi run (FlowEstimator.set_median; 0: off, 3 or 5).
+        flow_project: projection rounds of the warp (0: off): set on the estimator (the fused route's warp, FlowEstimator.set_project)
+        and on `self.interp` (the unfused route's, WgpuFrameInterpolator.set_flow_project), so both routes warp alike."""
+        from .flow import FlowEstimator, check_median, check_project, check_warps
 
         flow_warps = check_warps(flow_warps)
         flow_median = check_median(flow_median)
+        flow_project = check_project(flow_project)
 
         if getattr(self, "_flow", None) is None:
             self._flow = FlowEstimator(levels, coarse_iterations, refine_iterations, device=self.upscaler._device)
@@ -204,6 +207,10 @@ class FramePipeline:
             self._flow.set_warps(flow_warps)
         if self._flow.median_size != flow_median:
             self._flow.set_median(flow_median)
+        if self._flow.project != flow_project:
+            self._flow.set_project(flow_project)
+        if self.interp.flow_project != flow_project:
+            self.interp.set_flow_project(flow_project)
         n = mid.shape[0]
         base = frames.data_ptr()
         fb = self.frame_bytes

@@ -7,7 +7,12 @@ its brackets, and the smallest and largest bracket are printed beside it.  warps
 baseline of the ratios.  One JSON line per case.
 --median: the median mode instead (nus_flow_set_median): for EXACT and FAST at warps 1 and 2 the legs median 0 / 3 / 5 alternate the
 same way, and median 0 at the same warps is the baseline of the ratios.
-usage: python tools/flow_warps_bench.py [--median] [--reps R] [--rounds N] [--frames F] [--quick]"""
+--project: the warp's projection rounds instead (nus_flow_set_project / nus_interp_set_flow_project): rounds 0 / 1 / 2 / 3 of
+nus_flow_interpolate_device_stream (EXACT and FAST estimator, t = 0.5) and of nus_interp_interpolate_multi_device (3 times per pair,
+EXACT and FMA warp, on the flows of one estimate), the legs alternating the same way, rounds 0 the baseline of the ratios.
+--project-rounds 0 times the baseline alone and touches none of the new settings, so the same file also runs on a build from
+before the setting existed.
+usage: python tools/flow_warps_bench.py [--median | --project [--project-rounds 0,1,2,3]] [--reps R] [--rounds N] [--frames F] [--quick]"""
 import argparse
 import json
 import os
@@ -24,6 +29,7 @@ from nu_scaler_amd import synthetic as syn  # noqa: E402
 WARPS = (0, 1, 2)
 MEDIAN_WARPS = (1, 2)  # --median: the settings the mode is meant for
 MEDIANS = (0, 3, 5)
+PROJECT_TIMES = [0.25, 0.5, 0.75]  # --project: the multi-time warp's time set
 
 
 def timed_alternating(fns, reps, warm_seconds, rounds):
@@ -49,6 +55,55 @@ def timed_alternating(fns, reps, warm_seconds, rounds):
     return [sorted(g) for g in got]
 
 
+def project_legs(args, frames, flows, w, h, n_frames, s):
+    n = n_frames - 1
+    fb = w * h * 4
+    rounds = [int(r) for r in args.project_rounds.split(",")]
+    if not rounds or rounds[0] != 0:
+        raise SystemExit("flow_warps_bench: --project-rounds starts with 0, the baseline")
+    mid = torch.empty((n, len(PROJECT_TIMES), h, w, 4), dtype=torch.uint8, device=frames.device)
+
+    def report(case, extra, brackets):
+        us = [[x * 1e3 / n for x in g] for g in brackets]
+        med = [g[len(g) // 2] for g in us]
+        for r, g, m in zip(rounds, us, med):
+            print(json.dumps(dict({"case": f"{w}x{h}x{n}_{case}_project{r}", "width": w, "height": h, "pairs": n, "project": r}, **extra,
+                                  **{"working_set_bytes": frames.numel(), "brackets": len(g), "calls_per_bracket": args.reps,
+                                     "us_per_pair": round(m, 2), "us_per_pair_min": round(g[0], 2), "us_per_pair_max": round(g[-1], 2),
+                                     "over_project0": round(m / med[0], 3)})), flush=True)
+
+    for mode in ("exact", "fast"):  # estimator + warp through one entry point
+        handles = []
+        for r in rounds:
+            fe = nsc.FlowEstimator(levels=3, coarse_iterations=50, refine_iterations=10)
+            fe.set_mode(mode)
+            if r:
+                fe.set_project(r)
+            handles.append(fe)
+        legs = [lambda fe=fe: fe.interpolate_device_stream(frames.data_ptr(), n_frames, w, h, 0.5, mid.data_ptr(), flows.data_ptr(), s)
+                for fe in handles]
+        report(f"interpolate_device_stream_{mode}", {"entry": "nus_flow_interpolate_device_stream", "mode": mode, "levels": 3,
+                                                     "coarse_iterations": 50, "refine_iterations": 10},
+               timed_alternating(legs, args.reps, args.warm_seconds, args.rounds))
+        del handles, legs
+        torch.cuda.synchronize()
+    for mode in ("exact", "fma"):  # the warp alone, on the flows the last estimate left
+        handles = []
+        for r in rounds:
+            it = nsc.WgpuFrameInterpolator()
+            it.set_mode(mode)
+            if r:
+                it.set_flow_project(r)
+            handles.append(it)
+        legs = [lambda it=it: it.interpolate_multi_device(frames.data_ptr(), fb, frames.data_ptr() + fb, fb, flows.data_ptr(), w, h,
+                                                          PROJECT_TIMES, mid.data_ptr(), 0, n, s) for it in handles]
+        report(f"interpolate_multi_device_{mode}", {"entry": "nus_interp_interpolate_multi_device", "mode": mode,
+                                                    "times": len(PROJECT_TIMES)},
+               timed_alternating(legs, args.reps, args.warm_seconds, args.rounds))
+        del handles, legs
+        torch.cuda.synchronize()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5, help="calls per timed bracket")
@@ -57,7 +112,11 @@ def main():
     ap.add_argument("--frames", type=int, default=32)
     ap.add_argument("--quick", action="store_true", help="one warm-up call and one bracket of 2 calls per leg")
     ap.add_argument("--median", action="store_true", help="time median 0 / 3 / 5 at warps 1 and 2 instead of warps 0 / 1 / 2")
+    ap.add_argument("--project", action="store_true", help="time the warp's projection rounds instead (see the module text)")
+    ap.add_argument("--project-rounds", default="0,1,2,3", help="with --project: the legs (comma-separated round counts, 0 first)")
     args = ap.parse_args()
+    if args.median and args.project:
+        ap.error("--median and --project exclude each other")
     if nsc.device_count() < 1:
         raise SystemExit("flow_warps_bench: no HIP device")
     if args.quick:
@@ -70,6 +129,8 @@ def main():
     for k in range(n):
         frames[k + 1] = torch.roll(frames[k], (5 - 2 * (k % 6), 3 * (k % 7) - 9), (0, 1))
     flows = torch.empty((n, h, w, 2), dtype=torch.float32, device=dev)
+    if args.project:
+        return project_legs(args, frames, flows, w, h, n_frames, s)
     for mode, warps in [(m, wn) for m in ("exact", "fast") for wn in MEDIAN_WARPS] if args.median else []:
         handles = []
         for median in MEDIANS:
