@@ -317,85 +317,145 @@ int HipFlowEstimator::build_pyramid(const void *frame, Slot pyr, const Pyramid &
     return kOk;
 }
 
-// Coarse-to-fine Horn-Schunck between the pyramids in slots `pyr_a` and `pyr_b`.
-int HipFlowEstimator::solve(Slot pyr_a, Slot pyr_b, const Pyramid &g, const FlowParams &p, void *d_flow_out, hipStream_t stream)
+// A level whose Jacobi steps run in the streamed kernel needs no coefficient planes: that kernel takes the derivatives from the
+// luminance planes of the pair's two frames as it goes.
+bool HipFlowEstimator::Schedule::from_planes(uint32_t l) const
+{
+    return stream_planes && !warped_level(l) && hs_iterate_streams(g->w[l], g->h[l], n, kernel(l));
+}
+
+// The coarse-to-fine Horn-Schunck schedule of D.n pairs, every stage one launch over all of them: the coarsest level from zero flow
+// (compute_coarse_flow, :1136-1154), each finer one from the flow of the level below, upsampled.
+int HipFlowEstimator::solve_levels(const Schedule &D, Solved &done)
 {
     int rc;
-    float *f0 = f32(kFlowA), *f1 = f32(kFlowB);
+    const Pyramid &g = *D.g;
+    const FlowParams &p = D.p;
+    const hipStream_t stream = D.stream;
     const uint32_t L = g.levels - 1;
-    // the derivatives of level l: into kTemp, the blur temp, which is free once the pyramids exist (tiled pyramids hold luminance planes)
+    float *f0 = D.flow_a, *f1 = D.flow_b;
+    auto images = [&](uint32_t l) { return FlowImages{g.w[l], g.h[l], D.n, stream}; };
+    // the derivatives of level l from the level of each pair's two frames
     auto prepare = [&](uint32_t l) {
         HsPrepareLaunch P;
-        P.img = {g.w[l], g.h[l], 1, stream};
-        P.i1 = reinterpret_cast<const float *>(u8(pyr_a) + g.offset[l]), P.i2 = reinterpret_cast<const float *>(u8(pyr_b) + g.offset[l]);
-        P.luminance_planes = tiled_, P.coef = f32(kTemp); // (the plain kernels' pyramids hold f32 RGBA levels)
+        P.img = images(l);
+        P.i1 = D.level[l].i1, P.i2 = D.level[l].i2, P.luminance_planes = D.luminance_planes, P.img_stride = D.level[l].stride;
+        P.coef = D.coef, P.coef_stride = D.level[l].stride * 3;
         return P;
     };
     // the flow of level l + 1, in f0, as level l takes it up
-    auto coarse_of = [&](uint32_t l) { return HsCoarseFlow{f0, g.w[l + 1], g.h[l + 1], 2.0f, 0}; };
-    // compute_coarse_flow starts from zero flow (:1136-1154): the tiled kernel takes that as a null input;
-    // the last launch of the finest level writes the caller's buffer directly
-    bool zero = true;
-    // `last`: no further round of the level follows; `on_coef`: the coefficient kernels whatever set_tiled says (a warped round)
-    // the median behind a Jacobi run (FlowParams::median): from the buffer the run left into the other one -- the caller's, if this
-    // was the finest level's last run -- and the two names swapped
-    auto median_behind = [&](uint32_t l, bool last) -> int {
-        FlowMedianLaunch M;
-        M.img = {g.w[l], g.h[l], 1, stream};
-        M.size = p.median, M.in = f0, M.out = l == 0 && last ? static_cast<float *>(d_flow_out) : f1;
-        NUS_HIP(launch_flow_median(M));
-        if (M.out == f1) f1 = f0;
-        f0 = M.out;
-        return kOk;
-    };
-    auto iterate = [&](uint32_t l, uint32_t iters, bool prepared, bool last = true, bool on_coef = false) -> int {
+    auto coarse_of = [&](uint32_t l) { return HsCoarseFlow{f0, g.w[l + 1], g.h[l + 1], 2.0f, D.level[l + 1].stride}; };
+    // Who may write the caller's buffer: the launch that finishes level 0.  Without the median that is a Jacobi launch -- for
+    // Rg16Float only the FAST streamed kernel's, which stores halves itself (every other kernel writes 2 x f32 per cell and must be
+    // kept in the workspace, its flow converted afterwards).  With the median no Jacobi launch finishes level 0: each writes the
+    // workspace, f32, and the median behind the last one writes the caller's f32 buffer if there is one.
+    const bool fast_last = D.kernel(0) == kJacobiStreamFast && (L > 0 ? p.refine_iters > 0 : p.coarse_iters > 0);
+    float *const jacobi_out = p.median || (D.half && !fast_last) ? nullptr : D.out;
+    float *const median_out = D.half ? nullptr : D.out;
+    // One Jacobi run of level l on the flow in f0 (no steps: nothing), and the median behind it.  `last`: no further round of the
+    // level follows; `zero`: from zero flow, f0 is not read; `coarse`: f0 is the flow of level l + 1, which the first launch upsamples
+    // as it loads it.
+    auto run = [&](uint32_t l, uint32_t iters, bool last, bool zero = false, bool coarse = false) -> int {
         if (iters == 0) return kOk;
-        const HsPrepareLaunch P = prepare(l);
-        if (tiled_ || on_coef) {
-            if (!prepared) NUS_HIP(launch_hs_prepare(P));
+        if (D.per_step && !D.warped_level(l)) {
+            for (uint32_t i = 0; i < iters; ++i, std::swap(f0, f1))
+                NUS_HIP(launch_horn_schunck(D.level[l].i1, D.level[l].i2, f0, f1, g.w[l], g.h[l], p.lambda, stream));
+        } else {
             HsIterateLaunch I;
-            I.img = P.img;
-            I.coef = P.coef, I.lambda = p.lambda, I.iterations = iters, I.zero_start = zero, I.flow_a = f0, I.flow_b = f1;
-            I.final_out = l == 0 && last && !p.median ? static_cast<float *>(d_flow_out) : nullptr, I.kernel = jacobi_;
+            I.img = images(l);
+            I.coef = D.coef, I.coef_stride = D.level[l].stride * 3;
+            I.lum1 = D.from_planes(l) ? D.level[l].i1 : nullptr, I.lum_stride = D.level[l].stride;
+            I.lambda = p.lambda, I.iterations = iters, I.zero_start = zero;
+            I.flow_a = f0, I.flow_b = f1, I.flow_stride = D.level[l].stride;
+            I.final_out = l == 0 && last ? jacobi_out : nullptr, I.final_stride = D.level[0].stride;
+            I.kernel = D.kernel(l);
+            if (coarse) I.coarse = coarse_of(l);
+            I.final_half = l == 0 && D.half && !p.median;
             HsIterateResult R;
             NUS_HIP(launch_hs_iterate(I, &R));
             f0 = R.flow, f1 = R.spare;
-            zero = false;
-            return p.median ? median_behind(l, last) : kOk;
+            if (l == 0) done.wrote_half = R.wrote_half;
         }
-        for (uint32_t i = 0; i < iters; ++i, std::swap(f0, f1))
-            NUS_HIP(launch_horn_schunck(P.i1, P.i2, f0, f1, g.w[l], g.h[l], p.lambda, stream));
-        return p.median ? median_behind(l, last) : kOk;
+        if (p.median) { // from the buffer the run left into the other one, the two names swapped
+            FlowMedianLaunch M;
+            M.img = images(l);
+            M.size = p.median, M.in = f0, M.in_stride = M.out_stride = D.level[l].stride;
+            M.out = l == 0 && last && median_out ? median_out : f1;
+            NUS_HIP(launch_flow_median(M));
+            if (M.out == f1) f1 = f0;
+            f0 = M.out;
+        }
+        return kOk;
     };
-    if (!tiled_ || p.coarse_iters == 0) {
-        NUS_HIP(hipMemsetAsync(f0, 0, (size_t)g.w[L] * g.h[L] * 8, stream));
-        zero = false;
-    }
-    if ((rc = iterate(L, p.coarse_iters, false)) != kOk) return rc;
-    for (int l = (int)L - 1; l >= 0; --l) {
-        if (warped(p)) { // each round: the level's coefficients about the flow it has, then the steps (set_tiled(0) has no plain form of it)
+    // coarsest level: the multi-step kernels take zero flow as a null input
+    const bool zero = !D.per_step && p.coarse_iters > 0;
+    if (!zero) NUS_HIP(hipMemsetAsync(f0, 0, (size_t)g.w[L] * g.h[L] * D.n * 8, stream));
+    if (zero && !D.from_planes(L)) NUS_HIP(launch_hs_prepare(prepare(L)));
+    if ((rc = run(L, p.coarse_iters, true, zero)) != kOk) return rc;
+    for (uint32_t l = L; l-- > 0;) {
+        if (D.warped_level(l)) { // each round: the level's coefficients about the flow it has (round 1: the upsampled one), then the steps
             for (uint32_t r = 0; r < p.warps; ++r) {
                 if (r == 0) {
-                    NUS_HIP(launch_hs_warp_setup(prepare((uint32_t)l), coarse_of((uint32_t)l), nullptr, 0, f1, 0));
+                    NUS_HIP(launch_hs_warp_setup(prepare(l), coarse_of(l), nullptr, 0, f1, D.level[l].stride));
                     std::swap(f0, f1);
                 } else {
-                    NUS_HIP(launch_hs_warp_setup(prepare((uint32_t)l), HsCoarseFlow{}, f0, 0, nullptr, 0));
+                    NUS_HIP(launch_hs_warp_setup(prepare(l), HsCoarseFlow{}, f0, D.level[l].stride, nullptr, 0));
                 }
-                if ((rc = iterate((uint32_t)l, p.refine_iters, true, r + 1 == p.warps, true)) != kOk) return rc;
+                if ((rc = run(l, p.refine_iters, r + 1 == p.warps)) != kOk) return rc;
             }
-            continue;
+        } else if (p.refine_iters > 0 && D.from_planes(l)) { // derivatives and upsampled flow both computed inside the Jacobi kernel
+            if ((rc = run(l, p.refine_iters, true, false, true)) != kOk) return rc;
+        } else {
+            if (!D.per_step && p.refine_iters > 0) // the level's derivatives and the upsampled flow in one launch
+                NUS_HIP(launch_hs_level_setup(prepare(l), coarse_of(l), f1, D.level[l].stride));
+            else
+                NUS_HIP(launch_flow_upsample(images(l), coarse_of(l), f1, D.level[l].stride));
+            std::swap(f0, f1);
+            if ((rc = run(l, p.refine_iters, true)) != kOk) return rc;
         }
-        const bool fused_setup = tiled_ && p.refine_iters > 0; // the level's derivatives and the upsampled flow in one launch
-        if (fused_setup)
-            NUS_HIP(launch_hs_level_setup(prepare((uint32_t)l), coarse_of((uint32_t)l), f1, 0));
-        else
-            NUS_HIP(launch_flow_upsample({g.w[l], g.h[l], 1, stream}, coarse_of((uint32_t)l), f1, 0));
-        std::swap(f0, f1);
-        if ((rc = iterate((uint32_t)l, p.refine_iters, fused_setup)) != kOk) return rc;
     }
-    if (f0 != d_flow_out)
-        NUS_HIP(hipMemcpyAsync(d_flow_out, f0, (size_t)g.w[0] * g.h[0] * 8, hipMemcpyDeviceToDevice, stream));
+    done.flow = f0;
     return kOk;
+}
+
+// The flow solve_levels left, where and as J wants it -- f32 or Rg16Float, in J.flows if there is one -- and, with J.mid, the warp
+// kernel behind the estimator on the flow where it is (the caller's buffer, or the workspace).
+int HipFlowEstimator::place_flow(const StreamJob &J, const Solved &s)
+{
+    const size_t cells = (size_t)J.w * J.h * (J.n_frames - 1);
+    void *const out = J.flows;
+    const void *final_flow = s.flow;
+    if (!J.flow_half || s.wrote_half) { // as wanted already (halves: the launch wrote them, into the caller's buffer if there is one)
+        if (out && s.flow != out) NUS_HIP(hipMemcpyAsync(out, s.flow, cells * (J.flow_half ? 4 : 8), hipMemcpyDeviceToDevice, J.stream));
+        if (out) final_flow = out;
+    } else { // 2 x f32 per cell in the workspace: converted into the caller's buffer, or beside it
+        void *dst = out;
+        if (!dst) {
+            const int rc = reserve(cells * 4, kFlowsHalf);
+            if (rc != kOk) return rc;
+            dst = u8(kFlowsHalf);
+        }
+        NUS_HIP(launch_flow_to_half(s.flow, dst, cells, J.stream));
+        final_flow = dst;
+    }
+    if (J.mid) NUS_HIP(launch_warp_blend(warp_behind(J, final_flow)));
+    return kOk;
+}
+
+// Coarse-to-fine Horn-Schunck between the pyramids in slots `pyr_a` and `pyr_b`: one pair, its f32 flow to d_flow_out.
+int HipFlowEstimator::solve(Slot pyr_a, Slot pyr_b, const Pyramid &g, const FlowParams &p, void *d_flow_out, hipStream_t stream)
+{
+    Schedule D;
+    D.g = &g, D.p = p, D.stream = stream;
+    for (uint32_t l = 0; l < g.levels; ++l)
+        D.level[l] = {reinterpret_cast<const float *>(u8(pyr_a) + g.offset[l]), reinterpret_cast<const float *>(u8(pyr_b) + g.offset[l]), 0, jacobi_};
+    D.warped_kernel = jacobi_;
+    D.luminance_planes = tiled_, D.per_step = !tiled_; // (the plain kernels' pyramids hold f32 RGBA levels)
+    D.coef = f32(kTemp); // the blur temp, which is free once the pyramids exist (slot 5, the batch path's kCoef, is frame B's pyramid here)
+    D.flow_a = f32(kFlowA), D.flow_b = f32(kFlowB), D.out = static_cast<float *>(d_flow_out);
+    Solved done;
+    const int rc = solve_levels(D, done);
+    return rc != kOk ? rc : place_flow(StreamJob(nullptr, 2, g.w[0], g.h[0], d_flow_out, nullptr, stream), done);
 }
 
 int HipFlowEstimator::estimate_device(const void *d_a, const void *d_b, uint32_t w, uint32_t h, const FlowParams &p, void *d_flow_out,
@@ -415,17 +475,15 @@ int HipFlowEstimator::estimate_pair(const void *d_a, const void *d_b, uint32_t w
     if ((rc = plan(w, h, p.levels, g)) != kOk) return rc;
     // FAST arithmetic lives in the batch solver's register-pipelined kernels, which need a batch (or a frame) big enough to fill
     // the GPU; a single 1080p pair is 576 waves -- the LDS-tile kernels of the exact path are 2.7x faster there (220 against
-    // 605 us), and their result satisfies FAST's contract trivially.  So a pair alone takes the FAST kernels only where the
-    // finest level would stream anyway, or where the streamed kernel is forced (set_tiled(3)).
+    // 605 us when that was measured; the exact pair takes 245 us today), and their result satisfies FAST's contract trivially.
+    // So a pair alone takes the FAST kernels only where the finest level would stream anyway, or where the streamed kernel is
+    // forced (set_tiled(3)).
     if (fast_ && (jacobi_ == kJacobiStream || (jacobi_ == kJacobiAuto && hs_iterate_streams(g.w[0], g.h[0], 1, kJacobiAuto)))) {
-        StreamJob J;
-        J.w = w, J.h = h, J.n_frames = 2, J.flows = static_cast<uint8_t *>(d_flow_out), J.stream = stream;
-        const size_t fb = J.frame_bytes();
+        const size_t fb = (size_t)w * h * 4;
         if ((rc = reserve(2 * fb, kFastPair)) != kOk) return rc;
-        J.frames = u8(kFastPair);
         NUS_HIP(hipMemcpyAsync(u8(kFastPair), d_a, fb, hipMemcpyDeviceToDevice, stream));
         NUS_HIP(hipMemcpyAsync(u8(kFastPair) + fb, d_b, fb, hipMemcpyDeviceToDevice, stream));
-        return solve_batch(J, g, p);
+        return solve_batch(StreamJob(u8(kFastPair), 2, w, h, d_flow_out, nullptr, stream), g, p);
     }
     if ((rc = build_pyramid(d_a, kPyrA, g, stream)) != kOk || (rc = build_pyramid(d_b, kPyrB, g, stream)) != kOk) return rc;
     return solve(kPyrA, kPyrB, g, p, d_flow_out, stream);
@@ -438,10 +496,7 @@ int HipFlowEstimator::estimate_device_stream(const void *d_frames, uint32_t n_fr
 {
     std::lock_guard<std::mutex> lk(mu_);
     if (!d_flows) return fail(kInvalidArgument, "flow: null device pointer");
-    StreamJob J;
-    J.frames = static_cast<const uint8_t *>(d_frames), J.n_frames = n_frames, J.w = w, J.h = h;
-    J.flows = static_cast<uint8_t *>(d_flows), J.stream = stream;
-    return stream_impl(J, with_warps(p));
+    return stream_impl(StreamJob(d_frames, n_frames, w, h, d_flows, nullptr, stream), with_warps(p));
 }
 
 int HipFlowEstimator::interpolate_device_stream(const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t h, const FlowParams &p,
@@ -452,10 +507,8 @@ int HipFlowEstimator::interpolate_device_stream(const void *d_frames, uint32_t n
     if (!(t >= 0.0f && t <= 1.0f)) return fail(kInvalidArgument, "flow: t must be in [0, 1]");
     if (misaligned(d_mid, 16) || misaligned(d_flows, 16))
         return fail(kInvalidArgument, "flow: device pointers must be 16-byte aligned");
-    StreamJob J;
-    J.frames = static_cast<const uint8_t *>(d_frames), J.n_frames = n_frames, J.w = w, J.h = h;
-    J.flows = static_cast<uint8_t *>(d_flows), J.mid = static_cast<uint8_t *>(d_mid), J.t = t, J.flow_half = flow_half, J.stream = stream;
-    J.project = project_;
+    StreamJob J(d_frames, n_frames, w, h, d_flows, d_mid, stream);
+    J.t = t, J.flow_half = flow_half, J.project = project_;
     return stream_impl(J, with_warps(p));
 }
 
@@ -481,10 +534,8 @@ int HipFlowEstimator::interpolate_multi_device_stream(const void *d_frames, uint
         if (!too_many.empty()) return fail(kInvalidArgument, std::string(who) + ": " + too_many);
     }
     const MidTimes mt{times, n_times, mid_pair_stride ? mid_pair_stride : n_times * frame_bytes};
-    StreamJob J;
-    J.frames = static_cast<const uint8_t *>(d_frames), J.n_frames = n_frames, J.w = w, J.h = h;
-    J.flows = static_cast<uint8_t *>(d_flows), J.mid = static_cast<uint8_t *>(d_mid), J.t = times[0], J.flow_half = flow_half;
-    J.mt = &mt, J.stream = stream, J.project = project_;
+    StreamJob J(d_frames, n_frames, w, h, d_flows, d_mid, stream);
+    J.t = times[0], J.flow_half = flow_half, J.mt = &mt, J.project = project_;
     if ((rc = stream_impl(J, with_warps(p))) != kOk || !scene_) return rc;
     // behind estimate + warp, the detector (it reads the frames only, so its place in the order is free) and the flagged pairs'
     // frames overwritten with repeats
@@ -597,23 +648,21 @@ int HipFlowEstimator::solve_batch(const StreamJob &J, const Pyramid &g, const Fl
     int rc;
     const uint32_t pairs = J.n_frames - 1;
     const hipStream_t stream = J.stream;
+    Schedule D;
+    D.n = pairs, D.g = &g, D.p = p, D.stream = stream;
+    D.warped_kernel = jacobi_, D.stream_planes = true, D.half = J.flow_half;
     // The Jacobi kernel of a level.  FAST: k_hs_stream_fast where the level's batch would stream anyway (or the streamed kernel
     // is forced), the exact LDS-tile kernel -- on the FAST pyramid's planes -- where it would not (a small batch's coarse levels).
-    auto unwarped_kernel = [&](uint32_t l) -> int {
-        if (!fast_ || jacobi_ == kJacobiTiles) return jacobi_;
-        if (jacobi_ == kJacobiStream) return kJacobiStreamFast;
-        return hs_iterate_streams(g.w[l], g.h[l], pairs, kJacobiAuto) ? kJacobiStreamFast : kJacobiTiles;
-    };
-    // A warped level (FlowParams::warps: every level but the coarsest) runs the exact kernels on coefficient planes, FAST or not:
-    // k_hs_stream_fast takes It from the luminance planes itself.  The exact result is inside FAST's contract.
-    auto warped_level = [&](uint32_t l) { return warped(p) && l + 1 < g.levels; };
-    auto level_kernel = [&](uint32_t l) -> int { return warped_level(l) ? jacobi_ : unwarped_kernel(l); };
+    for (uint32_t l = 0; l < g.levels; ++l) {
+        if (!fast_ || jacobi_ == kJacobiTiles) D.level[l].kernel = jacobi_;
+        else if (jacobi_ == kJacobiStream) D.level[l].kernel = kJacobiStreamFast;
+        else D.level[l].kernel = hs_iterate_streams(g.w[l], g.h[l], pairs, kJacobiAuto) ? kJacobiStreamFast : kJacobiTiles;
+    }
     // The luminance-only pyramid streams rows per wave as well: where level 0 of the batch is too small for that, the exact
-    // LDS-tile pyramid runs instead (its planes serve either Jacobi kernel).
-    const bool fast_pyramid = fast_ && !getenv("NUS_FLOW_FAST_EXACT_PYRAMID") &&
-                              (jacobi_ == kJacobiStream || unwarped_kernel(0) == kJacobiStreamFast); // (the same pyramid with warps as without)
+    // LDS-tile pyramid runs instead (its planes serve either Jacobi kernel).  (The same pyramid with warps as without.)
+    const bool fast_pyramid = fast_ && (jacobi_ == kJacobiStream || D.level[0].kernel == kJacobiStreamFast);
     const int jacobi = fast_ ? (fast_pyramid ? kJacobiStream : kJacobiTiles) : jacobi_; // (for the exact pyramid launcher's choice)
-    const uint32_t nf = pairs + 1, nl = g.levels, L = nl - 1;
+    const uint32_t nf = pairs + 1, nl = g.levels;
     size_t cells[13] = {0}, lum_off[12], lum_total = 0; // (0 beyond the last level)
     for (uint32_t l = 0; l < nl; ++l) {
         cells[l] = (size_t)g.w[l] * g.h[l];
@@ -625,15 +674,12 @@ int HipFlowEstimator::solve_batch(const StreamJob &J, const Pyramid &g, const Fl
         (rc = reserve(cells[0] * pairs * 8, kFlowA)) != kOk || (rc = reserve(cells[0] * pairs * 8, kFlowB)) != kOk ||
         (rc = reserve(lum_total * 4, kLum)) != kOk)
         return rc;
-    // A level whose Jacobi steps run in the streamed kernel needs no coefficient planes: that kernel takes the
-    // derivatives from the luminance planes of the pair's two frames (consecutive planes of the level) as it goes.
-    auto from_planes = [&](uint32_t l) { return !warped_level(l) && hs_iterate_streams(g.w[l], g.h[l], pairs, level_kernel(l)); };
     size_t coef_cells = 0;
     for (uint32_t l = 0; l < nl; ++l)
-        if (!from_planes(l) && cells[l] > coef_cells) coef_cells = cells[l];
+        if (!D.from_planes(l) && cells[l] > coef_cells) coef_cells = cells[l];
     if (coef_cells != 0 && (rc = reserve(coef_cells * pairs * 12, kCoef)) != kOk) return rc;
     float *level_in[2] = {f32(kLevelInOdd), f32(kLevelInEven)}; // input of level l: [(l - 1) & 1]
-    float *lum = f32(kLum), *f0 = f32(kFlowA), *f1 = f32(kFlowB);
+    float *lum = f32(kLum);
     // pyramids of all frames, level by level
     for (uint32_t l = 0; l < nl; ++l) {
         PyramidLevelLaunch P;
@@ -643,108 +689,15 @@ int HipFlowEstimator::solve_batch(const StreamJob &J, const Pyramid &g, const Fl
         P.in_stride = l == 0 ? cells[0] * 4 /* bytes */ : cells[l] /* float4 */;
         P.level_lum = lum + lum_off[l], P.lum_stride = cells[l];
         P.next = l + 1 < nl ? level_in[l & 1] : nullptr, P.next_stride = cells[l + 1];
-        // luminance only (NUS_FLOW_FAST_EXACT_PYRAMID: dev switch, bisecting): one float per pixel between the levels (the buffers are sized for four)
+        // luminance only: one float per pixel between the levels (the buffers are sized for four)
         NUS_HIP(fast_pyramid ? launch_pyramid_level_fast(P) : launch_pyramid_level(P, jacobi));
+        // the planes of each pair's two frames are consecutive planes of the level
+        D.level[l].i1 = P.level_lum, D.level[l].i2 = P.level_lum + cells[l], D.level[l].stride = cells[l];
     }
-    float *const out = reinterpret_cast<float *>(J.flows);
-    HsIterateResult R; // of the finest level
-    // Rg16Float hand-off: only the FAST streamed kernel's last launch stores halves itself.  The caller's buffer (4 bytes per cell
-    // then) may be handed to the solver only if that launch is what finishes level 0 -- every other kernel writes 2 x f32 per cell
-    // and must be kept in the workspace, its flow converted afterwards.
-    const bool fast_last = level_kernel(0) == kJacobiStreamFast && (nl > 1 ? p.refine_iters > 0 : p.coarse_iters > 0);
-    // With the median (FlowParams::median) no Jacobi launch finishes level 0: each writes the workspace, f32, and the median behind
-    // the last one writes the caller's f32 buffer if there is one (halves: converted afterwards, wrote_half is never set).
-    float *const solver_out = p.median || (J.flow_half && !fast_last) ? nullptr : out;
-    auto prepare = [&](uint32_t l) { // the derivatives of level l from the luminance planes of each pair's two frames
-        HsPrepareLaunch P;
-        P.img = {g.w[l], g.h[l], pairs, stream};
-        P.i1 = lum + lum_off[l], P.i2 = P.i1 + cells[l], P.luminance_planes = true, P.img_stride = cells[l];
-        P.coef = f32(kCoef), P.coef_stride = cells[l] * 3;
-        return P;
-    };
-    // the flow of level l + 1, in f0, as level l takes it up
-    auto coarse_of = [&](uint32_t l) { return HsCoarseFlow{f0, g.w[l + 1], g.h[l + 1], 2.0f, cells[l + 1]}; };
-    // `coarse`: the level continues the flow of level l + 1 in f0, which the first launch upsamples as it loads it
-    // `last`: no further round of the level follows
-    auto iterate = [&](uint32_t l, uint32_t iters, bool zero, bool coarse, bool last = true) -> int {
-        HsIterateLaunch I;
-        I.img = {g.w[l], g.h[l], pairs, stream};
-        I.coef = f32(kCoef), I.coef_stride = cells[l] * 3;
-        I.lum1 = from_planes(l) ? lum + lum_off[l] : nullptr, I.lum_stride = cells[l];
-        I.lambda = p.lambda, I.iterations = iters, I.zero_start = zero;
-        I.flow_a = f0, I.flow_b = f1, I.flow_stride = cells[l];
-        I.final_out = l == 0 && last ? solver_out : nullptr, I.final_stride = cells[0];
-        I.kernel = level_kernel(l);
-        if (coarse) I.coarse = coarse_of(l);
-        I.coarse.scale = 2.0f;
-        I.final_half = l == 0 && J.flow_half && !p.median;
-        HsIterateResult r;
-        NUS_HIP(launch_hs_iterate(I, &r));
-        f0 = r.flow, f1 = r.spare;
-        if (l == 0) R = r;
-        if (p.median) { // from the buffer the run left into the other one, the two names swapped
-            FlowMedianLaunch M;
-            M.img = I.img;
-            M.size = p.median, M.in = f0, M.in_stride = cells[l];
-            M.out = l == 0 && last && out && !J.flow_half ? out : f1, M.out_stride = cells[l];
-            NUS_HIP(launch_flow_median(M));
-            if (M.out == f1) f1 = f0;
-            f0 = M.out;
-        }
-        return kOk;
-    };
-    // coarsest level: from zero flow (compute_coarse_flow, :1136-1154)
-    if (p.coarse_iters > 0) {
-        if (!from_planes(L)) NUS_HIP(launch_hs_prepare(prepare(L)));
-        if ((rc = iterate(L, p.coarse_iters, true, false)) != kOk) return rc;
-    } else {
-        NUS_HIP(hipMemsetAsync(f0, 0, cells[L] * pairs * 8, stream));
-    }
-    for (int li = (int)L - 1; li >= 0; --li) {
-        const uint32_t l = (uint32_t)li;
-        if (warped_level(l)) { // each round: the level's coefficients about the flow it has (round 1: the upsampled one), then the steps
-            for (uint32_t r = 0; r < p.warps; ++r) {
-                if (r == 0) {
-                    NUS_HIP(launch_hs_warp_setup(prepare(l), coarse_of(l), nullptr, 0, f1, cells[l]));
-                    std::swap(f0, f1);
-                } else {
-                    NUS_HIP(launch_hs_warp_setup(prepare(l), HsCoarseFlow{}, f0, cells[l], nullptr, 0));
-                }
-                if ((rc = iterate(l, p.refine_iters, false, false, r + 1 == p.warps)) != kOk) return rc;
-            }
-            continue;
-        }
-        if (p.refine_iters > 0 && from_planes(l)) { // derivatives and upsampled flow both computed inside the Jacobi kernel
-            if ((rc = iterate(l, p.refine_iters, false, true)) != kOk) return rc;
-            continue;
-        }
-        if (p.refine_iters > 0)
-            NUS_HIP(launch_hs_level_setup(prepare(l), coarse_of(l), f1, cells[l]));
-        else
-            NUS_HIP(launch_flow_upsample({g.w[l], g.h[l], pairs, stream}, coarse_of(l), f1, cells[l]));
-        std::swap(f0, f1);
-        if (p.refine_iters > 0 && (rc = iterate(l, p.refine_iters, false, false)) != kOk) return rc;
-    }
-    // Where the level's final flow is now, and in which format
-    const void *final_flow = f0;
-    if (!J.flow_half) {
-        if (out && f0 != out) NUS_HIP(hipMemcpyAsync(out, f0, cells[0] * pairs * 8, hipMemcpyDeviceToDevice, stream));
-        if (out) final_flow = out;
-    } else if (R.wrote_half) { // halves, in the caller's buffer if there is one (the launch wrote there), else in the workspace
-        if (out && f0 != out) NUS_HIP(hipMemcpyAsync(out, f0, cells[0] * pairs * 4, hipMemcpyDeviceToDevice, stream));
-        if (out) final_flow = out;
-    } else { // 2 x f32 per cell in the workspace (solver_out was null): converted into the caller's buffer, or beside it
-        void *dst = out;
-        if (!dst) {
-            if ((rc = reserve(cells[0] * pairs * 4, kFlowsHalf)) != kOk) return rc;
-            dst = u8(kFlowsHalf);
-        }
-        NUS_HIP(launch_flow_to_half(f0, dst, cells[0] * pairs, stream));
-        final_flow = dst;
-    }
-    // the warp kernel behind the estimator, on the flow where it is (the caller's buffer, or the workspace)
-    if (J.mid) NUS_HIP(launch_warp_blend(warp_behind(J, final_flow)));
-    return kOk;
+    D.coef = f32(kCoef), D.flow_a = f32(kFlowA), D.flow_b = f32(kFlowB), D.out = reinterpret_cast<float *>(J.flows);
+    Solved done;
+    if ((rc = solve_levels(D, done)) != kOk) return rc;
+    return place_flow(J, done);
 }
 
 // One lock across stage, estimate and download: no other thread's call can reuse the staging slots in between.

@@ -111,7 +111,8 @@ public:
 
 private:
     // The grow-only device workspace.  Slots 0, 1, 4 and 5 have two names: the pair path's (plan / build_pyramid / solve, and the
-    // primitives), then -- after the bar -- the batch path's (solve_batch).
+    // primitives), then -- after the bar -- the batch path's (solve_batch).  solve_levels names none of them: its caller says where
+    // the levels, the coefficients and the flows are (Schedule).
     enum Slot : int {
         kImage = 0, kLevelInOdd = 0,  // w*h*16: a primitive's input, a pyramid level's input | inputs of the odd levels of all frames
         kTemp = 1, kLevelInEven = 1,  // w*h*16: a primitive's output, blur temp, then the level's coefficients | ... of the even levels
@@ -146,10 +147,44 @@ private:
         size_t flow_bytes() const { return (size_t)w * h * (flow_half ? 4 : 8); }
         size_t mid_stride() const { return mt ? mt->pair_stride : frame_bytes(); }
         StreamJob pairs(uint32_t k0, uint32_t n) const; // the job of pairs [k0, k0 + n)
+        StreamJob(const void *d_frames, uint32_t n, uint32_t w_, uint32_t h_, void *d_flows, void *d_mid, hipStream_t s)
+            : frames(static_cast<const uint8_t *>(d_frames)), n_frames(n), w(w_), h(h_), flows(static_cast<uint8_t *>(d_flows)),
+              mid(static_cast<uint8_t *>(d_mid)), stream(s) {}
     };
     struct Pyramid { // level geometry; levels are packed at `offset` (16 bytes per pixel reserved)
         uint32_t levels = 0, w[12] = {0}, h[12] = {0};
         size_t offset[12] = {0}, total = 0;
+    };
+    // Where one run of the coarse-to-fine schedule (solve_levels) finds and leaves things: n pairs per launch, the pairs on the grid's
+    // z / y axis.  A level's item stride (in cells; 0 for a single pair) is also that of its flows and, x 3, of its coefficients.
+    struct Schedule {
+        uint32_t n = 1;
+        const Pyramid *g = nullptr;
+        FlowParams p;
+        hipStream_t stream = nullptr;
+        struct {
+            const float *i1, *i2; // the level of each pair's two frames
+            size_t stride;
+            int kernel;           // JacobiKernel of the level's steps, unless it is warped: then warped_kernel
+        } level[12] = {};
+        int warped_kernel = 0;
+        bool luminance_planes = true; // false: the levels are f32 RGBA
+        bool per_step = false;        // set_tiled(0): one launch_horn_schunck per step; the coefficient kernels only for warped rounds
+        bool stream_planes = false;   // a level that streams takes its derivatives from the planes, not from coefficient planes
+                                      // (setting it for a single pair is a performance experiment for a later change: it changes launches)
+        float *coef = nullptr;
+        float *flow_a = nullptr, *flow_b = nullptr; // ping-pong
+        float *out = nullptr;                       // the caller's buffer (item stride: level 0's), or null
+        bool half = false;                          // the final flow is wanted as Rg16Float
+        // a warped level: every one but the coarsest; it runs the exact kernels on coefficient planes, FAST or not (k_hs_stream_fast
+        // takes It from the luminance planes itself; the exact result is inside FAST's contract)
+        bool warped_level(uint32_t l) const { return warped(p) && l + 1 < g->levels; }
+        int kernel(uint32_t l) const { return warped_level(l) ? warped_kernel : level[l].kernel; }
+        bool from_planes(uint32_t l) const; // level l needs no coefficient planes
+    };
+    struct Solved { // where level 0's flow ended up (the caller's buffer or the workspace), and whether the last launch stored halves
+        float *flow = nullptr;
+        bool wrote_half = false;
     };
     struct Staged { // a slot a primitive needs, and the host buffer (if any) that fills it
         Slot slot;
@@ -164,6 +199,8 @@ private:
     int plan(uint32_t w, uint32_t h, uint32_t levels, Pyramid &g); // geometry + workspace
     int build_pyramid(const void *frame, Slot pyr, const Pyramid &g, hipStream_t stream);
     int solve(Slot pyr_a, Slot pyr_b, const Pyramid &g, const FlowParams &p, void *d_flow_out, hipStream_t stream);
+    int solve_levels(const Schedule &D, Solved &done);   // the schedule itself, for solve and solve_batch
+    int place_flow(const StreamJob &J, const Solved &s); // behind it: the flow where and as J wants it, and the warp
     int estimate_pair(const void *d_a, const void *d_b, uint32_t w, uint32_t h, const FlowParams &p, void *d_flow_out,
                       hipStream_t stream);
     // multi-step kernels, a chunk of consecutive pairs per launch (pairs on the grid's y / z axis): as many as fit the

@@ -1,4 +1,4 @@
-"""nus_flow_set_warps on the GPU, across what solve() and solve_batch() of nus_flow.cpp decide for a warped level: the estimator
+"""nus_flow_set_warps on the GPU, across what solve_levels() of nus_flow.cpp decides for a warped level, as solve() (a pair) and solve_batch() (a chunk) call it: the estimator
 itself against its CPU float32 restatement (tests/_flow_warp64.py::estimate_f32, which tests/test_flow_warp_yardstick.py holds to the
 float64 witness on the same cases) over W.LATTICE -- warps 1 .. 4, one to four levels, step counts that split into launches
 unevenly, no refining or no coarse steps, two and four row blocks, more than three strips, all three LDS-tile classes, sizes below a
