@@ -392,9 +392,10 @@ def test_flow_fast_mode_1080p_contract(nsc, oracle_mod):
                                                        (333, 100, 1, 37, 0)])
 def test_flow_fast_ring_form_equals_the_shifting_form(nsc, oracle_mod, w, h, levels, coarse, refine, monkeypatch):
     """Round 5: k_hs_stream_fast keeps every queue of its pipeline in rings with compile-time slot indices (six copies of the pass,
-    no register moves); the shifting form of rounds 3-4 is still in the library (launches of more than 5 steps use it) and
-    NUS_HS_FAST_SHIFT=1 selects it everywhere.  Same operations on the same operands in the same order: the flows of the two
-    forms are bit-identical -- ragged sizes, blocks shorter than a turn of the rings, several row blocks, 1..5 steps per launch."""
+    no register moves), for every launch of up to 8 steps (kHsFastRingMaxK: rings of 6 or 9 slots), which is every launch there is;
+    the shifting form of rounds 3-4 is still in the library and NUS_HS_FAST_SHIFT=1 selects it everywhere.  Same operations on the
+    same operands in the same order: the flows of the two forms are bit-identical -- ragged sizes, blocks shorter than a turn of the
+    rings, several row blocks, 1..8 steps per launch (37 and 50 steps: launches of 8 and 7; every K: tests/test_gpu_flow_steps.py)."""
     import torch
 
     dev = torch.device("cuda:0")
