@@ -576,6 +576,12 @@ int nus_flow_set_median(nus_flow *h, uint32_t size);
 int nus_flow_median_size(const nus_flow *h);
 /* Bytes of device workspace the handle holds now (grow-only; 0 for a null handle or before the first call that needs a device). */
 size_t nus_flow_workspace_bytes(nus_flow *h);
+/* TEST HOOK: every byte of the handle's device workspace -- every slot, over its whole capacity -- set to byte_value (0..255) on
+ * `stream`, which is synchronised before the call returns (so the host entry points, which run on the handle's own stream, see
+ * the fill as well).  What the tests use to show that no result depends on what the workspace held before the call.  Refused with
+ * NUS_ERR_INVALID_ARGUMENT, the text beginning "nus_flow_fill_workspace:", unless the PROCESS has NUS_TEST_HOOKS=1 in its
+ * environment (read per call), and for a value outside 0..255.  A null handle, or one that has reserved nothing: NUS_OK, no HIP call. */
+int nus_flow_fill_workspace(nus_flow *h, int byte_value, void *stream);
 /* Projection rounds (BUILD-DEFINED; the rule is stated at nus_interp_set_flow_project) of the warp behind the estimator:
  * nus_flow_interpolate_device_stream and nus_flow_interpolate_multi_device_stream (per time) warp with the projected vector g
  * instead of the flow at the output pixel.  0 (default) .. NUS_FLOW_MAX_PROJECT.  The flows written to d_flows are unchanged, the
@@ -617,6 +623,13 @@ int nus_flow_horn_schunck_coef(nus_flow *h, const float *coef, const float *flow
 int nus_flow_estimate(nus_flow *h, const uint8_t *a, const uint8_t *b, uint32_t w, uint32_t hgt,
                       uint32_t levels, uint32_t coarse_iters, uint32_t refine_iters, float lambda,
                       float *flow_out);
+/* THE STREAM RULE of the device entry points below (nus_flow_estimate_device, _estimate_device_stream, _interpolate_device_stream,
+ * _interpolate_multi_device_stream).  All calls of one handle share its device workspace, and no call's result depends on what the
+ * workspace held before it.  Calls enqueued on ONE stream need no synchronisation between them, whatever their sizes and settings:
+ * stream order keeps a call's kernels behind the previous call's, and a call that has to grow the workspace waits for the device
+ * before it frees the old memory.  Before the handle is used from ANOTHER stream, or a host entry point is called (nus_flow_estimate
+ * and the primitives run on the handle's own stream), the caller synchronises the stream of the calls before: nothing else orders
+ * the two streams' kernels in the shared workspace. */
 /* Device-resident variant; enqueues on `stream`, no synchronisation. */
 int nus_flow_estimate_device(nus_flow *h, const void *d_a, const void *d_b, uint32_t w, uint32_t hgt,
                              uint32_t levels, uint32_t coarse_iters, uint32_t refine_iters, float lambda,

@@ -142,6 +142,7 @@ SIGNATURES = [
     ("nus_flow_set_median", _i, [_vp, _u32]),
     ("nus_flow_median_size", _i, [_vp]),
     ("nus_flow_workspace_bytes", _sz, [_vp]),
+    ("nus_flow_fill_workspace", _i, [_vp, _i, _vp]),  # TEST HOOK (NUS_TEST_HOOKS=1)
     ("nus_flow_set_project", _i, [_vp, _u32]),
     ("nus_flow_project_rounds", _i, [_vp]),
     ("nus_flow_last_error", _cp, [_vp]),

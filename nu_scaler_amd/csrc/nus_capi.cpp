@@ -720,6 +720,11 @@ int nus_flow_set_median(nus_flow *h, uint32_t size)
 }
 int nus_flow_median_size(const nus_flow *h) { return h ? h->impl.median_size() : NUS_ERR_INVALID_ARGUMENT; }
 size_t nus_flow_workspace_bytes(nus_flow *h) { return h ? h->impl.workspace_bytes() : 0; }
+int nus_flow_fill_workspace(nus_flow *h, int byte_value, void *stream) // TEST HOOK (NUS_TEST_HOOKS=1); a null handle holds nothing
+{
+    return guarded<int>("nus_flow_fill_workspace",
+                        [&]() -> int { return h ? h->impl.fill_workspace(byte_value, static_cast<hipStream_t>(stream)) : NUS_OK; });
+}
 int nus_flow_set_project(nus_flow *h, uint32_t rounds)
 {
     return guarded<int>("nus_flow_set_project", [&]() -> int { return h ? h->impl.set_project(rounds) : null_handle(); });

@@ -2,6 +2,7 @@
 #include "nus_flow.hpp"
 
 #include <cstdlib>
+#include <cstring>
 
 #include "nus_host.hpp"
 #include "nus_host_util.hpp"
@@ -63,6 +64,27 @@ size_t HipFlowEstimator::workspace_bytes()
     return total;
 }
 
+// TEST HOOK: what the workspace held before a call must not show in the call's results (tests/test_gpu_flow_workspace.py).  The
+// slots are reachable from nowhere else, so the poison has to come from inside.
+int HipFlowEstimator::fill_workspace(int byte_value, hipStream_t stream)
+{
+    std::lock_guard<std::mutex> lk(mu_);
+    // refused unless the PROCESS asked for test hooks (as nus_upscaler_set_option's "inject_retire_error")
+    const char *hooks = getenv("NUS_TEST_HOOKS");
+    if (!hooks || strcmp(hooks, "1") != 0) return fail(kInvalidArgument, "nus_flow_fill_workspace: a test hook (NUS_TEST_HOOKS=1 only)");
+    if (byte_value < 0 || byte_value > 255) return fail(kInvalidArgument, fmt("nus_flow_fill_workspace: a byte value 0..255, got %d", byte_value));
+    if (!ready_) return kOk; // nothing reserved yet: no HIP call
+    bool any = false;
+    for (const DeviceBuffer &s : slot_) any = any || s.capacity() != 0;
+    if (!any) return kOk;
+    NUS_HIP(hipSetDevice(device_));
+    for (const DeviceBuffer &s : slot_)
+        if (s.capacity() != 0) NUS_HIP(hipMemsetAsync(s.get(), byte_value, s.capacity(), stream));
+    // the host entry points run on the handle's own stream: they see the fill only once `stream` has finished
+    NUS_HIP(hipStreamSynchronize(stream));
+    return kOk;
+}
+
 int HipFlowEstimator::set_device(int device)
 {
     std::lock_guard<std::mutex> lk(mu_);
@@ -85,7 +107,15 @@ int HipFlowEstimator::ensure_device()
     return kOk;
 }
 
-int HipFlowEstimator::reserve(size_t bytes, Slot slot) { return pass(slot_[slot].reserve(bytes, stream_)); }
+// Growing a slot frees the old memory: behind everything the handle has queued on its own stream AND on the stream of the call in
+// progress (the stream rule of the header: one stream's calls need no synchronisation between them, so the call before may still
+// be running in the slot).  hipFree's own implicit device synchronisation is documented; this does not lean on it.
+int HipFlowEstimator::reserve(size_t bytes, Slot slot)
+{
+    DeviceBuffer &s = slot_[slot];
+    if (bytes > s.capacity() && s.get() && call_stream_ != stream_) NUS_HIP(hipStreamSynchronize(call_stream_));
+    return pass(s.reserve(bytes, stream_));
+}
 
 void HipFlowEstimator::release()
 {
@@ -109,6 +139,7 @@ int HipFlowEstimator::primitive(std::initializer_list<std::pair<uint32_t, uint32
         if ((rc = check_size(d.first, d.second)) != kOk) return rc;
     if (!pointers_ok) return fail(kInvalidArgument, "flow: null pointer");
     if ((rc = ensure_device()) != kOk) return rc;
+    call_stream_ = stream_;
     for (const Staged &s : stage)
         if ((rc = reserve(s.bytes, s.slot)) != kOk) return rc;
     for (const Staged &s : stage)
@@ -462,6 +493,7 @@ int HipFlowEstimator::estimate_device(const void *d_a, const void *d_b, uint32_t
                                       hipStream_t stream)
 {
     std::lock_guard<std::mutex> lk(mu_);
+    call_stream_ = stream;
     return estimate_pair(d_a, d_b, w, h, with_warps(p), d_flow_out, stream);
 }
 
@@ -496,6 +528,7 @@ int HipFlowEstimator::estimate_device_stream(const void *d_frames, uint32_t n_fr
 {
     std::lock_guard<std::mutex> lk(mu_);
     if (!d_flows) return fail(kInvalidArgument, "flow: null device pointer");
+    call_stream_ = stream;
     return stream_impl(StreamJob(d_frames, n_frames, w, h, d_flows, nullptr, stream), with_warps(p));
 }
 
@@ -509,6 +542,7 @@ int HipFlowEstimator::interpolate_device_stream(const void *d_frames, uint32_t n
         return fail(kInvalidArgument, "flow: device pointers must be 16-byte aligned");
     StreamJob J(d_frames, n_frames, w, h, d_flows, d_mid, stream);
     J.t = t, J.flow_half = flow_half, J.project = project_;
+    call_stream_ = stream;
     return stream_impl(J, with_warps(p));
 }
 
@@ -536,6 +570,7 @@ int HipFlowEstimator::interpolate_multi_device_stream(const void *d_frames, uint
     const MidTimes mt{times, n_times, mid_pair_stride ? mid_pair_stride : n_times * frame_bytes};
     StreamJob J(d_frames, n_frames, w, h, d_flows, d_mid, stream);
     J.t = times[0], J.flow_half = flow_half, J.mt = &mt, J.project = project_;
+    call_stream_ = stream;
     if ((rc = stream_impl(J, with_warps(p))) != kOk || !scene_) return rc;
     // behind estimate + warp, the detector (it reads the frames only, so its place in the order is free) and the flagged pairs'
     // frames overwritten with repeats
@@ -708,6 +743,7 @@ int HipFlowEstimator::estimate(const uint8_t *a, const uint8_t *b, uint32_t w, u
     if (rc != kOk) return rc;
     if (!a || !b || !flow_out) return fail(kInvalidArgument, "flow: null pointer");
     if ((rc = ensure_device()) != kOk) return rc;
+    call_stream_ = stream_;
     const size_t fbytes = (size_t)w * h * 4;
     if ((rc = reserve(fbytes, kHostA)) != kOk || (rc = reserve((size_t)w * h * 8, kHostB)) != kOk) return rc;
     if ((rc = pass(upload(u8(kHostA), a, fbytes, stream_))) != kOk || (rc = pass(upload(u8(kHostB), b, fbytes, stream_))) != kOk) return rc;

@@ -85,6 +85,10 @@ public:
     int project_rounds() const { return (int)project_; }
     // Bytes of device workspace the handle holds (the sum of its grow-only slots): what "reserves the workspace it did" is checked with.
     size_t workspace_bytes();
+    // TEST HOOK (nus_flow_fill_workspace; refused unless the process has NUS_TEST_HOOKS=1, read per call): every byte of every slot,
+    // over its whole capacity, set to `byte_value` (0..255) on `stream`, which is synchronised before the call returns.  A handle
+    // that has reserved nothing: kOk, no HIP call.
+    int fill_workspace(int byte_value, hipStream_t stream);
     // Scene-cut detection in front of interpolate_multi_device_stream and the cut-aware output rule behind it (nus_scene_* of the C
     // header): off by default.  On, the in-between frames of a pair the detector flags are repeats of the nearer real frame.
     int set_scene_detect(int enabled, uint32_t mad_threshold, uint32_t hist_permille);
@@ -231,6 +235,7 @@ private:
     uint32_t project_ = 0; // set_project
     bool fast_ = false; // set_mode(1): the estimator's Jacobi steps in FAST arithmetic (k_hs_stream_fast), every level streamed
     hipStream_t stream_ = nullptr;
+    hipStream_t call_stream_ = nullptr; // (mu_ held) the stream of the entry point in progress: reserve() waits for it before it frees
     bool scene_ = false; // set_scene_detect
     uint32_t scene_mad_ = 20, scene_hist_ = 400;
     DeviceBuffer slot_[kSlotCount];

@@ -122,6 +122,11 @@ class FlowEstimator:
         """Bytes of device workspace the handle holds now (nus_flow_workspace_bytes; grow-only)."""
         return int(self._lib.nus_flow_workspace_bytes(self._h))
 
+    def _fill_workspace(self, byte: int, stream: int = 0) -> None:
+        """TEST HOOK (nus_flow_fill_workspace; the process needs NUS_TEST_HOOKS=1): every byte of the handle's device workspace set
+        to `byte` on `stream`, which is synchronised before this returns."""
+        self._check(self._lib.nus_flow_fill_workspace(self._h, int(byte), stream or None))
+
     def set_scene_detect(self, enabled: bool, mad_threshold: int = C.SCENE_DEFAULT_MAD,
                          hist_permille: int = C.SCENE_DEFAULT_HIST_PERMILLE) -> None:
         """Scene-cut detection in front of `interpolate_multi_device_stream` (nus_flow_set_scene_detect; off by default): the
