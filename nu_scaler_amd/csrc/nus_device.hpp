@@ -249,7 +249,22 @@ constexpr uint32_t kMaxGridZ = 65535;
 
 inline uint32_t cdiv(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 
-// Frames go on grid.z (<= 65535 per launch); longer batches are issued in chunks: f(in, out, n) per chunk.
+// Frames (or frame pairs) go on grid.z (<= 65535 per launch); longer batches are issued in chunks: f(done, n) launches items
+// done .. done + n, and the first launch error ends the loop.
+template <typename F>
+hipError_t for_grid_z_chunks(uint32_t total, F &&f)
+{
+    for (uint32_t done = 0; done < total;) {
+        const uint32_t n = total - done < kMaxGridZ ? total - done : kMaxGridZ;
+        f(done, n);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        done += n;
+    }
+    return hipSuccess;
+}
+
+// The upscalers' form: f(in, out, n) per chunk.
 inline size_t launch_in_frame_bytes(const UpscaleLaunch &L) { return L.in_stride ? L.in_stride : (size_t)L.iw * L.ih * 4; }
 // index of the chunk's first frame (for kernels that take a second input per frame), from the chunk's input pointer
 inline size_t chunk_first_frame(const UpscaleLaunch &L, const uint8_t *chunk_in)
@@ -260,14 +275,7 @@ template <typename F>
 hipError_t for_frame_chunks(const UpscaleLaunch &L, F &&f)
 {
     const size_t in_bytes = launch_in_frame_bytes(L), out_bytes = (size_t)L.ow * L.oh * 4;
-    for (uint32_t done = 0; done < L.n_frames;) {
-        const uint32_t n = L.n_frames - done < kMaxGridZ ? L.n_frames - done : kMaxGridZ;
-        f(L.in + (size_t)done * in_bytes, L.out + (size_t)done * out_bytes, n);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        done += n;
-    }
-    return hipSuccess;
+    return for_grid_z_chunks(L.n_frames, [&](uint32_t done, uint32_t n) { f(L.in + (size_t)done * in_bytes, L.out + (size_t)done * out_bytes, n); });
 }
 
 } // namespace

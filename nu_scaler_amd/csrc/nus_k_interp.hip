@@ -69,117 +69,53 @@ __global__ __launch_bounds__(256) void k_blend_zero_flow(
 //    MODE_FMA  : each of the three lerps of a sample as one multiply and one fused multiply-add, fma(b, f, a (1 - f)): 24
 //    instead of 36 operations per sample (and the sample positions as one FMA each), inside the +-1 LSB contract of the
 //    interpolation path (measured on noise frames with random flows: < 0.1 % of the samples differ, none by more than
-//    one count).  The blend of the two samples is exact in both modes (see the kernel).
+//    one count).  The blend of the two samples is exact in both modes (see warp_blend_pixel).
 // The truncation of each sample to u8 (sample_frame returns u8: interpolation/mod.rs:506) stays in both modes.
 // Dense flow (2 x f32 or 2 x f16 per pixel, delta A -> B): A sampled at p - t*flow, B at p + (1-t)*flow
-// (warp_blend.wgsl:36-37 in texel space).  A thread owns XV consecutive pixels in each of RV rows (rows y, y + 4, .. of the
-// block's 4 RV): its flow vectors are loaded first, then the gathers of its pixels -- independent chains -- are in flight
-// together.  XV = 2 (frame width even): the two flow vectors of a row are one 16-byte (8-byte) load, the two pixels one
-// 8-byte store, and a wave's gathers stay on few cache lines.  blockDim = (64, 4): a block covers 64 XV x 4 RV pixels.
-// HALF: the flow field is the Rg16Float texture of the reference's live path (wgpu_interpolator.rs:276), widened exactly.
-// Measured on one box, 1080p, us per pair, EXACT / FMA (profiles/r03_warp_kernel_layouts_ab.txt): the round-2 kernel (1 x 4, border
-// selects) 10.7 / -; 1 x 4 9.6-10.4 / 8.5-8.7; 4 x 1 11.2-13.1 / 11.1-13.1 (a wave's gathers spread over four times the
-// cache lines: the kernel stops being bound by its arithmetic); 2 x 2: 8.7-9.3 / 7.9-8.5.
-#ifndef NUS_WARP_XV
-#define NUS_WARP_XV 2
-#endif
-#ifndef NUS_WARP_RV
-#define NUS_WARP_RV 2
-#endif
-// MT: the multi-time form -- the thread's flow vectors are loaded once, then its pixels are warped, blended and stored once per
-// time of the set (frame k of the pair at out + k * w * h * 4; the gathers of the later times hit the lines the first one brought
-// into the L2).  MT = false is the single-time kernel: the set's one time, no loop.
+// (warp_blend.wgsl:36-37 in texel space).  The layout -- threads, rows, times, stores -- is warp_blend_tile's
+// (nus_warp_device.hpp), shared with the block-vector and the projecting kernels; this unit supplies the vectors: the flow at the
+// thread's own pixels.  XV = 2: the two flow vectors of a row are one 16-byte (8-byte) load (w even and the plane 16-byte aligned,
+// host-checked).  HALF: the flow field is the Rg16Float texture of the reference's live path (wgpu_interpolator.rs:276), widened
+// exactly.
+__device__ __forceinline__ float2 widen(uint32_t bits) // one 2 x f16 flow vector
+{
+    const __half2 hf = *reinterpret_cast<const __half2 *>(&bits);
+    return make_float2(__low2float(hf), __high2float(hf));
+}
+
+template <bool HALF, int XV, int RV>
+struct DenseFlowSource {
+    static constexpr bool kSwizzle = true;
+    const void *flow;
+    float2 f[RV][XV];
+
+    __device__ __forceinline__ void load(uint32_t ybase, uint32_t x0, uint32_t w, uint32_t h, size_t npx)
+    {
+#pragma unroll
+        for (int j = 0; j < RV; ++j) {
+            const size_t idx = (size_t)blockIdx.z * npx + (size_t)umin(ybase + 4 * j, h - 1) * w + x0;
+            if (XV == 2 && HALF) {
+                const uint2 raw = *reinterpret_cast<const uint2 *>(static_cast<const uint32_t *>(flow) + idx);
+                f[j][0] = widen(raw.x), f[j][XV - 1] = widen(raw.y);
+            } else if (XV == 2) {
+                const float4 v = *reinterpret_cast<const float4 *>(static_cast<const float2 *>(flow) + idx);
+                f[j][0] = make_float2(v.x, v.y), f[j][XV - 1] = make_float2(v.z, v.w);
+            } else {
+                f[j][0] = HALF ? widen(static_cast<const uint32_t *>(flow)[idx]) : static_cast<const float2 *>(flow)[idx];
+            }
+        }
+    }
+    __device__ __forceinline__ void at_time(uint32_t, uint32_t, uint32_t, uint32_t, float, float, float) {}
+    __device__ __forceinline__ float2 vec(int j, int i) const { return f[j][i]; }
+};
+
 template <int MODE, bool HALF, int XV, int RV, bool MT>
 __global__ __launch_bounds__(256) void k_warp_blend_flow(
     const uint8_t *__restrict__ a, const uint8_t *__restrict__ b, const void *__restrict__ flow,
     uint8_t *__restrict__ out, size_t a_stride, size_t b_stride, size_t out_pair_stride, uint32_t w, uint32_t h, TimeSet ts,
     uint32_t sel)
 {
-    const uint32_t ybase = __builtin_amdgcn_readfirstlane(blockIdx.y * (4 * RV) + threadIdx.y);
-    const uint32_t x0 = (blockIdx.x * kWave + threadIdx.x) * XV;
-    if (ybase >= h || x0 >= w) return;
-    const size_t npx = (size_t)w * h;
-    const uint32_t frame_bytes = (uint32_t)(npx * 4), row_bytes = w * 4;
-    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint8_t *>(a + (size_t)blockIdx.z * a_stride), 0, frame_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint8_t *>(b + (size_t)blockIdx.z * b_stride), 0, frame_bytes, 0x00020000);
-    // per-lane copies of the wave-uniform constants: scalar operands halve the VALU issue rate on gfx950
-    float wmax = (float)(w - 1), hmax = (float)(h - 1);
-    asm volatile("" : "+v"(wmax), "+v"(hmax));
-    const size_t frame0 = (size_t)blockIdx.z * npx;
-    float2 f[RV][XV];
-#pragma unroll
-    for (int j = 0; j < RV; ++j) { // the flow vectors of all the thread's pixels first (rows past the frame: the last row's)
-        const size_t idx = frame0 + (size_t)umin(ybase + 4 * j, h - 1) * w + x0;
-        if (XV == 4) {
-            if (HALF) {
-                const uint4 raw = *reinterpret_cast<const uint4 *>(reinterpret_cast<const __half2 *>(flow) + idx);
-                const uint32_t rw[4] = {raw.x, raw.y, raw.z, raw.w};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const __half2 hf = *reinterpret_cast<const __half2 *>(&rw[i]);
-                    f[j][i] = make_float2(__low2float(hf), __high2float(hf));
-                }
-            } else {
-                const float4 lo = reinterpret_cast<const float4 *>(reinterpret_cast<const float2 *>(flow) + idx)[0];
-                const float4 hi = reinterpret_cast<const float4 *>(reinterpret_cast<const float2 *>(flow) + idx)[1];
-                f[j][0] = make_float2(lo.x, lo.y);
-                f[j][1] = make_float2(lo.z, lo.w);
-                f[j][2] = make_float2(hi.x, hi.y);
-                f[j][3] = make_float2(hi.z, hi.w);
-            }
-        } else if (XV == 2) { // (w even, host-checked: the pair is 16-byte / 8-byte aligned)
-            if (HALF) {
-                const uint2 raw = *reinterpret_cast<const uint2 *>(reinterpret_cast<const __half2 *>(flow) + idx);
-                const __half2 h0 = *reinterpret_cast<const __half2 *>(&raw.x), h1 = *reinterpret_cast<const __half2 *>(&raw.y);
-                f[j][0] = make_float2(__low2float(h0), __high2float(h0));
-                f[j][1] = make_float2(__low2float(h1), __high2float(h1));
-            } else {
-                const float4 v = *reinterpret_cast<const float4 *>(reinterpret_cast<const float2 *>(flow) + idx);
-                f[j][0] = make_float2(v.x, v.y);
-                f[j][1] = make_float2(v.z, v.w);
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < XV; ++i) {
-                if (HALF) {
-                    const __half2 hf = reinterpret_cast<const __half2 *>(flow)[idx + i];
-                    f[j][i] = make_float2(__low2float(hf), __high2float(hf));
-                } else {
-                    f[j][i] = reinterpret_cast<const float2 *>(flow)[idx + i];
-                }
-            }
-        }
-    }
-    const uint32_t nk = MT ? ts.n : 1;
-    for (uint32_t k = 0; k < nk; ++k) {
-        float tv = ts.t[k];
-        asm volatile("" : "+v"(tv));
-        const float nt = 1.0f - tv;
-        uint32_t *const frame_out = reinterpret_cast<uint32_t *>(out + (size_t)blockIdx.z * out_pair_stride + (size_t)k * npx * 4);
-#pragma unroll
-        for (int j = 0; j < RV; ++j) {
-            const uint32_t y = ybase + 4 * j;
-            if (y >= h) break; // wave-uniform
-            const float yfl = (float)y;
-            uint32_t o[XV];
-#pragma unroll
-            for (int i = 0; i < XV; ++i) {
-                const uint32_t p = warp_blend_pixel<MODE>(ra, rb, row_bytes, wmax, hmax, w - 2, h - 2, (float)(x0 + i), yfl, f[j][i], tv, nt);
-                o[i] = swz(p, sel);
-            }
-            uint32_t *dst = frame_out + (size_t)y * w + x0;
-            if (XV == 4) {
-                store_out16<false>(dst, make_uint4(o[0], o[1], o[2], o[3]));
-            } else if (XV == 2) {
-                store_out8<false>(dst, make_uint2(o[0], o[1]));
-            } else {
-#pragma unroll
-                for (int i = 0; i < XV; ++i) dst[i] = o[i];
-            }
-        }
-    }
+    warp_blend_tile<MODE, XV, RV, MT>(a, b, out, a_stride, b_stride, out_pair_stride, w, h, ts, sel, DenseFlowSource<HALF, XV, RV>{flow, {}});
 }
 
 // Frames narrower or lower than 2 pixels, or of 4 GiB and more: one pixel per thread, 64-bit addressing (EXACT arithmetic).
@@ -196,24 +132,11 @@ __global__ __launch_bounds__(256) void k_warp_blend_flow_tiny(
     const size_t npx = (size_t)w * h, idx = (size_t)blockIdx.z * npx + (size_t)y * w + x, pix = (size_t)y * w + x;
     const uint32_t *fa = reinterpret_cast<const uint32_t *>(a + (size_t)blockIdx.z * a_stride);
     const uint32_t *fb = reinterpret_cast<const uint32_t *>(b + (size_t)blockIdx.z * b_stride);
-    float2 f;
-    if (half) {
-        const __half2 hf = reinterpret_cast<const __half2 *>(flow)[idx];
-        f = make_float2(__low2float(hf), __high2float(hf));
-    } else {
-        f = reinterpret_cast<const float2 *>(flow)[idx];
-    }
+    const float2 f = half ? widen(static_cast<const uint32_t *>(flow)[idx]) : static_cast<const float2 *>(flow)[idx];
     const uint32_t nk = MT ? ts.n : 1;
     for (uint32_t k = 0; k < nk; ++k) {
         const float t = ts.t[k];
-        const float nt = 1.0f - t;
-        const float4 sa = sample_trunc(fa, w, h, (float)x - t * f.x, (float)y - t * f.y);
-        const float4 sb = sample_trunc(fb, w, h, (float)x + nt * f.x, (float)y + nt * f.y);
-        uint32_t o = 0;
-        o = pack_trunc_u8(nt * sa.x + t * sb.x, 0, o);
-        o = pack_trunc_u8(nt * sa.y + t * sb.y, 1, o);
-        o = pack_trunc_u8(nt * sa.z + t * sb.z, 2, o);
-        o = pack_trunc_u8(nt * sa.w + t * sb.w, 3, o);
+        const uint32_t o = warp_blend_pixel_plain(fa, fb, w, h, x, y, f, t, 1.0f - t);
         reinterpret_cast<uint32_t *>(out + (size_t)blockIdx.z * out_pair_stride + (size_t)k * npx * 4)[pix] = swz(o, sel);
     }
 }
@@ -257,19 +180,11 @@ hipError_t launch_warp_blend(const WarpLaunch &L)
 {
     if (L.project > 0 && L.flow != nullptr) return launch_warp_blend_project(L); // nus_k_warp_project.hip; off: everything below, as before
     const size_t npx = (size_t)L.w * L.h;
-    TimeSet ts{};
-    if (L.n_times == 0) {
-        ts.t[0] = L.t;
-        ts.n = 1;
-    } else {
-        if (L.n_times > kInterpMaxTimes || L.times == nullptr) return hipErrorInvalidValue;
-        for (uint32_t k = 0; k < L.n_times; ++k) ts.t[k] = L.times[k];
-        ts.n = L.n_times;
-    }
+    TimeSet ts;
+    if (!warp_time_set(L.t, L.times, L.n_times, ts)) return hipErrorInvalidValue;
     const bool mt = ts.n > 1;
-    const size_t out_stride = L.out_pair_stride ? L.out_pair_stride : ts.n * npx * 4;
-    for (uint32_t done = 0; done < L.n_pairs;) {
-        const uint32_t n = L.n_pairs - done < kMaxGridZ ? L.n_pairs - done : kMaxGridZ;
+    const size_t out_stride = warp_out_stride(L.out_pair_stride, ts, npx);
+    return for_grid_z_chunks(L.n_pairs, [&](uint32_t done, uint32_t n) {
         const uint8_t *a = L.a + (size_t)done * L.a_stride;
         const uint8_t *b = L.b + (size_t)done * L.b_stride;
         uint8_t *out = L.out + (size_t)done * out_stride;
@@ -286,41 +201,26 @@ hipError_t launch_warp_blend(const WarpLaunch &L)
                 if (mt) NUS_ZB(false, true); else NUS_ZB(false, false);
             }
 #undef NUS_ZB
-        } else {
-            const void *fl = reinterpret_cast<const uint8_t *>(L.flow) + (size_t)done * npx * (L.flow_half ? 4 : 8);
-            const bool corner = L.w >= 2 && L.h >= 2 && npx * 4 < (1ull << 32) && L.w * 4ull < (1u << 24) && L.h < (1u << 24);
-            if (!corner) {
-                const dim3 block(kWave, 4), grid(cdiv(L.w, 64), cdiv(L.h, 4), n);
-                if (mt)
-                    hipLaunchKernelGGL(k_warp_blend_flow_tiny<true>, grid, block, 0, L.stream, a, b, fl, L.flow_half, out, L.a_stride,
-                                       L.b_stride, out_stride, L.w, L.h, ts, L.in_sel);
-                else
-                    hipLaunchKernelGGL(k_warp_blend_flow_tiny<false>, grid, block, 0, L.stream, a, b, fl, L.flow_half, out, L.a_stride,
-                                       L.b_stride, out_stride, L.w, L.h, ts, L.in_sel);
-            } else {
-                constexpr int XV = NUS_WARP_XV, RV = NUS_WARP_RV;
-                const uintptr_t align = XV == 4 ? 16 : 8; // of the thread's output pixels (its f16 flow vectors: the same bytes)
-                const bool xv_ok = XV == 1 || ((L.w % XV) == 0 && (reinterpret_cast<uintptr_t>(fl) % 16) == 0 &&
-                                               (reinterpret_cast<uintptr_t>(out) % align) == 0 && (out_stride % align) == 0);
-                const dim3 block(kWave, 4), grid(cdiv(L.w, 64 * (xv_ok ? XV : 1)), cdiv(L.h, 4 * RV), n);
-#define NUS_WB(M, H, X, MT) hipLaunchKernelGGL((k_warp_blend_flow<M, H, X, RV, MT>), grid, block, 0, L.stream, a, b, fl, out, L.a_stride, L.b_stride, out_stride, L.w, L.h, ts, L.in_sel)
-#define NUS_WB_T(M, H, X) do { if (mt) NUS_WB(M, H, X, true); else NUS_WB(M, H, X, false); } while (0)
-#define NUS_WB_X(M, H) do { if (xv_ok) NUS_WB_T(M, H, XV); else NUS_WB_T(M, H, 1); } while (0)
-                if (L.fma) {
-                    if (L.flow_half) NUS_WB_X(kWarpFma, true); else NUS_WB_X(kWarpFma, false);
-                } else {
-                    if (L.flow_half) NUS_WB_X(kWarpExact, true); else NUS_WB_X(kWarpExact, false);
-                }
-#undef NUS_WB_X
-#undef NUS_WB_T
-#undef NUS_WB
-            }
+            return;
         }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        done += n;
-    }
-    return hipSuccess;
+        const void *fl = reinterpret_cast<const uint8_t *>(L.flow) + (size_t)done * npx * (L.flow_half ? 4 : 8);
+        const dim3 block(kWave, 4);
+        if (!warp_corner_ok(L.w, L.h, 0)) { // (the flow is read through 64-bit addresses: no bound on its plane)
+            hipLaunchKernelGGL(mt ? k_warp_blend_flow_tiny<true> : k_warp_blend_flow_tiny<false>, warp_grid(L.w, L.h, 1, 1, n), block, 0,
+                               L.stream, a, b, fl, L.flow_half, out, L.a_stride, L.b_stride, out_stride, L.w, L.h, ts, L.in_sel);
+            return;
+        }
+        // a pair of pixels per thread: its output pixels are one 8-byte store, its f32 flow vectors one 16-byte load
+        const bool xv_ok = (L.w % 2) == 0 && (reinterpret_cast<uintptr_t>(fl) % 16) == 0 && (reinterpret_cast<uintptr_t>(out) % 8) == 0 &&
+                           (out_stride % 8) == 0;
+#define NUS_WB(M, H, X) {k_warp_blend_flow<M, H, X, kWarpRV, false>, k_warp_blend_flow<M, H, X, kWarpRV, true>}
+        static constexpr decltype(&k_warp_blend_flow<kWarpExact, false, 1, kWarpRV, false>) kernels[2][2][2][2] = { // [fma][half][pair][mt]
+            {{NUS_WB(kWarpExact, false, 1), NUS_WB(kWarpExact, false, 2)}, {NUS_WB(kWarpExact, true, 1), NUS_WB(kWarpExact, true, 2)}},
+            {{NUS_WB(kWarpFma, false, 1), NUS_WB(kWarpFma, false, 2)}, {NUS_WB(kWarpFma, true, 1), NUS_WB(kWarpFma, true, 2)}}};
+#undef NUS_WB
+        hipLaunchKernelGGL(kernels[L.fma][L.flow_half][xv_ok][mt], warp_grid(L.w, L.h, xv_ok ? 2 : 1, kWarpRV, n), block, 0, L.stream, a, b,
+                           fl, out, L.a_stride, L.b_stride, out_stride, L.w, L.h, ts, L.in_sel);
+    });
 }
 
 } // namespace nus

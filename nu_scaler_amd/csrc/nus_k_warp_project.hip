@@ -6,10 +6,11 @@
 // pixels of a motion boundary that is the wrong vector.  Here each pixel first runs N rounds of g <- bilinear f at (p - t g)
 // (nus_flow_project_device.hpp), then the unchanged warp_blend_pixel with g in place of f(p).
 //
-// The kernels follow k_warp_blend_flow: a thread owns XV consecutive pixels in each of RV rows, its own flow vectors are loaded
-// first, and per time of the set the N rounds run round by round over all its pixels, so the gathers of a round -- two loads per
-// pixel, independent chains -- are in flight together; then warp_blend_pixel and the same stores.  A round's gather depends on
-// the round before it, so N rounds are N exposed gather latencies per time which only the occupancy hides: the price of the mode.
+// The layout is warp_blend_tile's (nus_warp_device.hpp), shared with k_warp_blend_flow and k_bm_warp: a thread owns XV consecutive
+// pixels in each of RV rows and its own flow vectors are loaded first.  What this unit adds is the tile's per-time step: the N
+// rounds run round by round over all the thread's pixels, so the gathers of a round -- two loads per pixel, independent chains --
+// are in flight together; then the tile's warp_blend_pixel and stores.  A round's gather depends on the round before it, so N
+// rounds are N exposed gather latencies per time which only the occupancy hides: the price of the mode.
 // The flow plane is reached through a buffer resource bound to the pair's own plane, like the frames.
 #include "nus_device.hpp"
 #include "nus_flow_project_device.hpp"
@@ -19,61 +20,46 @@ namespace nus {
 
 namespace {
 
-template <int MODE, bool HALF, int XV, int RV, bool MT>
-__global__ __launch_bounds__(256) void k_warp_blend_flow_proj(
-    const uint8_t *__restrict__ a, const uint8_t *__restrict__ b, const void *__restrict__ flow,
-    uint8_t *__restrict__ out, size_t a_stride, size_t b_stride, size_t out_pair_stride, uint32_t w, uint32_t h, TimeSet ts,
-    uint32_t sel, uint32_t rounds)
-{
-    static_assert(XV == 1 || XV == 2, "one pixel, or a pair of an even-width frame");
-    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    const uint32_t ybase = __builtin_amdgcn_readfirstlane(blockIdx.y * (4 * RV) + threadIdx.y);
-    const uint32_t x0 = (blockIdx.x * kWave + threadIdx.x) * XV;
-    if (ybase >= h || x0 >= w) return;
-    const size_t npx = (size_t)w * h;
-    const uint32_t frame_bytes = (uint32_t)(npx * 4), row_bytes = w * 4;
-    const uint32_t cell_bytes = HALF ? 4 : 8;
-    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint8_t *>(a + (size_t)blockIdx.z * a_stride), 0, frame_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint8_t *>(b + (size_t)blockIdx.z * b_stride), 0, frame_bytes, 0x00020000);
-    // the pair's own flow plane (below 4 GiB: host-checked): a coordinate outside it reads zeros, never another pair's vectors
-    const __amdgpu_buffer_rsrc_t rf = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint8_t *>(static_cast<const uint8_t *>(flow) + (size_t)blockIdx.z * npx * cell_bytes), 0,
-        (uint32_t)(npx * cell_bytes), 0x00020000);
-    // per-lane copies of the wave-uniform constants: scalar operands halve the VALU issue rate on gfx950
-    float wmax = (float)(w - 1), hmax = (float)(h - 1);
-    asm volatile("" : "+v"(wmax), "+v"(hmax));
-    float2 f[RV][XV];
+template <bool HALF, int XV, int RV>
+struct ProjectedFlowSource {
+    static constexpr bool kSwizzle = true;
+    static constexpr uint32_t kCellBytes = HALF ? 4 : 8;
+    const void *flow;
+    uint32_t rounds;
+    __amdgpu_buffer_rsrc_t rf;
+    float2 f[RV][XV], g[RV][XV];
+
+    __device__ __forceinline__ void load(uint32_t ybase, uint32_t x0, uint32_t w, uint32_t h, size_t npx)
+    {
+        typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+        // the pair's own flow plane (below 4 GiB: host-checked): a coordinate outside it reads zeros, never another pair's vectors
+        rf = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(static_cast<const uint8_t *>(flow) + (size_t)blockIdx.z * npx * kCellBytes),
+                                               0, (uint32_t)(npx * kCellBytes), 0x00020000);
 #pragma unroll
-    for (int j = 0; j < RV; ++j) { // the flow vectors of all the thread's pixels first (rows past the frame: the last row's)
-        const uint32_t off = (umin(ybase + 4 * j, h - 1) * w + x0) * cell_bytes;
-        if (XV == 2) { // (w even: both cells are in the row)
-            if (HALF) {
-                const u32x2 raw = __builtin_amdgcn_raw_buffer_load_b64(rf, off, 0, 0);
-                f[j][0] = half2_bits_to_float2(raw.x), f[j][XV - 1] = half2_bits_to_float2(raw.y);
+        for (int j = 0; j < RV; ++j) {
+            const uint32_t off = (umin(ybase + 4 * j, h - 1) * w + x0) * kCellBytes;
+            if (XV == 2) { // (w even: both cells are in the row)
+                if (HALF) {
+                    const u32x2 raw = __builtin_amdgcn_raw_buffer_load_b64(rf, off, 0, 0);
+                    f[j][0] = half2_bits_to_float2(raw.x), f[j][XV - 1] = half2_bits_to_float2(raw.y);
+                } else {
+                    const u32x4 raw = __builtin_amdgcn_raw_buffer_load_b128(rf, off, 0, 0);
+                    f[j][0] = make_float2(__uint_as_float(raw.x), __uint_as_float(raw.y));
+                    f[j][XV - 1] = make_float2(__uint_as_float(raw.z), __uint_as_float(raw.w));
+                }
             } else {
-                const u32x4 raw = __builtin_amdgcn_raw_buffer_load_b128(rf, off, 0, 0);
-                f[j][0] = make_float2(__uint_as_float(raw.x), __uint_as_float(raw.y));
-                f[j][XV - 1] = make_float2(__uint_as_float(raw.z), __uint_as_float(raw.w));
-            }
-        } else {
-            if (HALF) {
-                f[j][0] = half2_bits_to_float2(__builtin_amdgcn_raw_buffer_load_b32(rf, off, 0, 0));
-            } else {
-                const u32x2 raw = __builtin_amdgcn_raw_buffer_load_b64(rf, off, 0, 0);
-                f[j][0] = make_float2(__uint_as_float(raw.x), __uint_as_float(raw.y));
+                if (HALF) {
+                    f[j][0] = half2_bits_to_float2(__builtin_amdgcn_raw_buffer_load_b32(rf, off, 0, 0));
+                } else {
+                    const u32x2 raw = __builtin_amdgcn_raw_buffer_load_b64(rf, off, 0, 0);
+                    f[j][0] = make_float2(__uint_as_float(raw.x), __uint_as_float(raw.y));
+                }
             }
         }
     }
-    const uint32_t nk = MT ? ts.n : 1;
-    for (uint32_t k = 0; k < nk; ++k) {
-        float tv = ts.t[k];
-        asm volatile("" : "+v"(tv));
-        const float nt = 1.0f - tv;
-        uint32_t *const frame_out = reinterpret_cast<uint32_t *>(out + (size_t)blockIdx.z * out_pair_stride + (size_t)k * npx * 4);
-        float2 g[RV][XV];
+    __device__ __forceinline__ void at_time(uint32_t ybase, uint32_t x0, uint32_t w, uint32_t h, float wmax, float hmax, float tv)
+    {
 #pragma unroll
         for (int j = 0; j < RV; ++j)
 #pragma unroll
@@ -93,25 +79,19 @@ __global__ __launch_bounds__(256) void k_warp_blend_flow_proj(
 #pragma unroll
                 for (int i = 0; i < XV; ++i) g[j][i] = project_finish_corner<HALF>(G[j][i]);
         }
-#pragma unroll
-        for (int j = 0; j < RV; ++j) {
-            const uint32_t y = ybase + 4 * j;
-            if (y >= h) break; // wave-uniform
-            const float yfl = (float)y;
-            uint32_t o[XV];
-#pragma unroll
-            for (int i = 0; i < XV; ++i) {
-                const uint32_t p = warp_blend_pixel<MODE>(ra, rb, row_bytes, wmax, hmax, w - 2, h - 2, (float)(x0 + i), yfl, g[j][i], tv, nt);
-                o[i] = swz(p, sel);
-            }
-            uint32_t *dst = frame_out + (size_t)y * w + x0;
-            if (XV == 2) {
-                store_out8<false>(dst, make_uint2(o[0], o[XV - 1]));
-            } else {
-                dst[0] = o[0];
-            }
-        }
     }
+    __device__ __forceinline__ float2 vec(int j, int i) const { return g[j][i]; }
+};
+
+template <int MODE, bool HALF, int XV, int RV, bool MT>
+__global__ __launch_bounds__(256) void k_warp_blend_flow_proj(
+    const uint8_t *__restrict__ a, const uint8_t *__restrict__ b, const void *__restrict__ flow,
+    uint8_t *__restrict__ out, size_t a_stride, size_t b_stride, size_t out_pair_stride, uint32_t w, uint32_t h, TimeSet ts,
+    uint32_t sel, uint32_t rounds)
+{
+    ProjectedFlowSource<HALF, XV, RV> src; // (a buffer resource has no initializer: the members are set by name and by load)
+    src.flow = flow, src.rounds = rounds;
+    warp_blend_tile<MODE, XV, RV, MT>(a, b, out, a_stride, b_stride, out_pair_stride, w, h, ts, sel, src);
 }
 
 // Frames narrower or lower than 2 pixels, or frames / flow planes of 4 GiB and more: one pixel per thread, 64-bit addressing
@@ -132,16 +112,9 @@ __global__ __launch_bounds__(256) void k_warp_blend_flow_proj_tiny(
     const uint32_t nk = MT ? ts.n : 1;
     for (uint32_t k = 0; k < nk; ++k) {
         const float t = ts.t[k];
-        const float nt = 1.0f - t;
         float2 g = f;
         for (uint32_t r = 0; r < rounds; ++r) g = project_round_plain(plane, half, w, h, (float)x, (float)y, g, t);
-        const float4 sa = sample_trunc(fa, w, h, (float)x - t * g.x, (float)y - t * g.y);
-        const float4 sb = sample_trunc(fb, w, h, (float)x + nt * g.x, (float)y + nt * g.y);
-        uint32_t o = 0;
-        o = pack_trunc_u8(nt * sa.x + t * sb.x, 0, o);
-        o = pack_trunc_u8(nt * sa.y + t * sb.y, 1, o);
-        o = pack_trunc_u8(nt * sa.z + t * sb.z, 2, o);
-        o = pack_trunc_u8(nt * sa.w + t * sb.w, 3, o);
+        const uint32_t o = warp_blend_pixel_plain(fa, fb, w, h, x, y, g, t, 1.0f - t);
         reinterpret_cast<uint32_t *>(out + (size_t)blockIdx.z * out_pair_stride + (size_t)k * npx * 4)[pix] = swz(o, sel);
     }
 }
@@ -170,22 +143,14 @@ __global__ __launch_bounds__(256) void k_flow_project(const float2 *__restrict__
     out_all[(size_t)blockIdx.z * npx + pix] = g;
 }
 
-// what the corner forms need: every cell pair inside the plane, 32-bit byte offsets into frames and flow plane, 24-bit multiplies
-bool project_corner_ok(uint32_t w, uint32_t h, bool flow_half)
-{
-    const size_t npx = (size_t)w * h;
-    return w >= 2 && h >= 2 && npx * 4 < (1ull << 32) && npx * (flow_half ? 4 : 8) < (1ull << 32) && w * 4ull < (1u << 24) && h < (1u << 24);
-}
-
 } // namespace
 
 hipError_t launch_flow_project(const FlowProjectLaunch &L)
 {
     if (L.rounds > kFlowMaxProject || L.in == nullptr || L.out == nullptr || L.in == L.out || !(L.t == L.t)) return hipErrorInvalidValue;
-    const dim3 block(kWave, 4), grid(cdiv(L.img.w, 64), cdiv(L.img.h, 4), L.img.n);
-    const auto kernel = project_corner_ok(L.img.w, L.img.h, false) ? k_flow_project<true> : k_flow_project<false>;
-    hipLaunchKernelGGL(kernel, grid, block, 0, L.img.stream, reinterpret_cast<const float2 *>(L.in), reinterpret_cast<float2 *>(L.out),
-                       L.img.w, L.img.h, L.t, L.rounds);
+    const auto kernel = warp_corner_ok(L.img.w, L.img.h, 8) ? k_flow_project<true> : k_flow_project<false>;
+    hipLaunchKernelGGL(kernel, warp_grid(L.img.w, L.img.h, 1, 1, L.img.n), dim3(kWave, 4), 0, L.img.stream, reinterpret_cast<const float2 *>(L.in),
+                       reinterpret_cast<float2 *>(L.out), L.img.w, L.img.h, L.t, L.rounds);
     return hipGetLastError();
 }
 
@@ -194,54 +159,32 @@ hipError_t launch_warp_blend_project(const WarpLaunch &L)
 {
     if (L.flow == nullptr || L.project == 0 || L.project > kFlowMaxProject) return hipErrorInvalidValue;
     const size_t npx = (size_t)L.w * L.h;
-    TimeSet ts{};
-    if (L.n_times == 0) {
-        ts.t[0] = L.t;
-        ts.n = 1;
-    } else {
-        if (L.n_times > kInterpMaxTimes || L.times == nullptr) return hipErrorInvalidValue;
-        for (uint32_t k = 0; k < L.n_times; ++k) ts.t[k] = L.times[k];
-        ts.n = L.n_times;
-    }
+    TimeSet ts;
+    if (!warp_time_set(L.t, L.times, L.n_times, ts)) return hipErrorInvalidValue;
     const bool mt = ts.n > 1;
-    const size_t out_stride = L.out_pair_stride ? L.out_pair_stride : ts.n * npx * 4;
-    const bool corner = project_corner_ok(L.w, L.h, L.flow_half);
-    for (uint32_t done = 0; done < L.n_pairs;) {
-        const uint32_t n = L.n_pairs - done < kMaxGridZ ? L.n_pairs - done : kMaxGridZ;
+    const size_t out_stride = warp_out_stride(L.out_pair_stride, ts, npx);
+    const uint32_t cell_bytes = L.flow_half ? 4 : 8;
+    return for_grid_z_chunks(L.n_pairs, [&](uint32_t done, uint32_t n) {
         const uint8_t *a = L.a + (size_t)done * L.a_stride;
         const uint8_t *b = L.b + (size_t)done * L.b_stride;
         uint8_t *out = L.out + (size_t)done * out_stride;
-        const void *fl = reinterpret_cast<const uint8_t *>(L.flow) + (size_t)done * npx * (L.flow_half ? 4 : 8);
-        if (!corner) {
-            const dim3 block(kWave, 4), grid(cdiv(L.w, 64), cdiv(L.h, 4), n);
-            if (mt)
-                hipLaunchKernelGGL(k_warp_blend_flow_proj_tiny<true>, grid, block, 0, L.stream, a, b, fl, L.flow_half, out, L.a_stride,
-                                   L.b_stride, out_stride, L.w, L.h, ts, L.in_sel, L.project);
-            else
-                hipLaunchKernelGGL(k_warp_blend_flow_proj_tiny<false>, grid, block, 0, L.stream, a, b, fl, L.flow_half, out, L.a_stride,
-                                   L.b_stride, out_stride, L.w, L.h, ts, L.in_sel, L.project);
-        } else {
-            constexpr int RV = 2;
-            // a pair of pixels per thread where the frame's width is even and the pair's 8-byte store is aligned
-            const bool xv_ok = (L.w % 2) == 0 && (reinterpret_cast<uintptr_t>(out) % 8) == 0 && (out_stride % 8) == 0;
-            const dim3 block(kWave, 4), grid(cdiv(L.w, 64 * (xv_ok ? 2 : 1)), cdiv(L.h, 4 * RV), n);
-#define NUS_WP(M, H, X, MT) hipLaunchKernelGGL((k_warp_blend_flow_proj<M, H, X, RV, MT>), grid, block, 0, L.stream, a, b, fl, out, L.a_stride, L.b_stride, out_stride, L.w, L.h, ts, L.in_sel, L.project)
-#define NUS_WP_T(M, H, X) do { if (mt) NUS_WP(M, H, X, true); else NUS_WP(M, H, X, false); } while (0)
-#define NUS_WP_X(M, H) do { if (xv_ok) NUS_WP_T(M, H, 2); else NUS_WP_T(M, H, 1); } while (0)
-            if (L.fma) {
-                if (L.flow_half) NUS_WP_X(kWarpFma, true); else NUS_WP_X(kWarpFma, false);
-            } else {
-                if (L.flow_half) NUS_WP_X(kWarpExact, true); else NUS_WP_X(kWarpExact, false);
-            }
-#undef NUS_WP_X
-#undef NUS_WP_T
-#undef NUS_WP
+        const void *fl = reinterpret_cast<const uint8_t *>(L.flow) + (size_t)done * npx * cell_bytes;
+        const dim3 block(kWave, 4);
+        if (!warp_corner_ok(L.w, L.h, cell_bytes)) {
+            hipLaunchKernelGGL(mt ? k_warp_blend_flow_proj_tiny<true> : k_warp_blend_flow_proj_tiny<false>, warp_grid(L.w, L.h, 1, 1, n), block,
+                               0, L.stream, a, b, fl, L.flow_half, out, L.a_stride, L.b_stride, out_stride, L.w, L.h, ts, L.in_sel, L.project);
+            return;
         }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        done += n;
-    }
-    return hipSuccess;
+        // a pair of pixels per thread where the frame's width is even and the pair's 8-byte store is aligned
+        const bool xv_ok = (L.w % 2) == 0 && (reinterpret_cast<uintptr_t>(out) % 8) == 0 && (out_stride % 8) == 0;
+#define NUS_WP(M, H, X) {k_warp_blend_flow_proj<M, H, X, kWarpRV, false>, k_warp_blend_flow_proj<M, H, X, kWarpRV, true>}
+        static constexpr decltype(&k_warp_blend_flow_proj<kWarpExact, false, 1, kWarpRV, false>) kernels[2][2][2][2] = { // [fma][half][pair][mt]
+            {{NUS_WP(kWarpExact, false, 1), NUS_WP(kWarpExact, false, 2)}, {NUS_WP(kWarpExact, true, 1), NUS_WP(kWarpExact, true, 2)}},
+            {{NUS_WP(kWarpFma, false, 1), NUS_WP(kWarpFma, false, 2)}, {NUS_WP(kWarpFma, true, 1), NUS_WP(kWarpFma, true, 2)}}};
+#undef NUS_WP
+        hipLaunchKernelGGL(kernels[L.fma][L.flow_half][xv_ok][mt], warp_grid(L.w, L.h, xv_ok ? 2 : 1, kWarpRV, n), block, 0, L.stream, a, b,
+                           fl, out, L.a_stride, L.b_stride, out_stride, L.w, L.h, ts, L.in_sel, L.project);
+    });
 }
 
 } // namespace nus

@@ -173,7 +173,8 @@ struct WarpLaunch {
 
 // Frame k of pair i goes to out + i * out_pair_stride + k * w * h * 4.  One time runs the single-time kernels; more, their
 // multi-time instantiations (the same per-pixel arithmetic, looped over the times after the loads).  With project > 0 and a flow
-// it hands the launch to launch_warp_blend_project.
+// it hands the launch to launch_warp_blend_project.  The dense-flow kernels of both and launch_bm_warp's are one tile body
+// (warp_blend_tile, nus_warp_device.hpp) fed from three vector sources; the three launchers share its host helpers.
 hipError_t launch_warp_blend(const WarpLaunch &L);
 
 // The flow evaluated at the in-between time (nus_k_warp_project.hip; BUILD-DEFINED).  Per output pixel p and time t: g = f(p), then
@@ -358,7 +359,8 @@ struct BmBidirLaunch {
 hipError_t launch_bm_bidir(const BmBidirLaunch &L);
 
 // Warp + blend straight from the block vectors (nus_k_bm_warp.hip; nus_bm_warp_device): the frames launch_warp_blend writes from
-// the flow launch_blockmatch expands those vectors to, without that flow.  RGBA8 frames; vectors in launch_blockmatch's layout at
+// the flow launch_blockmatch expands those vectors to, byte for byte (the same tile body reading another vector source), without
+// that flow.  RGBA8 frames; vectors in launch_blockmatch's layout at
 // block size bs; frame k of pair i at out + i * out_pair_stride + k * w * h * 4.
 struct BmWarpLaunch {
     const uint8_t *a = nullptr, *b = nullptr;

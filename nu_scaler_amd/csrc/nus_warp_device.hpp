@@ -1,5 +1,8 @@
-// nus_warp_device.hpp -- the dense-flow warp + blend of ONE pixel (device code shared by k_warp_blend_flow, nus_k_interp.hip, and by
-// the Jacobi kernel that warps with the flow it has just finished, nus_k_flow.hip): the same expressions in both, so the same bytes.
+// nus_warp_device.hpp -- the flow-driven warp + blend, device code and launcher helpers shared by its three kernel families:
+// k_warp_blend_flow (dense flow, nus_k_interp.hip), k_bm_warp (block vectors, nus_k_bm_warp.hip) and k_warp_blend_flow_proj (flow
+// projected to the in-between time, nus_k_warp_project.hip).  One pixel's arithmetic (warp_blend_pixel) and the tile around it
+// (warp_blend_tile) are written once; a family supplies only where a pixel's vector comes from, so all three write the same bytes
+// for the same vectors.
 //   geometry nu_scaler_core/src/shaders/warp_blend.wgsl:25-43, rounding nu_scaler_core/src/interpolation/mod.rs:386-411, :467-510
 #pragma once
 
@@ -94,6 +97,115 @@ __device__ __forceinline__ uint32_t warp_blend_pixel(__amdgpu_buffer_rsrc_t ra, 
     p = pack_trunc_u8(nt * sa.w + tv * sb.w, 3, p);
     return p;
 }
+
+// The same pixel for the one-pixel-per-thread kernels (sample_trunc's frames): EXACT arithmetic, the input's channel order.
+__device__ __forceinline__ uint32_t warp_blend_pixel_plain(const uint32_t *__restrict__ fa, const uint32_t *__restrict__ fb, uint32_t w,
+                                                           uint32_t h, uint32_t x, uint32_t y, float2 f, float t, float nt)
+{
+    const float4 sa = sample_trunc(fa, w, h, (float)x - t * f.x, (float)y - t * f.y);
+    const float4 sb = sample_trunc(fb, w, h, (float)x + nt * f.x, (float)y + nt * f.y);
+    uint32_t o = 0;
+    o = pack_trunc_u8(nt * sa.x + t * sb.x, 0, o);
+    o = pack_trunc_u8(nt * sa.y + t * sb.y, 1, o);
+    o = pack_trunc_u8(nt * sa.z + t * sb.z, 2, o);
+    o = pack_trunc_u8(nt * sa.w + t * sb.w, 3, o);
+    return o;
+}
+
+// The tile of the three dense kernels, frames of at least 2 x 2 pixels below 4 GiB (warp_corner_ok).  blockDim = (64, 4); a thread
+// owns XV consecutive pixels in each of RV rows (y, y + 4, .. of the block's 4 RV): its vectors are fetched first, then the gathers
+// of its pixels -- independent chains -- are in flight together.  XV = 2 (frame width even, host-checked): the two pixels are one
+// 8-byte store and a wave's gathers stay on few cache lines; else XV = 1.  Four pixels per thread (16-byte stores) was measured
+// and rejected: a wave's gathers spread over four times the cache lines and the kernel stops being bound by its arithmetic
+// (profiles/r03_warp_kernel_layouts_ab.txt, us per 1080p pair EXACT / FMA: 1 x 4 9.6-10.4 / 8.5-8.7; 4 x 1 11.2-13.1 / 11.1-13.1;
+// 2 x 2 8.7-9.3 / 7.9-8.5).
+// MT: the multi-time form -- the vectors are fetched once, then the pixels are warped, blended and stored once per time of the set
+// (frame k of the pair at out + k * w * h * 4; the gathers of the later times hit the lines the first one brought into the L2).
+// MT = false is the single-time kernel: the set's one time, no loop.
+// SRC supplies the vectors:
+//   load(ybase, x0, w, h, npx)                     once, before the times: the thread's own vectors (rows past the frame: the last row's)
+//   at_time(ybase, x0, w, h, wmax, hmax, tv)       once per time, before the pixels
+//   vec(j, i)                                      the vector of pixel i of thread row j
+//   kSwizzle                                       whether the family has an input channel selector (sel)
+constexpr int kWarpRV = 2;
+
+template <int MODE, int XV, int RV, bool MT, typename SRC>
+__device__ __forceinline__ void warp_blend_tile(const uint8_t *__restrict__ a, const uint8_t *__restrict__ b, uint8_t *__restrict__ out,
+                                                size_t a_stride, size_t b_stride, size_t out_pair_stride, uint32_t w, uint32_t h,
+                                                const TimeSet &ts, uint32_t sel, SRC src)
+{
+    static_assert(XV == 1 || XV == 2, "one pixel, or a pair of an even-width frame");
+    const uint32_t ybase = __builtin_amdgcn_readfirstlane(blockIdx.y * (4 * RV) + threadIdx.y);
+    const uint32_t x0 = (blockIdx.x * kWave + threadIdx.x) * XV;
+    if (ybase >= h || x0 >= w) return;
+    const size_t npx = (size_t)w * h;
+    const uint32_t frame_bytes = (uint32_t)(npx * 4), row_bytes = w * 4;
+    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<uint8_t *>(a + (size_t)blockIdx.z * a_stride), 0, frame_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<uint8_t *>(b + (size_t)blockIdx.z * b_stride), 0, frame_bytes, 0x00020000);
+    // per-lane copies of the wave-uniform constants: scalar operands halve the VALU issue rate on gfx950
+    float wmax = (float)(w - 1), hmax = (float)(h - 1);
+    asm volatile("" : "+v"(wmax), "+v"(hmax));
+    uint8_t *const pair_out = out + (size_t)blockIdx.z * out_pair_stride;
+    src.load(ybase, x0, w, h, npx);
+    const uint32_t nk = MT ? ts.n : 1;
+    for (uint32_t k = 0; k < nk; ++k) {
+        float tv = ts.t[k];
+        asm volatile("" : "+v"(tv));
+        const float nt = 1.0f - tv;
+        uint32_t *const frame_out = reinterpret_cast<uint32_t *>(pair_out + (size_t)k * npx * 4);
+        src.at_time(ybase, x0, w, h, wmax, hmax, tv);
+#pragma unroll
+        for (int j = 0; j < RV; ++j) {
+            const uint32_t y = ybase + 4 * j;
+            if (y >= h) break; // wave-uniform
+            const float yfl = (float)y;
+            uint32_t o[XV];
+#pragma unroll
+            for (int i = 0; i < XV; ++i) {
+                const uint32_t p = warp_blend_pixel<MODE>(ra, rb, row_bytes, wmax, hmax, w - 2, h - 2, (float)(x0 + i), yfl, src.vec(j, i), tv, nt);
+                o[i] = SRC::kSwizzle ? swz(p, sel) : p;
+            }
+            uint32_t *dst = frame_out + (size_t)y * w + x0;
+            if (XV == 2) {
+                store_out8<false>(dst, make_uint2(o[0], o[XV - 1]));
+            } else {
+                dst[0] = o[0];
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------
+// What the three launchers share (host)
+// ---------------------------------------------------------------------------------
+
+// The launch's times: times[0 .. n_times), or the one time t where n_times is 0.  false: more than kInterpMaxTimes, or no array.
+inline bool warp_time_set(float t, const float *times, uint32_t n_times, TimeSet &ts)
+{
+    if (n_times > kInterpMaxTimes || (n_times > 0 && times == nullptr)) return false;
+    ts = TimeSet{};
+    ts.n = n_times ? n_times : 1;
+    ts.t[0] = t;
+    for (uint32_t k = 0; k < n_times; ++k) ts.t[k] = times[k];
+    return true;
+}
+
+// bytes between the outputs of consecutive pairs: the caller's, or the pair's frames tightly packed
+inline size_t warp_out_stride(size_t out_pair_stride, const TimeSet &ts, size_t npx) { return out_pair_stride ? out_pair_stride : ts.n * npx * 4; }
+
+// What the tile (and the corner form of the projection) needs: every texel pair inside the frame, 32-bit byte offsets into the
+// frames and into a flow plane of flow_cell_bytes per pixel (0: no flow plane is addressed that way), 24-bit multiplies.  Frames
+// that fail it go to the _tiny kernels.
+inline bool warp_corner_ok(uint32_t w, uint32_t h, uint32_t flow_cell_bytes)
+{
+    const size_t npx = (size_t)w * h;
+    return w >= 2 && h >= 2 && npx * 4 < (1ull << 32) && npx * flow_cell_bytes < (1ull << 32) && w * 4ull < (1u << 24) && h < (1u << 24);
+}
+
+// grid of a (64, 4) block whose threads own xv x rv pixels; pairs on z
+inline dim3 warp_grid(uint32_t w, uint32_t h, uint32_t xv, uint32_t rv, uint32_t n) { return dim3(cdiv(w, kWave * xv), cdiv(h, 4 * rv), n); }
 
 } // namespace
 

@@ -190,3 +190,25 @@ def test_batch_as_a_sliding_stream_with_poisoned_gaps(nsc, w, h, bs):
                 for k, t in enumerate(times):
                     assert np.array_equal(got[i, k * fb:(k + 1) * fb].reshape(h, w, 4), _oracle.warp_blend(a, b, flow, t)), (i, k)
     assert np.array_equal(fetch(d_frames), frames), "the input stream was written"
+
+
+@pytest.mark.parametrize("w,h", [(33, 17), (34, 18), (1, 9)])  # one pixel per lane, two pixels per lane, the _tiny pair
+def test_block_vector_route_writes_the_dense_route_bytes(nsc, w, h):
+    """k_bm_warp and k_warp_blend_flow are one tile body fed from two sources, so nus_bm_warp_device and
+    nus_interp_interpolate_multi_device given the expanded vectors as an f32 flow write the same bytes: in EXACT and in FMA mode,
+    at times with full mantissas (no product is exact), as one two-time call and as a single-time call."""
+    import torch
+
+    bs, times = 8, [float(np.float32(0.31415927)), float(np.float32(0.70710677))]
+    a, b = _frames(w, h)
+    vec = _vectors(w, h, bs)
+    fb = w * h * 4
+    da, db = put(np.ascontiguousarray(a)), put(np.ascontiguousarray(b))
+    d_flow = put(np.ascontiguousarray(bmref.dense_flow(vec, w, h, bs)))
+    it = nsc.WgpuFrameInterpolator()
+    for mode in ("exact", "fma"):
+        it.set_mode(mode)
+        for ts in (times, times[:1]):
+            dense = guarded.empty((len(ts), h, w, 4), dtype=torch.uint8, device="cuda:0")
+            it.interpolate_multi_device(da.data_ptr(), fb, db.data_ptr(), fb, d_flow.data_ptr(), w, h, ts, dense.data_ptr(), 0, 1, _stream())
+            assert np.array_equal(_warp(nsc, a, b, vec, bs, ts, mode), fetch(dense)), (w, h, mode, len(ts))

@@ -1,6 +1,7 @@
 """The warp + blend kernels (nus_k_interp.hip) as hipcc builds them for gfx950, checked without a GPU: no instantiation spills to
 scratch, and the multi-time forms read their inputs once -- the vector zero-flow kernel's body holds exactly two 16-byte global
-loads (A and B) whatever the number of times, and a multi-time dense kernel loads the flow as its single-time form does."""
+loads (A and B) whatever the number of times, and a multi-time dense kernel loads the flow as its single-time form does.  The
+same for the two other units built on the dense kernel's tile, nus_k_bm_warp.hip and nus_k_warp_project.hip (at the end)."""
 import os
 import re
 import subprocess
@@ -89,3 +90,82 @@ def test_multi_time_dense_kernels_load_the_flow_once(interp_asm):
         assert _count(body, r"global_load\w*") <= 4, name
         checked += 1
     assert checked == 8
+
+
+# ---- the other two users of warp_blend_tile (nus_warp_device.hpp): the block-vector and the projecting kernels ----
+
+def _compile(tmp_path_factory, unit):
+    out = tmp_path_factory.mktemp("asm") / (unit + ".s")
+    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-x", "hip",
+           "--cuda-device-only", "-S", "-I", CSRC, "-I", os.path.join(ROOT, "include"), "-o", str(out), os.path.join(CSRC, unit + ".hip")]
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr
+    return out.read_text()
+
+
+@pytest.fixture(scope="module")
+def bm_warp_asm(tmp_path_factory):
+    return _compile(tmp_path_factory, "nus_k_bm_warp")
+
+
+@pytest.fixture(scope="module")
+def warp_project_asm(tmp_path_factory):
+    return _compile(tmp_path_factory, "nus_k_warp_project")
+
+
+def _kernels(asm, pattern):
+    """{mangled kernel name: its instruction text} for the kernels whose name matches."""
+    out = {}
+    for m in re.finditer(r"^(_Z\S*(?:" + pattern + r")\S*):", asm, re.M):
+        out[m.group(1)] = asm[m.end():asm.find(".Lfunc_end", m.end())]
+    return out
+
+
+def _private_sizes(asm, pattern):
+    """{kernel name: .private_segment_fixed_size} from the code object's metadata."""
+    out = {}
+    for m in re.finditer(r"^\s+\.name:\s+(\S+)\s*$", asm, re.M):
+        if re.search(pattern, m.group(1)) and not m.group(1).endswith(".kd"):
+            out[m.group(1)] = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", asm[m.start():m.start() + 4000]).group(1))
+    return out
+
+
+def _is_multi(name):
+    return name.split("EEEv")[0].endswith("ELb1")  # MT, the last template argument
+
+
+def _check_unit(asm, pattern, tile, n_tile, load):
+    """The instantiation counts, no scratch, and every multi-time tile kernel issuing its single-time form's vector loads."""
+    bodies = _kernels(asm, pattern)
+    dense = {n: b for n, b in bodies.items() if tile + "I" in n}
+    assert len(dense) == n_tile, sorted(dense)
+    assert sum(tile + "_tinyI" in n for n in bodies) == 2  # MT
+    assert len(bodies) == n_tile + 2, sorted(bodies)
+    assert sum(_is_multi(n) for n in dense) == n_tile // 2
+    assert _private_sizes(asm, pattern) == {n: 0 for n in bodies}
+    for name, body in bodies.items():
+        assert "scratch_" not in body, name
+    for name, body in dense.items():
+        if _is_multi(name):
+            single = dense[name.replace("ELb1EEEv", "ELb0EEEv", 1)]
+            assert _count(body, load) == _count(single, load) > 0, name
+    return dense
+
+
+def test_block_vector_warp_kernels(bm_warp_asm):
+    mk = open(os.path.join(CSRC, "Makefile")).read()
+    assert "nus_k_bm_warp.hip" in mk.split("KERNELS", 1)[1].split("\n", 1)[0]
+    dense = _check_unit(bm_warp_asm, "k_bm_warp", "k_bm_warp", 8, r"global_load\w*")  # MODE x (XV = 2, 1) x MT
+    for name, body in dense.items():
+        assert _count(body, r"global_load\w*") == 2, name  # one 4-byte vector per thread row, whatever XV and the number of times
+
+
+def test_projecting_warp_kernels(warp_project_asm):
+    mk = open(os.path.join(CSRC, "Makefile")).read()
+    assert "nus_k_warp_project.hip" in mk.split("KERNELS", 1)[1].split("\n", 1)[0]
+    # MODE x HALF x (XV = 2, 1) x MT.  Every load of these kernels goes through a buffer resource: the thread's own vectors, the
+    # rounds' gathers (one rolled loop, so the same instructions for every time) and the frame samples
+    dense = _check_unit(warp_project_asm, "k_warp_blend_flow_proj", "k_warp_blend_flow_proj", 16, r"buffer_load\w*")
+    for name, body in dense.items():
+        assert _count(body, r"(?:global|flat)_load\w*") == 0, name
+    assert len(_kernels(warp_project_asm, "k_flow_project")) == 2  # CORNER
