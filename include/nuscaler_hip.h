@@ -869,6 +869,67 @@ int nus_scene_apply_cuts_device(const void *d_a, size_t a_stride, const void *d_
 int nus_flow_set_scene_detect(nus_flow *h, int enabled, uint32_t mad_threshold, uint32_t hist_permille);
 int nus_bm_set_scene_detect(nus_blockmatch *h, int enabled, uint32_t mad_threshold, uint32_t hist_permille);
 
+/* ---- Frame-rate conversion by a rational ratio (24 -> 60, 25 -> 60, 30 -> 144, 60 -> 24) ------------------------------
+ * BUILD-DEFINED: the reference has no rate conversion.  The multi-time entry points give every pair the same time set; in a
+ * conversion by num / den = out_rate / in_rate every pair has its own in-between times and some pairs have none.  The entry points
+ * below take a device-resident stream and the ratio and write the whole output stream: the kernels evaluate the schedule
+ * themselves, per pair, so there is no host in the loop and no table in memory.
+ * The schedule.  n_frames >= 2 input frames; 1 <= num, den <= NUS_RETIME_MAX_TERM; the ratio is reduced by its gcd inside the
+ * library (60/24 and 5/2 give the same bytes) and the reduced ratio must satisfy num <= (NUS_INTERP_MAX_TIMES + 1) * den.  In 64-bit
+ * integers, with the reduced terms:
+ *     n_out = ((n_frames - 1) * num) / den + 1
+ *     output j = 0 .. n_out - 1:   k_j = (j * den) / num,   r_j = (j * den) % num,   t_j = the float32 nearest to r_j / num
+ * t_j is ONE correctly rounded f32 division of the two integers (both exact in f32), on the host and on the device alike.
+ *   r_j == 0: output j is real frame k_j -- the bytes the zero-flow nus_interp_interpolate_device writes at t = 0 for the input
+ *             format: RGBA order out, alpha 255 for the X formats.  Written by a copy kernel of its own, not by the warp.
+ *   r_j != 0: output j is byte for byte what the single-time entry point of the same handle writes for pair (k_j, k_j + 1) at t_j,
+ *             in the handle's mode, flow format, input format and projection rounds.
+ * k_j never decreases; a pair has at most ceil(num / den) <= 8 outputs; the last output is the last real frame iff den divides
+ * (n_frames - 1) * num; with den = 1 the in-between times of every pair are frame_times(num) of the Python package.
+ * Output j goes to d_out + j * out_frame_stride: 0 = tightly packed (w*h*4), else a multiple of 4 of at least w*h*4; the gaps are
+ * never written.  A pair's vectors are fetched once for all its outputs.
+ * Every entry point only enqueues: no allocation beyond a handle's grow-only workspace where its sibling entry point has one, no
+ * synchronisation.  Argument errors are NUS_ERR_INVALID_ARGUMENT, returned before any HIP call, with a text that names the entry
+ * point: a zero term, a term above the bound, a ratio above 8, n_frames < 2, a bad stride or alignment. */
+#define NUS_RETIME_MAX_TERM 4096
+typedef struct nus_retime_entry {
+    uint32_t pair;     /* k_j */
+    uint32_t rem;      /* r_j of the reduced ratio */
+    float t;           /* t_j */
+    uint32_t reserved; /* written as 0 */
+} nus_retime_entry;
+/* Host only, no GPU needed.  n_out, or a negative nus_status (and the text in nus_last_error). */
+int64_t nus_retime_count(uint32_t n_frames, uint32_t num, uint32_t den);
+/* Entries first .. first + count - 1 of the table into out (first + count <= n_out; count 0 writes nothing). */
+int nus_retime_schedule(uint32_t n_frames, uint32_t num, uint32_t den, uint64_t first, uint64_t count, nus_retime_entry *out);
+/* DIAGNOSTIC: the same table, all n_out entries, written by the device function the kernels use (d_entries 4-byte aligned). */
+int nus_retime_schedule_device(uint32_t n_frames, uint32_t num, uint32_t den, void *d_entries, void *stream);
+/* n_frames frames frame_stride bytes apart (a multiple of 4 of at least w*h*4); pair k's flow at d_flows + k * w*h*8 (NUS_FLOW_F32;
+ * k * w*h*4 with NUS_FLOW_F16), alignment as nus_interp_interpolate_device; d_flows == NULL: zero flow.  One warp launch over all
+ * pairs and one copy launch for the real frames. */
+int nus_interp_retime_device(nus_interp *h, const void *d_frames, size_t frame_stride, uint32_t n_frames, const void *d_flows,
+                             uint32_t w, uint32_t hgt, uint32_t num, uint32_t den, void *d_out, size_t out_frame_stride, void *stream);
+/* The estimator, then the retime warp in FMA mode: the bytes of nus_flow_estimate_device_stream followed by nus_interp_retime_device
+ * in FMA mode (with the handle's projection rounds), under the handle's warps, median and scene detection, for every chunking of
+ * the stream.  Frames tightly packed, pointers aligned as nus_flow_interpolate_multi_device_stream asks; the bytes at d_flows (may
+ * be NULL) are the estimate's.  With detection on, a cut pair's in-between outputs are overwritten as
+ * nus_scene_apply_cuts_retime_device states. */
+int nus_flow_retime_device_stream(nus_flow *h, const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t hgt, uint32_t levels,
+                                  uint32_t coarse_iters, uint32_t refine_iters, float lambda, uint32_t num, uint32_t den,
+                                  int flow_format, void *d_flows, void *d_out, size_t out_frame_stride, void *stream);
+/* nus_bm_interpolate_multi_device_stream with the schedule in place of the time set: in NUS_INTERP_MODE_EXACT an in-between output is
+ * byte for byte nus_bm_interpolate's frame for pair k_j at t_j, a real-frame output the copy.  d_workspace: 16-byte aligned, at least
+ * nus_bm_stream_workspace_size(h, w, hgt, n_frames) bytes. */
+int nus_bm_retime_device_stream(nus_blockmatch *h, const void *d_frames, size_t frame_stride, uint32_t n_frames, uint32_t w,
+                                uint32_t hgt, uint32_t num, uint32_t den, int mode, void *d_workspace, size_t workspace_bytes,
+                                void *d_vectors, void *d_out, size_t out_frame_stride, void *stream);
+/* The cut rule behind an unchanged rate conversion: for every pair k with d_cut[k] != 0 (n_frames - 1 flags), each output with
+ * k_j == k and r_j != 0 is overwritten with the copy -- as nus_scene_apply_cuts_device defines it for `format` -- of frame k if
+ * t_j < 0.5, else of frame k + 1.  Real-frame outputs and the outputs of other pairs are neither read nor written. */
+int nus_scene_apply_cuts_retime_device(const void *d_frames, size_t frame_stride, uint32_t n_frames, uint32_t w, uint32_t h, int format,
+                                       uint32_t num, uint32_t den, const uint8_t *d_cut, void *d_out, size_t out_frame_stride,
+                                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,7 @@ from .benchmark import PyBenchmarkResult, py_benchmark_upscaler, py_run_comparis
 from .flow import FlowEstimator
 from .imagefile import interpolate_image_files, interpolate_image_files_multi, upscale_image_file
 from .interpolator import WgpuFrameInterpolator, frame_times
+from .retime import retime_count, retime_ratio, retime_schedule
 from .queue import FrameBuffer, swizzle_bgra_to_rgba_device
 from .launch import launch_ranks
 from .metrics import ErrorMetrics
@@ -52,6 +53,7 @@ def create_fsr_upscaler(_quality: str):
 __all__ = [
     "PyWgpuUpscaler", "PyAdvancedWgpuUpscaler", "PyVramStats", "create_advanced_upscaler", "create_fsr_upscaler",
     "upscale_image_file", "interpolate_image_files", "interpolate_image_files_multi", "frame_times",
+    "retime_schedule", "retime_count", "retime_ratio",
     "PyBenchmarkResult", "py_benchmark_upscaler", "py_run_comparison_benchmark",
     "WgpuFrameInterpolator", "BlockMatcher", "PyFrameInterpolator", "FlowEstimator", "ErrorMetrics", "metrics", "SceneDetector", "scene", "FrameBuffer", "swizzle_bgra_to_rgba_device", "FramePipeline", "shard_frames", "broadcast_tables",
     "ShardedStream", "SyntheticSource", "run_sharded", "gather_rows", "spread", "launch_ranks",

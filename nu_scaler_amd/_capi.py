@@ -28,6 +28,7 @@ QUALITY_ULTRA_PERFORMANCE, QUALITY_ULTRA, QUALITY_QUALITY, QUALITY_BALANCED, QUA
 TECH_NONE, TECH_FSR, TECH_DLSS, TECH_WGPU, TECH_FALLBACK = range(5)
 WG_SQUARE_8X8, WG_SQUARE_16X16, WG_WIDE_32X8, WG_TALL_8X32 = range(4)
 RESIZE_MAX_TAPS = 32
+RETIME_MAX_TERM = 4096  # NUS_RETIME_MAX_TERM: the largest term of a rate-conversion ratio
 INTERP_MAX_TIMES = 7  # NUS_INTERP_MAX_TIMES: in-between frames per pair of one multi-time call (up to 8x frame rate)
 METRIC_MSE, METRIC_SSIM = 1, 2  # nus_metric (bit mask; PSNR comes with MSE)
 INTERP_QUALITY_HIGH, INTERP_QUALITY_MEDIUM, INTERP_QUALITY_LOW = 0, 1, 2  # nus_interp_quality_level
@@ -186,6 +187,13 @@ SIGNATURES = [
     ("nus_scene_apply_cuts_device", _i, [_vp, _sz, _vp, _sz, _u32, _u32, _i, _vp, _u32, _vp, _vp, _sz, _u32, _vp]),
     ("nus_flow_set_scene_detect", _i, [_vp, _i, _u32, _u32]),
     ("nus_bm_set_scene_detect", _i, [_vp, _i, _u32, _u32]),
+    ("nus_retime_count", _i64, [_u32, _u32, _u32]),
+    ("nus_retime_schedule", _i, [_u32, _u32, _u32, ctypes.c_uint64, ctypes.c_uint64, _vp]),
+    ("nus_retime_schedule_device", _i, [_u32, _u32, _u32, _vp, _vp]),
+    ("nus_interp_retime_device", _i, [_vp, _vp, _sz, _u32, _vp, _u32, _u32, _u32, _u32, _vp, _sz, _vp]),
+    ("nus_flow_retime_device_stream", _i, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _f, _u32, _u32, _i, _vp, _vp, _sz, _vp]),
+    ("nus_bm_retime_device_stream", _i, [_vp, _vp, _sz, _u32, _u32, _u32, _u32, _u32, _i, _vp, _sz, _vp, _vp, _sz, _vp]),
+    ("nus_scene_apply_cuts_retime_device", _i, [_vp, _sz, _u32, _u32, _u32, _i, _u32, _u32, _vp, _vp, _sz, _vp]),
 ]
 
 

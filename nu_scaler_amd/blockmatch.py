@@ -158,6 +158,19 @@ class BlockMatcher:
                                                                      d_vectors or None, d_mid or None, int(mid_pair_stride),
                                                                      stream or None))
 
+    def retime_stream_device(self, d_frames: int, frame_stride: int, n_frames: int, w: int, h: int, num: int, den: int,
+                             d_workspace: int, workspace_bytes: int, d_out: int, *, mode: str = "exact", d_vectors: int = 0,
+                             out_frame_stride: int = 0, stream: int = 0) -> None:
+        """Enqueue the block-matched conversion of the stream by num / den (nus_bm_retime_device_stream; retime.py has the
+        schedule): output j at d_out + j * out_frame_stride (0: tightly packed), real frames included; the workspace is
+        stream_workspace_size's.  Scene detection as set_scene_detect left it."""
+        m = _MODE.get(str(mode).lower())
+        if m is None:
+            raise ValueError("mode must be 'exact' or 'fma'")
+        self._check(self._lib.nus_bm_retime_device_stream(self._h, d_frames or None, int(frame_stride), int(n_frames), int(w), int(h),
+                                                          int(num), int(den), m, d_workspace or None, int(workspace_bytes),
+                                                          d_vectors or None, d_out or None, int(out_frame_stride), stream or None))
+
     def estimate(self, frame_a, frame_b, w: int, h: int):
         """Host frames (bytes or uint8 arrays) -> (vectors int16 (blocks_y, blocks_x, 2) as (dx, dy), sad uint32 (blocks_y,
         blocks_x), flags uint8 (blocks_y, blocks_x))."""
@@ -248,6 +261,23 @@ class PyFrameInterpolator:
             self._warp = WgpuFrameInterpolator(device=device)
             if flow_project:
                 self._warp.set_flow_project(flow_project)
+
+    def retime(self, frames, fps_in, fps_out) -> list[bytes]:
+        """A list of host frames of the initialize() size converted from `fps_in` to `fps_out` (ints or Fractions; retime.py has the
+        schedule): a list of host frames, real frames where the output grid meets one, else the method's in-between frame of the
+        pair at the schedule's time -- the frame `interpolate` returns for it, scene detection included.  One upload, the device
+        entry points (retime.retime_frames), one download; the bytes travel through `transfer`."""
+        from .retime import retime_frames
+
+        if self._size is None:
+            raise RuntimeError("Interpolator not initialized")
+        w, h = self._size
+        frames = list(frames)
+        if any(len(memoryview(f).cast("B")) != w * h * 4 for f in frames):
+            raise RuntimeError("Frame size mismatch")
+        if self._block:
+            return retime_frames(frames, w, h, fps_in, fps_out, matcher=self._bm, device=self._device)
+        return retime_frames(frames, w, h, fps_in, fps_out, warp=self._warp, flow=self._flow, scene=self._scene, device=self._device)
 
     @staticmethod
     def create_best_interpolator(quality: str = "medium") -> "PyFrameInterpolator":

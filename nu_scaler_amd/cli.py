@@ -4,7 +4,8 @@ legacy crate's `upscale_image_file` (Nu_scale/src/upscale/mod.rs:307-338) and th
 its `fullscreen` subcommand (Nu_scale/src/main.rs:36-73: --tech, --quality, --algorithm); `interpolate <a.png> <b.png> <out.png>`
 with zero flow, `--flow` (Horn-Schunck) or `--method block_matching [--quality high|medium|low] [--bidirectional]`; `compare <a.png> <b.png>`
 prints the `ErrorMetrics` of two images (Nu_scale/src/upscale/common.rs:475-543); `scene <a.png> <b.png>` prints the scene-cut
-detector's verdict on the pair, and `interpolate --multiplier M --scene-detect` writes repeats instead of blends across a cut.
+detector's verdict on the pair, and `interpolate --multiplier M --scene-detect` writes repeats instead of blends across a cut;
+`retime --from 24 --to 60 OUT_%04d.png IN0.png IN1.png ...` converts a PNG sequence by a rational frame-rate ratio.
 Everything runs on the HIP device; without one the command fails (no CPU path).
 """
 from __future__ import annotations
@@ -50,6 +51,19 @@ def build_parser() -> argparse.ArgumentParser:
     it.add_argument("--scene-detect", action="store_true",
                     help="with --multiplier: if the scene-cut detector flags the pair, write repeats of the nearer frame, not blends")
     it.add_argument("--device", type=int, default=0)
+    rt = sub.add_parser("retime", help="frame-rate conversion of a PNG sequence by a rational ratio: retime --from 24 --to 60 "
+                                       "OUT_%04d.png IN0.png IN1.png ...")
+    rt.add_argument("output_pattern", help="where output frame j goes, with one %%d conversion: OUT_%%04d.png")
+    rt.add_argument("inputs", nargs="*", help="the input frames in order, at least 2, of one size")
+    rt.add_argument("--from", dest="fps_in", required=True, help="input rate: an integer or a fraction such as 24000/1001")
+    rt.add_argument("--to", dest="fps_out", required=True, help="output rate, likewise; to/from reduced has terms <= 4096 and is <= 8")
+    rt.add_argument("--method", default="optical_flow", help="optical_flow (default), block_matching or blend (zero flow)")
+    rt.add_argument("--flow-warps", type=int, default=None, help="optical_flow: re-linearisation rounds per finer level (0 .. 4)")
+    rt.add_argument("--flow-median", type=int, default=None, help="optical_flow: median window behind every Jacobi run (0, 3 or 5)")
+    rt.add_argument("--flow-project", type=int, default=None, help="optical_flow: projection rounds of the warp (0 .. 4)")
+    rt.add_argument("--bidirectional", action="store_true", help="block_matching: the forward-backward check")
+    rt.add_argument("--scene-detect", action="store_true", help="across a scene cut write repeats of the nearer frame, not blends")
+    rt.add_argument("--device", type=int, default=0)
     sc = sub.add_parser("scene", help="scene-cut detector on two PNGs of equal size: prints cut=0|1 mad=.. hist_permille=..")
     sc.add_argument("a")
     sc.add_argument("b")
@@ -169,9 +183,48 @@ def scene_line(cut: bool, sad: int, hist_l1: int, w: int, h: int) -> str:
     return f"cut={1 if cut else 0} mad={sad / (3 * w * h):.3f} hist_permille={hist_l1 * 1000 / (2 * w * h):.1f}"
 
 
+def _rate(text: str):
+    """An integer or A/B -> Fraction; ValueError otherwise."""
+    from fractions import Fraction
+
+    parts = text.split("/")
+    if len(parts) > 2 or not all(p.strip().isdigit() for p in parts):
+        raise ValueError(f"a rate is an integer or a fraction A/B, got {text!r}")
+    return Fraction(int(parts[0]), int(parts[1]) if len(parts) == 2 else 1)  # (a zero denominator raises ZeroDivisionError)
+
+
+def _check_retime(args, parser) -> None:
+    """Usage errors of `retime`: status 2 before anything is read or written."""
+    from ._capi import FLOW_MAX_PROJECT, FLOW_MAX_WARPS
+    from .imagefile import retime_output_paths
+    from .retime import retime_ratio
+
+    try:
+        args.fps_in, args.fps_out = _rate(args.fps_in), _rate(args.fps_out)
+        retime_ratio(args.fps_in, args.fps_out)
+        retime_output_paths(args.output_pattern, 1)
+    except (ValueError, ZeroDivisionError) as e:
+        parser.error(str(e))
+    if len(args.inputs) < 2:
+        parser.error("retime needs at least 2 input frames")
+    args.method = args.method.lower()
+    if args.method not in ("optical_flow", "block_matching", "blend"):
+        parser.error(f"--method must be optical_flow, block_matching or blend, got {args.method}")
+    for name, v, ok in (("--flow-warps", args.flow_warps, range(FLOW_MAX_WARPS + 1)), ("--flow-median", args.flow_median, (0, 3, 5)),
+                        ("--flow-project", args.flow_project, range(FLOW_MAX_PROJECT + 1))):
+        if v is not None and args.method != "optical_flow":
+            parser.error(f"{name} needs --method optical_flow")
+        if v is not None and v not in ok:
+            parser.error(f"{name}: {v} is out of range")
+    if args.bidirectional and args.method != "block_matching":
+        parser.error("--bidirectional needs --method block_matching")
+
+
 def main(argv=None) -> int:
     parser = build_parser()
     args = parser.parse_args(argv)
+    if args.command == "retime":
+        _check_retime(args, parser)
     if args.command == "interpolate" and args.multiplier is not None:  # usage errors: status 2 before anything is read or written
         if args.t is not None:
             parser.error("--multiplier and --t exclude each other")
@@ -232,6 +285,12 @@ def main(argv=None) -> int:
             ow, oh = imagefile.upscale_image_file(args.input, args.output, args.tech, args.quality, args.scale,
                                                   args.algorithm, device=args.device)
             print(f"{args.output}: {ow}x{oh}")
+        elif args.command == "retime":
+            for path in imagefile.retime_image_files(args.output_pattern, args.inputs, args.fps_in, args.fps_out, args.method,
+                                                     device=args.device, scene_detect=args.scene_detect,
+                                                     bidirectional=args.bidirectional, flow_warps=args.flow_warps or 0,
+                                                     flow_median=args.flow_median or 0, flow_project=args.flow_project or 0):
+                print(path)
         elif args.command == "compare":
             import numpy as np
 

@@ -6,11 +6,13 @@
 //   nu_scaler_cli upscale <in.png> <out.png> [--algorithm A] [--scale S] [--tech T] [--quality Q] [--device N]
 //   nu_scaler_cli interpolate <a.png> <b.png> <out.png> [--t X | --multiplier M] [--flow [--flow-warps N] [--flow-median 0|3|5] [--flow-project N]] [--device N]
 //                             [--method block_matching [--quality high|medium|low] [--bidirectional [--bidir-tolerance N]]]
+//   nu_scaler_cli retime --from R --to R [--method M] [flow / block flags] [--scene-detect] OUT_%04d.png IN0.png IN1.png ...
 //   nu_scaler_cli scene <a.png> <b.png> [--mad N] [--hist N] [--device N]   (the scene-cut detector: cut=0|1 mad=.. hist_permille=..)
 //   nu_scaler_cli compare <a.png> <b.png> [--device N]   (MSE / PSNR / SSIM, ErrorMetrics: Nu_scale/src/upscale/common.rs:475-543)
 //   nu_scaler_cli png-copy <in.png> <out.png>        (decode + encode only; no GPU: codec self-check)
 //
 // Pixels go through the HIP kernels only: without a device the commands fail.
+#include <cctype>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -41,6 +43,9 @@ int usage(int rc)
                  "                             (--flow-project: rounds that look the flow up where each output pixel's content came from)\n"
                  "                             [--method block_matching [--quality high|medium|low]] [--scene-detect]\n"
                  "                             [--bidirectional [--bidir-tolerance 0..96]]   (block matching: forward-backward check)\n"
+                 "       nu_scaler_cli retime --from 24 --to 60 [--method optical_flow|block_matching|blend] [--flow-warps 0..4]\n"
+                 "                             [--flow-median 0|3|5] [--flow-project 0..4] [--bidirectional] [--scene-detect] [--device N]\n"
+                 "                             OUT_%%04d.png IN0.png IN1.png ...   (rates: integers or A/B; to/from reduced: terms <= 4096, <= 8)\n"
                  "       nu_scaler_cli scene <a.png> <b.png> [--mad 0..255] [--hist 0..1000] [--device N]\n"
                  "       nu_scaler_cli compare <a.png> <b.png> [--device N]\n"
                  "       nu_scaler_cli png-copy <in.png> <out.png>\n");
@@ -431,6 +436,199 @@ int cmd_png_copy(const Args &a)
     return 0;
 }
 
+// "24" or "24000/1001" -> (n, d), both positive and below 2^31
+bool parse_rate(const std::string &s, uint64_t &n, uint64_t &d)
+{
+    const size_t slash = s.find('/');
+    const std::string a = s.substr(0, slash), b = slash == std::string::npos ? "1" : s.substr(slash + 1);
+    for (const std::string *p : {&a, &b})
+        if (p->empty() || p->size() > 9 || p->find_first_not_of("0123456789") != std::string::npos) return false;
+    n = std::strtoull(a.c_str(), nullptr, 10), d = std::strtoull(b.c_str(), nullptr, 10);
+    return n != 0 && d != 0;
+}
+
+uint64_t gcd_u64(uint64_t a, uint64_t b)
+{
+    while (b) {
+        const uint64_t r = a % b;
+        a = b, b = r;
+    }
+    return a;
+}
+
+// exactly one integer conversion (%d, %4d, %04d) and no other '%'
+bool pattern_ok(const std::string &p)
+{
+    const size_t at = p.find('%');
+    if (at == std::string::npos || p.find('%', at + 1) != std::string::npos) return false;
+    size_t i = at + 1;
+    while (i < p.size() && std::isdigit((unsigned char)p[i])) ++i;
+    return i < p.size() && p[i] == 'd' && i - at <= 4;
+}
+
+std::string pattern_path(const std::string &p, uint64_t j)
+{
+    char buf[64];
+    const size_t at = p.find('%'), d = p.find('d', at);
+    std::snprintf(buf, sizeof buf, p.substr(at, d - at + 1).c_str(), (int)j);
+    return p.substr(0, at) + buf + p.substr(d + 1);
+}
+
+// retime --from 24 --to 60 [...] OUT_%04d.png IN0.png IN1.png ...: the schedule from nus_retime_schedule; a real-frame output is
+// the input frame, the in-between outputs of a pair come from one host call of the method per pair -- which by the contract of the
+// retime entry points are the bytes the device-resident conversion (`python -m nu_scaler_amd.cli retime`) writes.
+int cmd_retime(const Args &a)
+{
+    // usage errors before anything is read or written
+    const auto from_it = a.options.find("from"), to_it = a.options.find("to");
+    uint64_t fn, fd, tn, td;
+    if (from_it == a.options.end() || to_it == a.options.end() || !parse_rate(from_it->second, fn, fd) || !parse_rate(to_it->second, tn, td)) {
+        std::fprintf(stderr, "nu_scaler_cli: error: retime needs --from and --to, each a positive integer or a fraction A/B\n");
+        return usage(2);
+    }
+    uint64_t num = tn * fd, den = td * fn;
+    const uint64_t g = gcd_u64(num, den);
+    num /= g, den /= g;
+    if (num > NUS_RETIME_MAX_TERM || den > NUS_RETIME_MAX_TERM || num > (uint64_t)(NUS_INTERP_MAX_TIMES + 1) * den) {
+        std::fprintf(stderr, "nu_scaler_cli: error: the reduced ratio %llu/%llu needs terms of at most %d and a value of at most %d\n",
+                     (unsigned long long)num, (unsigned long long)den, NUS_RETIME_MAX_TERM, NUS_INTERP_MAX_TIMES + 1);
+        return usage(2);
+    }
+    if (a.positional.empty() || !pattern_ok(a.positional[0])) {
+        std::fprintf(stderr, "nu_scaler_cli: error: the output pattern needs exactly one %%d conversion (as OUT_%%04d.png)\n");
+        return usage(2);
+    }
+    if (a.positional.size() < 3) {
+        std::fprintf(stderr, "nu_scaler_cli: error: retime needs at least 2 input frames\n");
+        return usage(2);
+    }
+    const auto method_it = a.options.find("method");
+    const std::string method = method_it == a.options.end() ? "optical_flow" : lower(method_it->second);
+    if (method != "optical_flow" && method != "block_matching" && method != "blend") {
+        std::fprintf(stderr, "nu_scaler_cli: error: --method must be optical_flow, block_matching or blend, got %s\n", method.c_str());
+        return usage(2);
+    }
+    long flow_opt[3] = {0, 0, 0}; // warps, median, project
+    const char *const flow_names[3] = {"flow-warps", "flow-median", "flow-project"};
+    for (int i = 0; i < 3; ++i) {
+        const auto it = a.options.find(flow_names[i]);
+        if (it == a.options.end()) continue;
+        char *end = nullptr;
+        const long v = std::strtol(it->second.c_str(), &end, 10);
+        const bool in_range = i == 1 ? (v == 0 || v == 3 || v == 5) : (v >= 0 && v <= (i == 0 ? NUS_FLOW_MAX_WARPS : NUS_FLOW_MAX_PROJECT));
+        if (method != "optical_flow" || end == it->second.c_str() || *end != '\0' || !in_range) {
+            std::fprintf(stderr, "nu_scaler_cli: error: --%s needs --method optical_flow and a value in range, got %s\n", flow_names[i],
+                         it->second.c_str());
+            return usage(2);
+        }
+        flow_opt[i] = v;
+    }
+    if (a.bidirectional && method != "block_matching") {
+        std::fprintf(stderr, "nu_scaler_cli: error: --bidirectional needs --method block_matching\n");
+        return usage(2);
+    }
+    const auto d_it = a.options.find("device");
+    const int device = d_it == a.options.end() ? 0 : std::atoi(d_it->second.c_str());
+
+    const uint32_t n = (uint32_t)(a.positional.size() - 1);
+    std::vector<nus_cli::Image> in(n);
+    for (uint32_t k = 0; k < n; ++k) {
+        const std::string err = nus_cli::read_png(a.positional[k + 1], in[k]);
+        if (!err.empty()) return fail(err);
+        if (in[k].width != in[0].width || in[k].height != in[0].height) return fail("frame sizes differ");
+    }
+    const uint32_t w = in[0].width, h = in[0].height;
+    const size_t fb = in[0].rgba.size();
+    const int64_t n_out = nus_retime_count(n, (uint32_t)num, (uint32_t)den);
+    if (n_out < 0) return fail(nus_last_error());
+    std::vector<nus_retime_entry> sched((size_t)n_out);
+    if (nus_retime_schedule(n, (uint32_t)num, (uint32_t)den, 0, (uint64_t)n_out, sched.data()) != NUS_OK) return fail(nus_last_error());
+
+    nus_blockmatch *bm = nullptr;
+    nus_flow *fl = nullptr;
+    nus_interp *it = nullptr;
+    int rc = NUS_OK;
+    std::string msg;
+    if (method == "block_matching") {
+        if (!(bm = nus_bm_create())) return fail(nus_last_error());
+        rc = nus_bm_set_device(bm, device);
+        if (rc == NUS_OK) rc = nus_bm_set_quality(bm, NUS_INTERP_QUALITY_MEDIUM);
+        if (rc == NUS_OK && a.bidirectional) rc = nus_bm_set_bidirectional(bm, 1, NUS_BM_BIDIR_DEFAULT_TOLERANCE);
+        if (rc == NUS_OK && a.scene_detect) rc = nus_bm_set_scene_detect(bm, 1, NUS_SCENE_DEFAULT_MAD, NUS_SCENE_DEFAULT_HIST_PERMILLE);
+        if (rc != NUS_OK) msg = nus_bm_last_error(bm);
+    } else {
+        if (!(it = nus_interp_create(NUS_WG_WIDE_32X8))) return fail(nus_last_error());
+        rc = nus_interp_set_device(it, device);
+        if (rc == NUS_OK) rc = nus_interp_set_flow_project(it, (uint32_t)flow_opt[2]);
+        if (rc != NUS_OK) msg = nus_interp_last_error(it);
+        if (rc == NUS_OK && method == "optical_flow") {
+            if (!(fl = nus_flow_create())) {
+                nus_interp_destroy(it);
+                return fail(nus_last_error());
+            }
+            rc = nus_flow_set_device(fl, device);
+            if (rc == NUS_OK) rc = nus_flow_set_warps(fl, (uint32_t)flow_opt[0]);
+            if (rc == NUS_OK) rc = nus_flow_set_median(fl, (uint32_t)flow_opt[1]);
+            if (rc != NUS_OK) msg = nus_flow_last_error(fl);
+        }
+    }
+    std::vector<float> flow, times;
+    std::vector<uint8_t> frames;
+    std::string err;
+    for (size_t j = 0; rc == NUS_OK && err.empty() && j < sched.size();) {
+        const uint32_t k = sched[j].pair;
+        nus_cli::Image out;
+        out.width = w, out.height = h;
+        if (sched[j].rem == 0) { // a real frame
+            out.rgba = in[k].rgba;
+            err = nus_cli::write_png(pattern_path(a.positional[0], j), out);
+            if (err.empty()) std::printf("%s\n", pattern_path(a.positional[0], j).c_str());
+            ++j;
+            continue;
+        }
+        size_t end = j; // the in-between outputs of pair k: one call
+        times.clear();
+        while (end < sched.size() && sched[end].pair == k && sched[end].rem != 0) times.push_back(sched[end++].t);
+        const uint32_t nt = (uint32_t)times.size();
+        frames.resize(fb * nt);
+        const uint8_t *pa = in[k].rgba.data(), *pb = in[k + 1].rgba.data();
+        if (bm) {
+            rc = nus_bm_interpolate(bm, pa, fb, pb, fb, w, h, times.data(), nt, NUS_INTERP_MODE_EXACT, frames.data(), frames.size());
+            if (rc != NUS_OK) msg = nus_bm_last_error(bm);
+        } else {
+            uint8_t cut = 0;
+            if (a.scene_detect && (rc = nus_scene_detect(device, pa, fb, pb, fb, w, h, NUS_FORMAT_RGBA8, NUS_SCENE_DEFAULT_MAD,
+                                                         NUS_SCENE_DEFAULT_HIST_PERMILLE, nullptr, &cut)) != NUS_OK)
+                msg = nus_last_error();
+            if (rc == NUS_OK && cut) // repeats of the nearer frame: the zero-flow launch at t = 0 / 1
+                for (float &tk : times) tk = tk < 0.5f ? 0.0f : 1.0f;
+            if (rc == NUS_OK && fl && !cut) {
+                flow.resize((size_t)w * h * 2);
+                // 3 levels, 50 coarse + 10 refining Jacobi steps, lambda as the Python mirror's FlowEstimator defaults
+                rc = nus_flow_estimate(fl, pa, pb, w, h, 3, 50, 10, 0.0004f, flow.data());
+                if (rc != NUS_OK) msg = nus_flow_last_error(fl);
+            }
+            if (rc == NUS_OK) {
+                rc = nus_interp_interpolate_multi(it, pa, fb, pb, fb, fl && !cut ? flow.data() : nullptr, w, h, times.data(), nt,
+                                                  frames.data(), frames.size());
+                if (rc != NUS_OK) msg = nus_interp_last_error(it);
+            }
+        }
+        for (uint32_t i = 0; rc == NUS_OK && err.empty() && i < nt; ++i) {
+            out.rgba.assign(frames.begin() + (size_t)i * fb, frames.begin() + (size_t)(i + 1) * fb);
+            err = nus_cli::write_png(pattern_path(a.positional[0], j + i), out);
+            if (err.empty()) std::printf("%s\n", pattern_path(a.positional[0], j + i).c_str());
+        }
+        j = end;
+    }
+    if (bm) nus_bm_destroy(bm);
+    if (fl) nus_flow_destroy(fl);
+    if (it) nus_interp_destroy(it);
+    if (rc != NUS_OK) return fail(msg);
+    if (!err.empty()) return fail(err);
+    return 0;
+}
+
 } // namespace
 
 int main(int argc, char **argv)
@@ -443,6 +641,7 @@ int main(int argc, char **argv)
     if (!parse(argc, argv, a, err)) return fail(err);
     if (cmd == "upscale") return cmd_upscale(a);
     if (cmd == "interpolate") return cmd_interpolate(a);
+    if (cmd == "retime") return cmd_retime(a);
     if (cmd == "compare") return cmd_compare(a);
     if (cmd == "scene") return cmd_scene(a);
     if (cmd == "png-copy") return cmd_png_copy(a);

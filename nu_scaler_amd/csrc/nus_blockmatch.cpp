@@ -6,6 +6,7 @@
 
 #include "nus_host.hpp"
 #include "nus_host_util.hpp"
+#include "nus_retime.hpp"
 #include "nus_scene.hpp"
 #include "nus_transfer.hpp"
 
@@ -341,6 +342,56 @@ int BlockMatcher::interpolate_multi_device_stream(const void *d_frames, size_t f
         es = launch_scene_apply(S, n_times, scene_from_a_mask(times, n_times), ws + l.o_cut, static_cast<uint8_t *>(d_mid),
                                 mid_pair_stride ? mid_pair_stride : (size_t)n_times * frame_bytes);
         if (es != hipSuccess) return fail_hip(es, "scene-apply launch");
+    }
+    return kOk;
+}
+
+int BlockMatcher::retime_device_stream(const void *d_frames, size_t frame_stride, uint32_t n_frames, uint32_t w, uint32_t h, uint32_t num,
+                                       uint32_t den, int mode, void *d_workspace, size_t workspace_bytes, void *d_vectors, void *d_out,
+                                       size_t out_frame_stride, hipStream_t stream)
+{
+    static const char *const who = "nus_bm_retime_device_stream";
+    std::lock_guard<std::mutex> lk(mu_);
+    RetimeRatio r;
+    int st = pass(check_retime(who, n_frames, num, den, r));
+    if (st != kOk) return st;
+    const uint32_t n_pairs = n_frames - 1;
+    if ((st = check_shape(who, w, h, n_pairs)) != kOk) return st;
+    if (!d_frames || !d_workspace || !d_out) return fail(kInvalidArgument, fmt("%s: null device pointer", who));
+    if (mode != 0 && mode != 1) return fail(kInvalidArgument, fmt("%s: mode must be NUS_INTERP_MODE_EXACT or NUS_INTERP_MODE_FMA", who));
+    const size_t frame_bytes = (size_t)w * h * 4;
+    if ((st = pass(check_pixel_aligned(who, d_frames, frame_stride, d_frames, frame_stride, d_out, d_vectors, 4))) != kOk) return st;
+    if (frame_stride < frame_bytes)
+        return fail(kInvalidArgument, fmt("%s: frame_stride %zu is smaller than a %ux%u frame (%zu bytes)", who, frame_stride, w, h, frame_bytes));
+    if ((st = pass(check_out_frame_stride(who, out_frame_stride, frame_bytes))) != kOk) return st;
+    if (misaligned(d_workspace, 16)) return fail(kInvalidArgument, fmt("%s: workspace must be 16-byte aligned", who));
+    if (scene_) {
+        const std::string too_many = check_scene_launch(w, h, n_pairs);
+        if (!too_many.empty()) return fail(kInvalidArgument, fmt("%s: %s", who, too_many.c_str()));
+    }
+    const StreamLayout l = stream_layout(w, h, n_pairs);
+    if ((st = pass(check_workspace(who, workspace_bytes, l.total, "nus_bm_stream_workspace_size"))) != kOk) return st;
+    const uint8_t *const a = static_cast<const uint8_t *>(d_frames), *const b = a + frame_stride;
+    uint8_t *const ws = static_cast<uint8_t *>(d_workspace);
+    void *const vec = d_vectors ? d_vectors : ws + l.o_vec;
+    // one search over all pairs -> the confidence pass (or the forward-backward check) -> the retime warp from the block vectors
+    // and the real frames -> with detection on, the detector and the cut pairs' in-between outputs overwritten with repeats
+    int rc = enqueue(a, frame_stride, b, frame_stride, w, h, n_pairs, ws, vec, nullptr, nullptr, nullptr, 0, stream);
+    if (rc != kOk) return rc;
+    RetimeLaunch L;
+    L.frames = a, L.frame_stride = frame_stride, L.first_pair = 0, L.n_pairs = n_pairs, L.w = w, L.h = h, L.num = r.num, L.den = r.den;
+    L.out = static_cast<uint8_t *>(d_out), L.out_frame_stride = out_frame_stride ? out_frame_stride : frame_bytes, L.stream = stream;
+    RetimeWarp V;
+    V.vectors = static_cast<const int16_t *>(vec), V.bs = bs_, V.fma = mode == 1;
+    hipError_t e = enqueue_retime(L, V, true);
+    if (e != hipSuccess) return fail_hip(e, "retime block-vector warp+blend launch");
+    if (scene_) {
+        SceneLaunch S;
+        S.a = a, S.b = b, S.a_stride = S.b_stride = frame_stride;
+        S.w = w, S.h = h, S.n_pairs = n_pairs, S.stream = stream;
+        if ((e = launch_scene_detect(S, scene_mad_, scene_hist_, ws + l.o_scene, nullptr, ws + l.o_cut)) != hipSuccess)
+            return fail_hip(e, "scene-detect launch");
+        if ((e = launch_scene_apply_retime(L, ws + l.o_cut)) != hipSuccess) return fail_hip(e, "retime scene-apply launch");
     }
     return kOk;
 }

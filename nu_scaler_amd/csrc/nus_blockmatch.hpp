@@ -54,6 +54,12 @@ public:
     int interpolate_multi_device_stream(const void *d_frames, size_t frame_stride, uint32_t n_frames, uint32_t w, uint32_t h,
                                         const float *times, uint32_t n_times, int mode, void *d_workspace, size_t workspace_bytes,
                                         void *d_vectors, void *d_mid, size_t mid_pair_stride, hipStream_t stream);
+    // Frame-rate conversion of the stream by num / den (nus_bm_retime_device_stream; the schedule is nus_retime.hpp's): the search
+    // and the confidence pass as above, then the retime warp from the block vectors and the copy of the real frames; output j at
+    // d_out + j * out_frame_stride (0: tightly packed).  The workspace is stream_workspace_size's.
+    int retime_device_stream(const void *d_frames, size_t frame_stride, uint32_t n_frames, uint32_t w, uint32_t h, uint32_t num,
+                             uint32_t den, int mode, void *d_workspace, size_t workspace_bytes, void *d_vectors, void *d_out,
+                             size_t out_frame_stride, hipStream_t stream);
     int estimate(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, uint32_t w, uint32_t h, int16_t *vectors_out,
                  uint32_t *sad_out, uint8_t *flags_out);
     int interpolate(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, uint32_t w, uint32_t h, const float *times,

@@ -13,6 +13,7 @@
 #include "nus_metrics.hpp"
 #include "nus_queue.hpp"
 #include "nus_ranges.hpp"
+#include "nus_retime.hpp"
 #include "nus_scene.hpp"
 #include "nus_transfer.hpp"
 
@@ -1008,6 +1009,66 @@ int nus_scene_apply_cuts_device(const void *d_a, size_t a_stride, const void *d_
     return guarded<int>("nus_scene_apply_cuts_device", [&]() -> int {
         return nus::scene_apply_cuts_device(d_a, a_stride, d_b, b_stride, w, h, format, times, n_times, d_cut, d_out, out_pair_stride,
                                             n_pairs, static_cast<hipStream_t>(stream));
+    });
+}
+
+static_assert(NUS_RETIME_MAX_TERM == nus::kRetimeMaxTerm, "the C header's NUS_RETIME_MAX_TERM is the schedule's bound");
+static_assert(sizeof(nus_retime_entry) == sizeof(nus::RetimeEntry) && sizeof(nus_retime_entry) == 16, "nus_retime_entry is the kernels' entry");
+
+int64_t nus_retime_count(uint32_t n_frames, uint32_t num, uint32_t den)
+{
+    return guarded<int64_t>("nus_retime_count", [&]() -> int64_t { return nus::retime_count_checked(n_frames, num, den); });
+}
+int nus_retime_schedule(uint32_t n_frames, uint32_t num, uint32_t den, uint64_t first, uint64_t count, nus_retime_entry *out)
+{
+    return guarded<int>("nus_retime_schedule", [&]() -> int {
+        return nus::retime_schedule(n_frames, num, den, first, count, reinterpret_cast<nus::RetimeEntry *>(out));
+    });
+}
+int nus_retime_schedule_device(uint32_t n_frames, uint32_t num, uint32_t den, void *d_entries, void *stream)
+{
+    return guarded<int>("nus_retime_schedule_device", [&]() -> int { return nus::retime_schedule_device(n_frames, num, den, d_entries, stream); });
+}
+int nus_interp_retime_device(nus_interp *h, const void *d_frames, size_t frame_stride, uint32_t n_frames, const void *d_flows,
+                             uint32_t w, uint32_t hgt, uint32_t num, uint32_t den, void *d_out, size_t out_frame_stride, void *stream)
+{
+    return guarded<int>("nus_interp_retime_device", [&]() -> int {
+        return h ? h->impl.retime_device(d_frames, frame_stride, n_frames, d_flows, w, hgt, num, den, d_out, out_frame_stride,
+                                         static_cast<hipStream_t>(stream))
+                 : null_handle();
+    });
+}
+int nus_flow_retime_device_stream(nus_flow *h, const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t hgt, uint32_t levels,
+                                  uint32_t coarse_iters, uint32_t refine_iters, float lambda, uint32_t num, uint32_t den,
+                                  int flow_format, void *d_flows, void *d_out, size_t out_frame_stride, void *stream)
+{
+    return guarded<int>("nus_flow_retime_device_stream", [&]() -> int {
+        if (!h) return null_handle();
+        if (flow_format != NUS_FLOW_F32 && flow_format != NUS_FLOW_F16) {
+            nus::set_thread_error("nus_flow_retime_device_stream: flow_format must be NUS_FLOW_F32 or NUS_FLOW_F16");
+            return NUS_ERR_INVALID_ARGUMENT;
+        }
+        return h->impl.retime_device_stream(d_frames, n_frames, w, hgt, {levels, coarse_iters, refine_iters, lambda}, num, den,
+                                            flow_format == NUS_FLOW_F16, d_flows, d_out, out_frame_stride, static_cast<hipStream_t>(stream));
+    });
+}
+int nus_bm_retime_device_stream(nus_blockmatch *h, const void *d_frames, size_t frame_stride, uint32_t n_frames, uint32_t w,
+                                uint32_t hgt, uint32_t num, uint32_t den, int mode, void *d_workspace, size_t workspace_bytes,
+                                void *d_vectors, void *d_out, size_t out_frame_stride, void *stream)
+{
+    return guarded<int>("nus_bm_retime_device_stream", [&]() -> int {
+        return h ? h->impl.retime_device_stream(d_frames, frame_stride, n_frames, w, hgt, num, den, mode, d_workspace, workspace_bytes,
+                                                d_vectors, d_out, out_frame_stride, static_cast<hipStream_t>(stream))
+                 : null_handle();
+    });
+}
+int nus_scene_apply_cuts_retime_device(const void *d_frames, size_t frame_stride, uint32_t n_frames, uint32_t w, uint32_t h, int format,
+                                       uint32_t num, uint32_t den, const uint8_t *d_cut, void *d_out, size_t out_frame_stride,
+                                       void *stream)
+{
+    return guarded<int>("nus_scene_apply_cuts_retime_device", [&]() -> int {
+        return nus::scene_apply_cuts_retime_device(d_frames, frame_stride, n_frames, w, h, format, num, den, d_cut, d_out, out_frame_stride,
+                                                   stream);
     });
 }
 

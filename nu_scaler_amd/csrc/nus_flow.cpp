@@ -6,6 +6,7 @@
 
 #include "nus_host.hpp"
 #include "nus_host_util.hpp"
+#include "nus_retime.hpp"
 #include "nus_kernels.hpp"
 #include "nus_scene.hpp"
 #include "nus_transfer.hpp"
@@ -469,7 +470,7 @@ int HipFlowEstimator::place_flow(const StreamJob &J, const Solved &s)
         NUS_HIP(launch_flow_to_half(s.flow, dst, cells, J.stream));
         final_flow = dst;
     }
-    if (J.mid) NUS_HIP(launch_warp_blend(warp_behind(J, final_flow)));
+    if (J.mid) NUS_HIP(launch_warp_behind(J, final_flow));
     return kOk;
 }
 
@@ -585,6 +586,45 @@ int HipFlowEstimator::interpolate_multi_device_stream(const void *d_frames, uint
     return kOk;
 }
 
+int HipFlowEstimator::retime_device_stream(const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t h, const FlowParams &p, uint32_t num,
+                                           uint32_t den, bool flow_half, void *d_flows, void *d_out, size_t out_frame_stride,
+                                           hipStream_t stream)
+{
+    static const char *const who = "nus_flow_retime_device_stream";
+    std::lock_guard<std::mutex> lk(mu_);
+    RetimeRatio r;
+    int rc = pass(check_retime(who, n_frames, num, den, r));
+    if (rc != kOk || (rc = pass(check_dims(who, w, h, kMaxPixels, "bad image dimensions"))) != kOk) return rc;
+    if (!d_frames || !d_out) return fail(kInvalidArgument, std::string(who) + ": null device pointer");
+    if (misaligned(d_out, 16) || misaligned(d_flows, 16) || misaligned(d_frames, 4))
+        return fail(kInvalidArgument, std::string(who) + ": d_out and d_flows must be 16-byte aligned, d_frames 4-byte aligned");
+    const size_t frame_bytes = (size_t)w * h * 4;
+    if ((rc = pass(check_out_frame_stride(who, out_frame_stride, frame_bytes))) != kOk) return rc;
+    const uint32_t n_pairs = n_frames - 1;
+    if (scene_) {
+        const std::string too_many = check_scene_launch(w, h, n_pairs);
+        if (!too_many.empty()) return fail(kInvalidArgument, std::string(who) + ": " + too_many);
+    }
+    const RetimeJob rt{r.num, r.den, out_frame_stride ? out_frame_stride : frame_bytes, n_pairs};
+    StreamJob J(d_frames, n_frames, w, h, d_flows, d_out, stream);
+    J.flow_half = flow_half, J.rt = &rt, J.project = project_;
+    call_stream_ = stream;
+    if ((rc = stream_impl(J, with_warps(p))) != kOk || !scene_) return rc;
+    // behind estimate + warp, the detector and the cut pairs' in-between outputs overwritten with repeats
+    const size_t ws_bytes = scene_shape(w, h, n_pairs).workspace_bytes;
+    if ((rc = reserve(ws_bytes + n_pairs, kScene)) != kOk) return rc;
+    uint8_t *cut = u8(kScene) + ws_bytes;
+    SceneLaunch S;
+    S.a = J.frames, S.b = S.a + frame_bytes, S.a_stride = S.b_stride = frame_bytes;
+    S.w = w, S.h = h, S.n_pairs = n_pairs, S.stream = stream;
+    NUS_HIP(launch_scene_detect(S, scene_mad_, scene_hist_, u8(kScene), nullptr, cut));
+    RetimeLaunch L;
+    L.frames = J.frames, L.frame_stride = frame_bytes, L.first_pair = 0, L.n_pairs = n_pairs, L.w = w, L.h = h;
+    L.num = r.num, L.den = r.den, L.out = J.mid, L.out_frame_stride = rt.out_frame_stride, L.stream = stream;
+    NUS_HIP(launch_scene_apply_retime(L, cut));
+    return kOk;
+}
+
 int HipFlowEstimator::set_scene_detect(int enabled, uint32_t mad_threshold, uint32_t hist_permille)
 {
     std::lock_guard<std::mutex> lk(mu_);
@@ -603,8 +643,21 @@ HipFlowEstimator::StreamJob HipFlowEstimator::StreamJob::pairs(uint32_t k0, uint
     S.frames += (size_t)k0 * frame_bytes();
     S.n_frames = n + 1;
     if (flows) S.flows += (size_t)k0 * flow_bytes();
-    if (mid) S.mid += (size_t)k0 * mid_stride();
+    if (mid && !rt) S.mid += (size_t)k0 * mid_stride();
+    S.first_pair += k0;
     return S;
+}
+
+hipError_t HipFlowEstimator::launch_warp_behind(const StreamJob &J, const void *flow)
+{
+    if (!J.rt) return launch_warp_blend(warp_behind(J, flow));
+    RetimeLaunch L;
+    L.frames = J.frames, L.frame_stride = J.frame_bytes();
+    L.first_pair = J.first_pair, L.n_pairs = J.n_frames - 1, L.w = J.w, L.h = J.h, L.num = J.rt->num, L.den = J.rt->den;
+    L.out = J.mid, L.out_frame_stride = J.rt->out_frame_stride, L.stream = J.stream;
+    RetimeWarp V;
+    V.flow = flow, V.flow_half = J.flow_half, V.fma = true, V.project = J.project;
+    return enqueue_retime(L, V, J.first_pair + L.n_pairs == J.rt->n_pairs);
 }
 
 WarpLaunch HipFlowEstimator::warp_behind(const StreamJob &J, const void *flow)
@@ -647,7 +700,7 @@ int HipFlowEstimator::stream_impl(const StreamJob &J, const FlowParams &p)
                 NUS_HIP(launch_flow_to_half(static_cast<const float *>(fl), hf, (size_t)w * h, J.stream));
                 fl = hf;
             }
-            if (J.mid) NUS_HIP(launch_warp_blend(warp_behind(P, fl)));
+            if (J.mid) NUS_HIP(launch_warp_behind(P, fl));
         }
         return kOk;
     }

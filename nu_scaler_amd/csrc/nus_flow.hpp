@@ -112,6 +112,12 @@ public:
     int interpolate_multi_device_stream(const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t h, const FlowParams &p,
                                         const float *times, uint32_t n_times, bool flow_half, void *d_flows, void *d_mid,
                                         size_t mid_pair_stride, hipStream_t stream);
+    // Frame-rate conversion of the stream by num / den (nus_flow_retime_device_stream; the schedule is nus_retime.hpp's): the
+    // estimator, then the retime warp in FMA mode over each chunk's pairs and the copy of the real frames -- the bytes of
+    // estimate_device_stream followed by HipFrameInterpolator::retime_device in FMA mode.  Output j at d_out + j * out_frame_stride
+    // (0: tightly packed).  Honours warps, median, project and scene detection; the flows at d_flows are the estimate's.
+    int retime_device_stream(const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t h, const FlowParams &p, uint32_t num,
+                             uint32_t den, bool flow_half, void *d_flows, void *d_out, size_t out_frame_stride, hipStream_t stream);
 
 private:
     // The grow-only device workspace.  Slots 0, 1, 4 and 5 have two names: the pair path's (plan / build_pyramid / solve, and the
@@ -138,6 +144,11 @@ private:
         uint32_t n = 0;
         size_t pair_stride = 0; // bytes between the in-between frames of consecutive pairs
     };
+    struct RetimeJob { // the retime warp behind the estimator (retime_device_stream)
+        uint32_t num = 1, den = 1; // reduced
+        size_t out_frame_stride = 0;
+        uint32_t n_pairs = 0;      // of the whole stream
+    };
     struct StreamJob { // n_frames consecutive frames -> flows and / or in-between frames of the n_frames - 1 pairs
         const uint8_t *frames = nullptr;
         uint32_t n_frames = 0, w = 0, h = 0;
@@ -145,6 +156,8 @@ private:
         float t = 0.5f;                           // time of the in-between frame, unless
         bool flow_half = false;
         const MidTimes *mt = nullptr;             // ... several per pair
+        const RetimeJob *rt = nullptr;            // ... or the outputs of a rate conversion: mid is then the STREAM's output base
+        uint32_t first_pair = 0;                  // of this job in the stream (the rate conversion's schedule is global)
         uint32_t project = 0;                     // the warp's projection rounds (set_project)
         hipStream_t stream = nullptr;
         size_t frame_bytes() const { return (size_t)w * h * 4; }
@@ -217,6 +230,7 @@ private:
     int stream_impl(const StreamJob &J, const FlowParams &p);
     int solve_batch(const StreamJob &J, const Pyramid &g, const FlowParams &p); // J: one chunk
     static WarpLaunch warp_behind(const StreamJob &J, const void *flow); // the warp kernel behind the estimator, over J's pairs
+    static hipError_t launch_warp_behind(const StreamJob &J, const void *flow); // ... launched; J.rt: the retime warp and the real frames
     int ensure_device();
     static constexpr uint64_t kMaxPixels = (1ull << 28) - 1;
     int check_size(uint32_t w, uint32_t h) { return pass(check_dims("flow", w, h, kMaxPixels, "bad image dimensions")); }

@@ -285,6 +285,12 @@ public:
                                  uint32_t n_pairs, hipStream_t stream);
     int interpolate_multi(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, const float *flow, uint32_t w, uint32_t h,
                           const float *times, uint32_t n_times, uint8_t *out, size_t out_cap);
+    // Frame-rate conversion of a device-resident stream by num / den (nus_interp_retime_device; the schedule is nus_retime.hpp's):
+    // n_frames frames frame_stride apart, pair k's flow at d_flows + k * flow bytes (null: zero flow), output j at d_out +
+    // j * out_frame_stride (0: tightly packed).  An in-between output is byte for byte interpolate_device's at t_j under the
+    // handle's settings, a real-frame output the zero-flow copy.  One warp launch and one copy launch; enqueue only.
+    int retime_device(const void *d_frames, size_t frame_stride, uint32_t n_frames, const void *d_flows, uint32_t w, uint32_t h,
+                      uint32_t num, uint32_t den, void *d_out, size_t out_frame_stride, hipStream_t stream);
     const char *name() const override { return "HipWarpBlendInterpolator"; }
     const char *last_error() const override { return error_.c_str(); }
     int set_device(int device);

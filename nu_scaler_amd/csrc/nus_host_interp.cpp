@@ -4,6 +4,7 @@
 
 #include "nus_copy.hpp"
 #include "nus_host_util.hpp"
+#include "nus_retime.hpp"
 
 #include <cstring>
 
@@ -275,6 +276,34 @@ int HipFrameInterpolator::device_call(const char *who, const void *d_a, size_t a
     L.project = project_;
     const hipError_t e = launch_warp_blend(L);
     if (e != hipSuccess) return fail_hip(e, multi ? "multi-time warp+blend launch" : "warp+blend launch");
+    return kOk;
+}
+
+int HipFrameInterpolator::retime_device(const void *d_frames, size_t frame_stride, uint32_t n_frames, const void *d_flows, uint32_t w,
+                                        uint32_t h, uint32_t num, uint32_t den, void *d_out, size_t out_frame_stride, hipStream_t stream)
+{
+    static const char *const who = "nus_interp_retime_device";
+    std::lock_guard<std::mutex> lk(mu_);
+    RetimeRatio r;
+    int st = pass(check_retime(who, n_frames, num, den, r));
+    if (st != kOk || (st = pass(check_dims(who, w, h, kMaxPixels))) != kOk) return st;
+    if (!d_frames || !d_out) return fail(kInvalidArgument, fmt("%s: null device pointer", who));
+    const size_t frame_bytes = (size_t)w * h * 4;
+    if ((st = pass(check_pixel_aligned(who, d_frames, frame_stride, d_frames, frame_stride, d_out, d_flows, flow_half_ ? 4 : 8))) != kOk) return st;
+    if (frame_stride < frame_bytes)
+        return fail(kInvalidArgument, fmt("%s: frame_stride %zu is smaller than a %ux%u frame (%zu bytes)", who, frame_stride, w, h, frame_bytes));
+    if ((st = pass(check_out_frame_stride(who, out_frame_stride, frame_bytes))) != kOk) return st;
+    if (device_count() <= 0) return fail(kNoDevice, "no HIP device available (the gfx950 path has no CPU fallback)");
+    NUS_HIP(hipSetDevice(device_));
+    RetimeLaunch L;
+    L.frames = static_cast<const uint8_t *>(d_frames), L.frame_stride = frame_stride;
+    L.first_pair = 0, L.n_pairs = n_frames - 1, L.w = w, L.h = h, L.num = r.num, L.den = r.den;
+    L.out = static_cast<uint8_t *>(d_out), L.out_frame_stride = out_frame_stride ? out_frame_stride : frame_bytes;
+    L.in_sel = input_selector(in_format_), L.stream = stream;
+    RetimeWarp V;
+    V.flow = d_flows, V.flow_half = flow_half_, V.fma = fma_, V.project = d_flows ? project_ : 0;
+    const hipError_t e = enqueue_retime(L, V, true);
+    if (e != hipSuccess) return fail_hip(e, "retime warp+blend launch");
     return kOk;
 }
 

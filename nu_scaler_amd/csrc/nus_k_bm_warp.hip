@@ -21,32 +21,11 @@
 // No float flow field, no atomics, no LDS, no scratch.  Vectors beyond +-kBmMaxRadius are the caller's breach of contract, not a
 // memory fault: every sample position is clamped to the frame before it is used.
 #include "nus_device.hpp"
-#include "nus_warp_device.hpp"
+#include "nus_warp_sources.hpp"
 
 namespace nus {
 
 namespace {
-
-template <int RV>
-struct BlockVectorSource {
-    static constexpr bool kSwizzle = false;
-    const short2 *vectors;
-    uint32_t bs_log2, blocks_x, blocks_y;
-    float2 f[RV];
-
-    __device__ __forceinline__ void load(uint32_t ybase, uint32_t x0, uint32_t w, uint32_t h, size_t npx)
-    {
-        const short2 *const pair_vectors = vectors + (size_t)blockIdx.z * blocks_x * blocks_y;
-        const uint32_t bx = x0 >> bs_log2; // x0 % XV == 0 and XV divides the block size: the thread's XV pixels share the block
-#pragma unroll
-        for (int j = 0; j < RV; ++j) {
-            const short2 v = pair_vectors[(size_t)(umin(ybase + 4 * j, h - 1) >> bs_log2) * blocks_x + bx];
-            f[j] = make_float2((float)v.x, (float)v.y);
-        }
-    }
-    __device__ __forceinline__ void at_time(uint32_t, uint32_t, uint32_t, uint32_t, float, float, float) {}
-    __device__ __forceinline__ float2 vec(int j, int) const { return f[j]; } // (one f for all i: one copy of what does not depend on x)
-};
 
 template <int MODE, int XV, int RV, bool MT>
 __global__ __launch_bounds__(256) void k_bm_warp(const uint8_t *__restrict__ a, const uint8_t *__restrict__ b,

@@ -2,9 +2,7 @@
 //   warp+blend nu_scaler_core/src/shaders/warp_blend.wgsl:18-47 (geometry),
 //              nu_scaler_core/src/interpolation/mod.rs:386-411, :467-510 (rounding)
 #include "nus_device.hpp"
-#include "nus_warp_device.hpp"
-
-#include <hip/hip_fp16.h>
+#include "nus_warp_sources.hpp"
 
 namespace nus {
 
@@ -73,42 +71,10 @@ __global__ __launch_bounds__(256) void k_blend_zero_flow(
 // The truncation of each sample to u8 (sample_frame returns u8: interpolation/mod.rs:506) stays in both modes.
 // Dense flow (2 x f32 or 2 x f16 per pixel, delta A -> B): A sampled at p - t*flow, B at p + (1-t)*flow
 // (warp_blend.wgsl:36-37 in texel space).  The layout -- threads, rows, times, stores -- is warp_blend_tile's
-// (nus_warp_device.hpp), shared with the block-vector and the projecting kernels; this unit supplies the vectors: the flow at the
-// thread's own pixels.  XV = 2: the two flow vectors of a row are one 16-byte (8-byte) load (w even and the plane 16-byte aligned,
+// (nus_warp_device.hpp), shared with the block-vector and the projecting kernels; the vectors are DenseFlowSource's
+// (nus_warp_sources.hpp): the flow at the thread's own pixels.  XV = 2: the two flow vectors of a row are one 16-byte (8-byte) load (w even and the plane 16-byte aligned,
 // host-checked).  HALF: the flow field is the Rg16Float texture of the reference's live path (wgpu_interpolator.rs:276), widened
 // exactly.
-__device__ __forceinline__ float2 widen(uint32_t bits) // one 2 x f16 flow vector
-{
-    const __half2 hf = *reinterpret_cast<const __half2 *>(&bits);
-    return make_float2(__low2float(hf), __high2float(hf));
-}
-
-template <bool HALF, int XV, int RV>
-struct DenseFlowSource {
-    static constexpr bool kSwizzle = true;
-    const void *flow;
-    float2 f[RV][XV];
-
-    __device__ __forceinline__ void load(uint32_t ybase, uint32_t x0, uint32_t w, uint32_t h, size_t npx)
-    {
-#pragma unroll
-        for (int j = 0; j < RV; ++j) {
-            const size_t idx = (size_t)blockIdx.z * npx + (size_t)umin(ybase + 4 * j, h - 1) * w + x0;
-            if (XV == 2 && HALF) {
-                const uint2 raw = *reinterpret_cast<const uint2 *>(static_cast<const uint32_t *>(flow) + idx);
-                f[j][0] = widen(raw.x), f[j][XV - 1] = widen(raw.y);
-            } else if (XV == 2) {
-                const float4 v = *reinterpret_cast<const float4 *>(static_cast<const float2 *>(flow) + idx);
-                f[j][0] = make_float2(v.x, v.y), f[j][XV - 1] = make_float2(v.z, v.w);
-            } else {
-                f[j][0] = HALF ? widen(static_cast<const uint32_t *>(flow)[idx]) : static_cast<const float2 *>(flow)[idx];
-            }
-        }
-    }
-    __device__ __forceinline__ void at_time(uint32_t, uint32_t, uint32_t, uint32_t, float, float, float) {}
-    __device__ __forceinline__ float2 vec(int j, int i) const { return f[j][i]; }
-};
-
 template <int MODE, bool HALF, int XV, int RV, bool MT>
 __global__ __launch_bounds__(256) void k_warp_blend_flow(
     const uint8_t *__restrict__ a, const uint8_t *__restrict__ b, const void *__restrict__ flow,

@@ -13,75 +13,11 @@
 // rounds are N exposed gather latencies per time which only the occupancy hides: the price of the mode.
 // The flow plane is reached through a buffer resource bound to the pair's own plane, like the frames.
 #include "nus_device.hpp"
-#include "nus_flow_project_device.hpp"
-#include "nus_warp_device.hpp"
+#include "nus_warp_sources.hpp"
 
 namespace nus {
 
 namespace {
-
-template <bool HALF, int XV, int RV>
-struct ProjectedFlowSource {
-    static constexpr bool kSwizzle = true;
-    static constexpr uint32_t kCellBytes = HALF ? 4 : 8;
-    const void *flow;
-    uint32_t rounds;
-    __amdgpu_buffer_rsrc_t rf;
-    float2 f[RV][XV], g[RV][XV];
-
-    __device__ __forceinline__ void load(uint32_t ybase, uint32_t x0, uint32_t w, uint32_t h, size_t npx)
-    {
-        typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-        // the pair's own flow plane (below 4 GiB: host-checked): a coordinate outside it reads zeros, never another pair's vectors
-        rf = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(static_cast<const uint8_t *>(flow) + (size_t)blockIdx.z * npx * kCellBytes),
-                                               0, (uint32_t)(npx * kCellBytes), 0x00020000);
-#pragma unroll
-        for (int j = 0; j < RV; ++j) {
-            const uint32_t off = (umin(ybase + 4 * j, h - 1) * w + x0) * kCellBytes;
-            if (XV == 2) { // (w even: both cells are in the row)
-                if (HALF) {
-                    const u32x2 raw = __builtin_amdgcn_raw_buffer_load_b64(rf, off, 0, 0);
-                    f[j][0] = half2_bits_to_float2(raw.x), f[j][XV - 1] = half2_bits_to_float2(raw.y);
-                } else {
-                    const u32x4 raw = __builtin_amdgcn_raw_buffer_load_b128(rf, off, 0, 0);
-                    f[j][0] = make_float2(__uint_as_float(raw.x), __uint_as_float(raw.y));
-                    f[j][XV - 1] = make_float2(__uint_as_float(raw.z), __uint_as_float(raw.w));
-                }
-            } else {
-                if (HALF) {
-                    f[j][0] = half2_bits_to_float2(__builtin_amdgcn_raw_buffer_load_b32(rf, off, 0, 0));
-                } else {
-                    const u32x2 raw = __builtin_amdgcn_raw_buffer_load_b64(rf, off, 0, 0);
-                    f[j][0] = make_float2(__uint_as_float(raw.x), __uint_as_float(raw.y));
-                }
-            }
-        }
-    }
-    __device__ __forceinline__ void at_time(uint32_t ybase, uint32_t x0, uint32_t w, uint32_t h, float wmax, float hmax, float tv)
-    {
-#pragma unroll
-        for (int j = 0; j < RV; ++j)
-#pragma unroll
-            for (int i = 0; i < XV; ++i) g[j][i] = f[j][i];
-#pragma unroll 1
-        for (uint32_t r = 0; r < rounds; ++r) { // round by round: the gathers of all the thread's pixels issued, then their lerps
-            ProjectGather<HALF> G[RV][XV];
-#pragma unroll
-            for (int j = 0; j < RV; ++j) {
-                const float yfl = (float)umin(ybase + 4 * j, h - 1); // (rows past the frame repeat the last row's: no branch between the chains)
-#pragma unroll
-                for (int i = 0; i < XV; ++i)
-                    G[j][i] = project_gather_corner<HALF>(rf, w, wmax, hmax, w - 2, h - 2, (float)(x0 + i), yfl, g[j][i], tv);
-            }
-#pragma unroll
-            for (int j = 0; j < RV; ++j)
-#pragma unroll
-                for (int i = 0; i < XV; ++i) g[j][i] = project_finish_corner<HALF>(G[j][i]);
-        }
-    }
-    __device__ __forceinline__ float2 vec(int j, int i) const { return g[j][i]; }
-};
 
 template <int MODE, bool HALF, int XV, int RV, bool MT>
 __global__ __launch_bounds__(256) void k_warp_blend_flow_proj(

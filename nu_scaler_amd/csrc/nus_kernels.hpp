@@ -401,4 +401,51 @@ hipError_t launch_scene_detect(const SceneLaunch &L, uint32_t mad_threshold, uin
 hipError_t launch_scene_apply(const SceneLaunch &L, uint32_t n_times, uint32_t from_a, const uint8_t *cut, uint8_t *out,
                               size_t out_pair_stride);
 
+// Frame-rate conversion by the reduced ratio num / den (nus_k_retime.hip; the schedule is retime_pair of nus_retime.hpp).  Output j
+// of the whole stream goes to out + j * out_frame_stride.  A launch covers the pairs [first_pair, first_pair + n_pairs) of the
+// stream -- `frames` is frame first_pair, the pair's B one frame_stride further; `flow` / `vectors` / `cut` are entry first_pair's --
+// so that the estimators' chunks and the grid-z chunks all index one global schedule while `out` stays the stream's.
+struct RetimeLaunch {
+    const uint8_t *frames = nullptr;
+    size_t frame_stride = 0;
+    uint32_t first_pair = 0, n_pairs = 0;
+    uint32_t w = 0, h = 0;
+    uint32_t num = 1, den = 1;
+    uint8_t *out = nullptr;
+    size_t out_frame_stride = 0; // bytes, at least w * h * 4
+    uint32_t in_sel = kSelRGBA;
+    hipStream_t stream = nullptr;
+};
+// The in-between outputs (r_j != 0) of the launch's pairs: each pair's vectors fetched once, every one of its outputs warped,
+// blended and stored -- warp_blend_tile with the schedule as its time source, fed from the vector source given:
+//   vectors != nullptr  block vectors at block size bs (launch_bm_warp's layout; RGBA frames, no selector);
+//   flow != nullptr     dense flow, 2 x f32 or 2 x f16 per pixel, with `project` rounds of the projection (launch_warp_blend's);
+//   neither             zero flow: the streaming blend.
+// Real-frame outputs are NOT written here: launch_retime_real.
+struct RetimeWarp {
+    const void *flow = nullptr;
+    bool flow_half = false, fma = false;
+    uint32_t project = 0;
+    const int16_t *vectors = nullptr;
+    uint32_t bs = 16;
+};
+hipError_t launch_retime_warp(const RetimeLaunch &L, const RetimeWarp &V);
+// The real-frame outputs (r_j == 0) among the n_frames frames that start at the launch's first one (L.frames is frame
+// L.first_pair; L.n_pairs is not looked at): frame k with (k num) % den == 0 is copied through the input selector to output
+// k num / den; the other frames are not read.  A copy kernel of its own.
+hipError_t launch_retime_real(const RetimeLaunch &L, uint32_t n_frames);
+// The two launches every retime entry point ends with: the in-between outputs of the launch's pairs from V's vectors, then the
+// real-frame outputs among those pairs' first frames -- and, with the stream's last chunk, the stream's last frame.
+inline hipError_t enqueue_retime(const RetimeLaunch &L, const RetimeWarp &V, bool last_chunk)
+{
+    const hipError_t e = launch_retime_warp(L, V);
+    return e != hipSuccess ? e : launch_retime_real(L, L.n_pairs + (last_chunk ? 1 : 0));
+}
+// For every pair of the launch with cut[i] != 0 (i local): each of its in-between outputs becomes the copy (through the selector)
+// of the pair's A if t_j < 0.5, else of its B.  Pairs that are not cut are neither read nor written.
+hipError_t launch_scene_apply_retime(const RetimeLaunch &L, const uint8_t *cut);
+// entries: n_out x {u32 pair, u32 rem, f32 t, u32 0}, one thread per FRAME k: the entries of pair k's outputs through retime_pair; the
+// last frame has no pair behind it and writes its own entry alone
+hipError_t launch_retime_table(uint32_t n_frames, uint32_t num, uint32_t den, void *entries, hipStream_t stream);
+
 } // namespace nus

@@ -129,10 +129,28 @@ __device__ __forceinline__ uint32_t warp_blend_pixel_plain(const uint32_t *__res
 //   kSwizzle                                       whether the family has an input channel selector (sel)
 constexpr int kWarpRV = 2;
 
-template <int MODE, int XV, int RV, bool MT, typename SRC>
-__device__ __forceinline__ void warp_blend_tile(const uint8_t *__restrict__ a, const uint8_t *__restrict__ b, uint8_t *__restrict__ out,
-                                                size_t a_stride, size_t b_stride, size_t out_pair_stride, uint32_t w, uint32_t h,
-                                                const TimeSet &ts, uint32_t sel, SRC src)
+// TIMES supplies what the tile writes for the block's pair (blockIdx.z), all of it wave-uniform:
+//   begin()                                        once, before the vectors are loaded
+//   count()                                        how many frames
+//   time(k)                                        frame k's time
+//   frame(k, npx)                                  where frame k goes
+// PairTimes: the launch's time set, frame k of the pair at pair_out + k * w * h * 4 (MT = false: the set's one time, no loop).
+// The rate-conversion kernels (nus_k_retime.hip) take both from the conversion's schedule instead.
+template <bool MT>
+struct PairTimes {
+    const TimeSet &ts;
+    uint8_t *out;
+    size_t out_pair_stride;
+    uint8_t *pair_out;
+    __device__ __forceinline__ void begin() { pair_out = out + (size_t)blockIdx.z * out_pair_stride; }
+    __device__ __forceinline__ uint32_t count() const { return MT ? ts.n : 1; }
+    __device__ __forceinline__ float time(uint32_t k) const { return ts.t[k]; }
+    __device__ __forceinline__ uint32_t *frame(uint32_t k, size_t npx) const { return reinterpret_cast<uint32_t *>(pair_out + (size_t)k * npx * 4); }
+};
+
+template <int MODE, int XV, int RV, typename SRC, typename TIMES>
+__device__ __forceinline__ void warp_blend_tile_at(const uint8_t *__restrict__ a, const uint8_t *__restrict__ b, size_t a_stride,
+                                                   size_t b_stride, uint32_t w, uint32_t h, uint32_t sel, SRC src, TIMES times)
 {
     static_assert(XV == 1 || XV == 2, "one pixel, or a pair of an even-width frame");
     const uint32_t ybase = __builtin_amdgcn_readfirstlane(blockIdx.y * (4 * RV) + threadIdx.y);
@@ -147,14 +165,14 @@ __device__ __forceinline__ void warp_blend_tile(const uint8_t *__restrict__ a, c
     // per-lane copies of the wave-uniform constants: scalar operands halve the VALU issue rate on gfx950
     float wmax = (float)(w - 1), hmax = (float)(h - 1);
     asm volatile("" : "+v"(wmax), "+v"(hmax));
-    uint8_t *const pair_out = out + (size_t)blockIdx.z * out_pair_stride;
+    times.begin();
     src.load(ybase, x0, w, h, npx);
-    const uint32_t nk = MT ? ts.n : 1;
+    const uint32_t nk = times.count();
     for (uint32_t k = 0; k < nk; ++k) {
-        float tv = ts.t[k];
+        float tv = times.time(k);
         asm volatile("" : "+v"(tv));
         const float nt = 1.0f - tv;
-        uint32_t *const frame_out = reinterpret_cast<uint32_t *>(pair_out + (size_t)k * npx * 4);
+        uint32_t *const frame_out = times.frame(k, npx);
         src.at_time(ybase, x0, w, h, wmax, hmax, tv);
 #pragma unroll
         for (int j = 0; j < RV; ++j) {
@@ -175,6 +193,15 @@ __device__ __forceinline__ void warp_blend_tile(const uint8_t *__restrict__ a, c
             }
         }
     }
+}
+
+// the tile of a launch with one time set for all its pairs
+template <int MODE, int XV, int RV, bool MT, typename SRC>
+__device__ __forceinline__ void warp_blend_tile(const uint8_t *__restrict__ a, const uint8_t *__restrict__ b, uint8_t *__restrict__ out,
+                                                size_t a_stride, size_t b_stride, size_t out_pair_stride, uint32_t w, uint32_t h,
+                                                const TimeSet &ts, uint32_t sel, SRC src)
+{
+    warp_blend_tile_at<MODE, XV, RV>(a, b, a_stride, b_stride, w, h, sel, src, PairTimes<MT>{ts, out, out_pair_stride, nullptr});
 }
 
 // ---------------------------------------------------------------------------------

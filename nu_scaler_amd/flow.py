@@ -298,3 +298,17 @@ class FlowEstimator:
                                                                        self.coarse_iterations, self.refine_iterations, self.lambda_,
                                                                        ts, len(times), fmt, d_flows or None, d_mid, mid_pair_stride,
                                                                        stream or None))
+
+    def retime_device_stream(self, d_frames: int, n_frames: int, width: int, height: int, num: int, den: int, d_out: int,
+                             d_flows: int = 0, out_frame_stride: int = 0, stream: int = 0, flow_format: str = "f32") -> None:
+        """The stream converted by num / den (nus_flow_retime_device_stream; retime.py has the schedule): each pair's flow is
+        estimated once, then the retime warp in FMA mode writes output j at d_out + j * out_frame_stride (0: tightly packed), real
+        frames included; the flows at `d_flows` if that is not 0.  Warps, median, projection rounds and scene detection as the
+        handle is set."""
+        fmt = {"f32": 0, "f16": 1}.get(flow_format)
+        if fmt is None:
+            raise ValueError("flow_format must be 'f32' or 'f16'")
+        self._check(self._lib.nus_flow_retime_device_stream(self._h, d_frames or None, int(n_frames), int(width), int(height), self.levels,
+                                                            self.coarse_iterations, self.refine_iterations, self.lambda_, int(num),
+                                                            int(den), fmt, d_flows or None, d_out or None, int(out_frame_stride),
+                                                            stream or None))

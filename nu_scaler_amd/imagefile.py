@@ -284,3 +284,54 @@ def interpolate_image_files_block_matching(path_a: str, path_b: str, output_path
     for path, out in zip(paths, frames):
         write_png(path, w, h, out)
     return paths
+
+
+def retime_output_paths(pattern: str, n_out: int) -> list[str]:
+    """`pattern % j` for every output frame j; ValueError unless the pattern holds exactly one integer conversion (OUT_%04d.png)."""
+    import re
+
+    if len(re.findall(r"%0?\d*d", pattern)) != 1 or pattern.replace("%%", "").count("%") != 1:
+        raise ValueError(f"the output pattern needs exactly one %d conversion (as OUT_%04d.png), got {pattern!r}")
+    return [pattern % j for j in range(n_out)]
+
+
+def retime_image_files(output_pattern: str, input_paths, fps_in, fps_out, method: str = "optical_flow", *, device: int = 0,
+                       scene_detect: bool = False, bidirectional: bool = False, flow_warps: int = 0, flow_median: int = 0,
+                       flow_project: int = 0) -> list[str]:
+    """PNG frames at `fps_in` -> PNG frames at `fps_out`, written to `output_pattern % j` (retime.py has the schedule): method
+    "optical_flow" (Horn-Schunck, the estimator's defaults), "block_matching" (the Medium preset) or "blend" (zero flow).
+    Returns the paths written."""
+    import torch  # noqa: F401  (the device buffers are torch's: its HIP runtime has to be loaded before the library loads its own)
+
+    from .retime import retime_count, retime_frames
+
+    paths = retime_output_paths(output_pattern, retime_count(len(input_paths), fps_in, fps_out))
+    images = [read_png(p) for p in input_paths]
+    w, h = images[0][0], images[0][1]
+    if any((iw, ih) != (w, h) for iw, ih, _ in images):
+        raise ValueError("Images must have the same dimensions")
+    frames = [px for _, _, px in images]
+    if method == "block_matching":
+        from .blockmatch import BlockMatcher
+
+        bm = BlockMatcher("medium", device=device, bidirectional=bidirectional)
+        if scene_detect:
+            bm.set_scene_detect(True)
+        out = retime_frames(frames, w, h, fps_in, fps_out, matcher=bm, device=device)
+    else:
+        from .interpolator import WgpuFrameInterpolator
+        from .scene import SceneDetector
+
+        flow = None
+        warp = WgpuFrameInterpolator(device=device)
+        if method == "optical_flow":
+            from .flow import FlowEstimator
+
+            flow = FlowEstimator(device=device, warps=flow_warps, median=flow_median)
+            if flow_project:
+                warp.set_flow_project(flow_project)
+        scene = SceneDetector(device=device) if scene_detect else None
+        out = retime_frames(frames, w, h, fps_in, fps_out, warp=warp, flow=flow, scene=scene, device=device)
+    for path, px in zip(paths, out):
+        write_png(path, w, h, px)
+    return paths

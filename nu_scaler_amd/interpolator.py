@@ -136,6 +136,18 @@ class WgpuFrameInterpolator:
                                                                   height, ts, len(times), d_out, out_pair_stride, n_pairs,
                                                                   stream or None))
 
+    def retime_device(self, d_frames: int, frame_stride: int, n_frames: int, d_flows: int, width: int, height: int, num: int,
+                      den: int, d_out: int, out_frame_stride: int = 0, stream: int = 0) -> None:
+        """nus_interp_retime_device: the device-resident stream of `n_frames` frames converted by num / den (retime.py has the
+        schedule); pair k's flow at d_flows + k * flow bytes (0: zero flow); output j at d_out + j * out_frame_stride (0: tightly
+        packed).  Argument errors raise ValueError before any GPU work."""
+        st = self._lib.nus_interp_retime_device(self._h, d_frames or None, int(frame_stride), int(n_frames), d_flows or None,
+                                                int(width), int(height), int(num), int(den), d_out or None, int(out_frame_stride),
+                                                stream or None)
+        if st == C.ERR_INVALID_ARGUMENT:
+            raise ValueError(self._err())
+        self._raise(st)
+
     # -- trait FrameInterpolator (nu_scaler_core/src/interpolation/mod.rs:29-44; dead code in the reference, same shape here)
     def initialize(self, width: int, height: int) -> None:
         self._raise(self._lib.nus_interp_initialize(self._h, int(width), int(height)))
