@@ -918,8 +918,10 @@ int nus_flow_retime_device_stream(nus_flow *h, const void *d_frames, uint32_t n_
                                   uint32_t coarse_iters, uint32_t refine_iters, float lambda, uint32_t num, uint32_t den,
                                   int flow_format, void *d_flows, void *d_out, size_t out_frame_stride, void *stream);
 /* nus_bm_interpolate_multi_device_stream with the schedule in place of the time set: in NUS_INTERP_MODE_EXACT an in-between output is
- * byte for byte nus_bm_interpolate's frame for pair k_j at t_j, a real-frame output the copy.  d_workspace: 16-byte aligned, at least
- * nus_bm_stream_workspace_size(h, w, hgt, n_frames) bytes. */
+ * byte for byte nus_bm_interpolate's frame for pair k_j at t_j, a real-frame output the copy.  In either mode the bytes at d_vectors
+ * (may be NULL) are nus_bm_estimate_device's for the stream's pairs, and an in-between output is byte for byte what nus_bm_warp_device
+ * writes from pair k_j's vectors at t_j in that mode (NUS_INTERP_MODE_FMA: the FMA warp's contract, not nus_bm_interpolate's bytes).
+ * d_workspace: 16-byte aligned, at least nus_bm_stream_workspace_size(h, w, hgt, n_frames) bytes. */
 int nus_bm_retime_device_stream(nus_blockmatch *h, const void *d_frames, size_t frame_stride, uint32_t n_frames, uint32_t w,
                                 uint32_t hgt, uint32_t num, uint32_t den, int mode, void *d_workspace, size_t workspace_bytes,
                                 void *d_vectors, void *d_out, size_t out_frame_stride, void *stream);

@@ -29,6 +29,33 @@ def schedule(n_frames, num, den):
     return out
 
 
+def schedule_array(n_frames, num, den, first=0, count=None):
+    """Entries first .. first + count - 1 (default: to the end) of the same table as as_array lays it out, (count, 4) uint32,
+    vectorised for streams of a million frames: j den in uint64 (below 2^45 for every stream the library takes), its quotient and
+    remainder by num, and ONE np.float32 division of the remainder (below 4096: exact in f32) by num."""
+    num, den = reduce(num, den)
+    n_out = ((n_frames - 1) * num) // den + 1
+    cnt = n_out - first if count is None else count
+    assert 0 <= first and 0 <= cnt and first + cnt <= n_out, (first, cnt, n_out)
+    at = np.arange(first, first + cnt, dtype=np.uint64) * np.uint64(den)
+    k, r = at // np.uint64(num), at % np.uint64(num)
+    a = np.zeros((cnt, 4), np.uint32)
+    a[:, 0], a[:, 1] = k, r
+    a[:, 2] = (r.astype(np.float32) / np.float32(num)).view(np.uint32)
+    return a
+
+
+def times_of(table):
+    """The t column of a schedule_array / as_array table as np.float32."""
+    return np.ascontiguousarray(table[:, 2]).view(np.float32)
+
+
+def first_output(pair, num, den):
+    """Index of the first output at or behind frame `pair`: ceil(pair num / den), in Python ints."""
+    num, den = reduce(num, den)
+    return -((-pair * num) // den)
+
+
 def as_array(entries):
     """The table as the library lays it out: n x {u32 pair, u32 rem, f32 t, u32 0} viewed as (n, 4) uint32."""
     a = np.zeros((len(entries), 4), np.uint32)

@@ -3,7 +3,8 @@ nus_flow_estimate_device_stream followed by nus_interp_retime_device in FMA mode
 without re-linearisation, and with a chunk edge inside the schedule; nus_bm_retime_device_stream in EXACT mode equals
 nus_bm_interpolate pair by pair and copies at the real frames; with scene detection on, a cut pair's in-between outputs are repeats
 of the nearer frame and every other output is unchanged; the Python wrappers and PyFrameInterpolator.retime return the same bytes.
-Every device output comes from conftest.guarded."""
+The estimator stream and the scene-detecting streams run at 67 x 45 and at 66 x 44: the even width and the pixel count on a
+multiple of 4 select the pixel-pair and the 16-byte kernels.  Every device output comes from conftest.guarded."""
 import os
 
 import numpy as np
@@ -18,6 +19,7 @@ pytestmark = pytest.mark.gpu
 
 W, H, N = 67, 45, 5
 FB = W * H * 4
+EVEN = (66, 44)  # beside the odd width: the XV = 2 tile kernels and, with w*h % 4 == 0, the 16-byte streaming kernels
 RATIOS = [(5, 2), (2, 5)]
 POISON = 0x3C
 
@@ -35,19 +37,36 @@ def lattice():
     return frames
 
 
-def _out(n_out):
+@pytest.fixture(scope="module")
+def lattice_even():
+    frames = _flow_warp64.lattice_frames(*EVEN, N)
+    frames.setflags(write=False)
+    return frames
+
+
+def _out(n_out, w=W, h=H):
     import torch
 
-    return guarded.full((n_out, H, W, 4), POISON, dtype=torch.uint8, device="cuda:0")
+    return guarded.full((n_out, h, w, 4), POISON, dtype=torch.uint8, device="cuda:0")
 
 
 @pytest.mark.parametrize("chunk", [None, "2"])
 @pytest.mark.parametrize("warps", [0, 1])
 @pytest.mark.parametrize("mode", ["exact", "fast"])
-def test_flow_stream_equals_estimate_then_retime_warp(nsc, lattice, mode, warps, chunk):
+def test_flow_stream_equals_estimate_then_retime_warp(nsc, lattice, lattice_even, mode, warps, chunk):
+    """At 67 x 45 and at 66 x 44; at the even width the only test in which the estimator's route (StreamJob chunks with their
+    first_pair) launches the pixel-pair kernel k_retime_flow_proj<Fma, f32, XV = 2> and the 16-byte k_retime_real<true>."""
+    for size, frames in (((W, H), lattice), (EVEN, lattice_even)):
+        assert (size[0] % 2 == 0 and size[0] * size[1] % 4 == 0) == (size == EVEN)
+        _flow_stream_case(nsc, frames, size, mode, warps, chunk)
+
+
+def _flow_stream_case(nsc, frames, size, mode, warps, chunk):
     import torch
 
-    d_frames = put(lattice)
+    W, H = size
+    FB = W * H * 4
+    d_frames = put(frames)
     fe = nsc.FlowEstimator(warps=warps)
     fe.set_mode(mode)
     fe.set_project(1)
@@ -62,7 +81,7 @@ def test_flow_stream_equals_estimate_then_retime_warp(nsc, lattice, mode, warps,
             n_out = _retime.count(N, num, den)
             flows_a = guarded.empty((N - 1, H, W, 2), dtype=torch.float32, device="cuda:0")
             flows_b = guarded.empty((N - 1, H, W, 2), dtype=torch.float32, device="cuda:0")
-            got, want = _out(n_out), _out(n_out)
+            got, want = _out(n_out, W, H), _out(n_out, W, H)
             fe.retime_device_stream(d_frames.data_ptr(), N, W, H, num, den, got.data_ptr(), flows_a.data_ptr(), 0, _stream())
             fe.estimate_device_stream(d_frames.data_ptr(), N, W, H, flows_b.data_ptr(), _stream())
             it.retime_device(d_frames.data_ptr(), FB, N, flows_b.data_ptr(), W, H, num, den, want.data_ptr(), 0, _stream())
@@ -70,7 +89,7 @@ def test_flow_stream_equals_estimate_then_retime_warp(nsc, lattice, mode, warps,
             g, w_ = fetch(got), fetch(want)
             assert np.array_equal(g, w_), (mode, warps, chunk, num, den, [j for j in range(n_out) if not np.array_equal(g[j], w_[j])])
             # without d_flows the frames are the same
-            again = _out(n_out)
+            again = _out(n_out, W, H)
             fe.retime_device_stream(d_frames.data_ptr(), N, W, H, num, den, again.data_ptr(), 0, 0, _stream())
             assert np.array_equal(fetch(again), g), (mode, warps, chunk, num, den, "no d_flows")
     finally:
@@ -79,14 +98,14 @@ def test_flow_stream_equals_estimate_then_retime_warp(nsc, lattice, mode, warps,
             os.environ["NUS_FLOW_MAX_CHUNK_PAIRS"] = old
 
 
-def _bm_retime(bm, d_frames, n, num, den, mode="exact"):
+def _bm_retime(bm, d_frames, n, num, den, mode="exact", w=W, h=H):
     import torch
 
-    ws_bytes = bm.stream_workspace_size(W, H, n)
+    ws_bytes = bm.stream_workspace_size(w, h, n)
     ws = guarded.empty((ws_bytes + 16,), dtype=torch.uint8, device="cuda:0")
     d_ws = (ws.data_ptr() + 15) & ~15
-    out = _out(_retime.count(n, num, den))
-    bm.retime_stream_device(d_frames.data_ptr(), FB, n, W, H, num, den, d_ws, ws_bytes, out.data_ptr(), mode=mode, stream=_stream())
+    out = _out(_retime.count(n, num, den), w, h)
+    bm.retime_stream_device(d_frames.data_ptr(), w * h * 4, n, w, h, num, den, d_ws, ws_bytes, out.data_ptr(), mode=mode, stream=_stream())
     return fetch(out)
 
 
@@ -112,9 +131,19 @@ def _cut_stream(lattice):
 
 
 @pytest.mark.parametrize("engine", ["flow", "bm"])
-def test_scene_detection_repeats_the_nearer_frame_on_the_cut_pair_only(nsc, lattice, engine):
+def test_scene_detection_repeats_the_nearer_frame_on_the_cut_pair_only(nsc, lattice, lattice_even, engine):
+    """At 67 x 45 and at 66 x 44 (2904 px, a multiple of 4); at the latter the only test in which the detectors inside the two
+    stream entry points hand their flags to k_retime_scene_apply<true>, behind k_retime_bm<Exact, XV = 2> / k_retime_flow_proj's
+    pair form."""
+    for size, frames in (((W, H), lattice), (EVEN, lattice_even)):
+        assert (size[0] * size[1] % 4 == 0) == (size == EVEN)
+        _scene_detection_case(nsc, frames, size, engine)
+
+
+def _scene_detection_case(nsc, lattice, size, engine):
     import _scenecut as sc
 
+    W, H = size
     frames = _cut_stream(lattice)
     cut = [bool(sc.is_cut(*sc.measures(frames[k], frames[k + 1]), W, H)) for k in range(N - 1)]
     assert cut == [False, False, True, False]
@@ -123,8 +152,8 @@ def test_scene_detection_repeats_the_nearer_frame_on_the_cut_pair_only(nsc, latt
 
     def run(num, den):
         if engine == "bm":
-            return _bm_retime(h, d_frames, N, num, den)
-        out = _out(_retime.count(N, num, den))
+            return _bm_retime(h, d_frames, N, num, den, w=W, h=H)
+        out = _out(_retime.count(N, num, den), W, H)
         h.retime_device_stream(d_frames.data_ptr(), N, W, H, num, den, out.data_ptr(), 0, 0, _stream())
         return fetch(out)
 

@@ -42,6 +42,51 @@ def test_count_and_schedule_equal_the_restatement(nsc, n_frames, num, den):
     assert all(0.0 <= float(t) < 1.0 for _, _, t in want)
 
 
+@pytest.mark.parametrize("num,den", RATIOS + [(4096, 4095), (4095, 4096), (4093, 512)])
+def test_vectorised_restatement_equals_the_list(num, den):
+    """_retime.schedule_array (numpy uint64, what the million-frame GPU test takes its reference from) against the list in Python
+    ints, whole and in windows; and against Python ints again where j den is past 2^32."""
+    for n in N_FRAMES + [700]:
+        want = _retime.as_array(_retime.schedule(n, num, den))
+        assert np.array_equal(_retime.schedule_array(n, num, den), want), (n, num, den)
+        for first in (0, 1, len(want) // 2, len(want)):
+            cnt = min(3, len(want) - first)
+            assert np.array_equal(_retime.schedule_array(n, num, den, first, cnt), want[first:first + cnt]), (n, num, den, first)
+    n = 1050000
+    rn, rd = _retime.reduce(num, den)
+    n_out = _retime.count(n, num, den)
+    tail = _retime.schedule_array(n, num, den, n_out - 5, 5)
+    for i, j in enumerate(range(n_out - 5, n_out)):
+        k, r = (j * rd) // rn, (j * rd) % rn
+        assert tail[i].tolist() == [k, r, int(np.float32(np.float64(r) / rn).view(np.uint32)), 0], (num, den, j)
+    assert _retime.first_output(65535, num, den) == -(-65535 * rn // rd)
+    assert np.array_equal(_retime.times_of(tail).view(np.uint32), tail[:, 2])
+
+
+def test_host_table_at_the_bounds(nsc):
+    """nus_retime_schedule where j * den passes 2^32 (a million frames at den 4095 and 4096): windows at the start, across
+    j = 2^32 / den and at the end against the vectorised restatement."""
+    lib = nsc._capi.lib()
+    n = 1050000
+    for num, den in [(4096, 4095), (4095, 4096)]:
+        n_out = lib.nus_retime_count(n, num, den)
+        assert n_out == _retime.count(n, num, den)
+        across = (1 << 32) // den
+        assert 32 <= across <= n_out - 64
+        for first in (0, across - 32, n_out - 64):
+            assert np.array_equal(_table(lib, n, num, den, first, 64), _retime.schedule_array(n, num, den, first, 64)), (num, den, first)
+
+
+def test_block_matching_refuses_a_stream_that_would_need_a_second_launch(nsc):
+    """nus_bm_retime_device_stream takes at most 65 535 pairs (its search has the pairs on one grid axis): 65 537 frames are refused
+    before any HIP call, so the launch split of launch_retime_warp is never reached with block vectors."""
+    lib = nsc._capi.lib()
+    st, msg = _bm(nsc, lib, n_frames=65537)
+    assert st == nsc._capi.ERR_INVALID_ARGUMENT and msg.startswith("nus_bm_retime_device_stream:") and "too many" in msg, (st, msg)
+    st, msg = _bm(nsc, lib, n_frames=65536, frames=None)  # 65 535 pairs pass that check (and fail the next one)
+    assert st == nsc._capi.ERR_INVALID_ARGUMENT and "too many" not in msg, (st, msg)
+
+
 def test_reduced_ratio_gives_the_same_table(nsc):
     lib = nsc._capi.lib()
     for n in N_FRAMES:
