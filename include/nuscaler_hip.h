@@ -466,6 +466,41 @@ int nus_interp_interpolate_multi(nus_interp *h, const uint8_t *a, size_t a_len, 
                                  const float *flow, uint32_t w, uint32_t hgt, const float *times, uint32_t n_times,
                                  uint8_t *out, size_t out_cap);
 
+/* ---- The select warp: two flows per pair, each pixel takes the vector whose samples agree better ------------
+ * BUILD-DEFINED -- the reference has nothing like it.  A flow A -> B is worst where A's content has no counterpart in B (background
+ * about to be covered, content leaving the frame); the flow B -> A is worst somewhere else.  One pair of w x h frames A and B at
+ * time t: F is the flow A -> B on A's grid, R the flow B -> A on B's grid (both f32, or Rg16Float widened exactly), N the handle's
+ * projection rounds (nus_interp_set_flow_project, 0 .. NUS_FLOW_MAX_PROJECT), nt = 1.0f - t in f32.  Per output pixel p:
+ *     gF = F projected N rounds at time t, exactly as the rule above nus_interp_set_flow_project states it
+ *     gR = -(R projected N rounds at time nt) by the same rule: the content at p came from the B-pixel q with q + nt R(q) = p
+ *          (N = 0: gR = -R[y][x]; the negation is exact)
+ *     per candidate g: sa = A sampled at p - t g, sb = B sampled at p + nt g, exactly as the dense-flow warp samples them in the
+ *          handle's mode (clamp, bilinear weights, truncation to an integer count held in f32)
+ *     e(g) = |sa0 - sb0| + |sa1 - sb1| + |sa2 - sb2| over the three colour bytes of the pixel as stored; alpha does not vote.  An
+ *          integer 0 .. 765, exact in f32, symmetric in R and B: RGBA and BGRA input order give the same choice
+ *     the backward candidate wins if and only if e(gR) < e(gF); a tie goes forward
+ *     the pixel is the dense-flow warp's three-rounding blend trunc(nt sa + t sb) of the WINNER's samples, then the input channel
+ *          selector as there
+ * So with R = -F and N = 0 every pixel is a tie and the frame is byte for byte nus_interp_interpolate_multi_device's with F; an EXACT
+ * frame is, pixel by pixel, the oracle's warp + blend with flow gF or with flow gR, whichever the rule names; an FMA pixel meets the
+ * FMA contract with gF or gR as its flow, and it is the rule's choice wherever |e(gF) - e(gR)| > 12 on the EXACT samples (an FMA
+ * sample is within one count of the EXACT one).  Measured gains over the forward flow alone: DESIGN.md 8.1.
+ *
+ * nus_interp_interpolate_select_device: pointers, strides, alignment, time-set rules, output layout and error behaviour are those of
+ * nus_interp_interpolate_multi_device (n_times = 1 is the single-time call); pair i's flows at d_flow_fwd / d_flow_bwd + i * w*h*8
+ * (w*h*4 with NUS_FLOW_F16).  Both flows are required: a NULL flow is NUS_ERR_INVALID_ARGUMENT before any HIP call, the text
+ * beginning "nus_interp_interpolate_select_device:".  It honours the handle's mode, flow format, input format and flow_project.
+ * Enqueue only: no allocation, no workspace, no synchronisation. */
+int nus_interp_interpolate_select_device(nus_interp *h, const void *d_a, size_t a_stride, const void *d_b, size_t b_stride,
+                                         const void *d_flow_fwd, const void *d_flow_bwd, uint32_t w, uint32_t hgt,
+                                         const float *times, uint32_t n_times, void *d_out, size_t out_pair_stride, uint32_t n_pairs,
+                                         void *stream);
+/* The host form: host frames and two f32 flows of w*h*2 floats in, n_times frames out back to back.  Checks and texts as
+ * nus_interp_interpolate_multi (with this entry point's name), and a NULL flow is refused as above. */
+int nus_interp_interpolate_select(nus_interp *h, const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len,
+                                  const float *flow_fwd, const float *flow_bwd, uint32_t w, uint32_t hgt, const float *times,
+                                  uint32_t n_times, uint8_t *out, size_t out_cap);
+
 /* get_last_gpu_duration_ms: NUS_OK and *ms_out set, or NUS_ERR_NOT_INITIALIZED when
  * no interpolation has run yet (the reference returns None). */
 int nus_interp_last_gpu_ms(const nus_interp *h, double *ms_out);
@@ -590,6 +625,22 @@ int nus_flow_fill_workspace(nus_flow *h, int byte_value, void *stream);
  * rounds > NUS_FLOW_MAX_PROJECT: NUS_ERR_INVALID_ARGUMENT before any HIP call, the text beginning "nus_flow_set_project:". */
 int nus_flow_set_project(nus_flow *h, uint32_t rounds);
 int nus_flow_project_rounds(const nus_flow *h);
+/* Both flows of every pair and the select warp behind the estimator (BUILD-DEFINED; the rule is stated at
+ * nus_interp_interpolate_select_device).  Off by default; off means the kernels, the bytes and the nus_flow_workspace_bytes from
+ * before the setting existed (turning it off frees the slots it added).  On, nus_flow_interpolate_device_stream and
+ * nus_flow_interpolate_multi_device_stream estimate every pair both ways -- the flow B -> A of a pair is the same coarse-to-fine
+ * schedule on the same pyramids with the pair's two luminance planes swapped, honouring warps and median -- and warp with the select
+ * kernel in FMA mode with the handle's projection rounds: the frames equal nus_interp_interpolate_select_device in FMA mode fed
+ * with the forward and the backward estimate of each pair.  Both estimator families support it, the batch path and the pair-by-pair
+ * shader-shaped path.  In the batch path the backward solve's Jacobi steps run the exact kernels on coefficient planes, in
+ * NUS_FLOW_FAST too (inside FAST's contract, as a re-linearised level's).  d_flows, when given, receives the forward flows only, the
+ * bytes it receives with the setting off for every stream whose chunk size the setting's workspace (28 B per pixel and pair more)
+ * does not change; the backward flows stay in the workspace.  The stream rule below holds.  nus_flow_estimate* is not affected, and
+ * scene detection applies behind the warp as before.  nus_flow_retime_device_stream with the setting on returns
+ * NUS_ERR_INVALID_ARGUMENT before any HIP call ("... bidirectional flow is not supported by rate conversion yet").
+ * enabled other than 0 or 1: NUS_ERR_INVALID_ARGUMENT, the text beginning "nus_flow_set_bidirectional:", the setting unchanged. */
+int nus_flow_set_bidirectional(nus_flow *h, int enabled);
+int nus_flow_bidirectional(const nus_flow *h);
 const char *nus_flow_last_error(const nus_flow *h);
 
 /* primitives on host buffers */

@@ -119,6 +119,8 @@ SIGNATURES = [
     ("nus_interp_interpolate_device", _i, [_vp, _vp, _sz, _vp, _sz, _vp, _u32, _u32, _f, _vp, _u32, _vp]),
     ("nus_interp_interpolate_multi_device", _i, [_vp, _vp, _sz, _vp, _sz, _vp, _u32, _u32, _vp, _u32, _vp, _sz, _u32, _vp]),
     ("nus_interp_interpolate_multi", _i, [_vp, _vp, _sz, _vp, _sz, _vp, _u32, _u32, _vp, _u32, _vp, _sz]),
+    ("nus_interp_interpolate_select_device", _i, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _u32, _u32, _vp, _u32, _vp, _sz, _u32, _vp]),
+    ("nus_interp_interpolate_select", _i, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _u32, _u32, _vp, _u32, _vp, _sz]),
     ("nus_interp_last_gpu_ms", _i, [_vp, _dp]),
     ("nus_interp_last_error", _cp, [_vp]),
     ("nus_frame_queue_create", _vp, [_sz]),
@@ -146,6 +148,8 @@ SIGNATURES = [
     ("nus_flow_fill_workspace", _i, [_vp, _i, _vp]),  # TEST HOOK (NUS_TEST_HOOKS=1)
     ("nus_flow_set_project", _i, [_vp, _u32]),
     ("nus_flow_project_rounds", _i, [_vp]),
+    ("nus_flow_set_bidirectional", _i, [_vp, _i]),
+    ("nus_flow_bidirectional", _i, [_vp]),
     ("nus_flow_last_error", _cp, [_vp]),
     ("nus_flow_rgba8_to_f32", _i, [_vp, _vp, _u32, _u32, _vp]),
     ("nus_flow_blur", _i, [_vp, _vp, _u32, _u32, _vp]),

@@ -222,10 +222,14 @@ class PyFrameInterpolator:
     (not in the reference either; 0 .. FLOW_MAX_WARPS) is the optical-flow estimator's re-linearisation rounds per finer level
     (FlowEstimator.set_warps); a block method given a non-zero value raises.  `flow_median` (0, 3 or 5; likewise) is that estimator's
     median filter behind every Jacobi run (FlowEstimator.set_median).  `flow_project` (0 .. FLOW_MAX_PROJECT; likewise) is the
-    projection rounds of the optical-flow method's dense-flow warp (WgpuFrameInterpolator.set_flow_project)."""
+    projection rounds of the optical-flow method's dense-flow warp (WgpuFrameInterpolator.set_flow_project).  `flow_bidirectional`
+    (likewise) estimates every pair both ways and warps with the select warp -- each pixel takes the forward or the backward vector,
+    whichever makes its two samples agree better (FlowEstimator.set_bidirectional, WgpuFrameInterpolator.interpolate_select_py); it
+    is not the block matcher's `bidirectional`, and a block method given it raises; `retime` raises with it."""
 
     def __init__(self, method: str = "optical_flow", quality: str = "medium", *, device: int = 0, scene_detect: bool = False,
-                 bidirectional: bool = False, flow_warps: int = 0, flow_median: int = 0, flow_project: int = 0):
+                 bidirectional: bool = False, flow_warps: int = 0, flow_median: int = 0, flow_project: int = 0,
+                 flow_bidirectional: bool = False):
         from .flow import check_median, check_project, check_warps
 
         m = str(method).lower()
@@ -246,6 +250,10 @@ class PyFrameInterpolator:
         flow_project = check_project(flow_project)
         if flow_project and self._block:
             raise ValueError("flow_project: only the optical-flow method warps with a dense flow of its own to project")
+        if flow_bidirectional and self._block:
+            raise ValueError("flow_bidirectional: only the optical-flow method estimates a dense flow both ways (the block "
+                             "matcher's forward-backward check is `bidirectional`)")
+        self._flow_bidirectional = bool(flow_bidirectional)
         if self._block:
             self._bm = BlockMatcher(self._quality, device=device, bidirectional=bidirectional)
             if scene_detect:
@@ -253,7 +261,7 @@ class PyFrameInterpolator:
         else:
             from .flow import FlowEstimator
 
-            self._flow = FlowEstimator(device=device, warps=flow_warps, median=flow_median)
+            self._flow = FlowEstimator(device=device, warps=flow_warps, median=flow_median, bidirectional=self._flow_bidirectional)
             if scene_detect:
                 from .scene import SceneDetector
 
@@ -275,6 +283,8 @@ class PyFrameInterpolator:
         frames = list(frames)
         if any(len(memoryview(f).cast("B")) != w * h * 4 for f in frames):
             raise RuntimeError("Frame size mismatch")
+        if self._flow_bidirectional:  # the library's refusal (ValueError with its text), before any GPU work
+            self._flow.retime_device_stream(0, len(frames), w, h, 1, 1, 0)
         if self._block:
             return retime_frames(frames, w, h, fps_in, fps_out, matcher=self._bm, device=self._device)
         return retime_frames(frames, w, h, fps_in, fps_out, warp=self._warp, flow=self._flow, scene=self._scene, device=self._device)
@@ -303,6 +313,8 @@ class PyFrameInterpolator:
         if self._scene is not None and self._scene.detect(frame1, frame2, w, h)[0]:
             return self._warp.interpolate_py(frame1, frame2, w, h, time_t=0.0 if float(t) < 0.5 else 1.0)
         flow = self._flow.estimate(frame1, frame2, w, h)
+        if self._flow_bidirectional:
+            return self._warp.interpolate_select_py(frame1, frame2, w, h, flow, self._flow.estimate(frame2, frame1, w, h), time_t=float(t))
         return self._warp.interpolate_py(frame1, frame2, w, h, time_t=float(t), flow=flow)
 
     @property

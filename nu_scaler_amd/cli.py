@@ -42,6 +42,9 @@ def build_parser() -> argparse.ArgumentParser:
     it.add_argument("--flow-project", type=int, default=None,
                     help="with --flow: projection rounds of the warp -- the flow looked up where each output pixel's content came "
                          "from (0 .. 4; default 0)")
+    it.add_argument("--flow-bidirectional", action="store_true",
+                    help="with --flow: estimate the motion both ways, A -> B and B -> A, and warp each pixel with the vector whose "
+                         "two samples agree better (the select warp)")
     it.add_argument("--method", default=None, help="block_matching: the full-search block matcher supplies the motion field")
     it.add_argument("--quality", default="medium", help="block matching preset: high (8 / 24), medium (16 / 16) or low (32 / 8)")
     it.add_argument("--bidirectional", action="store_true",
@@ -265,6 +268,8 @@ def main(argv=None) -> int:
 
         if not 0 <= args.flow_project <= FLOW_MAX_PROJECT:
             parser.error(f"--flow-project must be from 0 to {FLOW_MAX_PROJECT}, got {args.flow_project}")
+    if args.command == "interpolate" and args.flow_bidirectional and not args.flow:
+        parser.error("--flow-bidirectional needs --flow")
     if args.command == "interpolate":
         if (args.bidirectional or args.bidir_tolerance is not None) and args.method is None:
             parser.error("--bidirectional needs --method block_matching")
@@ -324,13 +329,15 @@ def main(argv=None) -> int:
             for path in imagefile.interpolate_image_files_multi(args.frame_a, args.frame_b, args.output, args.multiplier, args.flow,
                                                                 device=args.device, scene_detect=args.scene_detect,
                                                                 flow_warps=args.flow_warps or 0, flow_median=args.flow_median or 0,
-                                                                flow_project=args.flow_project or 0):
+                                                                flow_project=args.flow_project or 0,
+                                                                flow_bidirectional=args.flow_bidirectional):
                 print(path)
         else:
             t = 0.5 if args.t is None else args.t
             w, h = imagefile.interpolate_image_files(args.frame_a, args.frame_b, args.output, t, args.flow, device=args.device,
                                                      flow_warps=args.flow_warps or 0, flow_median=args.flow_median or 0,
-                                                     flow_project=args.flow_project or 0)
+                                                     flow_project=args.flow_project or 0,
+                                                     flow_bidirectional=args.flow_bidirectional)
             print(f"{args.output}: {w}x{h}")
     except (OSError, ValueError, RuntimeError) as e:
         print(f"nu_scaler_cli: error: {e}", file=sys.stderr)

@@ -4,7 +4,7 @@
 // (Nu_scale/src/main.rs:36-73: --tech, --quality, --algorithm).
 //
 //   nu_scaler_cli upscale <in.png> <out.png> [--algorithm A] [--scale S] [--tech T] [--quality Q] [--device N]
-//   nu_scaler_cli interpolate <a.png> <b.png> <out.png> [--t X | --multiplier M] [--flow [--flow-warps N] [--flow-median 0|3|5] [--flow-project N]] [--device N]
+//   nu_scaler_cli interpolate <a.png> <b.png> <out.png> [--t X | --multiplier M] [--flow [--flow-warps N] [--flow-median 0|3|5] [--flow-project N] [--flow-bidirectional]] [--device N]
 //                             [--method block_matching [--quality high|medium|low] [--bidirectional [--bidir-tolerance N]]]
 //   nu_scaler_cli retime --from R --to R [--method M] [flow / block flags] [--scene-detect] OUT_%04d.png IN0.png IN1.png ...
 //   nu_scaler_cli scene <a.png> <b.png> [--mad N] [--hist N] [--device N]   (the scene-cut detector: cut=0|1 mad=.. hist_permille=..)
@@ -39,8 +39,9 @@ int usage(int rc)
                  "                             [--scale S] [--tech fsr|fallback|none] [--quality ultra|quality|balanced|performance]\n"
                  "                             [--device N]\n"
                  "       nu_scaler_cli interpolate <a.png> <b.png> <out.png> [--t X | --multiplier 2..8] [--flow [--flow-warps 0..4]\n"
-                 "                             [--flow-median 0|3|5] [--flow-project 0..4]] [--device N]\n"
-                 "                             (--flow-project: rounds that look the flow up where each output pixel's content came from)\n"
+                 "                             [--flow-median 0|3|5] [--flow-project 0..4] [--flow-bidirectional]] [--device N]\n"
+                 "                             (--flow-project: rounds that look the flow up where each output pixel's content came from;\n"
+                 "                              --flow-bidirectional: both flows, each pixel takes the vector whose samples agree better)\n"
                  "                             [--method block_matching [--quality high|medium|low]] [--scene-detect]\n"
                  "                             [--bidirectional [--bidir-tolerance 0..96]]   (block matching: forward-backward check)\n"
                  "       nu_scaler_cli retime --from 24 --to 60 [--method optical_flow|block_matching|blend] [--flow-warps 0..4]\n"
@@ -58,6 +59,7 @@ struct Args {
     bool flow = false;
     bool scene_detect = false;
     bool bidirectional = false;
+    bool flow_bidirectional = false;
 };
 
 bool parse(int argc, char **argv, Args &a, std::string &err)
@@ -70,6 +72,8 @@ bool parse(int argc, char **argv, Args &a, std::string &err)
             a.scene_detect = true;
         } else if (s == "--bidirectional") {
             a.bidirectional = true;
+        } else if (s == "--flow-bidirectional") {
+            a.flow_bidirectional = true;
         } else if (s.rfind("--", 0) == 0) {
             if (i + 1 >= argc) {
                 err = "option " + s + " needs a value";
@@ -267,6 +271,10 @@ int cmd_interpolate(const Args &a)
         }
         flow_project = (uint32_t)v;
     }
+    if (a.flow_bidirectional && !a.flow) { // both flows and the select warp (nus_interp_interpolate_select)
+        std::fprintf(stderr, "nu_scaler_cli: error: --flow-bidirectional needs --flow\n");
+        return usage(2);
+    }
     nus_cli::Image fa, fb;
     std::string err = nus_cli::read_png(a.positional[0], fa);
     if (err.empty()) err = nus_cli::read_png(a.positional[1], fb);
@@ -305,7 +313,7 @@ int cmd_interpolate(const Args &a)
         }
         return 0;
     }
-    std::vector<float> flow;
+    std::vector<float> flow, flow_bwd;
     if (a.flow) { // pyramid + Horn-Schunck front end instead of the reference's zero flow
         nus_flow *f = nus_flow_create();
         if (!f) return fail(nus_last_error());
@@ -316,6 +324,10 @@ int cmd_interpolate(const Args &a)
         // 3 levels, 50 coarse + 10 refining Jacobi steps, lambda as the Python mirror's FlowEstimator defaults
         if (rc == NUS_OK)
             rc = nus_flow_estimate(f, fa.rgba.data(), fb.rgba.data(), fa.width, fa.height, 3, 50, 10, 0.0004f, flow.data());
+        if (rc == NUS_OK && a.flow_bidirectional) { // the same estimate B -> A
+            flow_bwd.resize(flow.size());
+            rc = nus_flow_estimate(f, fb.rgba.data(), fa.rgba.data(), fa.width, fa.height, 3, 50, 10, 0.0004f, flow_bwd.data());
+        }
         const std::string msg = rc == NUS_OK ? "" : nus_flow_last_error(f);
         nus_flow_destroy(f);
         if (rc != NUS_OK) return fail(msg);
@@ -338,7 +350,10 @@ int cmd_interpolate(const Args &a)
             for (float &tk : times) tk = tk < 0.5f ? 0.0f : 1.0f;
         int rc = nus_interp_set_device(it, device);
         if (rc == NUS_OK) rc = nus_interp_set_flow_project(it, flow_project);
-        if (rc == NUS_OK)
+        if (rc == NUS_OK && a.flow_bidirectional && !cut)
+            rc = nus_interp_interpolate_select(it, fa.rgba.data(), fa.rgba.size(), fb.rgba.data(), fb.rgba.size(), flow.data(),
+                                               flow_bwd.data(), fa.width, fa.height, times.data(), n, frames.data(), frames.size());
+        else if (rc == NUS_OK)
             rc = nus_interp_interpolate_multi(it, fa.rgba.data(), fa.rgba.size(), fb.rgba.data(), fb.rgba.size(),
                                               a.flow && !cut ? flow.data() : nullptr, fa.width, fa.height, times.data(), n, frames.data(),
                                               frames.size());
@@ -363,7 +378,10 @@ int cmd_interpolate(const Args &a)
     out.rgba.resize(fa.rgba.size());
     int rc = nus_interp_set_device(it, device);
     if (rc == NUS_OK) rc = nus_interp_set_flow_project(it, flow_project);
-    if (rc == NUS_OK)
+    if (rc == NUS_OK && a.flow_bidirectional)
+        rc = nus_interp_interpolate_select(it, fa.rgba.data(), fa.rgba.size(), fb.rgba.data(), fb.rgba.size(), flow.data(), flow_bwd.data(),
+                                           fa.width, fa.height, &t, 1, out.rgba.data(), out.rgba.size());
+    else if (rc == NUS_OK)
         rc = nus_interp_interpolate(it, fa.rgba.data(), fa.rgba.size(), fb.rgba.data(), fb.rgba.size(),
                                     a.flow ? flow.data() : nullptr, fa.width, fa.height, t, out.rgba.data(), out.rgba.size());
     const std::string msg = rc == NUS_OK ? "" : nus_interp_last_error(it);

@@ -581,6 +581,26 @@ int nus_interp_interpolate_multi(nus_interp *h, const uint8_t *a, size_t a_len, 
     });
 }
 
+int nus_interp_interpolate_select_device(nus_interp *h, const void *d_a, size_t a_stride, const void *d_b, size_t b_stride,
+                                         const void *d_flow_fwd, const void *d_flow_bwd, uint32_t w, uint32_t hgt, const float *times,
+                                         uint32_t n_times, void *d_out, size_t out_pair_stride, uint32_t n_pairs, void *stream)
+{
+    return guarded<int>("nus_interp_interpolate_select_device", [&]() -> int {
+        return h ? h->impl.interpolate_select_device(d_a, a_stride, d_b, b_stride, d_flow_fwd, d_flow_bwd, w, hgt, times, n_times, d_out,
+                                                     out_pair_stride, n_pairs, static_cast<hipStream_t>(stream))
+                 : null_handle();
+    });
+}
+
+int nus_interp_interpolate_select(nus_interp *h, const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, const float *flow_fwd,
+                                  const float *flow_bwd, uint32_t w, uint32_t hgt, const float *times, uint32_t n_times, uint8_t *out,
+                                  size_t out_cap)
+{
+    return guarded<int>("nus_interp_interpolate_select", [&]() -> int {
+        return h ? h->impl.interpolate_select(a, a_len, b, b_len, flow_fwd, flow_bwd, w, hgt, times, n_times, out, out_cap) : null_handle();
+    });
+}
+
 int nus_interp_last_gpu_ms(const nus_interp *h, double *ms_out)
 {
     return guarded<int>("nus_interp_last_gpu_ms", [&]() -> int {
@@ -731,6 +751,11 @@ int nus_flow_set_project(nus_flow *h, uint32_t rounds)
     return guarded<int>("nus_flow_set_project", [&]() -> int { return h ? h->impl.set_project(rounds) : null_handle(); });
 }
 int nus_flow_project_rounds(const nus_flow *h) { return h ? h->impl.project_rounds() : NUS_ERR_INVALID_ARGUMENT; }
+int nus_flow_set_bidirectional(nus_flow *h, int enabled)
+{
+    return guarded<int>("nus_flow_set_bidirectional", [&]() -> int { return h ? h->impl.set_bidirectional(enabled) : null_handle(); });
+}
+int nus_flow_bidirectional(const nus_flow *h) { return h ? h->impl.bidirectional() : NUS_ERR_INVALID_ARGUMENT; }
 const char *nus_flow_last_error(const nus_flow *h) { return h ? h->impl.last_error() : "null handle"; }
 
 int nus_flow_rgba8_to_f32(nus_flow *h, const uint8_t *in, uint32_t w, uint32_t hgt, float *out)

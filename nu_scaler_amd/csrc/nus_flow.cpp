@@ -57,6 +57,20 @@ int HipFlowEstimator::set_project(uint32_t rounds)
     return kOk;
 }
 
+int HipFlowEstimator::set_bidirectional(int enabled)
+{
+    std::lock_guard<std::mutex> lk(mu_);
+    if (enabled != 0 && enabled != 1) return fail(kInvalidArgument, fmt("nus_flow_set_bidirectional: 0 or 1, got %d", enabled));
+    if (bidir_ && enabled == 0 && ready_ && (slot_[kFwdFlows].get() || slot_[kBwdFlows].get() || slot_[kBwdCoef].get())) {
+        // off is the old workspace too: the setting's own slots go, behind whatever the device still runs in them
+        NUS_HIP(hipSetDevice(device_));
+        NUS_HIP(hipDeviceSynchronize());
+        for (Slot s : {kFwdFlows, kBwdFlows, kBwdCoef}) slot_[s].release();
+    }
+    bidir_ = enabled == 1;
+    return kOk;
+}
+
 size_t HipFlowEstimator::workspace_bytes()
 {
     std::lock_guard<std::mutex> lk(mu_);
@@ -450,12 +464,11 @@ int HipFlowEstimator::solve_levels(const Schedule &D, Solved &done)
     return kOk;
 }
 
-// The flow solve_levels left, where and as J wants it -- f32 or Rg16Float, in J.flows if there is one -- and, with J.mid, the warp
-// kernel behind the estimator on the flow where it is (the caller's buffer, or the workspace).
-int HipFlowEstimator::place_flow(const StreamJob &J, const Solved &s)
+// The flow solve_levels left, where and as J wants it -- f32 or Rg16Float, in `out` if there is one (the caller's buffer, or the
+// slot that keeps a forward flow from the backward solve); else it stays where it is, its halves in `half_slot`.
+int HipFlowEstimator::place_flow(const StreamJob &J, const Solved &s, void *out, Slot half_slot, const void *&placed)
 {
     const size_t cells = (size_t)J.w * J.h * (J.n_frames - 1);
-    void *const out = J.flows;
     const void *final_flow = s.flow;
     if (!J.flow_half || s.wrote_half) { // as wanted already (halves: the launch wrote them, into the caller's buffer if there is one)
         if (out && s.flow != out) NUS_HIP(hipMemcpyAsync(out, s.flow, cells * (J.flow_half ? 4 : 8), hipMemcpyDeviceToDevice, J.stream));
@@ -463,14 +476,14 @@ int HipFlowEstimator::place_flow(const StreamJob &J, const Solved &s)
     } else { // 2 x f32 per cell in the workspace: converted into the caller's buffer, or beside it
         void *dst = out;
         if (!dst) {
-            const int rc = reserve(cells * 4, kFlowsHalf);
+            const int rc = reserve(cells * 4, half_slot);
             if (rc != kOk) return rc;
-            dst = u8(kFlowsHalf);
+            dst = u8(half_slot);
         }
         NUS_HIP(launch_flow_to_half(s.flow, dst, cells, J.stream));
         final_flow = dst;
     }
-    if (J.mid) NUS_HIP(launch_warp_behind(J, final_flow));
+    placed = final_flow;
     return kOk;
 }
 
@@ -487,7 +500,8 @@ int HipFlowEstimator::solve(Slot pyr_a, Slot pyr_b, const Pyramid &g, const Flow
     D.flow_a = f32(kFlowA), D.flow_b = f32(kFlowB), D.out = static_cast<float *>(d_flow_out);
     Solved done;
     const int rc = solve_levels(D, done);
-    return rc != kOk ? rc : place_flow(StreamJob(nullptr, 2, g.w[0], g.h[0], d_flow_out, nullptr, stream), done);
+    const void *placed;
+    return rc != kOk ? rc : place_flow(StreamJob(nullptr, 2, g.w[0], g.h[0], d_flow_out, nullptr, stream), done, d_flow_out, kFlowsHalf, placed);
 }
 
 int HipFlowEstimator::estimate_device(const void *d_a, const void *d_b, uint32_t w, uint32_t h, const FlowParams &p, void *d_flow_out,
@@ -542,7 +556,7 @@ int HipFlowEstimator::interpolate_device_stream(const void *d_frames, uint32_t n
     if (misaligned(d_mid, 16) || misaligned(d_flows, 16))
         return fail(kInvalidArgument, "flow: device pointers must be 16-byte aligned");
     StreamJob J(d_frames, n_frames, w, h, d_flows, d_mid, stream);
-    J.t = t, J.flow_half = flow_half, J.project = project_;
+    J.t = t, J.flow_half = flow_half, J.project = project_, J.bidir = bidir_;
     call_stream_ = stream;
     return stream_impl(J, with_warps(p));
 }
@@ -570,7 +584,7 @@ int HipFlowEstimator::interpolate_multi_device_stream(const void *d_frames, uint
     }
     const MidTimes mt{times, n_times, mid_pair_stride ? mid_pair_stride : n_times * frame_bytes};
     StreamJob J(d_frames, n_frames, w, h, d_flows, d_mid, stream);
-    J.t = times[0], J.flow_half = flow_half, J.mt = &mt, J.project = project_;
+    J.t = times[0], J.flow_half = flow_half, J.mt = &mt, J.project = project_, J.bidir = bidir_;
     call_stream_ = stream;
     if ((rc = stream_impl(J, with_warps(p))) != kOk || !scene_) return rc;
     // behind estimate + warp, the detector (it reads the frames only, so its place in the order is free) and the flagged pairs'
@@ -592,6 +606,7 @@ int HipFlowEstimator::retime_device_stream(const void *d_frames, uint32_t n_fram
 {
     static const char *const who = "nus_flow_retime_device_stream";
     std::lock_guard<std::mutex> lk(mu_);
+    if (bidir_) return fail(kInvalidArgument, std::string(who) + ": bidirectional flow is not supported by rate conversion yet");
     RetimeRatio r;
     int rc = pass(check_retime(who, n_frames, num, den, r));
     if (rc != kOk || (rc = pass(check_dims(who, w, h, kMaxPixels, "bad image dimensions"))) != kOk) return rc;
@@ -648,8 +663,9 @@ HipFlowEstimator::StreamJob HipFlowEstimator::StreamJob::pairs(uint32_t k0, uint
     return S;
 }
 
-hipError_t HipFlowEstimator::launch_warp_behind(const StreamJob &J, const void *flow)
+hipError_t HipFlowEstimator::launch_warp_behind(const StreamJob &J, const void *flow, const void *flow_bwd)
 {
+    if (J.bidir) return launch_warp_blend_select(WarpSelectLaunch{warp_behind(J, flow), static_cast<const float *>(flow_bwd)}); // (never with J.rt)
     if (!J.rt) return launch_warp_blend(warp_behind(J, flow));
     RetimeLaunch L;
     L.frames = J.frames, L.frame_stride = J.frame_bytes();
@@ -688,6 +704,9 @@ int HipFlowEstimator::stream_impl(const StreamJob &J, const FlowParams &p)
             if ((rc = reserve((size_t)w * h * 8, kPairFlow)) != kOk) return rc;
         }
         if (J.flow_half && !J.flows && (rc = reserve(J.flow_bytes(), kFlowsHalf)) != kOk) return rc;
+        const bool bidir = J.bidir && J.mid;
+        const size_t f32_bytes = (size_t)w * h * 8;
+        if (bidir && (rc = reserve(f32_bytes + (J.flow_half ? J.flow_bytes() : 0), kBwdFlows)) != kOk) return rc;
         if ((rc = build_pyramid(J.frames, kPyrA, g, J.stream)) != kOk) return rc;
         for (uint32_t k = 0; k < n_pairs; ++k) {
             const StreamJob P = J.pairs(k, 1);
@@ -700,7 +719,16 @@ int HipFlowEstimator::stream_impl(const StreamJob &J, const FlowParams &p)
                 NUS_HIP(launch_flow_to_half(static_cast<const float *>(fl), hf, (size_t)w * h, J.stream));
                 fl = hf;
             }
-            if (J.mid) NUS_HIP(launch_warp_behind(P, fl));
+            const void *bwd = nullptr;
+            if (bidir) { // the same pyramids the other way round (the forward flow is out of the ping-pong by now)
+                if ((rc = solve(pyr_b, pyr_a, g, p, u8(kBwdFlows), J.stream)) != kOk) return rc;
+                bwd = u8(kBwdFlows);
+                if (J.flow_half) {
+                    NUS_HIP(launch_flow_to_half(f32(kBwdFlows), u8(kBwdFlows) + f32_bytes, (size_t)w * h, J.stream));
+                    bwd = u8(kBwdFlows) + f32_bytes;
+                }
+            }
+            if (J.mid) NUS_HIP(launch_warp_behind(P, fl, bwd));
         }
         return kOk;
     }
@@ -716,12 +744,15 @@ int HipFlowEstimator::stream_impl(const StreamJob &J, const FlowParams &p)
         const uint32_t c = (uint32_t)(workspace / ((size_t)w * h * bytes_per_pixel));
         return c < 1 ? 1u : (c > max_pairs ? max_pairs : c);
     };
-    uint32_t chunk = chunk_for(31);
+    // set_bidirectional: two more flow buffers, 16 B -- the forward flows kept from the backward solve and the backward flows -- and
+    // the backward solve's own coefficients, 12 B
+    const size_t bidir_bytes = J.bidir && J.mid ? 28 : 0;
+    uint32_t chunk = chunk_for(31 + bidir_bytes);
     if (chunk > n_pairs) chunk = n_pairs;
     for (uint32_t l = 0; l < g.levels; ++l) // (a warped level -- every one but the coarsest -- always takes coefficient planes)
         if ((warped(p) && l + 1 < g.levels) ||
             !hs_iterate_streams(g.w[l], g.h[l], chunk, fast_ && jacobi_ == kJacobiStream ? kJacobiStreamFast : jacobi_)) {
-            chunk = chunk_for(43);
+            chunk = chunk_for(43 + bidir_bytes);
             break;
         }
     for (uint32_t c0 = 0; c0 < n_pairs; c0 += chunk)
@@ -782,10 +813,31 @@ int HipFlowEstimator::solve_batch(const StreamJob &J, const Pyramid &g, const Fl
         // the planes of each pair's two frames are consecutive planes of the level
         D.level[l].i1 = P.level_lum, D.level[l].i2 = P.level_lum + cells[l], D.level[l].stride = cells[l];
     }
-    D.coef = f32(kCoef), D.flow_a = f32(kFlowA), D.flow_b = f32(kFlowB), D.out = reinterpret_cast<float *>(J.flows);
+    const bool bidir = J.bidir && J.mid;
+    void *fwd_out = J.flows;
+    if (bidir) { // the forward flows must outlive the backward solve, which runs in the same ping-pong
+        if ((!fwd_out && (rc = reserve(cells[0] * pairs * (J.flow_half ? 4 : 8), kFwdFlows)) != kOk) ||
+            (rc = reserve(cells[0] * pairs * (J.flow_half ? 4 : 8), kBwdFlows)) != kOk || (rc = reserve(cells[0] * pairs * 12, kBwdCoef)) != kOk)
+            return rc;
+        if (!fwd_out) fwd_out = u8(kFwdFlows);
+    }
+    D.coef = f32(kCoef), D.flow_a = f32(kFlowA), D.flow_b = f32(kFlowB), D.out = static_cast<float *>(fwd_out);
     Solved done;
-    if ((rc = solve_levels(D, done)) != kOk) return rc;
-    return place_flow(J, done);
+    const void *flow = nullptr, *flow_bwd = nullptr;
+    if ((rc = solve_levels(D, done)) != kOk || (rc = place_flow(J, done, fwd_out, kFlowsHalf, flow)) != kOk) return rc;
+    if (bidir) {
+        // B -> A: the same schedule on the same planes, each pair's two swapped.  The streamed kernels that take their derivatives
+        // from the planes find the second frame's one plane BEHIND the first's, so this solve runs on coefficient planes, which
+        // name both -- the exact kernels, in FAST mode too (as a warped level: inside FAST's contract).
+        Schedule B = D;
+        B.stream_planes = false;
+        for (uint32_t l = 0; l < nl; ++l) std::swap(B.level[l].i1, B.level[l].i2), B.level[l].kernel = jacobi_;
+        B.coef = f32(kBwdCoef), B.out = f32(kBwdFlows);
+        Solved back;
+        if ((rc = solve_levels(B, back)) != kOk || (rc = place_flow(J, back, u8(kBwdFlows), kBwdFlows, flow_bwd)) != kOk) return rc;
+    }
+    if (J.mid) NUS_HIP(launch_warp_behind(J, flow, flow_bwd));
+    return kOk;
 }
 
 // One lock across stage, estimate and download: no other thread's call can reuse the staging slots in between.

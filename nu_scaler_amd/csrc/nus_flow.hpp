@@ -83,6 +83,13 @@ public:
     // interpolate_multi_device_stream), 0 (default) .. kFlowMaxProject.  The estimate and the flows handed out are untouched.
     int set_project(uint32_t rounds);
     int project_rounds() const { return (int)project_; }
+    // Both flows of every pair and the select warp behind them (WarpSelectLaunch; nus_flow_set_bidirectional): off by default.  On,
+    // interpolate_device_stream and interpolate_multi_device_stream also estimate every pair B -> A -- the same schedule on the same
+    // pyramids, the two luminance planes swapped -- and warp with launch_warp_blend_select.  The forward flows are the bytes they
+    // were (d_flows receives them alone); the backward ones stay in the workspace, in slots of their own which turning the setting
+    // off frees (so that off means the old workspace as well as the old kernels and bytes).  retime_device_stream refuses the setting.
+    int set_bidirectional(int enabled);
+    int bidirectional() const { return bidir_ ? 1 : 0; }
     // Bytes of device workspace the handle holds (the sum of its grow-only slots): what "reserves the workspace it did" is checked with.
     size_t workspace_bytes();
     // TEST HOOK (nus_flow_fill_workspace; refused unless the process has NUS_TEST_HOOKS=1, read per call): every byte of every slot,
@@ -134,8 +141,11 @@ private:
         kPairFlow = 9,                // one pair's f32 flow that no caller's buffer takes
         kFlowsHalf = 10,              // a chunk's flows as Rg16Float, likewise
         kScene = 11,                  // the scene detector's workspace and cut flags
+        kFwdFlows = 12,               // set_bidirectional: a chunk's forward flows that no caller's buffer takes (the backward solve reuses the ping-pong)
+        kBwdFlows = 13,               // ... its backward flows as the warp reads them (pair path: the f32 flow, then its halves)
+        kBwdCoef = 14,                // ... the backward solve's coefficients [pair][cells][3]
     };
-    static constexpr int kSlotCount = 12;
+    static constexpr int kSlotCount = 15;
     FlowParams with_warps(FlowParams p) const { return p.warps = warps_, p.median = median_, p; } // (mu_ held) what the entry points hand on: the handle's settings
     // the finer levels of such an estimate take `warps` rounds of launch_hs_warp_setup + Jacobi steps on coefficient planes
     static bool warped(const FlowParams &p) { return p.warps > 0 && p.refine_iters > 0; }
@@ -159,6 +169,7 @@ private:
         const RetimeJob *rt = nullptr;            // ... or the outputs of a rate conversion: mid is then the STREAM's output base
         uint32_t first_pair = 0;                  // of this job in the stream (the rate conversion's schedule is global)
         uint32_t project = 0;                     // the warp's projection rounds (set_project)
+        bool bidir = false;                       // with mid: the flows B -> A as well, and the select warp (set_bidirectional)
         hipStream_t stream = nullptr;
         size_t frame_bytes() const { return (size_t)w * h * 4; }
         size_t flow_bytes() const { return (size_t)w * h * (flow_half ? 4 : 8); }
@@ -217,7 +228,8 @@ private:
     int build_pyramid(const void *frame, Slot pyr, const Pyramid &g, hipStream_t stream);
     int solve(Slot pyr_a, Slot pyr_b, const Pyramid &g, const FlowParams &p, void *d_flow_out, hipStream_t stream);
     int solve_levels(const Schedule &D, Solved &done);   // the schedule itself, for solve and solve_batch
-    int place_flow(const StreamJob &J, const Solved &s); // behind it: the flow where and as J wants it, and the warp
+    // behind it: the flow where and as J wants it -- in `out` if there is one, else where it is or (halves) in `half_slot` -> placed
+    int place_flow(const StreamJob &J, const Solved &s, void *out, Slot half_slot, const void *&placed);
     int estimate_pair(const void *d_a, const void *d_b, uint32_t w, uint32_t h, const FlowParams &p, void *d_flow_out,
                       hipStream_t stream);
     // multi-step kernels, a chunk of consecutive pairs per launch (pairs on the grid's y / z axis): as many as fit the
@@ -230,7 +242,8 @@ private:
     int stream_impl(const StreamJob &J, const FlowParams &p);
     int solve_batch(const StreamJob &J, const Pyramid &g, const FlowParams &p); // J: one chunk
     static WarpLaunch warp_behind(const StreamJob &J, const void *flow); // the warp kernel behind the estimator, over J's pairs
-    static hipError_t launch_warp_behind(const StreamJob &J, const void *flow); // ... launched; J.rt: the retime warp and the real frames
+    // ... launched; J.rt: the retime warp and the real frames; J.bidir: the select warp with the flows B -> A at flow_bwd
+    static hipError_t launch_warp_behind(const StreamJob &J, const void *flow, const void *flow_bwd = nullptr);
     int ensure_device();
     static constexpr uint64_t kMaxPixels = (1ull << 28) - 1;
     int check_size(uint32_t w, uint32_t h) { return pass(check_dims("flow", w, h, kMaxPixels, "bad image dimensions")); }
@@ -247,6 +260,7 @@ private:
     uint32_t warps_ = 0; // set_warps
     uint32_t median_ = 0; // set_median
     uint32_t project_ = 0; // set_project
+    bool bidir_ = false; // set_bidirectional
     bool fast_ = false; // set_mode(1): the estimator's Jacobi steps in FAST arithmetic (k_hs_stream_fast), every level streamed
     hipStream_t stream_ = nullptr;
     hipStream_t call_stream_ = nullptr; // (mu_ held) the stream of the entry point in progress: reserve() waits for it before it frees

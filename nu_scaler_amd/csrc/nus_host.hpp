@@ -285,6 +285,14 @@ public:
                                  uint32_t n_pairs, hipStream_t stream);
     int interpolate_multi(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, const float *flow, uint32_t w, uint32_t h,
                           const float *times, uint32_t n_times, uint8_t *out, size_t out_cap);
+    // The select warp (WarpSelectLaunch; nus_interp_interpolate_select*): interpolate_multi_device / interpolate_multi with two flows
+    // per pair, A -> B and B -> A, each pixel warped with the candidate whose two samples agree better.  Both flows are required;
+    // checks, time-set rules and output layout are the multi-time entry points'.  The host form keeps both flows in d_flow_.
+    int interpolate_select_device(const void *d_a, size_t a_stride, const void *d_b, size_t b_stride, const void *d_flow_fwd,
+                                  const void *d_flow_bwd, uint32_t w, uint32_t h, const float *times, uint32_t n_times, void *d_out,
+                                  size_t out_pair_stride, uint32_t n_pairs, hipStream_t stream);
+    int interpolate_select(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, const float *flow_fwd, const float *flow_bwd,
+                           uint32_t w, uint32_t h, const float *times, uint32_t n_times, uint8_t *out, size_t out_cap);
     // Frame-rate conversion of a device-resident stream by num / den (nus_interp_retime_device; the schedule is nus_retime.hpp's):
     // n_frames frames frame_stride apart, pair k's flow at d_flows + k * flow bytes (null: zero flow), output j at d_out +
     // j * out_frame_stride (0: tightly packed).  An in-between output is byte for byte interpolate_device's at t_j under the
@@ -308,19 +316,21 @@ public:
     int wg_preset() const { return wg_preset_; }
 
 private:
-    int ensure(size_t frame_bytes, bool with_flow, uint32_t n_out = 1);
+    int ensure(size_t frame_bytes, uint32_t n_flows, uint32_t n_out = 1);
     void release();
     // (mu_ held, arguments checked) stage and upload the pair, run one launch of the frames at `t` or at times[0 .. n_times), bring
     // the n frames back into `out`
-    int host_pass(const uint8_t *a, const uint8_t *b, const float *flow, uint32_t w, uint32_t h, float t, const float *times,
-                  uint32_t n_times, uint8_t *out);
+    // (flow_bwd set: the select warp)
+    int host_pass(const uint8_t *a, const uint8_t *b, const float *flow, const float *flow_bwd, uint32_t w, uint32_t h, float t,
+                  const float *times, uint32_t n_times, uint8_t *out);
     // the host entry points: lock, the checks they share (times == nullptr: the single-time form), host_pass
-    int host_call(const char *who, const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, const float *flow, uint32_t w,
-                  uint32_t h, float t, const float *times, uint32_t n_times, bool multi, uint8_t *out, size_t out_cap);
+    // (select: the select warp, which requires flow and flow_bwd)
+    int host_call(const char *who, const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, const float *flow, const float *flow_bwd,
+                  bool select, uint32_t w, uint32_t h, float t, const float *times, uint32_t n_times, bool multi, uint8_t *out, size_t out_cap);
     // the device entry points: lock, the checks they share, one launch
-    int device_call(const char *who, const void *d_a, size_t a_stride, const void *d_b, size_t b_stride, const void *d_flow, uint32_t w,
-                    uint32_t h, float t, const float *times, uint32_t n_times, bool multi, void *d_out, size_t out_pair_stride,
-                    uint32_t n_pairs, hipStream_t stream);
+    int device_call(const char *who, const void *d_a, size_t a_stride, const void *d_b, size_t b_stride, const void *d_flow,
+                    const void *d_flow_bwd, bool select, uint32_t w, uint32_t h, float t, const float *times, uint32_t n_times, bool multi,
+                    void *d_out, size_t out_pair_stride, uint32_t n_pairs, hipStream_t stream);
 
     mutable std::mutex mu_;
     int wg_preset_;
@@ -331,7 +341,7 @@ private:
     int in_format_ = 0; // nus_pixel_format
     size_t cap_bytes_ = 0;
     uint32_t cap_out_ = 0; // frames d_out_ (and the staging's output part) holds
-    bool cap_flow_ = false;
+    uint32_t cap_flows_ = 0; // flows d_flow_ and h_flow_ hold (0, 1, or the select warp's 2)
     uint8_t *d_a_ = nullptr, *d_b_ = nullptr, *d_out_ = nullptr;
     bool flow_half_ = false; // interpolate_device reads 2 x f16 per pixel
     bool fma_ = false;       // dense-flow warp in FMA mode

@@ -57,10 +57,10 @@ void HipFrameInterpolator::release()
     h_flow_ = nullptr;
     cap_bytes_ = 0;
     cap_out_ = 0;
-    cap_flow_ = false;
+    cap_flows_ = 0;
 }
 
-int HipFrameInterpolator::ensure(size_t frame_bytes, bool with_flow, uint32_t n_out)
+int HipFrameInterpolator::ensure(size_t frame_bytes, uint32_t n_flows, uint32_t n_out)
 {
     if (!device_ready_) {
         const int rc = select_device(device_);
@@ -72,24 +72,24 @@ int HipFrameInterpolator::ensure(size_t frame_bytes, bool with_flow, uint32_t n_
         device_ready_ = true;
     }
     NUS_HIP(hipSetDevice(device_));
-    if (frame_bytes > cap_bytes_ || (with_flow && !cap_flow_) || n_out > cap_out_) {
+    if (frame_bytes > cap_bytes_ || n_flows > cap_flows_ || n_out > cap_out_) {
         // the reference reallocates its textures on every call (wgpu_interpolator.rs:253-321);
         // here buffers persist and only grow.
         const size_t want = frame_bytes > cap_bytes_ ? frame_bytes : cap_bytes_;
         const uint32_t outs = n_out > cap_out_ ? n_out : cap_out_;
-        const bool flow = with_flow || cap_flow_;
+        const uint32_t flows = n_flows > cap_flows_ ? n_flows : cap_flows_;
         release();
         NUS_HIP(hipMalloc(reinterpret_cast<void **>(&d_a_), want));
         NUS_HIP(hipMalloc(reinterpret_cast<void **>(&d_b_), want));
         NUS_HIP(hipMalloc(reinterpret_cast<void **>(&d_out_), want * outs));
         NUS_HIP(pinned_alloc(reinterpret_cast<void **>(&h_stage_), want * (2 + outs)));
-        if (flow) {
-            NUS_HIP(hipMalloc(reinterpret_cast<void **>(&d_flow_), want * 2));
-            NUS_HIP(pinned_alloc(reinterpret_cast<void **>(&h_flow_), want * 2));
+        if (flows) { // (the select warp's two flows back to back)
+            NUS_HIP(hipMalloc(reinterpret_cast<void **>(&d_flow_), want * 2 * flows));
+            NUS_HIP(pinned_alloc(reinterpret_cast<void **>(&h_flow_), want * 2 * flows));
         }
         cap_bytes_ = want;
         cap_out_ = outs;
-        cap_flow_ = flow;
+        cap_flows_ = flows;
     }
     return kOk;
 }
@@ -100,7 +100,7 @@ int HipFrameInterpolator::initialize(uint32_t width, uint32_t height)
     int rc = pass(check_dims("initialize", width, height, kMaxPixels));
     if (rc != kOk) return rc;
     if (init_w_ == width && init_h_ == height) return kOk; // interpolation/mod.rs:306-308
-    rc = ensure((size_t)width * height * 4, false);
+    rc = ensure((size_t)width * height * 4, 0);
     if (rc != kOk) return rc;
     init_w_ = width;
     init_h_ = height;
@@ -133,23 +133,32 @@ int HipFrameInterpolator::set_quality(InterpolationQuality q)
 int HipFrameInterpolator::interpolate(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, const float *flow,
                                       uint32_t w, uint32_t h, float t, uint8_t *out, size_t out_cap)
 {
-    return host_call("interpolate", a, a_len, b, b_len, flow, w, h, t, nullptr, 0, false, out, out_cap);
+    return host_call("interpolate", a, a_len, b, b_len, flow, nullptr, false, w, h, t, nullptr, 0, false, out, out_cap);
 }
 
 int HipFrameInterpolator::interpolate_multi(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, const float *flow,
                                             uint32_t w, uint32_t h, const float *times, uint32_t n_times, uint8_t *out, size_t out_cap)
 {
-    return host_call("nus_interp_interpolate_multi", a, a_len, b, b_len, flow, w, h, 0.0f, times, n_times, true, out, out_cap);
+    return host_call("nus_interp_interpolate_multi", a, a_len, b, b_len, flow, nullptr, false, w, h, 0.0f, times, n_times, true, out, out_cap);
+}
+
+int HipFrameInterpolator::interpolate_select(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, const float *flow_fwd,
+                                             const float *flow_bwd, uint32_t w, uint32_t h, const float *times, uint32_t n_times, uint8_t *out,
+                                             size_t out_cap)
+{
+    return host_call("nus_interp_interpolate_select", a, a_len, b, b_len, flow_fwd, flow_bwd, true, w, h, 0.0f, times, n_times, true, out,
+                     out_cap);
 }
 
 int HipFrameInterpolator::host_call(const char *who, const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, const float *flow,
-                                    uint32_t w, uint32_t h, float t, const float *times, uint32_t n_times, bool multi, uint8_t *out,
-                                    size_t out_cap)
+                                    const float *flow_bwd, bool select, uint32_t w, uint32_t h, float t, const float *times,
+                                    uint32_t n_times, bool multi, uint8_t *out, size_t out_cap)
 {
     std::lock_guard<std::mutex> lk(mu_);
     int st = pass(check_dims(who, w, h, kMaxPixels));
     if (st != kOk || (st = pass(check_frame_lengths(a_len, b_len, w, h))) != kOk) return st;
     if (!a || !b || !out) return fail(kInvalidArgument, fmt("%s: null frame pointer", who));
+    if (select && (!flow || !flow_bwd)) return fail(kInvalidArgument, fmt("%s: null flow pointer (the select warp takes both flows)", who));
     const size_t expected = (size_t)w * h * 4;
     if (!multi) {
         if (out_cap < expected) return fail(kInvalidArgument, fmt("%s: output capacity too small", who));
@@ -158,14 +167,14 @@ int HipFrameInterpolator::host_call(const char *who, const uint8_t *a, size_t a_
         if (out_cap / n_times < expected)
             return fail(kInvalidArgument, fmt("%s: output capacity %zu below n_times * w * h * 4 = %zu", who, out_cap, (size_t)n_times * expected));
     }
-    return host_pass(a, b, flow, w, h, t, times, n_times, out);
+    return host_pass(a, b, flow, select ? flow_bwd : nullptr, w, h, t, times, n_times, out);
 }
 
-int HipFrameInterpolator::host_pass(const uint8_t *a, const uint8_t *b, const float *flow, uint32_t w, uint32_t h, float t,
-                                    const float *times, uint32_t n_times, uint8_t *out)
+int HipFrameInterpolator::host_pass(const uint8_t *a, const uint8_t *b, const float *flow, const float *flow_bwd, uint32_t w, uint32_t h,
+                                    float t, const float *times, uint32_t n_times, uint8_t *out)
 {
     const size_t expected = (size_t)w * h * 4, total = expected * (n_times ? n_times : 1);
-    int rc = ensure(expected, flow != nullptr, n_times ? n_times : 1);
+    int rc = ensure(expected, flow_bwd ? 2 : (flow ? 1 : 0), n_times ? n_times : 1);
     if (rc != kOk) return rc;
     uint8_t *ha = h_stage_, *hb = h_stage_ + cap_bytes_, *ho = h_stage_ + 2 * cap_bytes_;
     // while the pair is staged, uploaded and on the GPU, idle workers of the copy pool make the pages of the result buffer
@@ -185,6 +194,13 @@ int HipFrameInterpolator::host_pass(const uint8_t *a, const uint8_t *b, const fl
         parallel_copy(h_flow_, flow, expected * 2);
         NUS_HIP(hipMemcpyAsync(d_flow_, h_flow_, expected * 2, hipMemcpyHostToDevice, stream_));
     }
+    float *d_bwd = nullptr;
+    if (flow_bwd) { // the second flow of the select warp, behind the first (cap_bytes_ * 2 bytes each)
+        float *const h_bwd = h_flow_ + cap_bytes_ / 2;
+        d_bwd = d_flow_ + cap_bytes_ / 2;
+        parallel_copy(h_bwd, flow_bwd, expected * 2);
+        NUS_HIP(hipMemcpyAsync(d_bwd, h_bwd, expected * 2, hipMemcpyHostToDevice, stream_));
+    }
     WarpLaunch L;
     L.a = d_a_;
     L.b = d_b_;
@@ -202,8 +218,8 @@ int HipFrameInterpolator::host_pass(const uint8_t *a, const uint8_t *b, const fl
     L.project = project_;
     L.in_sel = input_selector(in_format_);
     NUS_HIP(hipEventRecord(k_begin_, stream_));
-    hipError_t e = launch_warp_blend(L);
-    if (e != hipSuccess) return fail_hip(e, "warp+blend launch");
+    hipError_t e = flow_bwd ? launch_warp_blend_select(WarpSelectLaunch{L, d_bwd}) : launch_warp_blend(L);
+    if (e != hipSuccess) return fail_hip(e, flow_bwd ? "select warp+blend launch" : "warp+blend launch");
     NUS_HIP(hipEventRecord(k_end_, stream_));
     // the frames come back in two halves: the host copy of the first overlaps the DMA of the second
     const size_t half = (total / 2 + 4095) & ~(size_t)4095;
@@ -229,28 +245,40 @@ int HipFrameInterpolator::interpolate_device(const void *d_a, size_t a_stride, c
                                              const void *d_flow, uint32_t w, uint32_t h, float t, void *d_out,
                                              uint32_t n_pairs, hipStream_t stream)
 {
-    return device_call("interpolate_device", d_a, a_stride, d_b, b_stride, d_flow, w, h, t, nullptr, 0, false, d_out, 0, n_pairs, stream);
+    return device_call("interpolate_device", d_a, a_stride, d_b, b_stride, d_flow, nullptr, false, w, h, t, nullptr, 0, false, d_out, 0, n_pairs,
+                       stream);
 }
 
 int HipFrameInterpolator::interpolate_multi_device(const void *d_a, size_t a_stride, const void *d_b, size_t b_stride,
                                                    const void *d_flow, uint32_t w, uint32_t h, const float *times, uint32_t n_times,
                                                    void *d_out, size_t out_pair_stride, uint32_t n_pairs, hipStream_t stream)
 {
-    return device_call("nus_interp_interpolate_multi_device", d_a, a_stride, d_b, b_stride, d_flow, w, h, 0.5f, times, n_times, true, d_out,
-                       out_pair_stride, n_pairs, stream);
+    return device_call("nus_interp_interpolate_multi_device", d_a, a_stride, d_b, b_stride, d_flow, nullptr, false, w, h, 0.5f, times, n_times,
+                       true, d_out, out_pair_stride, n_pairs, stream);
+}
+
+int HipFrameInterpolator::interpolate_select_device(const void *d_a, size_t a_stride, const void *d_b, size_t b_stride, const void *d_flow_fwd,
+                                                    const void *d_flow_bwd, uint32_t w, uint32_t h, const float *times, uint32_t n_times,
+                                                    void *d_out, size_t out_pair_stride, uint32_t n_pairs, hipStream_t stream)
+{
+    return device_call("nus_interp_interpolate_select_device", d_a, a_stride, d_b, b_stride, d_flow_fwd, d_flow_bwd, true, w, h, 0.5f, times,
+                       n_times, true, d_out, out_pair_stride, n_pairs, stream);
 }
 
 int HipFrameInterpolator::device_call(const char *who, const void *d_a, size_t a_stride, const void *d_b, size_t b_stride,
-                                      const void *d_flow, uint32_t w, uint32_t h, float t, const float *times, uint32_t n_times, bool multi,
-                                      void *d_out, size_t out_pair_stride, uint32_t n_pairs, hipStream_t stream)
+                                      const void *d_flow, const void *d_flow_bwd, bool select, uint32_t w, uint32_t h, float t,
+                                      const float *times, uint32_t n_times, bool multi, void *d_out, size_t out_pair_stride,
+                                      uint32_t n_pairs, hipStream_t stream)
 {
     std::lock_guard<std::mutex> lk(mu_);
     int st = pass(check_dims(who, w, h, kMaxPixels));
     if (st != kOk) return st;
     if (!d_a || !d_b || !d_out) return fail(kInvalidArgument, fmt("%s: null device pointer", who));
+    if (select && (!d_flow || !d_flow_bwd)) return fail(kInvalidArgument, fmt("%s: null flow pointer (the select warp takes both flows)", who));
     if (multi && (st = pass(check_interp_times(who, times, n_times))) != kOk) return st;
     if (!multi && n_pairs == 0) return kOk; // (the single-time form has always answered this before it looks at the alignment)
     if ((st = pass(check_pixel_aligned(who, d_a, a_stride, d_b, b_stride, d_out, d_flow, flow_half_ ? 4 : 8))) != kOk) return st;
+    if (select && (st = pass(check_pixel_aligned(who, d_a, a_stride, d_b, b_stride, d_out, d_flow_bwd, flow_half_ ? 4 : 8))) != kOk) return st;
     if (multi && (st = pass(check_out_pair_stride(who, out_pair_stride, n_times, (size_t)w * h * 4))) != kOk) return st;
     if (n_pairs == 0) return kOk;
     if (device_count() <= 0) return fail(kNoDevice, "no HIP device available (the gfx950 path has no CPU fallback)");
@@ -274,8 +302,8 @@ int HipFrameInterpolator::device_call(const char *who, const void *d_a, size_t a
     L.stream = stream;
     L.in_sel = input_selector(in_format_);
     L.project = project_;
-    const hipError_t e = launch_warp_blend(L);
-    if (e != hipSuccess) return fail_hip(e, multi ? "multi-time warp+blend launch" : "warp+blend launch");
+    const hipError_t e = select ? launch_warp_blend_select(WarpSelectLaunch{L, static_cast<const float *>(d_flow_bwd)}) : launch_warp_blend(L);
+    if (e != hipSuccess) return fail_hip(e, select ? "select warp+blend launch" : multi ? "multi-time warp+blend launch" : "warp+blend launch");
     return kOk;
 }
 

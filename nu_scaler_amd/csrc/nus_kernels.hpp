@@ -183,6 +183,17 @@ hipError_t launch_warp_blend(const WarpLaunch &L);
 constexpr uint32_t kFlowMaxProject = 4; // NUS_FLOW_MAX_PROJECT
 hipError_t launch_warp_blend_project(const WarpLaunch &L);
 
+// The select warp (nus_k_warp_select.hip; BUILD-DEFINED): two flows per pair, warp.flow = F (A -> B, on A's grid) and flow_bwd = R
+// (B -> A, on B's grid), both in warp.flow_half's format, pair i's planes at i * w * h cells.  Per output pixel and time t the
+// candidates are gF = F projected warp.project (0 .. kFlowMaxProject) rounds at t and gR = -(R projected as many rounds at 1 - t);
+// each is sampled as launch_warp_blend samples; the pixel is the blend of the samples of the candidate whose two samples differ
+// less over the three colour bytes (a tie: the forward one).  Times, pair split and output layout are launch_warp_blend's.
+struct WarpSelectLaunch {
+    WarpLaunch warp;
+    const float *flow_bwd = nullptr;
+};
+hipError_t launch_warp_blend_select(const WarpSelectLaunch &L);
+
 // BGRA -> RGBA (in place allowed: in == out).
 hipError_t launch_swizzle_bgra(const uint8_t *in, uint8_t *out, size_t npx, hipStream_t stream);
 

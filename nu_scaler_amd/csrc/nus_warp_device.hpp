@@ -2,7 +2,8 @@
 // k_warp_blend_flow (dense flow, nus_k_interp.hip), k_bm_warp (block vectors, nus_k_bm_warp.hip) and k_warp_blend_flow_proj (flow
 // projected to the in-between time, nus_k_warp_project.hip).  One pixel's arithmetic (warp_blend_pixel) and the tile around it
 // (warp_blend_tile) are written once; a family supplies only where a pixel's vector comes from, so all three write the same bytes
-// for the same vectors.
+// for the same vectors.  The select warp (k_warp_blend_flow_sel, nus_k_warp_select.hip) samples with two candidate vectors per pixel
+// and blends the samples of one: it takes the pixel in its two halves, warp_sample_pair and warp_blend_pack.
 //   geometry nu_scaler_core/src/shaders/warp_blend.wgsl:25-43, rounding nu_scaler_core/src/interpolation/mod.rs:386-411, :467-510
 #pragma once
 
@@ -70,6 +71,35 @@ __device__ __forceinline__ float4 sample_trunc(const uint32_t *__restrict__ f, u
     return make_float4(r[0], r[1], r[2], r[3]);
 }
 
+// The pixel in its two halves, for the select warp (nus_k_warp_select.hip), which samples with two candidate vectors and blends the
+// samples of one: warp_sample_pair is the two truncated samples, warp_blend_pack their blend.
+template <int MODE>
+__device__ __forceinline__ void warp_sample_pair(__amdgpu_buffer_rsrc_t ra, __amdgpu_buffer_rsrc_t rb, uint32_t row_bytes, float wmax,
+                                                 float hmax, uint32_t xbmax, uint32_t ybmax, float xfl, float yfl, float2 f, float tv,
+                                                 float nt, float4 &sa, float4 &sb)
+{
+    float ax, ay, bx, by;
+    if (MODE == kWarpFma) {
+        ax = __builtin_fmaf(-tv, f.x, xfl), ay = __builtin_fmaf(-tv, f.y, yfl);
+        bx = __builtin_fmaf(nt, f.x, xfl), by = __builtin_fmaf(nt, f.y, yfl);
+    } else {
+        ax = xfl - tv * f.x, ay = yfl - tv * f.y;
+        bx = xfl + nt * f.x, by = yfl + nt * f.y;
+    }
+    sa = sample_corner<MODE>(ra, row_bytes, wmax, hmax, xbmax, ybmax, ax, ay);
+    sb = sample_corner<MODE>(rb, row_bytes, wmax, hmax, xbmax, ybmax, bx, by);
+}
+
+__device__ __forceinline__ uint32_t warp_blend_pack(const float4 &sa, const float4 &sb, float tv, float nt)
+{
+    uint32_t p = 0;
+    p = pack_trunc_u8(nt * sa.x + tv * sb.x, 0, p);
+    p = pack_trunc_u8(nt * sa.y + tv * sb.y, 1, p);
+    p = pack_trunc_u8(nt * sa.z + tv * sb.z, 2, p);
+    p = pack_trunc_u8(nt * sa.w + tv * sb.w, 3, p);
+    return p;
+}
+
 // One output pixel at (xfl, yfl) with flow f (delta A -> B): A sampled at p - t f, B at p + (1 - t) f, each sample truncated to u8 as
 // sample_frame returns it, then the blend of the two truncated samples with the CPU's three roundings in BOTH modes: with integer
 // operands and a t like 0.3 a tenth of the exact results are integers themselves (0.7 * 10 + 0.3 * 20 = 13), and there the truncation
@@ -80,36 +110,32 @@ __device__ __forceinline__ uint32_t warp_blend_pixel(__amdgpu_buffer_rsrc_t ra, 
                                                      float hmax, uint32_t xbmax, uint32_t ybmax, float xfl, float yfl, float2 f, float tv,
                                                      float nt)
 {
-    float ax, ay, bx, by;
-    if (MODE == kWarpFma) {
-        ax = __builtin_fmaf(-tv, f.x, xfl), ay = __builtin_fmaf(-tv, f.y, yfl);
-        bx = __builtin_fmaf(nt, f.x, xfl), by = __builtin_fmaf(nt, f.y, yfl);
-    } else {
-        ax = xfl - tv * f.x, ay = yfl - tv * f.y;
-        bx = xfl + nt * f.x, by = yfl + nt * f.y;
-    }
-    const float4 sa = sample_corner<MODE>(ra, row_bytes, wmax, hmax, xbmax, ybmax, ax, ay);
-    const float4 sb = sample_corner<MODE>(rb, row_bytes, wmax, hmax, xbmax, ybmax, bx, by);
-    uint32_t p = 0;
-    p = pack_trunc_u8(nt * sa.x + tv * sb.x, 0, p);
-    p = pack_trunc_u8(nt * sa.y + tv * sb.y, 1, p);
-    p = pack_trunc_u8(nt * sa.z + tv * sb.z, 2, p);
-    p = pack_trunc_u8(nt * sa.w + tv * sb.w, 3, p);
-    return p;
+    float4 sa, sb;
+    warp_sample_pair<MODE>(ra, rb, row_bytes, wmax, hmax, xbmax, ybmax, xfl, yfl, f, tv, nt, sa, sb);
+    return warp_blend_pack(sa, sb, tv, nt);
 }
 
 // The same pixel for the one-pixel-per-thread kernels (sample_trunc's frames): EXACT arithmetic, the input's channel order.
+__device__ __forceinline__ void warp_sample_pair_plain(const uint32_t *__restrict__ fa, const uint32_t *__restrict__ fb, uint32_t w, uint32_t h,
+                                                       uint32_t x, uint32_t y, float2 f, float t, float nt, float4 &sa, float4 &sb)
+{
+    sa = sample_trunc(fa, w, h, (float)x - t * f.x, (float)y - t * f.y);
+    sb = sample_trunc(fb, w, h, (float)x + nt * f.x, (float)y + nt * f.y);
+}
+
 __device__ __forceinline__ uint32_t warp_blend_pixel_plain(const uint32_t *__restrict__ fa, const uint32_t *__restrict__ fb, uint32_t w,
                                                            uint32_t h, uint32_t x, uint32_t y, float2 f, float t, float nt)
 {
-    const float4 sa = sample_trunc(fa, w, h, (float)x - t * f.x, (float)y - t * f.y);
-    const float4 sb = sample_trunc(fb, w, h, (float)x + nt * f.x, (float)y + nt * f.y);
-    uint32_t o = 0;
-    o = pack_trunc_u8(nt * sa.x + t * sb.x, 0, o);
-    o = pack_trunc_u8(nt * sa.y + t * sb.y, 1, o);
-    o = pack_trunc_u8(nt * sa.z + t * sb.z, 2, o);
-    o = pack_trunc_u8(nt * sa.w + t * sb.w, 3, o);
-    return o;
+    float4 sa, sb;
+    warp_sample_pair_plain(fa, fb, w, h, x, y, f, t, nt, sa, sb);
+    return warp_blend_pack(sa, sb, t, nt);
+}
+
+// What the select warp's pixel votes with: the summed absolute difference of the two samples' three colour counts as stored (alpha
+// does not vote) -- an integer 0 .. 765, exact in f32, the same for RGBA and BGRA input order.
+__device__ __forceinline__ float warp_sample_error(const float4 &sa, const float4 &sb)
+{
+    return (fabsf(sa.x - sb.x) + fabsf(sa.y - sb.y)) + fabsf(sa.z - sb.z);
 }
 
 // The tile of the three dense kernels, frames of at least 2 x 2 pixels below 4 GiB (warp_corner_ok).  blockDim = (64, 4); a thread

@@ -10,6 +10,8 @@ re-linearised N times about the flow it has -- frame B sampled through it -- whi
 With `median=3` or `5` (off by default; meant for `warps >= 1`) the level's flow is median-filtered after every Jacobi run, which
 keeps motion boundaries from turning into ramps.  With `project=N` (off by default) the warp behind the estimator evaluates the
 flow at the in-between time: every output pixel looks its vector up where its content came from before it is warped.
+With `bidirectional=True` (off by default) the stream interpolation estimates every pair both ways and each output pixel takes the
+forward or the backward vector, whichever makes its two samples agree better (the select warp).
 """
 from __future__ import annotations
 
@@ -49,7 +51,8 @@ def check_project(rounds) -> int:
 
 class FlowEstimator:
     def __init__(self, levels: int = 3, coarse_iterations: int = 50, refine_iterations: int = 10,
-                 lambda_: float = 0.02 ** 2, *, device: int = 0, warps: int = 0, median: int = 0, project: int = 0):
+                 lambda_: float = 0.02 ** 2, *, device: int = 0, warps: int = 0, median: int = 0, project: int = 0,
+                 bidirectional: bool = False):
         # lambda default: the value of the reference's own (ignored) test, wgpu_interpolator.rs:1535
         self._lib = C.lib()
         self._h = self._lib.nus_flow_create()
@@ -64,6 +67,8 @@ class FlowEstimator:
             self.set_median(median)
         if project != 0:
             self.set_project(project)
+        if bidirectional:
+            self.set_bidirectional(True)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -116,6 +121,20 @@ class FlowEstimator:
     @property
     def project(self) -> int:
         return int(self._lib.nus_flow_project_rounds(self._h))
+
+    def set_bidirectional(self, enabled: bool) -> None:
+        """Both flows of every pair and the select warp behind the estimator (nus_flow_set_bidirectional; off by default):
+        `interpolate_device_stream` and `interpolate_multi_device_stream` also estimate every pair B -> A on the same pyramids, and
+        each output pixel is warped with the forward vector or the negated backward one, whichever makes its sample of A and its
+        sample of B agree better.  The flows handed out are the forward ones, unchanged; the estimate entry points are not
+        affected; `retime_device_stream` refuses the setting (ValueError)."""
+        if not isinstance(enabled, (bool, np.bool_)) and enabled not in (0, 1):
+            raise ValueError(f"bidirectional must be a bool, got {enabled!r}")
+        self._check(self._lib.nus_flow_set_bidirectional(self._h, 1 if enabled else 0))
+
+    @property
+    def bidirectional(self) -> bool:
+        return self._lib.nus_flow_bidirectional(self._h) == 1
 
     @property
     def workspace_bytes(self) -> int:
@@ -308,7 +327,9 @@ class FlowEstimator:
         fmt = {"f32": 0, "f16": 1}.get(flow_format)
         if fmt is None:
             raise ValueError("flow_format must be 'f32' or 'f16'")
-        self._check(self._lib.nus_flow_retime_device_stream(self._h, d_frames or None, int(n_frames), int(width), int(height), self.levels,
-                                                            self.coarse_iterations, self.refine_iterations, self.lambda_, int(num),
-                                                            int(den), fmt, d_flows or None, d_out or None, int(out_frame_stride),
-                                                            stream or None))
+        st = self._lib.nus_flow_retime_device_stream(self._h, d_frames or None, int(n_frames), int(width), int(height), self.levels,
+                                                     self.coarse_iterations, self.refine_iterations, self.lambda_, int(num), int(den), fmt,
+                                                     d_flows or None, d_out or None, int(out_frame_stride), stream or None)
+        if st == C.ERR_INVALID_ARGUMENT and self.bidirectional:  # refused before any GPU work: the C text
+            raise ValueError(self._lib.nus_flow_last_error(self._h).decode("utf-8", "replace"))
+        self._check(st)

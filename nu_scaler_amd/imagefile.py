@@ -196,13 +196,21 @@ def _check_flow_project(flow_project, estimate_flow: bool) -> int:
     return flow_project
 
 
+def _check_flow_bidirectional(flow_bidirectional, estimate_flow: bool) -> None:
+    if flow_bidirectional and not estimate_flow:
+        raise ValueError("flow_bidirectional needs estimate_flow (--flow-bidirectional needs --flow)")
+
+
 def interpolate_image_files(path_a: str, path_b: str, output_path: str, time_t: float = 0.5, estimate_flow: bool = False,
-                            device: int = 0, flow_warps: int = 0, flow_median: int = 0, flow_project: int = 0) -> tuple[int, int]:
+                            device: int = 0, flow_warps: int = 0, flow_median: int = 0, flow_project: int = 0,
+                            flow_bidirectional: bool = False) -> tuple[int, int]:
     """The in-between frame of two equally sized images (wgpu_interpolator.rs:215-491); with
     `estimate_flow` the Horn-Schunck front end supplies the motion field (`flow_warps`: its re-linearisation rounds per finer
     level, FlowEstimator.set_warps; `flow_median`: its median filter behind every Jacobi run, 0, 3 or 5, FlowEstimator.set_median;
-    `flow_project`: projection rounds of the warp with that field, WgpuFrameInterpolator.set_flow_project), otherwise zero flow as
-    the reference's live path."""
+    `flow_project`: projection rounds of the warp with that field, WgpuFrameInterpolator.set_flow_project; `flow_bidirectional`:
+    the flow is estimated both ways and each pixel takes the vector whose two samples agree better,
+    WgpuFrameInterpolator.interpolate_select_py), otherwise zero flow as the reference's live path."""
+    _check_flow_bidirectional(flow_bidirectional, estimate_flow)
     flow_warps = _check_flow_warps(flow_warps, estimate_flow)
     flow_median = _check_flow_median(flow_median, estimate_flow)
     flow_project = _check_flow_project(flow_project, estimate_flow)
@@ -216,8 +224,12 @@ def interpolate_image_files(path_a: str, path_b: str, output_path: str, time_t: 
     flow = None
     if estimate_flow:
         from .flow import FlowEstimator
-        flow = FlowEstimator(device=device, warps=flow_warps, median=flow_median).estimate(a, b, w, h)
-    out = it.interpolate_py(a, b, w, h, time_t=time_t, flow=flow) if flow is not None else it.interpolate_py(a, b, w, h, time_t=time_t)
+        fe = FlowEstimator(device=device, warps=flow_warps, median=flow_median)
+        flow = fe.estimate(a, b, w, h)
+    if flow is not None and flow_bidirectional:
+        out = it.interpolate_select_py(a, b, w, h, flow, fe.estimate(b, a, w, h), time_t=time_t)
+    else:
+        out = it.interpolate_py(a, b, w, h, time_t=time_t, flow=flow) if flow is not None else it.interpolate_py(a, b, w, h, time_t=time_t)
     write_png(output_path, w, h, out)
     return w, h
 
@@ -230,12 +242,14 @@ def multi_output_paths(output_path: str, multiplier: int) -> list[str]:
 
 def interpolate_image_files_multi(path_a: str, path_b: str, output_path: str, multiplier: int, estimate_flow: bool = False,
                                   device: int = 0, scene_detect: bool = False, flow_warps: int = 0, flow_median: int = 0,
-                                  flow_project: int = 0) -> list[str]:
+                                  flow_project: int = 0, flow_bidirectional: bool = False) -> list[str]:
     """The M - 1 in-between frames of a frame-rate multiplier M (t = k / M) from one multi-time call, written to
     multi_output_paths(output_path, M); with `estimate_flow` the flow is estimated once for all of them.  `scene_detect`: a
-    pair the scene-cut detector flags gives repeats of the nearer frame instead of blends."""
+    pair the scene-cut detector flags gives repeats of the nearer frame instead of blends.  `flow_bidirectional`: both flows and
+    the select warp, as interpolate_image_files."""
     from .interpolator import frame_times
 
+    _check_flow_bidirectional(flow_bidirectional, estimate_flow)
     flow_warps = _check_flow_warps(flow_warps, estimate_flow)
     flow_median = _check_flow_median(flow_median, estimate_flow)
     flow_project = _check_flow_project(flow_project, estimate_flow)
@@ -250,8 +264,17 @@ def interpolate_image_files_multi(path_a: str, path_b: str, output_path: str, mu
     flow = None
     if estimate_flow:
         from .flow import FlowEstimator
-        flow = FlowEstimator(device=device, warps=flow_warps, median=flow_median).estimate(a, b, w, h)
-    frames = it.interpolate_multi_py(a, b, w, h, times=times, flow=flow, scene_detect=scene_detect)
+        fe = FlowEstimator(device=device, warps=flow_warps, median=flow_median)
+        flow = fe.estimate(a, b, w, h)
+    cut = False
+    if flow is not None and flow_bidirectional and scene_detect:
+        from .scene import SceneDetector
+
+        cut = SceneDetector(device=device).detect(a, b, w, h)[0]
+    if flow is not None and flow_bidirectional and not cut:
+        frames = it.interpolate_select_multi_py(a, b, w, h, flow, fe.estimate(b, a, w, h), times=times)
+    else:
+        frames = it.interpolate_multi_py(a, b, w, h, times=times, flow=flow, scene_detect=scene_detect)
     paths = multi_output_paths(output_path, multiplier)
     for path, out in zip(paths, frames):
         write_png(path, w, h, out)

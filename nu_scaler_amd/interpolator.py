@@ -136,6 +136,54 @@ class WgpuFrameInterpolator:
                                                                   height, ts, len(times), d_out, out_pair_stride, n_pairs,
                                                                   stream or None))
 
+    def _flow_buffer(self, flow, name: str, expected: int):
+        if flow is None:
+            raise ValueError(f"{name} is required: the select warp takes both flows")
+        addr, length, keep = _as_buffer(flow)
+        if length != expected * 2:
+            raise ValueError(f"Expected {expected * 2} bytes of {name} for 2 f32 per pixel, got {length}")
+        return addr, keep
+
+    def interpolate_select_multi_py(self, frame_a_bytes, frame_b_bytes, width: int, height: int, flow_fwd, flow_bwd, *,
+                                    times: Optional[Sequence[float]] = None, multiplier: Optional[int] = None) -> list[bytes]:
+        """The select warp (nus_interp_interpolate_select): `flow_fwd` is the flow A -> B on A's grid, `flow_bwd` the flow B -> A
+        on B's grid, both (h, w, 2) float32.  Each output pixel is warped with the forward vector or with the negated backward
+        one -- both evaluated at the in-between time with the handle's projection rounds -- whichever makes its sample of A and
+        its sample of B agree better over the three colour bytes; a tie goes forward.  The frames at `times`, or at
+        frame_times(multiplier).  Argument errors raise ValueError before any GPU work."""
+        ts = _time_array(times, multiplier)
+        n = len(ts)
+        a_addr, a_len, ka = _as_buffer(frame_a_bytes)
+        b_addr, b_len, kb = _as_buffer(frame_b_bytes)
+        expected = int(width) * int(height) * 4
+        f_addr, kf = self._flow_buffer(flow_fwd, "flow_fwd", expected)
+        r_addr, kr = self._flow_buffer(flow_bwd, "flow_bwd", expected)
+        out, oarr, oaddr = _out_buffer(expected * n)
+        st = self._lib.nus_interp_interpolate_select(self._h, a_addr, a_len, b_addr, b_len, f_addr, r_addr, width, height, ts, n,
+                                                     oaddr, expected * n)
+        del oarr, ka, kb, kf, kr
+        self._raise(st)
+        mv = memoryview(out)
+        return [bytes(mv[k * expected:(k + 1) * expected]) for k in range(n)]
+
+    def interpolate_select_py(self, frame_a_bytes, frame_b_bytes, width: int, height: int, flow_fwd, flow_bwd, *,
+                              time_t: float = 0.5) -> bytes:
+        """One frame of the select warp at `time_t` in [0, 1]: see interpolate_select_multi_py."""
+        return self.interpolate_select_multi_py(frame_a_bytes, frame_b_bytes, width, height, flow_fwd, flow_bwd, times=[time_t])[0]
+
+    def interpolate_select_device(self, d_a: int, a_stride: int, d_b: int, b_stride: int, d_flow_fwd: int, d_flow_bwd: int,
+                                  width: int, height: int, times: Sequence[float], d_out: int, out_pair_stride: int = 0,
+                                  n_pairs: int = 1, stream: int = 0) -> None:
+        """nus_interp_interpolate_select_device: as interpolate_multi_device with both flows of every pair, in the handle's
+        flow format.  Argument errors raise ValueError before any GPU work."""
+        ts = (ctypes.c_float * len(times))(*[float(t) for t in times])
+        st = self._lib.nus_interp_interpolate_select_device(self._h, d_a, a_stride, d_b, b_stride, d_flow_fwd or None,
+                                                            d_flow_bwd or None, width, height, ts, len(times), d_out,
+                                                            out_pair_stride, n_pairs, stream or None)
+        if st == C.ERR_INVALID_ARGUMENT:
+            raise ValueError(self._err())
+        self._raise(st)
+
     def retime_device(self, d_frames: int, frame_stride: int, n_frames: int, d_flows: int, width: int, height: int, num: int,
                       den: int, d_out: int, out_frame_stride: int = 0, stream: int = 0) -> None:
         """nus_interp_retime_device: the device-resident stream of `n_frames` frames converted by num / den (retime.py has the

@@ -12,7 +12,13 @@ nus_flow_interpolate_device_stream (EXACT and FAST estimator, t = 0.5) and of nu
 EXACT and FMA warp, on the flows of one estimate), the legs alternating the same way, rounds 0 the baseline of the ratios.
 --project-rounds 0 times the baseline alone and touches none of the new settings, so the same file also runs on a build from
 before the setting existed.
-usage: python tools/flow_warps_bench.py [--median | --project [--project-rounds 0,1,2,3]] [--reps R] [--rounds N] [--frames F] [--quick]"""
+--bidirectional: the select warp and the estimator's bidirectional setting instead (nus_interp_interpolate_select_device,
+nus_flow_set_bidirectional): per projection round count of --project-rounds (default here 0,3) and K = 1 and K = 3 times per pair,
+the plain warp (nus_interp_interpolate_multi_device: k_warp_blend_flow, or k_warp_blend_flow_proj with rounds) against the select
+warp on the same forward flows plus the backward ones, EXACT and FMA; then nus_flow_interpolate_device_stream with the setting off
+against on, EXACT and FAST estimator, at the last round count.  Off and on alternate in one process; off is the baseline.
+usage: python tools/flow_warps_bench.py [--median | --project [--project-rounds 0,1,2,3] | --bidirectional [--project-rounds 0,3]]
+                                        [--reps R] [--rounds N] [--frames F] [--quick]"""
 import argparse
 import json
 import os
@@ -104,6 +110,58 @@ def project_legs(args, frames, flows, w, h, n_frames, s):
         torch.cuda.synchronize()
 
 
+def bidirectional_legs(args, frames, flows, w, h, n_frames, s):
+    n = n_frames - 1
+    fb = w * h * 4
+    rounds = [int(r) for r in args.project_rounds.split(",")]
+    mid = torch.empty((n, len(PROJECT_TIMES), h, w, 4), dtype=torch.uint8, device=frames.device)
+    bwd = torch.empty_like(flows)
+    fe = nsc.FlowEstimator(levels=3, coarse_iterations=50, refine_iterations=10)
+    fe.estimate_device_stream(frames.data_ptr(), n_frames, w, h, flows.data_ptr(), s)
+    for k in range(n):  # the flows B -> A of the same pairs
+        fe.estimate_device(frames[k + 1].data_ptr(), frames[k].data_ptr(), w, h, bwd[k].data_ptr(), s)
+    torch.cuda.synchronize()
+    del fe
+
+    def report(case, extra, brackets):
+        us = [[x * 1e3 / n for x in g] for g in brackets]
+        med = [g[len(g) // 2] for g in us]
+        for on, g, m in zip((0, 1), us, med):
+            print(json.dumps(dict({"case": f"{w}x{h}x{n}_{case}_bidirectional{on}", "width": w, "height": h, "pairs": n, "bidirectional": on},
+                                  **extra, **{"working_set_bytes": frames.numel(), "brackets": len(g), "calls_per_bracket": args.reps,
+                                              "us_per_pair": round(m, 2), "us_per_pair_min": round(g[0], 2),
+                                              "us_per_pair_max": round(g[-1], 2), "over_off": round(m / med[0], 3)})), flush=True)
+
+    for mode in ("exact", "fma"):  # the warp alone
+        for r in rounds:
+            for times in (PROJECT_TIMES[1:2], PROJECT_TIMES):
+                it = nsc.WgpuFrameInterpolator()
+                it.set_mode(mode)
+                it.set_flow_project(r)
+                legs = [lambda: it.interpolate_multi_device(frames.data_ptr(), fb, frames.data_ptr() + fb, fb, flows.data_ptr(), w, h, times,
+                                                            mid.data_ptr(), 0, n, s),
+                        lambda: it.interpolate_select_device(frames.data_ptr(), fb, frames.data_ptr() + fb, fb, flows.data_ptr(),
+                                                             bwd.data_ptr(), w, h, times, mid.data_ptr(), 0, n, s)]
+                report(f"warp_{mode}_project{r}_times{len(times)}", {"entry": "nus_interp_interpolate_multi_device / _select_device",
+                                                                      "mode": mode, "project": r, "times": len(times)},
+                       timed_alternating(legs, args.reps, args.warm_seconds, args.rounds))
+                torch.cuda.synchronize()
+    for mode in ("exact", "fast"):  # estimator + warp through one entry point
+        handles = []
+        for on in (False, True):
+            fe = nsc.FlowEstimator(levels=3, coarse_iterations=50, refine_iterations=10, project=rounds[-1], bidirectional=on)
+            fe.set_mode(mode)
+            handles.append(fe)
+        legs = [lambda fe=fe: fe.interpolate_device_stream(frames.data_ptr(), n_frames, w, h, 0.5, mid.data_ptr(), flows.data_ptr(), s)
+                for fe in handles]
+        report(f"interpolate_device_stream_{mode}_project{rounds[-1]}", {"entry": "nus_flow_interpolate_device_stream", "mode": mode,
+                                                                          "project": rounds[-1], "levels": 3, "coarse_iterations": 50,
+                                                                          "refine_iterations": 10},
+               timed_alternating(legs, args.reps, args.warm_seconds, args.rounds))
+        del handles, legs
+        torch.cuda.synchronize()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5, help="calls per timed bracket")
@@ -113,10 +171,15 @@ def main():
     ap.add_argument("--quick", action="store_true", help="one warm-up call and one bracket of 2 calls per leg")
     ap.add_argument("--median", action="store_true", help="time median 0 / 3 / 5 at warps 1 and 2 instead of warps 0 / 1 / 2")
     ap.add_argument("--project", action="store_true", help="time the warp's projection rounds instead (see the module text)")
-    ap.add_argument("--project-rounds", default="0,1,2,3", help="with --project: the legs (comma-separated round counts, 0 first)")
+    ap.add_argument("--project-rounds", default=None, help="with --project: the legs (comma-separated round counts, 0 first; default "
+                                                           "0,1,2,3); with --bidirectional: the round counts timed (default 0,3)")
+    ap.add_argument("--bidirectional", action="store_true", help="time the select warp and the bidirectional estimator against the "
+                                                                 "forward-only route instead (see the module text)")
     args = ap.parse_args()
-    if args.median and args.project:
-        ap.error("--median and --project exclude each other")
+    if args.median + args.project + args.bidirectional > 1:
+        ap.error("--median, --project and --bidirectional exclude each other")
+    if args.project_rounds is None:
+        args.project_rounds = "0,3" if args.bidirectional else "0,1,2,3"
     if nsc.device_count() < 1:
         raise SystemExit("flow_warps_bench: no HIP device")
     if args.quick:
@@ -131,6 +194,8 @@ def main():
     flows = torch.empty((n, h, w, 2), dtype=torch.float32, device=dev)
     if args.project:
         return project_legs(args, frames, flows, w, h, n_frames, s)
+    if args.bidirectional:
+        return bidirectional_legs(args, frames, flows, w, h, n_frames, s)
     for mode, warps in [(m, wn) for m in ("exact", "fast") for wn in MEDIAN_WARPS] if args.median else []:
         handles = []
         for median in MEDIANS:
