@@ -633,7 +633,11 @@ int nus_flow_project_rounds(const nus_flow *h);
  * kernel in FMA mode with the handle's projection rounds: the frames equal nus_interp_interpolate_select_device in FMA mode fed
  * with the forward and the backward estimate of each pair.  Both estimator families support it, the batch path and the pair-by-pair
  * shader-shaped path.  In the batch path the backward solve's Jacobi steps run the exact kernels on coefficient planes, in
- * NUS_FLOW_FAST too (inside FAST's contract, as a re-linearised level's).  d_flows, when given, receives the forward flows only, the
+ * NUS_FLOW_FAST too (inside FAST's contract, as a re-linearised level's).  So in NUS_FLOW_FAST, where the forward solve runs the
+ * streamed FAST kernels, the backward flow is NOT the bytes nus_flow_estimate_device returns for (B, A) in that mode, and the frames
+ * have no byte reference: each flow is within FAST's bound of the exact estimate of its direction, and every pixel is the select
+ * warp's for flows within that bound.  In NUS_FLOW_EXACT the equality above holds byte for byte, the backward estimate being
+ * nus_flow_estimate_device of (B, A).  d_flows, when given, receives the forward flows only, the
  * bytes it receives with the setting off for every stream whose chunk size the setting's workspace (28 B per pixel and pair more)
  * does not change; the backward flows stay in the workspace.  The stream rule below holds.  nus_flow_estimate* is not affected, and
  * scene detection applies behind the warp as before.  nus_flow_retime_device_stream with the setting on returns

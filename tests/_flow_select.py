@@ -163,10 +163,37 @@ def select_loop(a, b, F, R, t, rounds):
 
 
 # ---- FMA mode: which pixels, as a whole, the warp contract admits for a given vector field ----------------------------------------------
-def contract_pixels(got, a, b, flow, t, position_ulps):
+def _banded_candidates(img, p_x, p_y, coef, flow, position_ulps, flow_band):
+    """_warp64._candidates for a flow known to `flow_band` px per component only: the position p + coef flow moves by up to
+    |coef| flow_band on each axis, and the bilinear sample, continuous and of slope at most 255 counts per pixel on each axis, by
+    255 times that.  An axis clamps to a border only where the position is beyond it by more than that reach."""
+    import _warp64 as C
+
+    if flow_band == 0.0:
+        return C._candidates(img, p_x, p_y, coef, flow, position_ulps)
+    h, w = img.shape[:2]
+    reach = abs(coef) * flow_band
+
+    def axis(p, f, n):
+        x, e = C._axis(p, coef, f, n, position_ulps)  # (e is 0 outside [0, n - 1])
+        raw = p + coef * f
+        return x, np.where((raw <= -reach) | (raw >= n - 1.0 + reach), e, e + reach)
+
+    x, ex = axis(p_x, flow[..., 0], w)
+    y, ey = axis(p_y, flow[..., 1], h)
+    s = C.warp_samples64(img, x, y)
+    eps = (255.0 * (ex + ey) + C.ARITH_BAND)[..., None]
+    exact = ((ex == 0.0) & (ey == 0.0) & (x * 256.0 == np.floor(x * 256.0)) & (y * 256.0 == np.floor(y * 256.0)))[..., None]
+    lo = np.floor(s)
+    return s, lo, ~exact & (s - lo <= eps) & (lo >= 1.0), ~exact & (lo + 1.0 - s <= eps) & (lo <= 254.0)
+
+
+def contract_pixels(got, a, b, flow, t, position_ulps, flow_band=0.0):
     """(h, w) bool: the pixels of uint8 `got` (h, w, 4) whose four bytes all meet the FMA warp contract of tests/_warp64.py with
     `flow` (h, w, 2) as the pair's flow at time t -- each byte is trunc(f32(nt sa) + f32(t sb)) for a pair of sample counts the
-    contract admits (floor(s), or a neighbouring integer where the float64 sample s is within its error band of it)."""
+    contract admits (floor(s), or a neighbouring integer where the float64 sample s is within its error band of it).
+    flow_band (px, absolute): the warp's flow is `flow` to within that much per component (an estimator mode's stated bound); the
+    error band of each sample widens by 255 counts per pixel of it and axis.  0: the contract as it is."""
     import _warp64 as C
 
     h, w = a.shape[:2]
@@ -175,8 +202,8 @@ def contract_pixels(got, a, b, flow, t, position_ulps):
     p_x = np.arange(w, dtype=np.float64)[None, :]
     p_y = np.arange(h, dtype=np.float64)[:, None]
     fl = np.asarray(flow).astype(np.float64)
-    _, lo_a, below_a, above_a = C._candidates(a, p_x, p_y, -float(t32), fl, position_ulps)
-    _, lo_b, below_b, above_b = C._candidates(b, p_x, p_y, float(nt32), fl, position_ulps)
+    _, lo_a, below_a, above_a = _banded_candidates(a, p_x, p_y, -float(t32), fl, position_ulps, float(flow_band))
+    _, lo_b, below_b, above_b = _banded_candidates(b, p_x, p_y, float(nt32), fl, position_ulps, float(flow_band))
     g = got.astype(_f)
     ok = g == C._blend32(lo_a, lo_b, t32, nt32)
     for d_a, m_a in ((0.0, None), (-1.0, below_a), (1.0, above_a)):

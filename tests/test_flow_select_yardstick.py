@@ -96,6 +96,38 @@ def test_bgra_order_gives_the_same_choice():
             assert rgba[1].any() and not rgba[1].all()  # both branches
 
 
+def test_contract_pixels_flow_band():
+    """contract_pixels' absolute flow band: 0 is the contract as it was (tests/_warp64.py::warp_contract's verdict, pixel by pixel);
+    a frame warped with a flow that differs from the stated one by less than the band passes everywhere, where the unwidened
+    contract refuses some of its pixels; a flow a pixel off still fails."""
+    from _warp64 import warp_contract
+
+    h, w = 9, 13
+    a, b = _frames(h, w, 21)
+    rng = np.random.default_rng(22)
+    band = 0.01
+    refused = 0
+    for name, F, _ in _flow_pairs(h, w, 9):
+        for t in (0.0, 0.3, 0.5, 1.0):
+            frame = oracle.warp_blend(a, b, F, t)
+            damaged = frame.copy()
+            damaged[::2, 1::3, 1] ^= 0x10  # one byte of some pixels, 16 counts off
+            for got in (frame, damaged):
+                old = warp_contract(got, a, b, F, np.float32(t), 1.0, name, raise_on_violation=False)["violations"]
+                for mask in (S.contract_pixels(got, a, b, F, t, 1.0), S.contract_pixels(got, a, b, F, t, 1.0, 0.0)):
+                    assert int((~mask).sum()) == old, (name, t)
+                    assert np.array_equal(~mask, got[..., 1] != frame[..., 1]), (name, t)
+            near = (F + rng.uniform(-0.9 * band, 0.9 * band, F.shape)).astype(np.float32)
+            shifted = oracle.warp_blend(a, b, near, t)
+            assert S.contract_pixels(shifted, a, b, F, t, 1.0, band).all(), (name, t)
+            refused += int((~S.contract_pixels(shifted, a, b, F, t, 1.0)).sum())
+            far = oracle.warp_blend(a, b, (F + np.float32(1.0)).astype(np.float32), t)
+            if name != "outside" and 0.0 < t < 1.0:  # (at an end time one frame alone is sampled, at p; far outside, the border texel)
+                assert not S.contract_pixels(far, a, b, F, t, 1.0, band).all(), (name, t)
+            assert not S.contract_pixels(damaged, a, b, F, t, 1.0, band).all(), (name, t)  # 16 counts off is no neighbouring count
+    assert refused > 0  # without the band the shifted frames do not pass: the parameter is what admits them
+
+
 @pytest.fixture(scope="module")
 def table():
     return [(row, S.table_row(row)) for row in W.ROWS]

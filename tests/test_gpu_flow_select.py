@@ -287,7 +287,7 @@ def test_estimator_frames_equal_estimates_both_ways_then_select_warp(nsc, monkey
 
 
 # ---- off means off -------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("mode,tiled", [("fast", 1), ("exact", 0)])
+@pytest.mark.parametrize("mode,tiled", [("fast", 1), ("exact", 0), ("exact", 1), ("exact", 2), ("exact", 3), ("fast", 3)])
 def test_off_after_on_equals_a_fresh_handle(nsc, mode, tiled):
     import torch
 

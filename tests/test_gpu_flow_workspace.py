@@ -14,7 +14,11 @@ nus_flow_fill_workspace, FlowEstimator._fill_workspace) between identical calls:
   the EXACT flows equal the float32 restatement of the estimator (tests/_flow_median.py::estimate_f32, which is
   oracle.flow_estimate at warps = median = 0 and _flow_warp64's estimator at median = 0); the primitives equal theirs.  FAST cases
   are held to byte equality as well: the same kernels on the same inputs.
-* history without poison, across the slot aliases: A, B, A on one handle (HISTORY).
+  nus_flow_set_bidirectional adds three slots of its own (the forward flows kept from the backward solve, the backward flows, the
+  backward solve's coefficients) and a flow that never leaves the workspace: cases with the setting on are held in the same way,
+  and their EXACT frames to the select warp of the CPU-restated forward and backward flows (select_frames, shared with
+  tests/test_gpu_flow_bidir.py).
+* history without poison, across the slot aliases: A, B, A on one handle (HISTORY), the setting on, off and on again among them.
 * the stream rule of the header: two calls of different shape and content back to back on ONE stream with no host
   synchronisation between them, primed, primed and poisoned, and with the second call growing the workspace.
 
@@ -50,16 +54,19 @@ CHUNK_ENV = "NUS_FLOW_MAX_CHUNK_PAIRS"
 
 S97, S64, S33, S160 = (97, 61), (64, 48), (33, 17), (160, 96)  # 97 x 61: odd sides on every level, 49 x 31, 25 x 16, 13 x 8
 PAIR, BATCH, PER_STEP = "pair", "batch", "per-step"
+BACKWARD = "+backward"
 ESTIMATORS = ("estimate", "estimate_device", "estimate_device_stream", "interpolate_device_stream", "interpolate_multi_device_stream")
 PRIMITIVES = ("rgba8_to_f32", "blur", "downsample", "horn_schunck", "horn_schunck+flow_in", "horn_schunck_coef", "horn_schunck_coef+flow_in",
               "warp_coefficients", "warp_coefficients+flow", "upsample", "median3", "median5", "project_flow")
 
-Case = collections.namedtuple("Case", "entry size steps tiled mode warps median project n ffmt flows chunk scene")
+Case = collections.namedtuple("Case", "entry size steps tiled mode warps median project n ffmt flows chunk scene bidir")
 
 
 def C(entry, size, steps=(3, 9, 6), tiled=1, mode="exact", warps=0, median=0, project=0, n=2, ffmt="f32", flows=True, chunk=None,
-      scene=False):
-    return Case(entry, size, steps, tiled, mode, warps, median, project, n, ffmt, flows, chunk, scene)
+      scene=False, bidir=False):
+    """bidir: nus_flow_set_bidirectional -- both flows of every pair and the select warp behind the interpolating entry points."""
+    assert not bidir or entry in ESTIMATORS[3:]  # (the estimate entry points are not affected by the setting)
+    return Case(entry, size, steps, tiled, mode, warps, median, project, n, ffmt, flows, chunk, scene, bidir)
 
 
 def case_id(c):
@@ -68,17 +75,19 @@ def case_id(c):
         s += f"-{c.n}fr"
     if c.entry in ESTIMATORS[3:]:
         s += f"-{c.ffmt}-{'flows' if c.flows else 'noflows'}"
-    return s + (f"-chunk{c.chunk}" if c.chunk else "") + ("-scene" if c.scene else "")
+    return s + (f"-chunk{c.chunk}" if c.chunk else "") + ("-scene" if c.scene else "") + ("-bidir" if c.bidir else "")
 
 
 def path_of(c):
     """Which road through nus_flow.cpp an estimator case takes: solve() for a pair, solve_batch() for a chunk (a FAST pair whose
-    streamed kernel is forced goes there as a two-frame stream), or one launch per Jacobi step (set_tiled(0), EXACT)."""
+    streamed kernel is forced goes there as a two-frame stream), or one launch per Jacobi step (set_tiled(0), EXACT).  With the
+    setting on the backward solve takes the same road a second time (BACKWARD behind the name): solve() with the pyramids
+    exchanged pair by pair, or solve_batch()'s second schedule on coefficient planes."""
     if c.tiled == 0 and c.mode == "exact":
-        return PER_STEP
+        return PER_STEP + BACKWARD * c.bidir
     if c.entry in ("estimate", "estimate_device") and not (c.mode == "fast" and c.tiled == 3):
         return PAIR
-    return BATCH
+    return BATCH + BACKWARD * c.bidir
 
 
 IDS, IMS = "interpolate_device_stream", "interpolate_multi_device_stream"
@@ -138,6 +147,22 @@ CASES = [
     C(IMS, S160, tiled=3, warps=2, median=5, n=4, ffmt="f16", flows=False),
     C(IMS, S160, tiled=1, mode="fast", n=4, ffmt="f32", flows=True),
     C(IMS, S160, tiled=3, mode="fast", warps=2, project=2, n=4, ffmt="f16", flows=False),
+    # ---- both flows of every pair and the select warp behind them (nus_flow_set_bidirectional): kFwdFlows, kBwdFlows, kBwdCoef
+    C(IDS, S160, tiled=0, n=4, ffmt="f32", flows=True, bidir=True),  # pair by pair: kBwdFlows holds one pair's f32 flow
+    C(IDS, S160, tiled=0, warps=2, median=3, project=2, n=4, ffmt="f16", flows=False, bidir=True),  # ... and its halves behind it
+    C(IDS, S160, tiled=1, warps=2, median=5, n=4, ffmt="f16", flows=True, bidir=True),
+    C(IDS, S160, tiled=2, project=2, n=4, ffmt="f32", flows=False, bidir=True),  # no d_flows: the forward flows wait in kFwdFlows
+    C(IDS, S160, tiled=3, median=3, n=4, ffmt="f16", flows=False, bidir=True),
+    C(IDS, S160, tiled=1, mode="fast", n=4, ffmt="f32", flows=False, bidir=True),
+    C(IDS, S160, tiled=3, mode="fast", warps=2, project=2, n=4, ffmt="f16", flows=True, bidir=True),  # forward: k_hs_stream_fast's halves
+    C(IDS, S160, tiled=3, warps=2, n=6, ffmt="f32", flows=True, bidir=True, chunk=2),  # chunks of 2, 2 and 1 pairs
+    C(IMS, S160, tiled=0, median=5, n=4, ffmt="f32", flows=False, bidir=True),
+    C(IMS, S160, tiled=1, project=2, n=4, ffmt="f32", flows=True, bidir=True),
+    C(IMS, S160, tiled=2, warps=2, median=3, n=4, ffmt="f16", flows=True, bidir=True),
+    C(IMS, S160, tiled=3, warps=2, median=5, project=2, n=4, ffmt="f32", flows=True, bidir=True),
+    C(IMS, S160, tiled=1, mode="fast", warps=2, median=3, n=4, ffmt="f16", flows=False, bidir=True),
+    C(IMS, S160, tiled=3, mode="fast", n=4, ffmt="f32", flows=True, bidir=True),
+    C(IMS, S160, tiled=1, warps=2, median=3, project=2, n=5, ffmt="f16", flows=False, scene=True, bidir=True),  # pair 2 is a cut
     # ---- the host primitives (steps[1]: Jacobi steps)
     C("rgba8_to_f32", S97),
     C("blur", S97),
@@ -169,7 +194,8 @@ def _stream():
 
 
 def _estimator(nsc, c):
-    fe = nsc.FlowEstimator(c.steps[0], c.steps[1], c.steps[2], LAM, warps=c.warps, median=c.median, project=c.project)
+    fe = nsc.FlowEstimator(c.steps[0], c.steps[1], c.steps[2], LAM, warps=c.warps, median=c.median, project=c.project, bidirectional=c.bidir)
+    assert fe.bidirectional is c.bidir
     fe.set_mode(c.mode)
     fe.set_tiled(c.tiled)
     if c.scene:
@@ -200,10 +226,12 @@ def _frames(size, n, scene=False):
 
 
 @functools.lru_cache(maxsize=None)
-def _restated(size, n, scene, steps, warps, median, k):
-    """The float32 restatement of the estimate of frames (k, k + 1)."""
+def _restated(size, n, scene, steps, warps, median, k, back=False):
+    """The float32 restatement of the estimate of frames (k, k + 1); back: of (k + 1, k), the flow B -> A on B's grid -- the same
+    schedule on the same per-frame pyramids with the two exchanged, which is what nus_flow_set_bidirectional states."""
     f = _frames(size, n, scene)
-    out = M.estimate_f32(oracle, f[k], f[k + 1], steps[0], steps[1], steps[2], LAM, warps=warps, median=median)
+    a, b = (f[k + 1], f[k]) if back else (f[k], f[k + 1])
+    out = M.estimate_f32(oracle, a, b, steps[0], steps[1], steps[2], LAM, warps=warps, median=median)
     assert out.dtype == np.float32 and out.shape == (size[1], size[0], 2)
     return _frozen(out)
 
@@ -315,10 +343,59 @@ def _assert_same_bytes(got, want, tag):
                                  f"{first}: got {g[first]!r}, want {x[first]!r}")
 
 
-def _assert_restated(c, out):
+def times_of(c):
+    return [T_ONE] if c.entry == IDS else list(TIMES)
+
+
+_SELECT_FRAMES = {}  # (what select_frames depends on) -> frames, read-only
+
+
+def select_frames(nsc, c):
+    """What an EXACT handle with the setting on owes for its in-between frames, (n - 1, times, h, w, 4): the CPU restatement of
+    each pair's forward and backward flow, rounded to f16 where the hand-off is Rg16Float, uploaded and run through
+    nus_interp_interpolate_select_device in FMA mode with the handle's projection rounds (the header's statement of the setting;
+    tests/test_gpu_flow_select_forms.py holds that entry point to its own restatement).  The backward flow never leaves the
+    workspace: this is what makes it answerable to the CPU.  (A cut pair's frames are the select warp's here: _assert_cut_pair.)"""
+    import torch
+
+    key = (c.size, c.n, c.scene, c.steps, c.warps, c.median, c.project, c.ffmt, tuple(times_of(c)))
+    if key not in _SELECT_FRAMES:
+        w, h = c.size
+        times = times_of(c)
+        fields = [np.stack([_restated(c.size, c.n, c.scene, c.steps, c.warps, c.median, k, back) for k in range(c.n - 1)]) for back in (False, True)]
+        if c.ffmt == "f16":
+            fields = [f.astype(np.float16) for f in fields]
+        d_frames, d_fwd, d_bwd = put(_frames(c.size, c.n, c.scene), "cuda:0"), put(fields[0]), put(fields[1])
+        warp = nsc.WgpuFrameInterpolator()
+        warp.set_mode("fma"), warp.set_flow_format(c.ffmt), warp.set_flow_project(c.project)
+        fb = w * h * 4
+        out = guarded.empty((c.n - 1, len(times), h, w, 4), dtype=torch.uint8, device="cuda:0")
+        warp.interpolate_select_device(d_frames.data_ptr(), fb, d_frames.data_ptr() + fb, fb, d_fwd.data_ptr(), d_bwd.data_ptr(), w, h, times,
+                                       out.data_ptr(), 0, c.n - 1, _stream())
+        _SELECT_FRAMES[key] = _frozen(fetch(out))
+    return _SELECT_FRAMES[key]
+
+
+def assert_select_frames(nsc, c, out):
+    """The frames of a call with the setting on against select_frames, byte for byte (a cut pair's are repeats: _assert_cut_pair)."""
+    want = select_frames(nsc, c)
+    got = out["mid"].reshape(want.shape)
+    pairs = [k for k in range(c.n - 1) if not (c.scene and k == 2)]
+    if not np.array_equal(got[pairs], want[pairs]):
+        diff = got[pairs] != want[pairs]
+        first = tuple(int(v) for v in np.argwhere(diff)[0])
+        raise AssertionError(f"{case_id(c)}: the frames are not the select warp's of the restated forward and backward flows: {int(diff.sum())} "
+                             f"of {diff.size} bytes differ in pairs {sorted({pairs[i] for i in np.argwhere(diff)[:, 0]})}, largest difference "
+                             f"{int(np.abs(got[pairs].astype(int) - want[pairs]).max())}, first at (pair, time, y, x, c) {first}")
+
+
+def _assert_restated(c, out, nsc=None):
     """EXACT: the flows are the float32 restatement's (values where a median ran: a selection may return either zero), the
-    Rg16Float flows its rounding to nearest even; a primitive's result is its restatement's."""
+    Rg16Float flows its rounding to nearest even; a primitive's result is its restatement's.  With the setting on also the frames:
+    assert_select_frames."""
     tag = case_id(c)
+    if c.bidir:
+        assert_select_frames(nsc, c, out)
     if c.entry in PRIMITIVES:
         want = _primitive_reference(c.entry, c.size, c.steps[1])
         got = out["out"]
@@ -356,6 +433,7 @@ def _assert_cut_pair(c, out):
     for j, t in enumerate(TIMES):
         assert np.array_equal(out["mid"][2, j], frames[2] if t < 0.5 else frames[3]), (case_id(c), j)
         assert not np.array_equal(out["mid"][1, j], frames[1]) and not np.array_equal(out["mid"][1, j], frames[2]), (case_id(c), j)
+    assert c.entry == IMS  # (scene detection is the multi-time entry point's)
 
 
 # ---- the lattice ------------------------------------------------------------------------------------------------------------------
@@ -392,7 +470,7 @@ def test_poisoned_workspace(nsc, monkeypatch, c):
         if name != "flows" or c.flows:
             assert np.isfinite(a.astype(np.float64)).all(), (tag, name)
     if c.mode == "exact":
-        _assert_restated(c, first)
+        _assert_restated(c, first, nsc)
     if c.scene:
         _assert_cut_pair(c, first)
     if d is not None:
@@ -403,9 +481,17 @@ def test_poisoned_workspace(nsc, monkeypatch, c):
         if c.entry.startswith("horn_schunck"):
             _SEEN.add((c.entry.split("+")[0], c.tiled))
         return
-    _SEEN.add((c.entry, c.tiled, c.mode))
-    path = path_of(c)
+    path = path_of(c)  # (with the setting on: a path of its own)
     _SEEN.update({("warps", c.warps, path), ("median", c.median, path), ("project", c.project, path)})
+    if c.bidir:  # entries of their own: a case with the setting on stands in for no case with it off
+        _SEEN.update({("bidir", c.entry, c.tiled, c.mode), ("bidir", c.ffmt, c.flows)})
+        if c.chunk:
+            assert c.n - 1 == 5 and c.chunk == 2  # chunks of 2, 2 and 1 pairs
+            _SEEN.add(("bidir", "chunked", c.entry))
+        if c.scene:
+            _SEEN.add(("bidir", "scene", c.entry))
+        return
+    _SEEN.add((c.entry, c.tiled, c.mode))
     if c.entry in ESTIMATORS[3:]:
         _SEEN.add((c.entry, c.ffmt, c.flows))
     if c.chunk:
@@ -434,6 +520,15 @@ HISTORY = {
     "fast-streamed-then-exact-per-step": (C("estimate_device_stream", S97, (3, 9, 6), 3, "fast", n=5), C("estimate_device_stream", S97, (3, 9, 6), 0, n=5)),
     # the halves beside the flows, then f32 flows in the caller's buffer
     "f16-noflows-then-f32-flows": (C(IDS, S160, tiled=1, n=4, ffmt="f16", flows=False), C(IDS, S160, tiled=1, n=4, ffmt="f32", flows=True)),
+    # the setting on, off, on: its three slots are released and reserved again
+    "bidir-on-off-on": (C(IMS, S160, tiled=1, warps=2, project=2, n=4, ffmt="f32", flows=False, bidir=True),
+                        C(IMS, S160, tiled=1, warps=2, project=2, n=4, ffmt="f32", flows=False)),
+    # kFwdFlows and kBwdFlows hold halves, then kBwdFlows f32 flows and the forward flows go to the caller
+    "bidir-f16-noflows-then-f32-flows": (C(IDS, S160, tiled=1, n=4, ffmt="f16", flows=False, bidir=True),
+                                         C(IDS, S160, tiled=1, n=4, ffmt="f32", flows=True, bidir=True)),
+    # kBwdFlows: the chunk's halves, then one pair's f32 flow with its halves behind it
+    "bidir-batch-then-pair-by-pair": (C(IMS, S160, tiled=1, median=3, n=4, ffmt="f16", flows=True, bidir=True),
+                                      C(IMS, S160, tiled=0, median=3, n=4, ffmt="f16", flows=True, bidir=True)),
 }
 
 
@@ -441,6 +536,7 @@ def _set(fe, c):
     """The settings of case c on a used handle."""
     fe.levels, fe.coarse_iterations, fe.refine_iterations = c.steps
     fe.set_warps(c.warps), fe.set_median(c.median), fe.set_project(c.project), fe.set_mode(c.mode), fe.set_tiled(c.tiled)
+    fe.set_bidirectional(c.bidir)
 
 
 @pytest.mark.parametrize("name", sorted(HISTORY), ids=str)
@@ -458,11 +554,14 @@ def test_history_across_the_slot_aliases(nsc, monkeypatch, name):
         torch.cuda.synchronize()  # the stream rule: a host entry point (and nothing else here) needs it
         got = _call(fe, c, dev[c])
         _assert_same_bytes(got, fresh[c], (name, f"stop {stop}", case_id(c)))
-        assert fe.workspace_bytes >= held > 0 or stop == 0, (name, stop, fe.workspace_bytes, held)  # grow-only
+        if stop and (a, b, a)[stop - 1].bidir and not c.bidir:  # turning the setting off is the one thing that gives memory back
+            assert 0 < fe.workspace_bytes < held, (name, stop, fe.workspace_bytes, held)
+        else:
+            assert fe.workspace_bytes >= held > 0 or stop == 0, (name, stop, fe.workspace_bytes, held)  # grow-only
         held = fe.workspace_bytes
     for c in (a, b):
         if c.mode == "exact":
-            _assert_restated(c, fresh[c])
+            _assert_restated(c, fresh[c], nsc)
 
 
 # ---- the stream rule ----------------------------------------------------------------------------------------------------------------
@@ -514,6 +613,36 @@ def test_calls_on_one_stream_need_no_synchronisation(nsc, monkeypatch, how):
     _assert_restated(small, {"flows": fresh[small]})
 
 
+def test_bidirectional_calls_on_one_stream_need_no_synchronisation(nsc, monkeypatch):
+    """The stream rule with the setting on: two calls of different shape on one non-default stream with nothing between them, the
+    second growing the workspace -- kFwdFlows, kBwdFlows and kBwdCoef among the slots it frees while the first may still run in them."""
+    import torch
+
+    monkeypatch.delenv(CHUNK_ENV, raising=False)
+    small = C(IMS, S64, tiled=1, warps=2, project=2, n=4, ffmt="f16", flows=False, bidir=True)
+    big = C(IMS, S97, tiled=1, warps=2, project=2, n=5, ffmt="f16", flows=False, bidir=True)
+    fresh = {c: _call(_estimator(nsc, c), c, put(_frames(c.size, c.n), "cuda:0"))["mid"] for c in (small, big)}
+    fe = _estimator(nsc, small)
+    stream = torch.cuda.Stream()
+    with torch.cuda.stream(stream):
+        s = stream.cuda_stream
+        assert s != 0 and s == _stream()
+        dev = {c: put(_frames(c.size, c.n), "cuda:0") for c in (small, big)}
+        _call(fe, small, dev[small])  # prime: the handle has seen the small call only
+        primed = fe.workspace_bytes
+        outs = []
+        for c in (small, big):  # back to back: no fetch, no synchronisation in between
+            out = guarded.empty((c.n - 1, len(TIMES), c.size[1], c.size[0], 4), dtype=torch.uint8, device="cuda:0")
+            fe.interpolate_multi_device_stream(dev[c].data_ptr(), c.n, c.size[0], c.size[1], list(TIMES), out.data_ptr(), 0, 0, s, flow_format=c.ffmt)
+            outs.append(out)
+        stream.synchronize()  # the one wait
+        got = [fetch(o) for o in outs]
+    assert fe.workspace_bytes > primed > 0
+    for c, g in zip((small, big), got):
+        _assert_same_bytes({"mid": g}, {"mid": fresh[c]}, ("bidirectional, second call grows", case_id(c)))
+        assert_select_frames(nsc, c, {"mid": fresh[c]})
+
+
 # ---- the census ---------------------------------------------------------------------------------------------------------------------
 def test_every_entry_was_held_with_a_poisoned_workspace():
     """Runs last: what the lattice above saw is what the handle can be asked for."""
@@ -526,6 +655,13 @@ def test_every_entry_was_held_with_a_poisoned_workspace():
     want |= {(name, path) for name in ("coarse_iters 0", "refine_iters 0", "two launches a level") for path in (PAIR, BATCH, PER_STEP)}
     want |= {("levels 1", PAIR), ("levels 1", BATCH), ("4 levels", PAIR), ("4 levels", BATCH)}
     want |= {("scene", IMS)}
+    # the setting on: every reachable entry x set_tiled x mode, both hand-offs with and without a flow buffer, chunks, a cut, and
+    # every setting on both roads of the backward solve
+    want |= {("bidir", e, tiled, "exact") for e in (IDS, IMS) for tiled in (0, 1, 2, 3)} | {("bidir", e, tiled, "fast") for e in (IDS, IMS) for tiled in (1, 3)}
+    want |= {("bidir", ffmt, flows) for ffmt in ("f32", "f16") for flows in (True, False)}
+    want |= {("bidir", "chunked", IDS), ("bidir", "scene", IMS)}
+    want |= {(setting, v, path + BACKWARD) for setting, values in (("warps", (0, 2)), ("median", (0, 3, 5)), ("project", (0, 2))) for v in values
+             for path in (BATCH, PER_STEP)}
     want |= {("horn_schunck", t) for t in (0, 1, 2, 3)} | {("horn_schunck_coef", t) for t in (1, 2, 3)}
     want |= {("size", s) for s in (S97, S64, S33, S160)}
     missing = sorted(map(str, want - _SEEN))
