@@ -987,6 +987,77 @@ int nus_scene_apply_cuts_retime_device(const void *d_frames, size_t frame_stride
                                        uint32_t num, uint32_t den, const uint8_t *d_cut, void *d_out, size_t out_frame_stride,
                                        void *stream);
 
+/* ---- YUV 4:2:0 frames: 8-bit planar I420 <-> RGBA8 ------------------------------------------------------------------------
+ * BUILD-DEFINED: the reference has no YUV; its frames are RGBA (or BGRA capture surfaces) from end to end.  Decoded video is planar
+ * YUV 4:2:0; these entry points are the road between such frames and the RGBA8 frames every other entry point takes.  One layout:
+ * I420, 8 bits.  No NV12, no 4:2:2 / 4:4:4, no 10-bit, no interlace.
+ * Frame layout.  An I420 frame of w x h is a Y plane of w*h bytes, then a U plane and a V plane of cw*ch bytes each, cw = (w+1)/2,
+ * ch = (h+1)/2, rows tight: w*h + 2*cw*ch bytes (nus_yuv420_frame_bytes).  Frames of a batch are yuv_frame_stride bytes apart (0 =
+ * tight, else at least one frame; no alignment rule), RGBA frames rgba_frame_stride bytes apart (0 = tight, else a multiple of 4 of
+ * at least w*h*4; the frames 4-byte aligned).  The gaps between frames are never written.
+ * The RGBA side is any nus_pixel_format: to-RGBA writes alpha 255 (X formats too), to-YUV ignores the fourth byte.
+ * Arithmetic: integers only, so that every byte can be checked for equality.  S = 14, H = 1 << 13; Q(x) = the integer nearest to
+ * x * 2^14, computed in double; >> is an arithmetic shift; clamp is to 0 .. 255.
+ *   (Kr, Kb) = (0.299, 0.114) for NUS_YUV_MATRIX_BT601, (0.2126, 0.0722) for NUS_YUV_MATRIX_BT709; Kg = 1 - Kr - Kb.
+ *   (Ys, Cs, Yo) = (219, 224, 16) for NUS_YUV_RANGE_LIMITED, (255, 255, 0) for NUS_YUV_RANGE_FULL.
+ * To YUV.  Yc = Q([Kr, Kg, Kb] Ys/255),  Uc = Q([-Kr, -Kg, 1-Kb] / (2 (1-Kb)) Cs/255),  Vc = Q([1-Kr, -Kg, -Kb] / (2 (1-Kr)) Cs/255).
+ *   luma, per pixel:     Y = clamp(((Yc . (R,G,B) + H) >> S) + Yo)
+ *   chroma, per chroma cell (cx, cy): (SR, SG, SB) = the integer-weighted sums over the cell's taps, tap coordinates clamped
+ *   into the frame, the weights totalling W;   U = clamp(((Uc . (SR,SG,SB) + H W) >> (S + log2 W)) + 128),  V likewise: ONE rounding.
+ *     NUS_YUV_SITING_CENTER (Y4M 420jpeg):  taps (2cx+i, 2cy+j), i, j in {0, 1}, weight 1 each, W = 4.
+ *     NUS_YUV_SITING_LEFT (Y4M 420mpeg2):   columns 2cx-1, 2cx, 2cx+1 with weights 1, 2, 1 in rows 2cy and 2cy+1, W = 8.
+ *   to-YUV always filters by the siting; chroma_filter is not looked at.
+ * To RGBA.  cy = Q(255/Ys),  rv = Q(2 (1-Kr) 255/Cs),  bu = Q(2 (1-Kb) 255/Cs),  gu = Q(-2 Kb (1-Kb)/Kg 255/Cs),
+ *   gv = Q(-2 Kr (1-Kr)/Kg 255/Cs).
+ *   NUS_YUV_CHROMA_NEAREST:  u = U[y>>1][x>>1] - 128, v likewise;
+ *     R = clamp((cy (Y-Yo) + rv v + H) >> S),  G = clamp((cy (Y-Yo) + gu u + gv v + H) >> S),  B = clamp((cy (Y-Yo) + bu u + H) >> S)
+ *   NUS_YUV_CHROMA_BILINEAR: u16 = the chroma summed with integer weights totalling 16, minus 16 * 128; chroma coordinates clamped.
+ *     vertical, both sitings: luma row y even: chroma rows cy-1 (weight 1) and cy (3); y odd: rows cy (3) and cy+1 (1), cy = y>>1.
+ *     horizontal, CENTER: the same rule in x.  LEFT: x even: column cx (4); x odd: columns cx (2) and cx+1 (2), cx = x>>1.
+ *     R = clamp((16 cy (Y-Yo) + rv v16 + 16 H) >> (S+4)), G and B likewise: ONE rounding.
+ *   Every intermediate fits int32 (the largest is about 1.4e8).
+ * Against the same taps evaluated with the real-valued coefficients in double and rounded once, a byte differs by at most 1, and
+ * fewer than 1 % of the bytes differ (tests/test_yuv_contract.py; DESIGN.md 8.8 has the shares).
+ * The *_device entry points only enqueue on `stream`: no allocation, no synchronisation.  Argument errors are
+ * NUS_ERR_INVALID_ARGUMENT (sizes of the host entry points: NUS_ERR_SIZE_MISMATCH), returned before any HIP call, with a text
+ * that names the entry point: a null pointer, a zero or too large dimension, an unknown enum value, n_frames == 0, a bad stride. */
+typedef enum nus_yuv_matrix {
+    NUS_YUV_MATRIX_BT601 = 0,
+    NUS_YUV_MATRIX_BT709 = 1
+} nus_yuv_matrix;
+typedef enum nus_yuv_range {
+    NUS_YUV_RANGE_LIMITED = 0,
+    NUS_YUV_RANGE_FULL = 1
+} nus_yuv_range;
+typedef enum nus_yuv_siting {
+    NUS_YUV_SITING_CENTER = 0,
+    NUS_YUV_SITING_LEFT = 1
+} nus_yuv_siting;
+typedef enum nus_yuv_chroma_filter {
+    NUS_YUV_CHROMA_NEAREST = 0,
+    NUS_YUV_CHROMA_BILINEAR = 1
+} nus_yuv_chroma_filter;
+typedef struct nus_yuv_format {
+    int matrix;        /* nus_yuv_matrix */
+    int range;         /* nus_yuv_range */
+    int siting;        /* nus_yuv_siting */
+    int chroma_filter; /* nus_yuv_chroma_filter: to-RGBA only */
+} nus_yuv_format;
+/* Host only.  Bytes of one I420 frame; 0 (and nus_last_error) for bad dimensions: zero, more than 2^30 pixels, higher than 524280. */
+size_t nus_yuv420_frame_bytes(uint32_t w, uint32_t h);
+/* DIAGNOSTIC, host only: the tables the kernels use.  to_yuv[9] = Yc, Uc, Vc over (R, G, B); to_rgb[5] = cy, rv, bu, gu, gv. */
+int nus_yuv_coefficients(int matrix, int range, int32_t *to_yuv, int32_t *to_rgb);
+int nus_yuv420_to_rgba8_device(const void *d_yuv, size_t yuv_frame_stride, uint32_t w, uint32_t h, const nus_yuv_format *fmt,
+                               int rgba_format, void *d_rgba, size_t rgba_frame_stride, uint32_t n_frames, void *stream);
+int nus_rgba8_to_yuv420_device(const void *d_rgba, size_t rgba_frame_stride, uint32_t w, uint32_t h, const nus_yuv_format *fmt,
+                               int rgba_format, void *d_yuv, size_t yuv_frame_stride, uint32_t n_frames, void *stream);
+/* One host frame on `device` (pageable is fine: the bytes travel as nus_upload / nus_download move them, through device buffers the
+ * library keeps per device).  yuv_len / rgba_len must be the frame's size exactly; the capacity at least the other frame's. */
+int nus_yuv420_to_rgba8(int device, const uint8_t *yuv, size_t yuv_len, uint32_t w, uint32_t h, const nus_yuv_format *fmt,
+                        int rgba_format, uint8_t *rgba, size_t rgba_cap);
+int nus_rgba8_to_yuv420(int device, const uint8_t *rgba, size_t rgba_len, uint32_t w, uint32_t h, const nus_yuv_format *fmt,
+                        int rgba_format, uint8_t *yuv, size_t yuv_cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,7 @@ When the same process also uses PyTorch-ROCm (bench.py, the device-resident test
 BEFORE this package: torch ships its own HIP runtime and fails to see the GPU if /opt/rocm's
 libamdhip64 (pulled in by libnuscaler_hip.so) is loaded first.
 """
-from . import _capi, metrics, scene, transfer
+from . import _capi, metrics, scene, transfer, video, y4m, yuv
 from ._capi import NuScalerLibraryError, PinnedBuffer, build, device_count
 from .blockmatch import BlockMatcher, PyFrameInterpolator
 from .benchmark import PyBenchmarkResult, py_benchmark_upscaler, py_run_comparison_benchmark
@@ -25,6 +25,9 @@ from .scene import SceneDetector
 from .stream import (FramePipeline, ShardedStream, SyntheticSource, broadcast_blob, broadcast_tables, build_tables_blob,
                      gather_rows, run_sharded, shard_frames, spread, validate_tables_blob)
 from .transfer import download, upload
+from .y4m import Y4MReader, Y4MWriter
+from .yuv import YuvFormat
+from .video import convert_y4m, plan_windows
 from .upscaler import PyAdvancedWgpuUpscaler, PyVramStats, PyWgpuUpscaler, create_advanced_upscaler
 
 # module constants of the reference's #[pymodule] (nu_scaler_core/src/lib.rs:746-761)
@@ -59,6 +62,7 @@ __all__ = [
     "ShardedStream", "SyntheticSource", "run_sharded", "gather_rows", "spread", "launch_ranks",
     "broadcast_blob", "build_tables_blob", "validate_tables_blob",
     "NuScalerLibraryError", "PinnedBuffer", "build", "device_count", "download", "upload", "transfer", "install_fatal_trace",
+    "yuv", "y4m", "video", "YuvFormat", "Y4MReader", "Y4MWriter", "convert_y4m", "plan_windows",
     "QUALITY_ULTRA", "QUALITY_QUALITY", "QUALITY_BALANCED", "QUALITY_PERFORMANCE",
     "TECH_FSR", "TECH_DLSS", "TECH_WGPU", "TECH_FALLBACK",
     "VENDOR_NVIDIA", "VENDOR_AMD", "VENDOR_INTEL", "VENDOR_OTHER",

@@ -41,6 +41,10 @@ BM_TIES_SCAN, BM_TIES_CENTER = 0, 1  # nus_bm_tie_order
 BM_MAX_RADIUS = 24  # NUS_BM_MAX_RADIUS
 BM_BIDIR_DEFAULT_TOLERANCE = 2  # NUS_BM_BIDIR_DEFAULT_TOLERANCE: a setting, not a measurement
 SCENE_DEFAULT_MAD, SCENE_DEFAULT_HIST_PERMILLE = 20, 400  # NUS_SCENE_DEFAULT_*: settings, not measurements
+YUV_MATRIX_BT601, YUV_MATRIX_BT709 = 0, 1  # nus_yuv_matrix
+YUV_RANGE_LIMITED, YUV_RANGE_FULL = 0, 1  # nus_yuv_range
+YUV_SITING_CENTER, YUV_SITING_LEFT = 0, 1  # nus_yuv_siting: Y4M 420jpeg / 420mpeg2
+YUV_CHROMA_NEAREST, YUV_CHROMA_BILINEAR = 0, 1  # nus_yuv_chroma_filter (to-RGBA only)
 BM_NO_MATCH = 0xFFFFFFFF  # NUS_BM_NO_MATCH: the SAD of a block with no admitted candidate
 
 # Every symbol include/nuscaler_hip.h declares: (name, restype, argtypes)
@@ -198,6 +202,12 @@ SIGNATURES = [
     ("nus_flow_retime_device_stream", _i, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _f, _u32, _u32, _i, _vp, _vp, _sz, _vp]),
     ("nus_bm_retime_device_stream", _i, [_vp, _vp, _sz, _u32, _u32, _u32, _u32, _u32, _i, _vp, _sz, _vp, _vp, _sz, _vp]),
     ("nus_scene_apply_cuts_retime_device", _i, [_vp, _sz, _u32, _u32, _u32, _i, _u32, _u32, _vp, _vp, _sz, _vp]),
+    ("nus_yuv420_frame_bytes", _sz, [_u32, _u32]),
+    ("nus_yuv_coefficients", _i, [_i, _i, _vp, _vp]),
+    ("nus_yuv420_to_rgba8_device", _i, [_vp, _sz, _u32, _u32, _vp, _i, _vp, _sz, _u32, _vp]),
+    ("nus_rgba8_to_yuv420_device", _i, [_vp, _sz, _u32, _u32, _vp, _i, _vp, _sz, _u32, _vp]),
+    ("nus_yuv420_to_rgba8", _i, [_i, _vp, _sz, _u32, _u32, _vp, _i, _vp, _sz]),
+    ("nus_rgba8_to_yuv420", _i, [_i, _vp, _sz, _u32, _u32, _vp, _i, _vp, _sz]),
 ]
 
 

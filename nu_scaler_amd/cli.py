@@ -5,7 +5,9 @@ its `fullscreen` subcommand (Nu_scale/src/main.rs:36-73: --tech, --quality, --al
 with zero flow, `--flow` (Horn-Schunck) or `--method block_matching [--quality high|medium|low] [--bidirectional]`; `compare <a.png> <b.png>`
 prints the `ErrorMetrics` of two images (Nu_scale/src/upscale/common.rs:475-543); `scene <a.png> <b.png>` prints the scene-cut
 detector's verdict on the pair, and `interpolate --multiplier M --scene-detect` writes repeats instead of blends across a cut;
-`retime --from 24 --to 60 OUT_%04d.png IN0.png IN1.png ...` converts a PNG sequence by a rational frame-rate ratio.
+`retime --from 24 --to 60 OUT_%04d.png IN0.png IN1.png ...` converts a PNG sequence by a rational frame-rate ratio;
+`video IN.y4m OUT.y4m (--to FPS | --multiplier M)` does the same for a YUV4MPEG2 file of 4:2:0 frames, window by window, with an
+optional `--scale S --algorithm A` up-scale of every output frame.
 Everything runs on the HIP device; without one the command fails (no CPU path).
 """
 from __future__ import annotations
@@ -67,6 +69,24 @@ def build_parser() -> argparse.ArgumentParser:
     rt.add_argument("--bidirectional", action="store_true", help="block_matching: the forward-backward check")
     rt.add_argument("--scene-detect", action="store_true", help="across a scene cut write repeats of the nearer frame, not blends")
     rt.add_argument("--device", type=int, default=0)
+    vd = sub.add_parser("video", help="frame-rate conversion (and up-scaling) of a YUV4MPEG2 file of 8-bit 4:2:0 frames: video IN.y4m "
+                                      "OUT.y4m --to 60")
+    vd.add_argument("input", help="IN.y4m: C420jpeg, C420mpeg2 or C420, progressive")
+    vd.add_argument("output", help="OUT.y4m")
+    vd.add_argument("--to", dest="fps_out", default=None, help="output rate: an integer or a fraction such as 60000/1001")
+    vd.add_argument("--multiplier", type=int, default=None, help="output rate as a multiple of the input's (1 .. 8) instead of --to")
+    vd.add_argument("--method", default="optical_flow", help="optical_flow (default), block_matching or blend (zero flow)")
+    vd.add_argument("--scale", type=int, default=1, help="up-scale every output frame by this integer factor (1 .. 4; default 1: off)")
+    vd.add_argument("--algorithm", default="lanczos3", help="with --scale: nearest, bilinear, bicubic, lanczos3, triangle")
+    vd.add_argument("--matrix", default=None, help="bt601 or bt709 (default: bt709 from 720 rows up, else bt601)")
+    vd.add_argument("--window", type=int, default=None,
+                    help="input frames on the device at a time, at least den + 1 of the reduced ratio (default: from the free memory)")
+    vd.add_argument("--scene-detect", action="store_true", help="across a scene cut write repeats of the nearer frame, not blends")
+    vd.add_argument("--flow-warps", type=int, default=None, help="optical_flow: re-linearisation rounds per finer level (0 .. 4)")
+    vd.add_argument("--flow-median", type=int, default=None, help="optical_flow: median window behind every Jacobi run (0, 3 or 5)")
+    vd.add_argument("--flow-project", type=int, default=None, help="optical_flow: projection rounds of the warp (0 .. 4)")
+    vd.add_argument("--bidirectional", action="store_true", help="block_matching: the forward-backward check")
+    vd.add_argument("--device", type=int, default=0)
     sc = sub.add_parser("scene", help="scene-cut detector on two PNGs of equal size: prints cut=0|1 mad=.. hist_permille=..")
     sc.add_argument("a")
     sc.add_argument("b")
@@ -223,11 +243,61 @@ def _check_retime(args, parser) -> None:
         parser.error("--bidirectional needs --method block_matching")
 
 
+def _check_video(args, parser) -> None:
+    """Usage errors of `video`: status 2 before anything is read or written."""
+    from ._capi import FLOW_MAX_PROJECT, FLOW_MAX_WARPS, INTERP_MAX_TIMES
+
+    if (args.fps_out is None) == (args.multiplier is None):
+        parser.error("video needs --to or --multiplier, one of them")
+    if args.fps_out is not None:
+        try:
+            args.fps_out = _rate(args.fps_out)
+            if args.fps_out <= 0:
+                raise ValueError(f"fps_out must be positive, got {args.fps_out!r}")
+        except (ValueError, ZeroDivisionError) as e:
+            parser.error(str(e))
+    elif not 1 <= args.multiplier <= INTERP_MAX_TIMES + 1:
+        parser.error(f"--multiplier must be from 1 to {INTERP_MAX_TIMES + 1}, got {args.multiplier}")
+    args.method = args.method.lower()
+    if args.method not in ("optical_flow", "block_matching", "blend"):
+        parser.error(f"--method must be optical_flow, block_matching or blend, got {args.method}")
+    for name, v, ok in (("--flow-warps", args.flow_warps, range(FLOW_MAX_WARPS + 1)), ("--flow-median", args.flow_median, (0, 3, 5)),
+                        ("--flow-project", args.flow_project, range(FLOW_MAX_PROJECT + 1))):
+        if v is not None and args.method != "optical_flow":
+            parser.error(f"{name} needs --method optical_flow")
+        if v is not None and v not in ok:
+            parser.error(f"{name}: {v} is out of range")
+    if args.bidirectional and args.method != "block_matching":
+        parser.error("--bidirectional needs --method block_matching")
+    if not 1 <= args.scale <= 4:
+        parser.error(f"--scale must be from 1 to 4, got {args.scale}")
+    if args.matrix is not None and args.matrix.lower() not in ("bt601", "bt709"):
+        parser.error(f"--matrix must be bt601 or bt709, got {args.matrix}")
+    if args.window is not None and args.window < 2:
+        parser.error(f"--window must be at least 2, got {args.window}")
+
+
 def main(argv=None) -> int:
     parser = build_parser()
     args = parser.parse_args(argv)
     if args.command == "retime":
         _check_retime(args, parser)
+    if args.command == "video":
+        _check_video(args, parser)
+        try:
+            from .video import convert_y4m
+
+            r = convert_y4m(args.input, args.output, fps_out=args.fps_out, multiplier=args.multiplier, method=args.method,
+                            scale=args.scale, algorithm=args.algorithm, window_frames=args.window,
+                            matrix=args.matrix.lower() if args.matrix else None, device=args.device, scene_detect=args.scene_detect,
+                            flow_warps=args.flow_warps or 0, flow_median=args.flow_median or 0, flow_project=args.flow_project or 0,
+                            bidirectional=args.bidirectional)
+            print(f"{args.output}: {r['frames_out']} frames {r['width']}x{r['height']} at {r['fps']} fps "
+                  f"({r['frames_in']} read, {r['windows']} windows)")
+        except (OSError, ValueError, RuntimeError) as e:
+            print(f"nu_scaler_cli: error: {e}", file=sys.stderr)
+            return 1
+        return 0
     if args.command == "interpolate" and args.multiplier is not None:  # usage errors: status 2 before anything is read or written
         if args.t is not None:
             parser.error("--multiplier and --t exclude each other")

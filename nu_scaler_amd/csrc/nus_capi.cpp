@@ -16,6 +16,7 @@
 #include "nus_retime.hpp"
 #include "nus_scene.hpp"
 #include "nus_transfer.hpp"
+#include "nus_yuv.hpp"
 
 struct nus_upscaler {
     nus::HipUpscaler impl;
@@ -1094,6 +1095,52 @@ int nus_scene_apply_cuts_retime_device(const void *d_frames, size_t frame_stride
     return guarded<int>("nus_scene_apply_cuts_retime_device", [&]() -> int {
         return nus::scene_apply_cuts_retime_device(d_frames, frame_stride, n_frames, w, h, format, num, den, d_cut, d_out, out_frame_stride,
                                                    stream);
+    });
+}
+
+static_assert(sizeof(nus_yuv_format) == sizeof(nus::YuvFormat) && sizeof(nus_yuv_format) == 16, "nus_yuv_format is the host module's YuvFormat");
+
+size_t nus_yuv420_frame_bytes(uint32_t w, uint32_t h)
+{
+    try {
+        return nus::yuv420_frame_bytes(w, h);
+    } catch (...) {
+        nus::set_thread_error("nus_yuv420_frame_bytes: unexpected exception");
+        return 0;
+    }
+}
+int nus_yuv_coefficients(int matrix, int range, int32_t *to_yuv, int32_t *to_rgb)
+{
+    return guarded<int>("nus_yuv_coefficients", [&]() -> int { return nus::yuv_coefficients(matrix, range, to_yuv, to_rgb); });
+}
+int nus_yuv420_to_rgba8_device(const void *d_yuv, size_t yuv_frame_stride, uint32_t w, uint32_t h, const nus_yuv_format *fmt,
+                               int rgba_format, void *d_rgba, size_t rgba_frame_stride, uint32_t n_frames, void *stream)
+{
+    return guarded<int>("nus_yuv420_to_rgba8_device", [&]() -> int {
+        return nus::yuv420_to_rgba8_device(d_yuv, yuv_frame_stride, w, h, reinterpret_cast<const nus::YuvFormat *>(fmt), rgba_format, d_rgba,
+                                           rgba_frame_stride, n_frames, static_cast<hipStream_t>(stream));
+    });
+}
+int nus_rgba8_to_yuv420_device(const void *d_rgba, size_t rgba_frame_stride, uint32_t w, uint32_t h, const nus_yuv_format *fmt,
+                               int rgba_format, void *d_yuv, size_t yuv_frame_stride, uint32_t n_frames, void *stream)
+{
+    return guarded<int>("nus_rgba8_to_yuv420_device", [&]() -> int {
+        return nus::rgba8_to_yuv420_device(d_rgba, rgba_frame_stride, w, h, reinterpret_cast<const nus::YuvFormat *>(fmt), rgba_format, d_yuv,
+                                           yuv_frame_stride, n_frames, static_cast<hipStream_t>(stream));
+    });
+}
+int nus_yuv420_to_rgba8(int device, const uint8_t *yuv, size_t yuv_len, uint32_t w, uint32_t h, const nus_yuv_format *fmt,
+                        int rgba_format, uint8_t *rgba, size_t rgba_cap)
+{
+    return guarded<int>("nus_yuv420_to_rgba8", [&]() -> int {
+        return nus::yuv420_to_rgba8(device, yuv, yuv_len, w, h, reinterpret_cast<const nus::YuvFormat *>(fmt), rgba_format, rgba, rgba_cap);
+    });
+}
+int nus_rgba8_to_yuv420(int device, const uint8_t *rgba, size_t rgba_len, uint32_t w, uint32_t h, const nus_yuv_format *fmt,
+                        int rgba_format, uint8_t *yuv, size_t yuv_cap)
+{
+    return guarded<int>("nus_rgba8_to_yuv420", [&]() -> int {
+        return nus::rgba8_to_yuv420(device, rgba, rgba_len, w, h, reinterpret_cast<const nus::YuvFormat *>(fmt), rgba_format, yuv, yuv_cap);
     });
 }
 

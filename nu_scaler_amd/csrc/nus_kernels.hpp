@@ -459,4 +459,24 @@ hipError_t launch_scene_apply_retime(const RetimeLaunch &L, const uint8_t *cut);
 // last frame has no pair behind it and writes its own entry alone
 hipError_t launch_retime_table(uint32_t n_frames, uint32_t num, uint32_t den, void *entries, hipStream_t stream);
 
+// 8-bit planar YUV 4:2:0 (I420) <-> RGBA8 (nus_k_yuv.hip; nus_yuv420_* in include/nuscaler_hip.h, where the integer contract is
+// written).  Frame i of the batch: its Y, U and V planes, rows tight, from yuv + i * yuv_frame_stride; its pixels from
+// rgba + i * rgba_frame_stride (4-byte aligned, the stride a multiple of 4).  Both strides in bytes and at least one frame (never 0
+// here); the gaps are not written.  The side a launch reads is only read.  to_yuv / to_rgb / y_offset: the Q14 tables of the
+// format's matrix and range (yuv_coefficients of nus_yuv.hpp); `sel`: input_selector of the RGBA side's nus_pixel_format, applied
+// to the pixels loaded (to YUV) or stored (to RGBA; alpha 255).  chroma_filter is to-RGBA's alone.
+struct YuvLaunch {
+    uint8_t *yuv = nullptr, *rgba = nullptr;
+    size_t yuv_frame_stride = 0, rgba_frame_stride = 0;
+    uint32_t w = 0, h = 0, n_frames = 1;
+    int siting = 0, chroma_filter = 0; // NUS_YUV_SITING_*, NUS_YUV_CHROMA_* (matrix and range are in the tables)
+    int32_t to_yuv[9] = {0}, to_rgb[5] = {0}, y_offset = 0;
+    uint32_t sel = kSelRGBA;
+    hipStream_t stream = nullptr;
+};
+// The form is chosen per launch: the aligned kernels (8 pixels x 2 rows per thread towards RGBA, 16 x 2 towards YUV) where the
+// width fills the run and every base and stride keeps its 16-byte accesses aligned, else one pixel / one chroma cell per thread.
+hipError_t launch_yuv_to_rgba(const YuvLaunch &L);
+hipError_t launch_rgba_to_yuv(const YuvLaunch &L);
+
 } // namespace nus

@@ -1,0 +1,114 @@
+"""8-bit planar YUV 4:2:0 (I420) frames <-> RGBA8 on the HIP device, bound to `nus_yuv*` of include/nuscaler_hip.h (the integer
+contract is written there).  Build-defined: the reference has no YUV.  An I420 frame of w x h is its Y plane (w*h bytes), then
+the U and V planes ((w+1)//2 * (h+1)//2 bytes each), rows tight.  No torch type crosses into this module: the device entry points
+take integer device addresses, as `SceneDetector.detect_device` does."""
+from __future__ import annotations
+
+import ctypes
+
+from . import _capi as C
+from .scene import _check, pixel_format
+from .upscaler import _as_buffer
+
+_MATRIX = {"bt601": C.YUV_MATRIX_BT601, "bt709": C.YUV_MATRIX_BT709}
+_RANGE = {"limited": C.YUV_RANGE_LIMITED, "full": C.YUV_RANGE_FULL}
+_SITING = {"center": C.YUV_SITING_CENTER, "left": C.YUV_SITING_LEFT}
+_CHROMA = {"nearest": C.YUV_CHROMA_NEAREST, "bilinear": C.YUV_CHROMA_BILINEAR}
+
+
+class _Format(ctypes.Structure):  # nus_yuv_format
+    _fields_ = [("matrix", ctypes.c_int), ("range", ctypes.c_int), ("siting", ctypes.c_int), ("chroma_filter", ctypes.c_int)]
+
+
+def _enum(name: str, table: dict, value) -> int:
+    if isinstance(value, str):
+        v = table.get(value.lower())
+        if v is None:
+            raise ValueError(f"{name} must be one of {', '.join(repr(k) for k in table)}, got {value!r}")
+        return v
+    if isinstance(value, bool) or not isinstance(value, int):
+        raise ValueError(f"{name} must be one of {', '.join(repr(k) for k in table)}, got {value!r}")
+    return value  # (an integer goes to the library as it is: the library refuses what it does not know)
+
+
+class YuvFormat:
+    """How the YUV side of a conversion is read or written: matrix "bt601" | "bt709", range "limited" | "full", siting "center"
+    (Y4M 420jpeg) | "left" (420mpeg2), chroma "nearest" | "bilinear" (the up-sampling filter of to-RGBA; to-YUV always filters by
+    the siting)."""
+
+    def __init__(self, matrix="bt709", range="limited", siting="center", chroma="bilinear"):
+        self.matrix = _enum("matrix", _MATRIX, matrix)
+        self.range = _enum("range", _RANGE, range)
+        self.siting = _enum("siting", _SITING, siting)
+        self.chroma = _enum("chroma", _CHROMA, chroma)
+
+    def _c(self) -> _Format:
+        return _Format(self.matrix, self.range, self.siting, self.chroma)
+
+    def __repr__(self):
+        def name(table, v):
+            return next((k for k, x in table.items() if x == v), v)
+
+        return (f"YuvFormat(matrix={name(_MATRIX, self.matrix)!r}, range={name(_RANGE, self.range)!r}, "
+                f"siting={name(_SITING, self.siting)!r}, chroma={name(_CHROMA, self.chroma)!r})")
+
+
+def frame_bytes(w: int, h: int) -> int:
+    """Bytes of one I420 frame (nus_yuv420_frame_bytes); ValueError for dimensions the library does not take."""
+    n = int(C.lib().nus_yuv420_frame_bytes(int(w), int(h)))
+    if n == 0:
+        raise ValueError(C.last_error())
+    return n
+
+
+def coefficients(matrix="bt709", range="limited") -> tuple[list[int], list[int]]:
+    """The Q14 tables the kernels use (nus_yuv_coefficients): (Yc, Uc, Vc over R, G, B; cy, rv, bu, gu, gv)."""
+    a, b = (ctypes.c_int32 * 9)(), (ctypes.c_int32 * 5)()
+    _check(C.lib().nus_yuv_coefficients(_enum("matrix", _MATRIX, matrix), _enum("range", _RANGE, range), ctypes.addressof(a),
+                                        ctypes.addressof(b)))
+    return list(a), list(b)
+
+
+def to_rgba_device(d_yuv: int, w: int, h: int, d_rgba: int, fmt: YuvFormat | None = None, n_frames: int = 1, yuv_frame_stride: int = 0,
+                   rgba_frame_stride: int = 0, rgba_format="rgba", stream: int = 0) -> None:
+    """Enqueue I420 -> RGBA8 of `n_frames` device frames on `stream` (nus_yuv420_to_rgba8_device); strides in bytes, 0 = tight."""
+    f = (fmt or YuvFormat())._c()
+    _check(C.lib().nus_yuv420_to_rgba8_device(d_yuv or None, int(yuv_frame_stride), int(w), int(h), ctypes.addressof(f),
+                                              pixel_format(rgba_format), d_rgba or None, int(rgba_frame_stride), int(n_frames),
+                                              stream or None))
+
+
+def to_yuv_device(d_rgba: int, w: int, h: int, d_yuv: int, fmt: YuvFormat | None = None, n_frames: int = 1, rgba_frame_stride: int = 0,
+                  yuv_frame_stride: int = 0, rgba_format="rgba", stream: int = 0) -> None:
+    """Enqueue RGBA8 -> I420 of `n_frames` device frames on `stream` (nus_rgba8_to_yuv420_device)."""
+    f = (fmt or YuvFormat())._c()
+    _check(C.lib().nus_rgba8_to_yuv420_device(d_rgba or None, int(rgba_frame_stride), int(w), int(h), ctypes.addressof(f),
+                                              pixel_format(rgba_format), d_yuv or None, int(yuv_frame_stride), int(n_frames),
+                                              stream or None))
+
+
+def to_rgba(yuv_bytes, w: int, h: int, fmt: YuvFormat | None = None, rgba_format="rgba", device: int = 0) -> bytes:
+    """One host I420 frame -> its RGBA8 pixels (nus_yuv420_to_rgba8)."""
+    addr, n, keep = _as_buffer(yuv_bytes)
+    out = bytearray(int(w) * int(h) * 4) if int(w) > 0 and int(h) > 0 else bytearray(4)
+    o = (ctypes.c_ubyte * len(out)).from_buffer(out)
+    f = (fmt or YuvFormat())._c()
+    st = C.lib().nus_yuv420_to_rgba8(int(device), addr, n, int(w), int(h), ctypes.addressof(f), pixel_format(rgba_format),
+                                     ctypes.addressof(o), len(out))
+    del keep, o
+    _check(st)
+    return bytes(out)
+
+
+def to_yuv(rgba_bytes, w: int, h: int, fmt: YuvFormat | None = None, rgba_format="rgba", device: int = 0) -> bytes:
+    """One host RGBA8 frame -> its I420 frame (nus_rgba8_to_yuv420)."""
+    addr, n, keep = _as_buffer(rgba_bytes)
+    cap = int(w) * int(h) + 2 * ((int(w) + 1) // 2) * ((int(h) + 1) // 2) if int(w) > 0 and int(h) > 0 else 4
+    out = bytearray(cap)
+    o = (ctypes.c_ubyte * len(out)).from_buffer(out)
+    f = (fmt or YuvFormat())._c()
+    st = C.lib().nus_rgba8_to_yuv420(int(device), addr, n, int(w), int(h), ctypes.addressof(f), pixel_format(rgba_format),
+                                     ctypes.addressof(o), len(out))
+    del keep, o
+    _check(st)
+    return bytes(out)
