@@ -641,7 +641,9 @@ int nus_flow_project_rounds(const nus_flow *h);
  * bytes it receives with the setting off for every stream whose chunk size the setting's workspace (28 B per pixel and pair more)
  * does not change; the backward flows stay in the workspace.  The stream rule below holds.  nus_flow_estimate* is not affected, and
  * scene detection applies behind the warp as before.  nus_flow_retime_device_stream with the setting on returns
- * NUS_ERR_INVALID_ARGUMENT before any HIP call ("... bidirectional flow is not supported by rate conversion yet").
+ * NUS_ERR_INVALID_ARGUMENT before any HIP call ("... bidirectional flow is not supported by rate conversion yet"): rate conversion
+ * with the select warp is nus_flow_retime_select_device_stream, and the backward flows leave the workspace through
+ * nus_flow_estimate_both_device_stream; neither looks at this setting.
  * enabled other than 0 or 1: NUS_ERR_INVALID_ARGUMENT, the text beginning "nus_flow_set_bidirectional:", the setting unchanged. */
 int nus_flow_set_bidirectional(nus_flow *h, int enabled);
 int nus_flow_bidirectional(const nus_flow *h);
@@ -972,6 +974,36 @@ int nus_interp_retime_device(nus_interp *h, const void *d_frames, size_t frame_s
 int nus_flow_retime_device_stream(nus_flow *h, const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t hgt, uint32_t levels,
                                   uint32_t coarse_iters, uint32_t refine_iters, float lambda, uint32_t num, uint32_t den,
                                   int flow_format, void *d_flows, void *d_out, size_t out_frame_stride, void *stream);
+/* Rate conversion with the select warp (nus_interp_interpolate_select_device): nus_interp_retime_device with TWO flows per pair.
+ * Pair k's forward plane (frame k -> frame k+1, on frame k's grid) at d_flows_fwd + k * w*h*8 and its backward plane (frame k+1 ->
+ * frame k, on frame k+1's grid) at d_flows_bwd + k * w*h*8 (k * w*h*4 with NUS_FLOW_F16); layout and alignment of each as d_flows
+ * there.  Output j with r_j == 0 is the real-frame copy, as there; output j with r_j != 0 is byte for byte what
+ * nus_interp_interpolate_select_device of the same handle writes for pair (k_j, k_j + 1) at t_j, in the handle's mode, flow format,
+ * input format and projection rounds.  Either flow pointer NULL: NUS_ERR_INVALID_ARGUMENT before any HIP call (the select warp takes
+ * both flows); every other argument check is nus_interp_retime_device's.  One warp launch over all pairs and one copy launch. */
+int nus_interp_retime_select_device(nus_interp *h, const void *d_frames, size_t frame_stride, uint32_t n_frames, const void *d_flows_fwd,
+                                    const void *d_flows_bwd, uint32_t w, uint32_t hgt, uint32_t num, uint32_t den, void *d_out,
+                                    size_t out_frame_stride, void *stream);
+/* Both flows of every pair of a device-resident stream, NUS_FLOW_F32 both, as nus_flow_estimate_device_stream takes and gives its
+ * arguments.  d_flows_fwd receives the bytes of nus_flow_estimate_device_stream.  d_flows_bwd receives, per pair k, the flow
+ * frame k+1 -> frame k on frame k+1's grid: the backward solve nus_flow_set_bidirectional runs -- the same pyramids, the pair's two
+ * planes swapped, the handle's warps and median -- written to the caller's buffer.  In NUS_FLOW_EXACT pair k's backward plane is
+ * byte for byte nus_flow_estimate_device(frame k+1, frame k); in NUS_FLOW_FAST it is the plane the setting's select warp reads.
+ * Both pointers are required.  It does not look at the handle's bidirectional setting. */
+int nus_flow_estimate_both_device_stream(nus_flow *h, const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t hgt, uint32_t levels,
+                                         uint32_t coarse_iters, uint32_t refine_iters, float lambda, void *d_flows_fwd, void *d_flows_bwd,
+                                         void *stream);
+/* nus_flow_retime_device_stream with both flows and the select warp: for every chunking of the stream, in every mode and tiling, the
+ * bytes of nus_flow_estimate_both_device_stream followed by nus_interp_retime_select_device in FMA mode (with the handle's projection
+ * rounds), under the handle's warps, median and scene detection.  The flows in flow_format between estimator and warp, and at
+ * d_flows_fwd / d_flows_bwd where given; either may be NULL, the handle then keeps that direction in its workspace.  Arguments and
+ * alignment otherwise as nus_flow_retime_device_stream.  It does not look at the handle's bidirectional setting (which
+ * nus_flow_retime_device_stream still refuses).  Workspace: at most 28 bytes per pixel and pair of a chunk more than
+ * nus_flow_retime_device_stream reserves for the same call; the result does not depend on what the workspace held before. */
+int nus_flow_retime_select_device_stream(nus_flow *h, const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t hgt, uint32_t levels,
+                                         uint32_t coarse_iters, uint32_t refine_iters, float lambda, uint32_t num, uint32_t den,
+                                         int flow_format, void *d_flows_fwd, void *d_flows_bwd, void *d_out, size_t out_frame_stride,
+                                         void *stream);
 /* nus_bm_interpolate_multi_device_stream with the schedule in place of the time set: in NUS_INTERP_MODE_EXACT an in-between output is
  * byte for byte nus_bm_interpolate's frame for pair k_j at t_j, a real-frame output the copy.  In either mode the bytes at d_vectors
  * (may be NULL) are nus_bm_estimate_device's for the stream's pairs, and an in-between output is byte for byte what nus_bm_warp_device

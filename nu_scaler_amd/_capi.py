@@ -200,6 +200,9 @@ SIGNATURES = [
     ("nus_retime_schedule_device", _i, [_u32, _u32, _u32, _vp, _vp]),
     ("nus_interp_retime_device", _i, [_vp, _vp, _sz, _u32, _vp, _u32, _u32, _u32, _u32, _vp, _sz, _vp]),
     ("nus_flow_retime_device_stream", _i, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _f, _u32, _u32, _i, _vp, _vp, _sz, _vp]),
+    ("nus_interp_retime_select_device", _i, [_vp, _vp, _sz, _u32, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _sz, _vp]),
+    ("nus_flow_estimate_both_device_stream", _i, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _f, _vp, _vp, _vp]),
+    ("nus_flow_retime_select_device_stream", _i, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _f, _u32, _u32, _i, _vp, _vp, _vp, _sz, _vp]),
     ("nus_bm_retime_device_stream", _i, [_vp, _vp, _sz, _u32, _u32, _u32, _u32, _u32, _i, _vp, _sz, _vp, _vp, _sz, _vp]),
     ("nus_scene_apply_cuts_retime_device", _i, [_vp, _sz, _u32, _u32, _u32, _i, _u32, _u32, _vp, _vp, _sz, _vp]),
     ("nus_yuv420_frame_bytes", _sz, [_u32, _u32]),

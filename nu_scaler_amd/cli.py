@@ -5,7 +5,8 @@ its `fullscreen` subcommand (Nu_scale/src/main.rs:36-73: --tech, --quality, --al
 with zero flow, `--flow` (Horn-Schunck) or `--method block_matching [--quality high|medium|low] [--bidirectional]`; `compare <a.png> <b.png>`
 prints the `ErrorMetrics` of two images (Nu_scale/src/upscale/common.rs:475-543); `scene <a.png> <b.png>` prints the scene-cut
 detector's verdict on the pair, and `interpolate --multiplier M --scene-detect` writes repeats instead of blends across a cut;
-`retime --from 24 --to 60 OUT_%04d.png IN0.png IN1.png ...` converts a PNG sequence by a rational frame-rate ratio;
+`retime --from 24 --to 60 OUT_%04d.png IN0.png IN1.png ...` converts a PNG sequence by a rational frame-rate ratio
+(`--flow-bidirectional`: with the select warp, here and in `video`);
 `video IN.y4m OUT.y4m (--to FPS | --multiplier M)` does the same for a YUV4MPEG2 file of 4:2:0 frames, window by window, with an
 optional `--scale S --algorithm A` up-scale of every output frame.
 Everything runs on the HIP device; without one the command fails (no CPU path).
@@ -66,6 +67,9 @@ def build_parser() -> argparse.ArgumentParser:
     rt.add_argument("--flow-warps", type=int, default=None, help="optical_flow: re-linearisation rounds per finer level (0 .. 4)")
     rt.add_argument("--flow-median", type=int, default=None, help="optical_flow: median window behind every Jacobi run (0, 3 or 5)")
     rt.add_argument("--flow-project", type=int, default=None, help="optical_flow: projection rounds of the warp (0 .. 4)")
+    rt.add_argument("--flow-bidirectional", action="store_true",
+                    help="optical_flow: estimate every pair both ways and warp each pixel with the vector whose two samples agree "
+                         "better (the select warp)")
     rt.add_argument("--bidirectional", action="store_true", help="block_matching: the forward-backward check")
     rt.add_argument("--scene-detect", action="store_true", help="across a scene cut write repeats of the nearer frame, not blends")
     rt.add_argument("--device", type=int, default=0)
@@ -85,6 +89,9 @@ def build_parser() -> argparse.ArgumentParser:
     vd.add_argument("--flow-warps", type=int, default=None, help="optical_flow: re-linearisation rounds per finer level (0 .. 4)")
     vd.add_argument("--flow-median", type=int, default=None, help="optical_flow: median window behind every Jacobi run (0, 3 or 5)")
     vd.add_argument("--flow-project", type=int, default=None, help="optical_flow: projection rounds of the warp (0 .. 4)")
+    vd.add_argument("--flow-bidirectional", action="store_true",
+                    help="optical_flow: estimate every pair both ways and warp each pixel with the vector whose two samples agree "
+                         "better (the select warp)")
     vd.add_argument("--bidirectional", action="store_true", help="block_matching: the forward-backward check")
     vd.add_argument("--device", type=int, default=0)
     sc = sub.add_parser("scene", help="scene-cut detector on two PNGs of equal size: prints cut=0|1 mad=.. hist_permille=..")
@@ -239,6 +246,8 @@ def _check_retime(args, parser) -> None:
             parser.error(f"{name} needs --method optical_flow")
         if v is not None and v not in ok:
             parser.error(f"{name}: {v} is out of range")
+    if args.flow_bidirectional and args.method != "optical_flow":
+        parser.error("--flow-bidirectional needs --method optical_flow")
     if args.bidirectional and args.method != "block_matching":
         parser.error("--bidirectional needs --method block_matching")
 
@@ -267,6 +276,8 @@ def _check_video(args, parser) -> None:
             parser.error(f"{name} needs --method optical_flow")
         if v is not None and v not in ok:
             parser.error(f"{name}: {v} is out of range")
+    if args.flow_bidirectional and args.method != "optical_flow":
+        parser.error("--flow-bidirectional needs --method optical_flow")
     if args.bidirectional and args.method != "block_matching":
         parser.error("--bidirectional needs --method block_matching")
     if not 1 <= args.scale <= 4:
@@ -291,7 +302,7 @@ def main(argv=None) -> int:
                             scale=args.scale, algorithm=args.algorithm, window_frames=args.window,
                             matrix=args.matrix.lower() if args.matrix else None, device=args.device, scene_detect=args.scene_detect,
                             flow_warps=args.flow_warps or 0, flow_median=args.flow_median or 0, flow_project=args.flow_project or 0,
-                            bidirectional=args.bidirectional)
+                            bidirectional=args.bidirectional, flow_bidirectional=args.flow_bidirectional)
             print(f"{args.output}: {r['frames_out']} frames {r['width']}x{r['height']} at {r['fps']} fps "
                   f"({r['frames_in']} read, {r['windows']} windows)")
         except (OSError, ValueError, RuntimeError) as e:
@@ -364,7 +375,8 @@ def main(argv=None) -> int:
             for path in imagefile.retime_image_files(args.output_pattern, args.inputs, args.fps_in, args.fps_out, args.method,
                                                      device=args.device, scene_detect=args.scene_detect,
                                                      bidirectional=args.bidirectional, flow_warps=args.flow_warps or 0,
-                                                     flow_median=args.flow_median or 0, flow_project=args.flow_project or 0):
+                                                     flow_median=args.flow_median or 0, flow_project=args.flow_project or 0,
+                                                     flow_bidirectional=args.flow_bidirectional):
                 print(path)
         elif args.command == "compare":
             import numpy as np

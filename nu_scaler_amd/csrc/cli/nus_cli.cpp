@@ -6,7 +6,7 @@
 //   nu_scaler_cli upscale <in.png> <out.png> [--algorithm A] [--scale S] [--tech T] [--quality Q] [--device N]
 //   nu_scaler_cli interpolate <a.png> <b.png> <out.png> [--t X | --multiplier M] [--flow [--flow-warps N] [--flow-median 0|3|5] [--flow-project N] [--flow-bidirectional]] [--device N]
 //                             [--method block_matching [--quality high|medium|low] [--bidirectional [--bidir-tolerance N]]]
-//   nu_scaler_cli retime --from R --to R [--method M] [flow / block flags] [--scene-detect] OUT_%04d.png IN0.png IN1.png ...
+//   nu_scaler_cli retime --from R --to R [--method M] [flow / block flags, --flow-bidirectional] [--scene-detect] OUT_%04d.png IN0.png IN1.png ...
 //   nu_scaler_cli scene <a.png> <b.png> [--mad N] [--hist N] [--device N]   (the scene-cut detector: cut=0|1 mad=.. hist_permille=..)
 //   nu_scaler_cli compare <a.png> <b.png> [--device N]   (MSE / PSNR / SSIM, ErrorMetrics: Nu_scale/src/upscale/common.rs:475-543)
 //   nu_scaler_cli png-copy <in.png> <out.png>        (decode + encode only; no GPU: codec self-check)
@@ -45,7 +45,8 @@ int usage(int rc)
                  "                             [--method block_matching [--quality high|medium|low]] [--scene-detect]\n"
                  "                             [--bidirectional [--bidir-tolerance 0..96]]   (block matching: forward-backward check)\n"
                  "       nu_scaler_cli retime --from 24 --to 60 [--method optical_flow|block_matching|blend] [--flow-warps 0..4]\n"
-                 "                             [--flow-median 0|3|5] [--flow-project 0..4] [--bidirectional] [--scene-detect] [--device N]\n"
+                 "                             [--flow-median 0|3|5] [--flow-project 0..4] [--flow-bidirectional] [--bidirectional]\n"
+                 "                             [--scene-detect] [--device N]\n"
                  "                             OUT_%%04d.png IN0.png IN1.png ...   (rates: integers or A/B; to/from reduced: terms <= 4096, <= 8)\n"
                  "       nu_scaler_cli scene <a.png> <b.png> [--mad 0..255] [--hist 0..1000] [--device N]\n"
                  "       nu_scaler_cli compare <a.png> <b.png> [--device N]\n"
@@ -541,6 +542,10 @@ int cmd_retime(const Args &a)
         }
         flow_opt[i] = v;
     }
+    if (a.flow_bidirectional && method != "optical_flow") {
+        std::fprintf(stderr, "nu_scaler_cli: error: --flow-bidirectional needs --method optical_flow\n");
+        return usage(2);
+    }
     if (a.bidirectional && method != "block_matching") {
         std::fprintf(stderr, "nu_scaler_cli: error: --bidirectional needs --method block_matching\n");
         return usage(2);
@@ -590,7 +595,7 @@ int cmd_retime(const Args &a)
             if (rc != NUS_OK) msg = nus_flow_last_error(fl);
         }
     }
-    std::vector<float> flow, times;
+    std::vector<float> flow, flow_bwd, times;
     std::vector<uint8_t> frames;
     std::string err;
     for (size_t j = 0; rc == NUS_OK && err.empty() && j < sched.size();) {
@@ -624,9 +629,17 @@ int cmd_retime(const Args &a)
                 flow.resize((size_t)w * h * 2);
                 // 3 levels, 50 coarse + 10 refining Jacobi steps, lambda as the Python mirror's FlowEstimator defaults
                 rc = nus_flow_estimate(fl, pa, pb, w, h, 3, 50, 10, 0.0004f, flow.data());
+                if (rc == NUS_OK && a.flow_bidirectional) { // the same estimate B -> A
+                    flow_bwd.resize(flow.size());
+                    rc = nus_flow_estimate(fl, pb, pa, w, h, 3, 50, 10, 0.0004f, flow_bwd.data());
+                }
                 if (rc != NUS_OK) msg = nus_flow_last_error(fl);
             }
-            if (rc == NUS_OK) {
+            if (rc == NUS_OK && fl && !cut && a.flow_bidirectional) { // both flows and the select warp
+                rc = nus_interp_interpolate_select(it, pa, fb, pb, fb, flow.data(), flow_bwd.data(), w, h, times.data(), nt, frames.data(),
+                                                   frames.size());
+                if (rc != NUS_OK) msg = nus_interp_last_error(it);
+            } else if (rc == NUS_OK) {
                 rc = nus_interp_interpolate_multi(it, pa, fb, pb, fb, fl && !cut ? flow.data() : nullptr, w, h, times.data(), nt,
                                                   frames.data(), frames.size());
                 if (rc != NUS_OK) msg = nus_interp_last_error(it);

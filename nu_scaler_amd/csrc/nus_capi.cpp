@@ -1078,6 +1078,42 @@ int nus_flow_retime_device_stream(nus_flow *h, const void *d_frames, uint32_t n_
                                             flow_format == NUS_FLOW_F16, d_flows, d_out, out_frame_stride, static_cast<hipStream_t>(stream));
     });
 }
+int nus_interp_retime_select_device(nus_interp *h, const void *d_frames, size_t frame_stride, uint32_t n_frames, const void *d_flows_fwd,
+                                    const void *d_flows_bwd, uint32_t w, uint32_t hgt, uint32_t num, uint32_t den, void *d_out,
+                                    size_t out_frame_stride, void *stream)
+{
+    return guarded<int>("nus_interp_retime_select_device", [&]() -> int {
+        return h ? h->impl.retime_select_device(d_frames, frame_stride, n_frames, d_flows_fwd, d_flows_bwd, w, hgt, num, den, d_out,
+                                                out_frame_stride, static_cast<hipStream_t>(stream))
+                 : null_handle();
+    });
+}
+int nus_flow_estimate_both_device_stream(nus_flow *h, const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t hgt, uint32_t levels,
+                                         uint32_t coarse_iters, uint32_t refine_iters, float lambda, void *d_flows_fwd, void *d_flows_bwd,
+                                         void *stream)
+{
+    return guarded<int>("nus_flow_estimate_both_device_stream", [&]() -> int {
+        return h ? h->impl.estimate_both_device_stream(d_frames, n_frames, w, hgt, {levels, coarse_iters, refine_iters, lambda}, d_flows_fwd,
+                                                       d_flows_bwd, static_cast<hipStream_t>(stream))
+                 : null_handle();
+    });
+}
+int nus_flow_retime_select_device_stream(nus_flow *h, const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t hgt, uint32_t levels,
+                                         uint32_t coarse_iters, uint32_t refine_iters, float lambda, uint32_t num, uint32_t den,
+                                         int flow_format, void *d_flows_fwd, void *d_flows_bwd, void *d_out, size_t out_frame_stride,
+                                         void *stream)
+{
+    return guarded<int>("nus_flow_retime_select_device_stream", [&]() -> int {
+        if (!h) return null_handle();
+        if (flow_format != NUS_FLOW_F32 && flow_format != NUS_FLOW_F16) {
+            nus::set_thread_error("nus_flow_retime_select_device_stream: flow_format must be NUS_FLOW_F32 or NUS_FLOW_F16");
+            return NUS_ERR_INVALID_ARGUMENT;
+        }
+        return h->impl.retime_select_device_stream(d_frames, n_frames, w, hgt, {levels, coarse_iters, refine_iters, lambda}, num, den,
+                                                   flow_format == NUS_FLOW_F16, d_flows_fwd, d_flows_bwd, d_out, out_frame_stride,
+                                                   static_cast<hipStream_t>(stream));
+    });
+}
 int nus_bm_retime_device_stream(nus_blockmatch *h, const void *d_frames, size_t frame_stride, uint32_t n_frames, uint32_t w,
                                 uint32_t hgt, uint32_t num, uint32_t den, int mode, void *d_workspace, size_t workspace_bytes,
                                 void *d_vectors, void *d_out, size_t out_frame_stride, void *stream)

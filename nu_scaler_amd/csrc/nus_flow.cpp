@@ -607,11 +607,39 @@ int HipFlowEstimator::retime_device_stream(const void *d_frames, uint32_t n_fram
     static const char *const who = "nus_flow_retime_device_stream";
     std::lock_guard<std::mutex> lk(mu_);
     if (bidir_) return fail(kInvalidArgument, std::string(who) + ": bidirectional flow is not supported by rate conversion yet");
+    return retime_stream_call(who, false, d_frames, n_frames, w, h, p, num, den, flow_half, d_flows, nullptr, d_out, out_frame_stride, stream);
+}
+
+int HipFlowEstimator::retime_select_device_stream(const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t h, const FlowParams &p,
+                                                  uint32_t num, uint32_t den, bool flow_half, void *d_flows_fwd, void *d_flows_bwd, void *d_out,
+                                                  size_t out_frame_stride, hipStream_t stream)
+{
+    std::lock_guard<std::mutex> lk(mu_); // (the bidirectional setting is not looked at: this entry point is the request)
+    return retime_stream_call("nus_flow_retime_select_device_stream", true, d_frames, n_frames, w, h, p, num, den, flow_half, d_flows_fwd,
+                              d_flows_bwd, d_out, out_frame_stride, stream);
+}
+
+int HipFlowEstimator::estimate_both_device_stream(const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t h, const FlowParams &p,
+                                                  void *d_flows_fwd, void *d_flows_bwd, hipStream_t stream)
+{
+    std::lock_guard<std::mutex> lk(mu_);
+    if (!d_flows_fwd || !d_flows_bwd) return fail(kInvalidArgument, "nus_flow_estimate_both_device_stream: null device pointer");
+    StreamJob J(d_frames, n_frames, w, h, d_flows_fwd, nullptr, stream);
+    J.flows_bwd = static_cast<uint8_t *>(d_flows_bwd);
+    call_stream_ = stream;
+    return stream_impl(J, with_warps(p));
+}
+
+// (mu_ held)
+int HipFlowEstimator::retime_stream_call(const char *who, bool select, const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t h,
+                                         const FlowParams &p, uint32_t num, uint32_t den, bool flow_half, void *d_flows, void *d_flows_bwd,
+                                         void *d_out, size_t out_frame_stride, hipStream_t stream)
+{
     RetimeRatio r;
     int rc = pass(check_retime(who, n_frames, num, den, r));
     if (rc != kOk || (rc = pass(check_dims(who, w, h, kMaxPixels, "bad image dimensions"))) != kOk) return rc;
     if (!d_frames || !d_out) return fail(kInvalidArgument, std::string(who) + ": null device pointer");
-    if (misaligned(d_out, 16) || misaligned(d_flows, 16) || misaligned(d_frames, 4))
+    if (misaligned(d_out, 16) || misaligned(d_flows, 16) || misaligned(d_flows_bwd, 16) || misaligned(d_frames, 4))
         return fail(kInvalidArgument, std::string(who) + ": d_out and d_flows must be 16-byte aligned, d_frames 4-byte aligned");
     const size_t frame_bytes = (size_t)w * h * 4;
     if ((rc = pass(check_out_frame_stride(who, out_frame_stride, frame_bytes))) != kOk) return rc;
@@ -623,6 +651,7 @@ int HipFlowEstimator::retime_device_stream(const void *d_frames, uint32_t n_fram
     const RetimeJob rt{r.num, r.den, out_frame_stride ? out_frame_stride : frame_bytes, n_pairs};
     StreamJob J(d_frames, n_frames, w, h, d_flows, d_out, stream);
     J.flow_half = flow_half, J.rt = &rt, J.project = project_;
+    J.bidir = select, J.flows_bwd = static_cast<uint8_t *>(d_flows_bwd);
     call_stream_ = stream;
     if ((rc = stream_impl(J, with_warps(p))) != kOk || !scene_) return rc;
     // behind estimate + warp, the detector and the cut pairs' in-between outputs overwritten with repeats
@@ -658,6 +687,7 @@ HipFlowEstimator::StreamJob HipFlowEstimator::StreamJob::pairs(uint32_t k0, uint
     S.frames += (size_t)k0 * frame_bytes();
     S.n_frames = n + 1;
     if (flows) S.flows += (size_t)k0 * flow_bytes();
+    if (flows_bwd) S.flows_bwd += (size_t)k0 * flow_bytes();
     if (mid && !rt) S.mid += (size_t)k0 * mid_stride();
     S.first_pair += k0;
     return S;
@@ -665,7 +695,7 @@ HipFlowEstimator::StreamJob HipFlowEstimator::StreamJob::pairs(uint32_t k0, uint
 
 hipError_t HipFlowEstimator::launch_warp_behind(const StreamJob &J, const void *flow, const void *flow_bwd)
 {
-    if (J.bidir) return launch_warp_blend_select(WarpSelectLaunch{warp_behind(J, flow), static_cast<const float *>(flow_bwd)}); // (never with J.rt)
+    if (J.bidir && !J.rt) return launch_warp_blend_select(WarpSelectLaunch{warp_behind(J, flow), static_cast<const float *>(flow_bwd)});
     if (!J.rt) return launch_warp_blend(warp_behind(J, flow));
     RetimeLaunch L;
     L.frames = J.frames, L.frame_stride = J.frame_bytes();
@@ -673,6 +703,7 @@ hipError_t HipFlowEstimator::launch_warp_behind(const StreamJob &J, const void *
     L.out = J.mid, L.out_frame_stride = J.rt->out_frame_stride, L.stream = J.stream;
     RetimeWarp V;
     V.flow = flow, V.flow_half = J.flow_half, V.fma = true, V.project = J.project;
+    if (J.bidir) V.flow_bwd = flow_bwd; // the retime select warp
     return enqueue_retime(L, V, J.first_pair + L.n_pairs == J.rt->n_pairs);
 }
 
@@ -704,9 +735,12 @@ int HipFlowEstimator::stream_impl(const StreamJob &J, const FlowParams &p)
             if ((rc = reserve((size_t)w * h * 8, kPairFlow)) != kOk) return rc;
         }
         if (J.flow_half && !J.flows && (rc = reserve(J.flow_bytes(), kFlowsHalf)) != kOk) return rc;
-        const bool bidir = J.bidir && J.mid;
+        const bool bidir = (J.bidir && J.mid) || J.flows_bwd;
         const size_t f32_bytes = (size_t)w * h * 8;
-        if (bidir && (rc = reserve(f32_bytes + (J.flow_half ? J.flow_bytes() : 0), kBwdFlows)) != kOk) return rc;
+        // (a caller's buffer takes the backward flow as the warp reads it; its f32 form needs the slot only where that is halves)
+        if (bidir && (!J.flows_bwd || J.flow_half) &&
+            (rc = reserve(f32_bytes + (J.flow_half && !J.flows_bwd ? J.flow_bytes() : 0), kBwdFlows)) != kOk)
+            return rc;
         if ((rc = build_pyramid(J.frames, kPyrA, g, J.stream)) != kOk) return rc;
         for (uint32_t k = 0; k < n_pairs; ++k) {
             const StreamJob P = J.pairs(k, 1);
@@ -721,11 +755,13 @@ int HipFlowEstimator::stream_impl(const StreamJob &J, const FlowParams &p)
             }
             const void *bwd = nullptr;
             if (bidir) { // the same pyramids the other way round (the forward flow is out of the ping-pong by now)
-                if ((rc = solve(pyr_b, pyr_a, g, p, u8(kBwdFlows), J.stream)) != kOk) return rc;
-                bwd = u8(kBwdFlows);
+                void *bf = P.flows_bwd && !J.flow_half ? static_cast<void *>(P.flows_bwd) : u8(kBwdFlows);
+                if ((rc = solve(pyr_b, pyr_a, g, p, bf, J.stream)) != kOk) return rc;
+                bwd = bf;
                 if (J.flow_half) {
-                    NUS_HIP(launch_flow_to_half(f32(kBwdFlows), u8(kBwdFlows) + f32_bytes, (size_t)w * h, J.stream));
-                    bwd = u8(kBwdFlows) + f32_bytes;
+                    void *hb = P.flows_bwd ? static_cast<void *>(P.flows_bwd) : u8(kBwdFlows) + f32_bytes;
+                    NUS_HIP(launch_flow_to_half(static_cast<const float *>(bf), hb, (size_t)w * h, J.stream));
+                    bwd = hb;
                 }
             }
             if (J.mid) NUS_HIP(launch_warp_behind(P, fl, bwd));
@@ -746,7 +782,7 @@ int HipFlowEstimator::stream_impl(const StreamJob &J, const FlowParams &p)
     };
     // set_bidirectional: two more flow buffers, 16 B -- the forward flows kept from the backward solve and the backward flows -- and
     // the backward solve's own coefficients, 12 B
-    const size_t bidir_bytes = J.bidir && J.mid ? 28 : 0;
+    const size_t bidir_bytes = (J.bidir && J.mid) || J.flows_bwd ? 28 : 0;
     uint32_t chunk = chunk_for(31 + bidir_bytes);
     if (chunk > n_pairs) chunk = n_pairs;
     for (uint32_t l = 0; l < g.levels; ++l) // (a warped level -- every one but the coarsest -- always takes coefficient planes)
@@ -813,13 +849,15 @@ int HipFlowEstimator::solve_batch(const StreamJob &J, const Pyramid &g, const Fl
         // the planes of each pair's two frames are consecutive planes of the level
         D.level[l].i1 = P.level_lum, D.level[l].i2 = P.level_lum + cells[l], D.level[l].stride = cells[l];
     }
-    const bool bidir = J.bidir && J.mid;
-    void *fwd_out = J.flows;
+    const bool bidir = (J.bidir && J.mid) || J.flows_bwd;
+    void *fwd_out = J.flows, *bwd_out = J.flows_bwd;
     if (bidir) { // the forward flows must outlive the backward solve, which runs in the same ping-pong
         if ((!fwd_out && (rc = reserve(cells[0] * pairs * (J.flow_half ? 4 : 8), kFwdFlows)) != kOk) ||
-            (rc = reserve(cells[0] * pairs * (J.flow_half ? 4 : 8), kBwdFlows)) != kOk || (rc = reserve(cells[0] * pairs * 12, kBwdCoef)) != kOk)
+            (!bwd_out && (rc = reserve(cells[0] * pairs * (J.flow_half ? 4 : 8), kBwdFlows)) != kOk) ||
+            (rc = reserve(cells[0] * pairs * 12, kBwdCoef)) != kOk)
             return rc;
         if (!fwd_out) fwd_out = u8(kFwdFlows);
+        if (!bwd_out) bwd_out = u8(kBwdFlows);
     }
     D.coef = f32(kCoef), D.flow_a = f32(kFlowA), D.flow_b = f32(kFlowB), D.out = static_cast<float *>(fwd_out);
     Solved done;
@@ -832,9 +870,9 @@ int HipFlowEstimator::solve_batch(const StreamJob &J, const Pyramid &g, const Fl
         Schedule B = D;
         B.stream_planes = false;
         for (uint32_t l = 0; l < nl; ++l) std::swap(B.level[l].i1, B.level[l].i2), B.level[l].kernel = jacobi_;
-        B.coef = f32(kBwdCoef), B.out = f32(kBwdFlows);
+        B.coef = f32(kBwdCoef), B.out = static_cast<float *>(bwd_out);
         Solved back;
-        if ((rc = solve_levels(B, back)) != kOk || (rc = place_flow(J, back, u8(kBwdFlows), kBwdFlows, flow_bwd)) != kOk) return rc;
+        if ((rc = solve_levels(B, back)) != kOk || (rc = place_flow(J, back, bwd_out, kBwdFlows, flow_bwd)) != kOk) return rc;
     }
     if (J.mid) NUS_HIP(launch_warp_behind(J, flow, flow_bwd));
     return kOk;

@@ -87,7 +87,8 @@ public:
     // interpolate_device_stream and interpolate_multi_device_stream also estimate every pair B -> A -- the same schedule on the same
     // pyramids, the two luminance planes swapped -- and warp with launch_warp_blend_select.  The forward flows are the bytes they
     // were (d_flows receives them alone); the backward ones stay in the workspace, in slots of their own which turning the setting
-    // off frees (so that off means the old workspace as well as the old kernels and bytes).  retime_device_stream refuses the setting.
+    // off frees (so that off means the old workspace as well as the old kernels and bytes).  retime_device_stream refuses the setting;
+    // estimate_both_device_stream and retime_select_device_stream, which do the same work on request, do not look at it.
     int set_bidirectional(int enabled);
     int bidirectional() const { return bidir_ ? 1 : 0; }
     // Bytes of device workspace the handle holds (the sum of its grow-only slots): what "reserves the workspace it did" is checked with.
@@ -125,6 +126,19 @@ public:
     // (0: tightly packed).  Honours warps, median, project and scene detection; the flows at d_flows are the estimate's.
     int retime_device_stream(const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t h, const FlowParams &p, uint32_t num,
                              uint32_t den, bool flow_half, void *d_flows, void *d_out, size_t out_frame_stride, hipStream_t stream);
+    // Both flows of every pair of the stream (nus_flow_estimate_both_device_stream), f32: d_flows_fwd receives the bytes of
+    // estimate_device_stream, d_flows_bwd pair k's flow frame k+1 -> frame k on frame k+1's grid -- the backward solve of
+    // set_bidirectional (the same pyramids, the two planes swapped, the handle's warps and median), written to the caller's buffer
+    // instead of kBwdFlows.  Does not look at the bidirectional setting.
+    int estimate_both_device_stream(const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t h, const FlowParams &p, void *d_flows_fwd,
+                                    void *d_flows_bwd, hipStream_t stream);
+    // retime_device_stream with both flows and the select warp (nus_flow_retime_select_device_stream): the bytes of
+    // estimate_both_device_stream followed by HipFrameInterpolator::retime_select_device in FMA mode.  Either flow pointer may be
+    // null: that direction then stays in the workspace.  Does not look at the bidirectional setting; at most 28 bytes per pixel and
+    // pair of a chunk more workspace than retime_device_stream.
+    int retime_select_device_stream(const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t h, const FlowParams &p, uint32_t num,
+                                    uint32_t den, bool flow_half, void *d_flows_fwd, void *d_flows_bwd, void *d_out, size_t out_frame_stride,
+                                    hipStream_t stream);
 
 private:
     // The grow-only device workspace.  Slots 0, 1, 4 and 5 have two names: the pair path's (plan / build_pyramid / solve, and the
@@ -170,6 +184,8 @@ private:
         uint32_t first_pair = 0;                  // of this job in the stream (the rate conversion's schedule is global)
         uint32_t project = 0;                     // the warp's projection rounds (set_project)
         bool bidir = false;                       // with mid: the flows B -> A as well, and the select warp (set_bidirectional)
+        uint8_t *flows_bwd = nullptr;             // the caller's buffer for the flows B -> A (the *_both_* / *_select_* entry points):
+                                                  // with it the backward solve runs without mid too
         hipStream_t stream = nullptr;
         size_t frame_bytes() const { return (size_t)w * h * 4; }
         size_t flow_bytes() const { return (size_t)w * h * (flow_half ? 4 : 8); }
@@ -240,9 +256,14 @@ private:
     static constexpr uint32_t kStreamMaxChunkPairs = 150;
     static constexpr size_t kStreamWorkspaceBytes = (size_t)12 << 30;
     int stream_impl(const StreamJob &J, const FlowParams &p);
+    // what retime_device_stream and retime_select_device_stream share: the checks, the job, the cut rule behind it
+    int retime_stream_call(const char *who, bool select, const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t h, const FlowParams &p,
+                           uint32_t num, uint32_t den, bool flow_half, void *d_flows, void *d_flows_bwd, void *d_out, size_t out_frame_stride,
+                           hipStream_t stream);
     int solve_batch(const StreamJob &J, const Pyramid &g, const FlowParams &p); // J: one chunk
     static WarpLaunch warp_behind(const StreamJob &J, const void *flow); // the warp kernel behind the estimator, over J's pairs
-    // ... launched; J.rt: the retime warp and the real frames; J.bidir: the select warp with the flows B -> A at flow_bwd
+    // ... launched; J.rt: the retime warp and the real frames; J.bidir: the select warp with the flows B -> A at flow_bwd (with J.rt:
+    // the retime select warp)
     static hipError_t launch_warp_behind(const StreamJob &J, const void *flow, const void *flow_bwd = nullptr);
     int ensure_device();
     static constexpr uint64_t kMaxPixels = (1ull << 28) - 1;

@@ -299,6 +299,10 @@ public:
     // handle's settings, a real-frame output the zero-flow copy.  One warp launch and one copy launch; enqueue only.
     int retime_device(const void *d_frames, size_t frame_stride, uint32_t n_frames, const void *d_flows, uint32_t w, uint32_t h,
                       uint32_t num, uint32_t den, void *d_out, size_t out_frame_stride, hipStream_t stream);
+    // ... with the select warp (nus_interp_retime_select_device): two flows per pair, pair k's forward plane on frame k's grid and its
+    // backward plane on frame k + 1's, both required; an in-between output is byte for byte interpolate_select_device's at t_j.
+    int retime_select_device(const void *d_frames, size_t frame_stride, uint32_t n_frames, const void *d_flows_fwd, const void *d_flows_bwd,
+                             uint32_t w, uint32_t h, uint32_t num, uint32_t den, void *d_out, size_t out_frame_stride, hipStream_t stream);
     const char *name() const override { return "HipWarpBlendInterpolator"; }
     const char *last_error() const override { return error_.c_str(); }
     int set_device(int device);
@@ -331,6 +335,9 @@ private:
     int device_call(const char *who, const void *d_a, size_t a_stride, const void *d_b, size_t b_stride, const void *d_flow,
                     const void *d_flow_bwd, bool select, uint32_t w, uint32_t h, float t, const float *times, uint32_t n_times, bool multi,
                     void *d_out, size_t out_pair_stride, uint32_t n_pairs, hipStream_t stream);
+    // the two rate-conversion entry points: lock, the checks they share, the warp launch and the copy launch
+    int retime_call(const char *who, const void *d_frames, size_t frame_stride, uint32_t n_frames, const void *d_flows, const void *d_flows_bwd,
+                    bool select, uint32_t w, uint32_t h, uint32_t num, uint32_t den, void *d_out, size_t out_frame_stride, hipStream_t stream);
 
     mutable std::mutex mu_;
     int wg_preset_;

@@ -310,14 +310,32 @@ int HipFrameInterpolator::device_call(const char *who, const void *d_a, size_t a
 int HipFrameInterpolator::retime_device(const void *d_frames, size_t frame_stride, uint32_t n_frames, const void *d_flows, uint32_t w,
                                         uint32_t h, uint32_t num, uint32_t den, void *d_out, size_t out_frame_stride, hipStream_t stream)
 {
-    static const char *const who = "nus_interp_retime_device";
+    return retime_call("nus_interp_retime_device", d_frames, frame_stride, n_frames, d_flows, nullptr, false, w, h, num, den, d_out,
+                       out_frame_stride, stream);
+}
+
+int HipFrameInterpolator::retime_select_device(const void *d_frames, size_t frame_stride, uint32_t n_frames, const void *d_flows_fwd,
+                                               const void *d_flows_bwd, uint32_t w, uint32_t h, uint32_t num, uint32_t den, void *d_out,
+                                               size_t out_frame_stride, hipStream_t stream)
+{
+    return retime_call("nus_interp_retime_select_device", d_frames, frame_stride, n_frames, d_flows_fwd, d_flows_bwd, true, w, h, num, den,
+                       d_out, out_frame_stride, stream);
+}
+
+int HipFrameInterpolator::retime_call(const char *who, const void *d_frames, size_t frame_stride, uint32_t n_frames, const void *d_flows,
+                                      const void *d_flows_bwd, bool select, uint32_t w, uint32_t h, uint32_t num, uint32_t den, void *d_out,
+                                      size_t out_frame_stride, hipStream_t stream)
+{
     std::lock_guard<std::mutex> lk(mu_);
+    if (select && (!d_flows || !d_flows_bwd)) return fail(kInvalidArgument, fmt("%s: null flow pointer (the select warp takes both flows)", who));
     RetimeRatio r;
     int st = pass(check_retime(who, n_frames, num, den, r));
     if (st != kOk || (st = pass(check_dims(who, w, h, kMaxPixels))) != kOk) return st;
     if (!d_frames || !d_out) return fail(kInvalidArgument, fmt("%s: null device pointer", who));
     const size_t frame_bytes = (size_t)w * h * 4;
     if ((st = pass(check_pixel_aligned(who, d_frames, frame_stride, d_frames, frame_stride, d_out, d_flows, flow_half_ ? 4 : 8))) != kOk) return st;
+    if (select && (st = pass(check_pixel_aligned(who, d_frames, frame_stride, d_frames, frame_stride, d_out, d_flows_bwd, flow_half_ ? 4 : 8))) != kOk)
+        return st;
     if (frame_stride < frame_bytes)
         return fail(kInvalidArgument, fmt("%s: frame_stride %zu is smaller than a %ux%u frame (%zu bytes)", who, frame_stride, w, h, frame_bytes));
     if ((st = pass(check_out_frame_stride(who, out_frame_stride, frame_bytes))) != kOk) return st;
@@ -330,8 +348,9 @@ int HipFrameInterpolator::retime_device(const void *d_frames, size_t frame_strid
     L.in_sel = input_selector(in_format_), L.stream = stream;
     RetimeWarp V;
     V.flow = d_flows, V.flow_half = flow_half_, V.fma = fma_, V.project = d_flows ? project_ : 0;
+    V.flow_bwd = select ? d_flows_bwd : nullptr;
     const hipError_t e = enqueue_retime(L, V, true);
-    if (e != hipSuccess) return fail_hip(e, "retime warp+blend launch");
+    if (e != hipSuccess) return fail_hip(e, select ? "retime select warp+blend launch" : "retime warp+blend launch");
     return kOk;
 }
 

@@ -8,7 +8,10 @@
 //                    (t, frame) from the launch's TimeSet and pair_out + k * frame_bytes, these take them from the schedule.  The
 //                    per-pixel code is the same, so an in-between output is byte for byte the single-time kernel's at t_j.  A pair's
 //                    vectors are fetched once for all its outputs; a pair without in-between outputs leaves after the schedule.
+//   k_retime_flow_sel             warp_select_tile_at (nus_warp_select_device.hpp) with both flows of every pair and the schedule: the
+//                    select warp's per-pixel code, so an in-between output is byte for byte k_warp_blend_flow_sel's at t_j.
 //   k_retime_warp_tiny<KIND>      the three families' one-pixel-per-thread forms (frames the tile does not take: warp_corner_ok).
+//   k_retime_flow_sel_tiny        ... and the select warp's (k_warp_blend_flow_sel_tiny's body).
 //   k_retime_blend   the zero-flow streaming blend (k_blend_zero_flow's arithmetic).
 //   k_retime_real    REAL-FRAME OUTPUTS (r_j == 0, the stream's last frame included) COME FROM THIS COPY KERNEL OF ITS OWN, not from
 //                    the warps: frame k with (k num) % den == 0 goes through the input selector to output k num / den -- the bytes
@@ -19,6 +22,7 @@
 // Output j of the stream is at out + j * out_frame_stride; gaps are never written.  No atomics, no LDS, no scratch.
 #include "nus_device.hpp"
 #include "nus_retime.hpp"
+#include "nus_warp_select_device.hpp"
 #include "nus_warp_sources.hpp"
 
 namespace nus {
@@ -74,6 +78,34 @@ __global__ __launch_bounds__(256) void k_retime_flow_proj(const uint8_t *__restr
     warp_blend_tile_at<MODE, XV, RV>(a, b, frame_stride, frame_stride, w, h, sel, src, T);
 }
 
+// The schedule for the select tile, whose loop over the outputs is the register-heaviest of the unit: `num` is made opaque per output,
+// in a scalar register, so that the division's loop-invariant half (the conversion and reciprocal of num) is not hoisted into
+// vector registers that would then live across the whole tile, and the wave-uniform quotient goes back into a scalar register, as the
+// multi-time kernel's times are (the tile makes its own per-lane copy).  The same division, the same t_j.
+struct RetimeSelTimes : RetimeTimes {
+    __device__ __forceinline__ RetimeSelTimes(const RetimeArgs &R, uint32_t local_pair) : RetimeTimes(R, local_pair) {}
+    __device__ __forceinline__ float time(uint32_t k) const
+    {
+        uint32_t n = num;
+        asm volatile("" : "+s"(n));
+        return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(retime_time(rem + k * den, n))));
+    }
+};
+
+// Both flows of the pair, each pixel warped with the vector whose two samples agree better.  The pair's own vectors of both flows are
+// loaded once for all its outputs; the projection rounds depend on t and run per output.
+// The occupancy asked for is the multi-time select kernel's of the same form or better (7 waves per SIMD with f32 flows, 8 with
+// halves): left alone, the register allocator ends one register above the f32 pair form's step.
+template <int MODE, bool HALF, int XV, int RV>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HALF ? 8 : 7))) void k_retime_flow_sel(
+    const uint8_t *__restrict__ a, const uint8_t *__restrict__ b, const void *__restrict__ flow_fwd, const void *__restrict__ flow_bwd,
+    size_t frame_stride, uint32_t w, uint32_t h, RetimeArgs R, uint32_t sel, uint32_t rounds)
+{
+    const RetimeSelTimes T(R, blockIdx.z);
+    if (T.count() == 0) return;
+    warp_select_tile_at<MODE, HALF, XV, RV>(a, b, flow_fwd, flow_bwd, frame_stride, frame_stride, w, h, sel, rounds, T);
+}
+
 template <int MODE, int XV, int RV>
 __global__ __launch_bounds__(256) void k_retime_bm(const uint8_t *__restrict__ a, const uint8_t *__restrict__ b,
                                                    const short2 *__restrict__ vectors, size_t frame_stride, uint32_t w, uint32_t h,
@@ -115,6 +147,39 @@ __global__ __launch_bounds__(256) void k_retime_warp_tiny(const uint8_t *__restr
             for (uint32_t r = 0; r < rounds; ++r) g = project_round_plain(plane, half, w, h, (float)x, (float)y, g, t);
         const uint32_t o = warp_blend_pixel_plain(fa, fb, w, h, x, y, g, t, 1.0f - t);
         T.frame(k, npx)[pix] = KIND == kTinyBlocks ? o : swz(o, sel);
+    }
+}
+
+// The select warp's one-pixel-per-thread form: the body of k_warp_blend_flow_sel_tiny with the schedule's times.
+__global__ __launch_bounds__(256) void k_retime_flow_sel_tiny(const uint8_t *__restrict__ a, const uint8_t *__restrict__ b,
+                                                              const void *__restrict__ flow_fwd, const void *__restrict__ flow_bwd, bool half,
+                                                              size_t frame_stride, uint32_t w, uint32_t h, RetimeArgs R, uint32_t sel,
+                                                              uint32_t rounds)
+{
+    const uint32_t y = blockIdx.y * 4 + threadIdx.y, x = blockIdx.x * kWave + threadIdx.x;
+    if (y >= h || x >= w) return;
+    const RetimeTimes T(R, blockIdx.z);
+    const size_t npx = (size_t)w * h, pix = (size_t)y * w + x;
+    const uint32_t *fa = reinterpret_cast<const uint32_t *>(a + (size_t)blockIdx.z * frame_stride);
+    const uint32_t *fb = reinterpret_cast<const uint32_t *>(b + (size_t)blockIdx.z * frame_stride);
+    const size_t plane_bytes = npx * (half ? 4 : 8); // the pair's own planes
+    const void *const pf = static_cast<const uint8_t *>(flow_fwd) + (size_t)blockIdx.z * plane_bytes;
+    const void *const pr = static_cast<const uint8_t *>(flow_bwd) + (size_t)blockIdx.z * plane_bytes;
+    const float2 f = half ? half2_bits_to_float2(static_cast<const uint32_t *>(pf)[pix]) : static_cast<const float2 *>(pf)[pix];
+    const float2 rv = half ? half2_bits_to_float2(static_cast<const uint32_t *>(pr)[pix]) : static_cast<const float2 *>(pr)[pix];
+    for (uint32_t k = 0; k < T.count(); ++k) {
+        const float t = T.time(k), nt = 1.0f - t;
+        float2 gf = f, gb = rv;
+        for (uint32_t r = 0; r < rounds; ++r) {
+            gf = project_round_plain(pf, half, w, h, (float)x, (float)y, gf, t);
+            gb = project_round_plain(pr, half, w, h, (float)x, (float)y, gb, nt);
+        }
+        float4 saf, sbf, sar, sbr;
+        warp_sample_pair_plain(fa, fb, w, h, x, y, gf, t, nt, saf, sbf);
+        warp_sample_pair_plain(fa, fb, w, h, x, y, make_float2(-gb.x, -gb.y), t, nt, sar, sbr);
+        const bool back = warp_sample_error(sar, sbr) < warp_sample_error(saf, sbf);
+        const uint32_t o = back ? warp_blend_pack(sar, sbr, t, nt) : warp_blend_pack(saf, sbf, t, nt);
+        T.frame(k, npx)[pix] = swz(o, sel);
     }
 }
 
@@ -231,6 +296,7 @@ inline StreamShape stream_shape(const RetimeLaunch &L, const uint8_t *frames)
 hipError_t launch_retime_warp(const RetimeLaunch &L, const RetimeWarp &V)
 {
     if (!retime_launch_ok(L) || V.project > kFlowMaxProject) return hipErrorInvalidValue;
+    if (V.flow_bwd != nullptr && (V.flow == nullptr || V.vectors != nullptr)) return hipErrorInvalidValue; // the select warp takes both flows, and flows only
     const size_t npx = (size_t)L.w * L.h;
     const uint32_t cell_bytes = V.flow_half ? 4 : 8;
     uint32_t lg = 3;
@@ -265,6 +331,22 @@ hipError_t launch_retime_warp(const RetimeLaunch &L, const RetimeWarp &V)
             return;
         }
         const void *fl = static_cast<const uint8_t *>(V.flow) + (size_t)done * npx * cell_bytes;
+        if (V.flow_bwd != nullptr) { // the select warp, with or without projection rounds
+            const void *fr = static_cast<const uint8_t *>(V.flow_bwd) + (size_t)done * npx * cell_bytes;
+            if (!warp_corner_ok(L.w, L.h, cell_bytes)) {
+                hipLaunchKernelGGL(k_retime_flow_sel_tiny, warp_grid(L.w, L.h, 1, 1, n), block, 0, L.stream, a, b, fl, fr, V.flow_half,
+                                   L.frame_stride, L.w, L.h, R, L.in_sel, V.project);
+                return;
+            }
+#define NUS_RS(M, H) {k_retime_flow_sel<M, H, 1, kSelRV[0]>, k_retime_flow_sel<M, H, 2, kSelRV[1]>}
+            static constexpr decltype(&k_retime_flow_sel<kWarpExact, false, 1, kSelRV[0]>) kernels[2][2][2] = { // [fma][half][pair]
+                {NUS_RS(kWarpExact, false), NUS_RS(kWarpExact, true)}, {NUS_RS(kWarpFma, false), NUS_RS(kWarpFma, true)}};
+#undef NUS_RS
+            // (the select tile's rows per thread are its own: kSelRV, not kWarpRV)
+            hipLaunchKernelGGL(kernels[V.fma][V.flow_half][pair_ok], warp_grid(L.w, L.h, pair_ok ? 2 : 1, kSelRV[pair_ok], n), block, 0, L.stream, a,
+                               b, fl, fr, L.frame_stride, L.w, L.h, R, L.in_sel, V.project);
+            return;
+        }
         if (V.project > 0) {
             if (!warp_corner_ok(L.w, L.h, cell_bytes)) {
                 hipLaunchKernelGGL(k_retime_warp_tiny<kTinyProjected>, warp_grid(L.w, L.h, 1, 1, n), block, 0, L.stream, a, b, fl, V.flow_half,

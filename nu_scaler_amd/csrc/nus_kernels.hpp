@@ -431,6 +431,8 @@ struct RetimeLaunch {
 // blended and stored -- warp_blend_tile with the schedule as its time source, fed from the vector source given:
 //   vectors != nullptr  block vectors at block size bs (launch_bm_warp's layout; RGBA frames, no selector);
 //   flow != nullptr     dense flow, 2 x f32 or 2 x f16 per pixel, with `project` rounds of the projection (launch_warp_blend's);
+//   flow and flow_bwd   the select warp (launch_warp_blend_select's): flow_bwd is the flow B -> A of every pair on B's grid, in
+//                       flow's format and layout, with `project` rounds on both.  flow_bwd with vectors, or without flow: refused;
 //   neither             zero flow: the streaming blend.
 // Real-frame outputs are NOT written here: launch_retime_real.
 struct RetimeWarp {
@@ -439,6 +441,7 @@ struct RetimeWarp {
     uint32_t project = 0;
     const int16_t *vectors = nullptr;
     uint32_t bs = 16;
+    const void *flow_bwd = nullptr;
 };
 hipError_t launch_retime_warp(const RetimeLaunch &L, const RetimeWarp &V);
 // The real-frame outputs (r_j == 0) among the n_frames frames that start at the launch's first one (L.frames is frame

@@ -127,7 +127,8 @@ class FlowEstimator:
         `interpolate_device_stream` and `interpolate_multi_device_stream` also estimate every pair B -> A on the same pyramids, and
         each output pixel is warped with the forward vector or the negated backward one, whichever makes its sample of A and its
         sample of B agree better.  The flows handed out are the forward ones, unchanged; the estimate entry points are not
-        affected; `retime_device_stream` refuses the setting (ValueError)."""
+        affected; `retime_device_stream` refuses the setting (ValueError) -- rate conversion with the select warp is
+        `retime_select_device_stream`, which does not look at it."""
         if not isinstance(enabled, (bool, np.bool_)) and enabled not in (0, 1):
             raise ValueError(f"bidirectional must be a bool, got {enabled!r}")
         self._check(self._lib.nus_flow_set_bidirectional(self._h, 1 if enabled else 0))
@@ -331,5 +332,35 @@ class FlowEstimator:
                                                      self.coarse_iterations, self.refine_iterations, self.lambda_, int(num), int(den), fmt,
                                                      d_flows or None, d_out or None, int(out_frame_stride), stream or None)
         if st == C.ERR_INVALID_ARGUMENT and self.bidirectional:  # refused before any GPU work: the C text
+            raise ValueError(self._lib.nus_flow_last_error(self._h).decode("utf-8", "replace"))
+        self._check(st)
+
+    def estimate_both_device_stream(self, d_frames: int, n_frames: int, width: int, height: int, d_flows_fwd: int, d_flows_bwd: int,
+                                    stream: int = 0) -> None:
+        """Both flows of every pair (nus_flow_estimate_both_device_stream), f32: `d_flows_fwd` receives the bytes of
+        `estimate_device_stream`, `d_flows_bwd` pair k's flow frame k+1 -> frame k on frame k+1's grid -- the backward solve of
+        `set_bidirectional`, handed out.  Does not look at that setting.  Argument errors raise ValueError before any GPU work."""
+        st = self._lib.nus_flow_estimate_both_device_stream(self._h, d_frames or None, int(n_frames), int(width), int(height), self.levels,
+                                                            self.coarse_iterations, self.refine_iterations, self.lambda_,
+                                                            d_flows_fwd or None, d_flows_bwd or None, stream or None)
+        if st == C.ERR_INVALID_ARGUMENT:
+            raise ValueError(self._lib.nus_flow_last_error(self._h).decode("utf-8", "replace"))
+        self._check(st)
+
+    def retime_select_device_stream(self, d_frames: int, n_frames: int, width: int, height: int, num: int, den: int, d_out: int,
+                                    d_flows_fwd: int = 0, d_flows_bwd: int = 0, out_frame_stride: int = 0, stream: int = 0,
+                                    flow_format: str = "f32") -> None:
+        """`retime_device_stream` with both flows of every pair and the select warp (nus_flow_retime_select_device_stream): the
+        bytes of `estimate_both_device_stream` followed by `WgpuFrameInterpolator.retime_select_device` in FMA mode.  The flows at
+        `d_flows_fwd` / `d_flows_bwd` where those are not 0.  Does not look at `set_bidirectional`.  Argument errors raise
+        ValueError before any GPU work."""
+        fmt = {"f32": 0, "f16": 1}.get(flow_format)
+        if fmt is None:
+            raise ValueError("flow_format must be 'f32' or 'f16'")
+        st = self._lib.nus_flow_retime_select_device_stream(self._h, d_frames or None, int(n_frames), int(width), int(height), self.levels,
+                                                            self.coarse_iterations, self.refine_iterations, self.lambda_, int(num),
+                                                            int(den), fmt, d_flows_fwd or None, d_flows_bwd or None, d_out or None,
+                                                            int(out_frame_stride), stream or None)
+        if st == C.ERR_INVALID_ARGUMENT:
             raise ValueError(self._lib.nus_flow_last_error(self._h).decode("utf-8", "replace"))
         self._check(st)

@@ -320,10 +320,13 @@ def retime_output_paths(pattern: str, n_out: int) -> list[str]:
 
 def retime_image_files(output_pattern: str, input_paths, fps_in, fps_out, method: str = "optical_flow", *, device: int = 0,
                        scene_detect: bool = False, bidirectional: bool = False, flow_warps: int = 0, flow_median: int = 0,
-                       flow_project: int = 0) -> list[str]:
+                       flow_project: int = 0, flow_bidirectional: bool = False) -> list[str]:
     """PNG frames at `fps_in` -> PNG frames at `fps_out`, written to `output_pattern % j` (retime.py has the schedule): method
     "optical_flow" (Horn-Schunck, the estimator's defaults), "block_matching" (the Medium preset) or "blend" (zero flow).
-    Returns the paths written."""
+    `flow_bidirectional` (optical_flow only): every pair's flow is estimated both ways and each pixel takes the vector whose two
+    samples agree better (retime_frames' `select`).  Returns the paths written."""
+    if flow_bidirectional and method != "optical_flow":
+        raise ValueError("flow_bidirectional needs method optical_flow")
     import torch  # noqa: F401  (the device buffers are torch's: its HIP runtime has to be loaded before the library loads its own)
 
     from .retime import retime_count, retime_frames
@@ -354,7 +357,8 @@ def retime_image_files(output_pattern: str, input_paths, fps_in, fps_out, method
             if flow_project:
                 warp.set_flow_project(flow_project)
         scene = SceneDetector(device=device) if scene_detect else None
-        out = retime_frames(frames, w, h, fps_in, fps_out, warp=warp, flow=flow, scene=scene, device=device)
+        out = retime_frames(frames, w, h, fps_in, fps_out, warp=warp, flow=flow, scene=scene, device=device,
+                            select=bool(flow_bidirectional))
     for path, px in zip(paths, out):
         write_png(path, w, h, px)
     return paths

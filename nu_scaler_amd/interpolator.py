@@ -196,6 +196,18 @@ class WgpuFrameInterpolator:
             raise ValueError(self._err())
         self._raise(st)
 
+    def retime_select_device(self, d_frames: int, frame_stride: int, n_frames: int, d_flows_fwd: int, d_flows_bwd: int, width: int,
+                             height: int, num: int, den: int, d_out: int, out_frame_stride: int = 0, stream: int = 0) -> None:
+        """nus_interp_retime_select_device: `retime_device` with both flows of every pair and the select warp -- pair k's forward
+        plane on frame k's grid, its backward plane on frame k + 1's, both required, in the handle's flow format.  Argument errors
+        raise ValueError before any GPU work."""
+        st = self._lib.nus_interp_retime_select_device(self._h, d_frames or None, int(frame_stride), int(n_frames), d_flows_fwd or None,
+                                                       d_flows_bwd or None, int(width), int(height), int(num), int(den), d_out or None,
+                                                       int(out_frame_stride), stream or None)
+        if st == C.ERR_INVALID_ARGUMENT:
+            raise ValueError(self._err())
+        self._raise(st)
+
     # -- trait FrameInterpolator (nu_scaler_core/src/interpolation/mod.rs:29-44; dead code in the reference, same shape here)
     def initialize(self, width: int, height: int) -> None:
         self._raise(self._lib.nus_interp_initialize(self._h, int(width), int(height)))

@@ -80,17 +80,21 @@ def library_schedule(n_frames: int, num: int, den: int, first: int = 0, count: i
 
 
 def retime_frames(frames, w: int, h: int, fps_in, fps_out, *, matcher=None, warp=None, flow=None, scene=None,
-                  device: int = 0) -> list[bytes]:
+                  device: int = 0, select: bool = False) -> list[bytes]:
     """Host frames (w*h*4 bytes each) -> the host frames of the conversion, through the device entry points: one upload, then
     `matcher.retime_stream_device` (a BlockMatcher, EXACT mode, its own scene detection), or -- with `warp`, a
     WgpuFrameInterpolator -- `flow.estimate_device_stream` (a FlowEstimator; None: zero flow) and `warp.retime_device`, with `scene`
     (a SceneDetector or None) the detector over all pairs and nus_scene_apply_cuts_retime_device behind it; one download.
+    `select` (with `flow` and `warp`): both flows of every pair, `flow.estimate_both_device_stream`, and the select warp,
+    `warp.retime_select_device`; scene detection behind it as before.
     The device buffers are torch tensors, so -- as for every device-resident use of the package -- a process imports torch before
     the first call that loads the library (the handles' constructors included)."""
     import torch
 
     from . import transfer
 
+    if select and (flow is None or warp is None):
+        raise ValueError("select needs a flow estimator and a warp (flow=..., warp=...)")
     frames = list(frames)
     n, fb = len(frames), int(w) * int(h) * 4
     num, den = retime_ratio(fps_in, fps_out)
@@ -115,11 +119,17 @@ def retime_frames(frames, w: int, h: int, fps_in, fps_out, *, matcher=None, warp
             matcher.retime_stream_device(d_in.data_ptr(), fb, n, w, h, num, den, d_ws, ws_bytes, d_out.data_ptr(), stream=s)
         else:
             flows = None
-            if flow is not None:
-                flows = torch.empty((n - 1, h, w, 2), dtype=torch.float32, device=dev)
-                flow.estimate_device_stream(d_in.data_ptr(), n, w, h, flows.data_ptr(), s)
-            d_flows = flows.data_ptr() if flows is not None else 0
-            warp.retime_device(d_in.data_ptr(), fb, n, d_flows, w, h, num, den, d_out.data_ptr(), 0, s)
+            if select:
+                flows = torch.empty((2, max(n - 1, 1), h, w, 2), dtype=torch.float32, device=dev)
+                flow.estimate_both_device_stream(d_in.data_ptr(), n, w, h, flows[0].data_ptr(), flows[1].data_ptr(), s)
+                warp.retime_select_device(d_in.data_ptr(), fb, n, flows[0].data_ptr(), flows[1].data_ptr(), w, h, num, den,
+                                          d_out.data_ptr(), 0, s)
+            else:
+                if flow is not None:
+                    flows = torch.empty((n - 1, h, w, 2), dtype=torch.float32, device=dev)
+                    flow.estimate_device_stream(d_in.data_ptr(), n, w, h, flows.data_ptr(), s)
+                d_flows = flows.data_ptr() if flows is not None else 0
+                warp.retime_device(d_in.data_ptr(), fb, n, d_flows, w, h, num, den, d_out.data_ptr(), 0, s)
             if scene is not None:
                 ws_bytes = scene.workspace_size(w, h, n - 1)
                 ws, d_ws = scratch(ws_bytes)

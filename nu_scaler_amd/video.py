@@ -67,7 +67,8 @@ def default_window_frames(w: int, h: int, num: int, den: int, scale: int, device
     return max(den + 1, int(free.value // 4 // window_bytes_per_frame(w, h, num, den, scale)))
 
 
-def check_convert_args(fps_in, fps_out, multiplier, method, scale, bidirectional) -> tuple[Fraction, int, int]:
+def check_convert_args(fps_in, fps_out, multiplier, method, scale, bidirectional, *,
+                       flow_bidirectional: bool = False) -> tuple[Fraction, int, int]:
     """The usage rules of `convert_y4m` that need no file and no device: (fps_out, num, den); ValueError otherwise."""
     from .retime import retime_ratio
 
@@ -83,6 +84,8 @@ def check_convert_args(fps_in, fps_out, multiplier, method, scale, bidirectional
         raise ValueError(f"method must be optical_flow, block_matching or blend, got {method}")
     if bidirectional and method != "block_matching":
         raise ValueError("bidirectional needs method block_matching")
+    if flow_bidirectional and method != "optical_flow":
+        raise ValueError("flow_bidirectional needs method optical_flow")
     if isinstance(scale, bool) or not isinstance(scale, int) or not 1 <= scale <= 4:
         raise ValueError(f"scale must be an integer from 1 to 4, got {scale!r}")
     return fps_out, num, den
@@ -92,8 +95,10 @@ class _Route:
     """The handles of one conversion and the device-resident retime of a window: `retime.retime_frames`' route without its upload
     and download."""
 
-    def __init__(self, method, device, scene_detect, flow_warps, flow_median, flow_project, bidirectional):
+    def __init__(self, method, device, scene_detect, flow_warps, flow_median, flow_project, bidirectional,
+                 flow_bidirectional: bool = False):
         self.matcher = self.warp = self.flow = self.scene = None
+        self.select = bool(flow_bidirectional) and method == "optical_flow"  # both flows of every pair and the select warp
         if method == "block_matching":
             from .blockmatch import BlockMatcher
 
@@ -129,12 +134,18 @@ class _Route:
             self.matcher.retime_stream_device(d_in, fb, n, w, h, num, den, scratch(ws_bytes), ws_bytes, d_out, stream=s)
             return keep
         d_flows = 0
-        if self.flow is not None:
-            flows = torch.empty((n - 1, h, w, 2), dtype=torch.float32, device=dev)
+        if self.select:
+            flows = torch.empty((2, n - 1, h, w, 2), dtype=torch.float32, device=dev)
             keep.append(flows)
-            self.flow.estimate_device_stream(d_in, n, w, h, flows.data_ptr(), s)
-            d_flows = flows.data_ptr()
-        self.warp.retime_device(d_in, fb, n, d_flows, w, h, num, den, d_out, 0, s)
+            self.flow.estimate_both_device_stream(d_in, n, w, h, flows[0].data_ptr(), flows[1].data_ptr(), s)
+            self.warp.retime_select_device(d_in, fb, n, flows[0].data_ptr(), flows[1].data_ptr(), w, h, num, den, d_out, 0, s)
+        else:
+            if self.flow is not None:
+                flows = torch.empty((n - 1, h, w, 2), dtype=torch.float32, device=dev)
+                keep.append(flows)
+                self.flow.estimate_device_stream(d_in, n, w, h, flows.data_ptr(), s)
+                d_flows = flows.data_ptr()
+            self.warp.retime_device(d_in, fb, n, d_flows, w, h, num, den, d_out, 0, s)
         if self.scene is not None:
             ws_bytes = self.scene.workspace_size(w, h, n - 1)
             d_ws, d_cut = scratch(ws_bytes), scratch(n - 1)
@@ -146,10 +157,11 @@ class _Route:
 
 def convert_y4m(in_path, out_path, *, fps_out=None, multiplier=None, method: str = "optical_flow", scale: int = 1,
                 algorithm: str = "lanczos3", window_frames=None, matrix=None, device: int = 0, scene_detect: bool = False,
-                flow_warps: int = 0, flow_median: int = 0, flow_project: int = 0, bidirectional: bool = False) -> dict:
+                flow_warps: int = 0, flow_median: int = 0, flow_project: int = 0, bidirectional: bool = False,
+                flow_bidirectional: bool = False) -> dict:
     """IN.y4m at its rate -> OUT.y4m at `fps_out` (an int or a Fraction) or at `multiplier` times the input's rate, every output
     frame `scale` times as large with `algorithm` when scale > 1.  method "optical_flow" (Horn-Schunck, the estimator's defaults,
-    with flow_warps / flow_median / flow_project), "block_matching" (the Medium preset; `bidirectional`: its forward-backward
+    with flow_warps / flow_median / flow_project; `flow_bidirectional`: both flows of every pair and the select warp), "block_matching" (the Medium preset; `bidirectional`: its forward-backward
     check) or "blend" (zero flow); `scene_detect`: repeats instead of blends across a cut.  matrix "bt601" | "bt709" (None: by the
     input's height); the range and the chroma siting are the input's, the chroma is up-sampled bilinearly.  window_frames: input
     frames on the device at a time (None: from the device's free memory), at least den + 1 of the reduced ratio.  The output
@@ -161,7 +173,8 @@ def convert_y4m(in_path, out_path, *, fps_out=None, multiplier=None, method: str
     from .y4m import Y4MReader, Y4MWriter
 
     with Y4MReader(in_path) as rd:
-        fps_out, num, den = check_convert_args(rd.fps, fps_out, multiplier, method, scale, bidirectional)
+        fps_out, num, den = check_convert_args(rd.fps, fps_out, multiplier, method, scale, bidirectional,
+                                                flow_bidirectional=flow_bidirectional)
         w, h = rd.width, rd.height
         ow, oh = w * scale, h * scale
         if matrix is None:
@@ -173,7 +186,7 @@ def convert_y4m(in_path, out_path, *, fps_out=None, multiplier=None, method: str
         if window_frames < den + 1:
             raise ValueError(f"a window needs at least den + 1 = {den + 1} frames for the ratio {num}/{den}, got {window_frames}")
         step = (window_frames - 1) // den * den
-        route = _Route(method, device, scene_detect, flow_warps, flow_median, flow_project, bidirectional)
+        route = _Route(method, device, scene_detect, flow_warps, flow_median, flow_project, bidirectional, flow_bidirectional)
         up = None
         if scale > 1:
             from .upscaler import PyWgpuUpscaler

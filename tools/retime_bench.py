@@ -2,16 +2,20 @@
 """Device-resident timing of the frame-rate conversion by a rational ratio (the nus_*_retime_* entry points) against the route a
 caller had to take before they existed: one multi-time call per pair with that pair's times plus a hipMemcpyDtoDAsync per real
 frame, the schedule walked on the host.  A stream of 121 frames of 1080p (1 GB of frames, every frame the one before moved by a few
-pixels, as tools/flow_warps_bench.py), the ratios 5/2, 12/5 and 2/5, three legs:
+pixels, as tools/flow_warps_bench.py), the ratios 5/2, 12/5 and 2/5, five legs:
   dense   flows given: nus_interp_retime_device  |  per pair nus_interp_interpolate_multi_device (FMA warp on both sides);
   flow    estimator + warp, FAST mode: nus_flow_retime_device_stream  |  nus_flow_estimate_device_stream, then the dense per-pair
           route in FMA mode;
   bm      block matching, Medium preset: nus_bm_retime_device_stream  |  nus_bm_estimate_device over all pairs, then per pair
-          nus_bm_warp_device (EXACT on both sides).
+          nus_bm_warp_device (EXACT on both sides);
+  select  both flows given, the select warp: nus_interp_retime_select_device  |  per pair nus_interp_interpolate_select_device with that
+          pair's times (FMA on both sides);
+  select_flow   estimator both ways + select warp, FAST mode: nus_flow_retime_select_device_stream  |
+          nus_flow_estimate_both_device_stream, then the select per-pair route in FMA mode.
 Both routes of a leg write the same bytes into the same buffer (checked once per case before the timing).  hipEvents on the launch
 stream, both routes warmed, then they alternate bracket by bracket in one process; each figure is the median of its brackets with
 the smallest and the largest beside it, in microseconds per OUTPUT frame.  One JSON line per case.
-usage: python tools/retime_bench.py [--legs dense,flow,bm] [--ratios 5/2,12/5,2/5] [--frames 121] [--reps R] [--rounds N] [--quick]"""
+usage: python tools/retime_bench.py [--legs dense,flow,bm,select,select_flow] [--ratios 5/2,12/5,2/5] [--frames 121] [--reps R] [--rounds N] [--quick]"""
 import argparse
 import json
 import os
@@ -65,7 +69,7 @@ def pair_plan(n_frames, num, den):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--legs", default="dense,flow,bm")
+    ap.add_argument("--legs", default="dense,flow,bm,select,select_flow")
     ap.add_argument("--ratios", default="5/2,12/5,2/5")
     ap.add_argument("--frames", type=int, default=121)
     ap.add_argument("--reps", type=int, default=2, help="calls per timed bracket")
@@ -89,6 +93,11 @@ def main():
     fe = nsc.FlowEstimator(levels=3, coarse_iterations=50, refine_iterations=10)
     fe.set_mode("fast")
     fe.estimate_device_stream(base, n_frames, w, h, flows.data_ptr(), s)  # the dense leg's given flows
+    flows_bwd = None
+    if "select" in args.legs:  # the select legs' second flow: every pair B -> A
+        flows_bwd = torch.empty((n, h, w, 2), dtype=torch.float32, device=dev)
+        fe.estimate_both_device_stream(base, n_frames, w, h, flows.data_ptr(), flows_bwd.data_ptr(), s)
+    d_bwd = flows_bwd.data_ptr() if flows_bwd is not None else 0
     it = nsc.WgpuFrameInterpolator()
     it.set_mode("fma")
     bm = nsc.BlockMatcher("medium")
@@ -119,6 +128,16 @@ def main():
             fe.estimate_device_stream(base, n_frames, w, h, flows.data_ptr(), s)
             dense_pairs()
 
+        def select_pairs():
+            for k, j, ts in pairs:
+                it.interpolate_select_device(base + k * fb, fb, base + (k + 1) * fb, fb, flows.data_ptr() + k * w * h * 8, d_bwd + k * w * h * 8,
+                                             w, h, ts, d_out + j * fb, 0, 1, s)
+            copy_reals()
+
+        def select_flow_pairs():
+            fe.estimate_both_device_stream(base, n_frames, w, h, flows.data_ptr(), d_bwd, s)
+            select_pairs()
+
         def bm_pairs():
             bm.estimate_device(base, fb, base + fb, fb, w, h, n, d_bm_ws, bm_ws_bytes, vectors.data_ptr(), stream=s)
             for k, j, ts in pairs:
@@ -134,6 +153,11 @@ def main():
             "bm": ("nus_bm_retime_device_stream",
                    lambda: bm.retime_stream_device(base, fb, n_frames, w, h, num, den, d_bm_ws, bm_ws_bytes, d_out, mode="exact",
                                                    d_vectors=vectors.data_ptr(), stream=s), bm_pairs),
+            "select": ("nus_interp_retime_select_device",
+                       lambda: it.retime_select_device(base, fb, n_frames, flows.data_ptr(), d_bwd, w, h, num, den, d_out, 0, s), select_pairs),
+            "select_flow": ("nus_flow_retime_select_device_stream",
+                            lambda: fe.retime_select_device_stream(base, n_frames, w, h, num, den, d_out, flows.data_ptr(), d_bwd, 0, s),
+                            select_flow_pairs),
         }
         for leg in args.legs.split(","):
             entry, one_launch, per_pair = legs[leg]
