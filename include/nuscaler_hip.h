@@ -1090,6 +1090,47 @@ int nus_yuv420_to_rgba8(int device, const uint8_t *yuv, size_t yuv_len, uint32_t
 int nus_rgba8_to_yuv420(int device, const uint8_t *rgba, size_t rgba_len, uint32_t w, uint32_t h, const nus_yuv_format *fmt,
                         int rgba_format, uint8_t *yuv, size_t yuv_cap);
 
+/* ---- Up-scaling I420 frames plane by plane ----------------------------------------------------------------------------------
+ * BUILD-DEFINED: the reference has no YUV.  Y, U and V of an I420 frame (layout: nus_yuv420_frame_bytes) are resampled as three
+ * single-channel 8-bit images, with no colour conversion on the way: luma becomes the filter of the luma, and chroma is resampled
+ * once, at the position its siting gives it.
+ * Dimension rule.  iw, ih, ow, oh are all even, ow >= iw and oh >= ih: the chroma planes are then exactly half the luma planes
+ * on both sides and the chroma ratio is the luma ratio.  Odd dimensions and down-scaling on an axis are NUS_ERR_UNSUPPORTED (the
+ * RGBA route, nus_upscaler, takes them).  Equal sizes on both axes: the frame is copied.
+ * Arithmetic.  Each plane goes through image-0.24.9 imageops::resize as the NUS_ALG_LANCZOS3 / _BICUBIC / _TRIANGLE up-scalers
+ * do it per channel: a vertical pass into f32 (taps ascending), a horizontal pass (taps ascending), clamp to 0 .. 255, round to
+ * nearest.  NUS_LANCZOS_EXACT: separate multiplies and adds, ties away from zero -- every plane equals the crate's resize of that
+ * plane, bit for bit, under centre siting.  NUS_LANCZOS_FMA: fused, ties to even; each sample is the nearest integer to the
+ * float64 resample of the same f32 weights, except within the accumulation error of a rounding tie.
+ * Geometry.  A sample of index i sits at i + phi in continuous coordinates, on both sides of an axis.  phi = 0.5 for luma, for
+ * chroma vertically, and for chroma horizontally under NUS_YUV_SITING_CENTER; phi = 0.25 for chroma horizontally under
+ * NUS_YUV_SITING_LEFT (chroma co-sited with the even luma column).  Per output o of an axis in_n -> out_n, in f32, each operation
+ * rounded on its own:  ratio = in_n / out_n;  sratio = max(ratio, 1);  centre = (o + phi) * ratio, and if phi != 0.5
+ * centre = centre + (0.5 - phi);  left = clamp(floor(centre - support * sratio), 0, in_n - 1);  right = clamp(ceil(centre +
+ * support * sratio), left + 1, in_n);  centre = centre - 0.5;  w_i = kernel((left + i - centre) / sratio) for i < right - left,
+ * divided by their sum.  With phi = 0.5 these are nus_resize_build_axis' tables bit for bit.
+ * A handle holds the four axis tables (luma x / y, chroma x / y; U and V share theirs); they are built on the host by
+ * nus_yuv_resizer_initialize and uploaded by the handle's first device call, which therefore also allocates and synchronises;
+ * later calls of nus_yuv420_resize_device only enqueue.  One call at a time per handle.
+ * Errors: a null pointer, a zero or too large dimension, an unknown siting or mode, n_frames == 0 and a stride below the frame are
+ * NUS_ERR_INVALID_ARGUMENT; a call before initialize NUS_ERR_NOT_INITIALIZED; the host entry point's sizes NUS_ERR_SIZE_MISMATCH;
+ * all returned before any HIP call, with a text that begins with the entry point's name. */
+typedef struct nus_yuv_resizer nus_yuv_resizer;
+nus_yuv_resizer *nus_yuv_resizer_create(void);                       /* never touches the GPU */
+void nus_yuv_resizer_destroy(nus_yuv_resizer *h);
+const char *nus_yuv_resizer_last_error(const nus_yuv_resizer *h);
+int nus_yuv_resizer_set_device(nus_yuv_resizer *h, int device);     /* before the first device call */
+/* algorithm: NUS_ALG_LANCZOS3 | NUS_ALG_BICUBIC | NUS_ALG_TRIANGLE (others: NUS_ERR_UNSUPPORTED); siting: nus_yuv_siting;
+ * mode: nus_lanczos_mode.  Builds the four axis tables on the host; no HIP call. */
+int nus_yuv_resizer_initialize(nus_yuv_resizer *h, uint32_t iw, uint32_t ih, uint32_t ow, uint32_t oh, int algorithm, int siting, int mode);
+/* DIAGNOSTIC, host only: plane 0 luma / 1 chroma, axis 0 x / 1 y; left[out_n], ntaps[out_n], weights[out_n * NUS_RESIZE_MAX_TAPS]. */
+int nus_yuv_resizer_export_axis(const nus_yuv_resizer *h, int plane, int axis, int32_t *left, uint32_t *ntaps, float *weights);
+/* I420 frames as nus_yuv420_frame_bytes lays them out; frame i at base + i * stride (0 = tight; gaps never read or written).
+ * Enqueue only on `stream`; the handle's first device call uploads its tables. */
+int nus_yuv420_resize_device(nus_yuv_resizer *h, const void *d_in, size_t in_frame_stride, void *d_out, size_t out_frame_stride,
+                             uint32_t n_frames, void *stream);
+int nus_yuv420_resize(nus_yuv_resizer *h, const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap);   /* one host frame */
+
 #ifdef __cplusplus
 }
 #endif

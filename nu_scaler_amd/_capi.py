@@ -37,6 +37,7 @@ FLOW_MAX_WARPS = 4  # NUS_FLOW_MAX_WARPS
 FLOW_MAX_PROJECT = 4  # NUS_FLOW_MAX_PROJECT: projection rounds of the dense-flow warp (nus_interp_set_flow_project, nus_flow_set_project)
 FLOW_MEDIAN_MAX = 5  # NUS_FLOW_MEDIAN_MAX: nus_flow_set_median takes 0 (off), 3 or 5
 INTERP_MODE_EXACT, INTERP_MODE_FMA = 0, 1  # nus_interp_mode_t
+LANCZOS_FMA, LANCZOS_EXACT = 0, 1  # nus_lanczos_mode
 BM_TIES_SCAN, BM_TIES_CENTER = 0, 1  # nus_bm_tie_order
 BM_MAX_RADIUS = 24  # NUS_BM_MAX_RADIUS
 BM_BIDIR_DEFAULT_TOLERANCE = 2  # NUS_BM_BIDIR_DEFAULT_TOLERANCE: a setting, not a measurement
@@ -211,6 +212,14 @@ SIGNATURES = [
     ("nus_rgba8_to_yuv420_device", _i, [_vp, _sz, _u32, _u32, _vp, _i, _vp, _sz, _u32, _vp]),
     ("nus_yuv420_to_rgba8", _i, [_i, _vp, _sz, _u32, _u32, _vp, _i, _vp, _sz]),
     ("nus_rgba8_to_yuv420", _i, [_i, _vp, _sz, _u32, _u32, _vp, _i, _vp, _sz]),
+    ("nus_yuv_resizer_create", _vp, []),
+    ("nus_yuv_resizer_destroy", None, [_vp]),
+    ("nus_yuv_resizer_last_error", _cp, [_vp]),
+    ("nus_yuv_resizer_set_device", _i, [_vp, _i]),
+    ("nus_yuv_resizer_initialize", _i, [_vp, _u32, _u32, _u32, _u32, _i, _i, _i]),
+    ("nus_yuv_resizer_export_axis", _i, [_vp, _i, _i, _vp, _vp, _vp]),
+    ("nus_yuv420_resize_device", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _vp]),
+    ("nus_yuv420_resize", _i, [_vp, _vp, _sz, _vp, _sz]),
 ]
 
 

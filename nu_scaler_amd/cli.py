@@ -8,7 +8,7 @@ detector's verdict on the pair, and `interpolate --multiplier M --scene-detect` 
 `retime --from 24 --to 60 OUT_%04d.png IN0.png IN1.png ...` converts a PNG sequence by a rational frame-rate ratio
 (`--flow-bidirectional`: with the select warp, here and in `video`);
 `video IN.y4m OUT.y4m (--to FPS | --multiplier M)` does the same for a YUV4MPEG2 file of 4:2:0 frames, window by window, with an
-optional `--scale S --algorithm A` up-scale of every output frame.
+optional `--scale S --algorithm A` up-scale of every output frame (`--scale-domain yuv`: of its Y, U and V planes themselves).
 Everything runs on the HIP device; without one the command fails (no CPU path).
 """
 from __future__ import annotations
@@ -82,6 +82,9 @@ def build_parser() -> argparse.ArgumentParser:
     vd.add_argument("--method", default="optical_flow", help="optical_flow (default), block_matching or blend (zero flow)")
     vd.add_argument("--scale", type=int, default=1, help="up-scale every output frame by this integer factor (1 .. 4; default 1: off)")
     vd.add_argument("--algorithm", default="lanczos3", help="with --scale: nearest, bilinear, bicubic, lanczos3, triangle")
+    vd.add_argument("--scale-domain", dest="scale_domain", choices=("rgb", "yuv"), default="rgb",
+                    help="with --scale: rgb (default) up-scales the RGBA frames and converts them to YUV; yuv resamples the Y, U and V "
+                         "planes themselves (bicubic, lanczos3 or triangle; even sizes)")
     vd.add_argument("--matrix", default=None, help="bt601 or bt709 (default: bt709 from 720 rows up, else bt601)")
     vd.add_argument("--window", type=int, default=None,
                     help="input frames on the device at a time, at least den + 1 of the reduced ratio (default: from the free memory)")
@@ -302,7 +305,8 @@ def main(argv=None) -> int:
                             scale=args.scale, algorithm=args.algorithm, window_frames=args.window,
                             matrix=args.matrix.lower() if args.matrix else None, device=args.device, scene_detect=args.scene_detect,
                             flow_warps=args.flow_warps or 0, flow_median=args.flow_median or 0, flow_project=args.flow_project or 0,
-                            bidirectional=args.bidirectional, flow_bidirectional=args.flow_bidirectional)
+                            bidirectional=args.bidirectional, flow_bidirectional=args.flow_bidirectional,
+                            scale_domain=args.scale_domain)
             print(f"{args.output}: {r['frames_out']} frames {r['width']}x{r['height']} at {r['fps']} fps "
                   f"({r['frames_in']} read, {r['windows']} windows)")
         except (OSError, ValueError, RuntimeError) as e:

@@ -17,6 +17,7 @@
 #include "nus_scene.hpp"
 #include "nus_transfer.hpp"
 #include "nus_yuv.hpp"
+#include "nus_yuv_resize.hpp"
 
 struct nus_upscaler {
     nus::HipUpscaler impl;
@@ -39,6 +40,10 @@ struct nus_blockmatch {
 struct nus_interp {
     nus::HipFrameInterpolator impl;
     explicit nus_interp(int preset) : impl(preset) {}
+};
+
+struct nus_yuv_resizer {
+    nus::YuvResizer impl;
 };
 
 namespace {
@@ -1178,6 +1183,58 @@ int nus_rgba8_to_yuv420(int device, const uint8_t *rgba, size_t rgba_len, uint32
     return guarded<int>("nus_rgba8_to_yuv420", [&]() -> int {
         return nus::rgba8_to_yuv420(device, rgba, rgba_len, w, h, reinterpret_cast<const nus::YuvFormat *>(fmt), rgba_format, yuv, yuv_cap);
     });
+}
+
+static_assert(NUS_RESIZE_MAX_TAPS == nus::kResizeMaxTaps, "nus_yuv_resizer_export_axis lays its weights out as the tables do");
+
+namespace {
+int null_resizer(const char *who)
+{
+    nus::set_thread_error(std::string(who) + ": null handle");
+    return NUS_ERR_INVALID_ARGUMENT;
+}
+} // namespace
+
+nus_yuv_resizer *nus_yuv_resizer_create(void)
+{
+    return guarded<nus_yuv_resizer *>("nus_yuv_resizer_create", [&]() -> nus_yuv_resizer * { return new (std::nothrow) nus_yuv_resizer(); });
+}
+
+void nus_yuv_resizer_destroy(nus_yuv_resizer *h) { delete h; }
+
+const char *nus_yuv_resizer_last_error(const nus_yuv_resizer *h) { return h ? h->impl.last_error() : "null handle"; }
+
+int nus_yuv_resizer_set_device(nus_yuv_resizer *h, int device)
+{
+    return guarded<int>("nus_yuv_resizer_set_device", [&]() -> int { return h ? h->impl.set_device(device) : null_resizer("nus_yuv_resizer_set_device"); });
+}
+
+int nus_yuv_resizer_initialize(nus_yuv_resizer *h, uint32_t iw, uint32_t ih, uint32_t ow, uint32_t oh, int algorithm, int siting, int mode)
+{
+    return guarded<int>("nus_yuv_resizer_initialize", [&]() -> int {
+        return h ? h->impl.initialize(iw, ih, ow, oh, algorithm, siting, mode) : null_resizer("nus_yuv_resizer_initialize");
+    });
+}
+
+int nus_yuv_resizer_export_axis(const nus_yuv_resizer *h, int plane, int axis, int32_t *left, uint32_t *ntaps, float *weights)
+{
+    return guarded<int>("nus_yuv_resizer_export_axis", [&]() -> int {
+        return h ? const_cast<nus_yuv_resizer *>(h)->impl.export_axis(plane, axis, left, ntaps, weights) : null_resizer("nus_yuv_resizer_export_axis");
+    });
+}
+
+int nus_yuv420_resize_device(nus_yuv_resizer *h, const void *d_in, size_t in_frame_stride, void *d_out, size_t out_frame_stride,
+                             uint32_t n_frames, void *stream)
+{
+    return guarded<int>("nus_yuv420_resize_device", [&]() -> int {
+        return h ? h->impl.resize_device(d_in, in_frame_stride, d_out, out_frame_stride, n_frames, static_cast<hipStream_t>(stream))
+                 : null_resizer("nus_yuv420_resize_device");
+    });
+}
+
+int nus_yuv420_resize(nus_yuv_resizer *h, const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap)
+{
+    return guarded<int>("nus_yuv420_resize", [&]() -> int { return h ? h->impl.resize(in, in_len, out, out_cap) : null_resizer("nus_yuv420_resize"); });
 }
 
 } // extern "C"

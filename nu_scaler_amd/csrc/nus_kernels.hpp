@@ -482,4 +482,40 @@ struct YuvLaunch {
 hipError_t launch_yuv_to_rgba(const YuvLaunch &L);
 hipError_t launch_rgba_to_yuv(const YuvLaunch &L);
 
+// Separable resampling of the 8-bit planes of I420 frame batches (nus_k_yuv_resize.hip; nus_yuv_resizer of include/nuscaler_hip.h,
+// where the contract is written).  One launch resamples one CLASS of planes: the luma plane of every frame (planes_per_frame 1)
+// or both chroma planes (2), which share their tables.  Plane p of frame i starts at base + i * frame_stride + plane_offset +
+// p * plane_step on either side; rows tight, iw x ih bytes in, ow x oh out.  Tables as build_resize_axis lays them out, in device
+// memory, table_stride floats per output; max_taps the widest window of the four axes' two that this class uses.
+struct PlaneTables {
+    const int32_t *lx = nullptr, *ly = nullptr;
+    const uint32_t *nx = nullptr, *ny = nullptr;
+    const float *wx = nullptr, *wy = nullptr;
+};
+struct PlaneResizeLaunch {
+    const uint8_t *in = nullptr;
+    uint8_t *out = nullptr;
+    size_t in_frame_stride = 0, out_frame_stride = 0; // bytes, never 0 here
+    size_t in_plane_offset = 0, in_plane_step = 0, out_plane_offset = 0, out_plane_step = 0;
+    uint32_t planes_per_frame = 1, n_frames = 1;
+    uint32_t iw = 0, ih = 0, ow = 0, oh = 0;
+    PlaneTables t;
+    uint32_t table_stride = 0, max_taps = 0;
+    // the row kernel's geometry, from the host's copy of the x tables (YuvResizer::initialize): widest LDS row of a wave's segment
+    // and widest union of a lane's windows; union_taps 0 = the geometry does not fit the row kernel
+    uint32_t ncols_max = 0, union_taps = 0;
+    bool exact = false;
+    hipStream_t stream = nullptr;
+};
+constexpr uint32_t kPlaneRun = 4;                 // adjacent output bytes a lane of the row kernel owns: one dword
+constexpr uint32_t kPlaneSegment = 64 * kPlaneRun; // output columns of one wave
+constexpr uint32_t kPlaneMaxUnion = 12;
+// The row kernel (a lane owns kPlaneRun adjacent outputs, dword accesses) where both widths are multiples of 4, every plane of
+// the class starts on a dword on either side, no window has more than 8 taps and the geometry fits; else one output per thread.
+bool plane_rows_form(const PlaneResizeLaunch &L);
+hipError_t launch_plane_resize(const PlaneResizeLaunch &L);
+// n_frames frames of frame_bytes each, the strides apart: a copy kernel (dwords where everything is dword aligned, else bytes)
+hipError_t launch_frame_copy(const uint8_t *in, size_t in_frame_stride, uint8_t *out, size_t out_frame_stride, size_t frame_bytes,
+                             uint32_t n_frames, hipStream_t stream);
+
 } // namespace nus

@@ -69,7 +69,7 @@ float triangle(float x)
 
 } // namespace
 
-int build_resize_axis(ResizeFilter filter, uint32_t in_n, uint32_t out_n, int32_t *left, uint32_t *ntaps, float *weights)
+int build_resize_axis(ResizeFilter filter, uint32_t in_n, uint32_t out_n, int32_t *left, uint32_t *ntaps, float *weights, float phi)
 {
     if (in_n == 0 || out_n == 0) return -1;
     float (*kernel)(float) = lanczos3;
@@ -89,7 +89,8 @@ int build_resize_axis(ResizeFilter filter, uint32_t in_n, uint32_t out_n, int32_
         float *ws = weights + (size_t)o * kResizeMaxTaps;
         std::memset(ws, 0, sizeof(float) * kResizeMaxTaps);
         // centre of output pixel o in input coordinates (half-pixel convention)
-        float centre = ((float)o + 0.5f) * ratio;
+        float centre = ((float)o + phi) * ratio;
+        if (phi != 0.5f) centre = centre + (0.5f - phi); // a sample of index i sits at i + phi: back to the half-pixel frame below
         int64_t lo = (int64_t)std::floor(centre - src_support);
         if (lo < 0) lo = 0;
         if (lo > (int64_t)in_n - 1) lo = (int64_t)in_n - 1;

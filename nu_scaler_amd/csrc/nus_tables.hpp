@@ -26,7 +26,11 @@ enum class ResizeFilter : int { Lanczos3 = 0, CatmullRom = 1, Triangle = 2 };
 // Tap windows, image-0.24.9 vertical_sample / horizontal_sample convention.
 // weights is out_n * kResizeMaxTaps, zero padded.  Returns max ntaps, or -1 when a
 // window needs more than kResizeMaxTaps taps (Lanczos-3: down-scaling by more than ~4.8x).
-int build_resize_axis(ResizeFilter filter, uint32_t in_n, uint32_t out_n, int32_t *left, uint32_t *ntaps, float *weights);
+// phi: where a sample of index i sits in continuous coordinates, i + phi, on both sides of the axis.  0.5 is the crate's
+// half-pixel convention (the tables are then bit for bit what they were without the parameter); 0.25 is 4:2:0 chroma co-sited
+// with the even luma column (nus_yuv_resizer): centre = (o + phi) * ratio + (0.5 - phi), everything after it unchanged.
+int build_resize_axis(ResizeFilter filter, uint32_t in_n, uint32_t out_n, int32_t *left, uint32_t *ntaps, float *weights,
+                      float phi = 0.5f);
 inline int build_lanczos3_axis(uint32_t in_n, uint32_t out_n, int32_t *left, uint32_t *ntaps, float *weights)
 {
     return build_resize_axis(ResizeFilter::Lanczos3, in_n, out_n, left, ntaps, weights);

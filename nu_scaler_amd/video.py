@@ -17,6 +17,8 @@ from math import gcd
 from . import _capi as C
 
 METHODS = ("optical_flow", "block_matching", "blend")
+SCALE_DOMAINS = ("rgb", "yuv")
+YUV_DOMAIN_ALGORITHMS = ("lanczos3", "lanczos", "bicubic", "catmullrom", "triangle")  # what yuv.YuvResizer resamples planes with
 
 
 def plan_windows(n_frames: int, num: int, den: int, max_frames: int) -> list[tuple[int, int, int, int]]:
@@ -48,28 +50,37 @@ def default_matrix(height: int) -> str:
     return "bt709" if int(height) >= 720 else "bt601"
 
 
-def window_bytes_per_frame(w: int, h: int, num: int, den: int, scale: int) -> int:
+def window_bytes_per_frame(w: int, h: int, num: int, den: int, scale: int, scale_domain: str = "rgb") -> int:
     """Device bytes one more input frame of a window costs: its I420 and RGBA forms, and num / den output frames in RGBA, in
-    up-scaled RGBA (scale > 1) and in I420 (rounded up)."""
+    up-scaled RGBA (scale > 1) and in I420 (rounded up).  scale_domain "yuv" with scale > 1, the planar route: no up-scaled RGBA
+    but an output's I420 form at the source size; at the ratio 1/1 only the frame's I420 form and the up-scaled one."""
     yuv_in, rgba_in = w * h + 2 * ((w + 1) // 2) * ((h + 1) // 2), w * h * 4
     ow, oh = w * scale, h * scale
+    if scale_domain == "yuv" and scale > 1:
+        yuv_out = ow * oh + 2 * ((ow + 1) // 2) * ((oh + 1) // 2)
+        if num == den:
+            return yuv_in + yuv_out
+        return yuv_in + rgba_in + -(-(rgba_in + yuv_in + yuv_out) * num // den)
     per_out = rgba_in + (ow * oh * 4 if scale > 1 else 0) + ow * oh + 2 * ((ow + 1) // 2) * ((oh + 1) // 2)
     return yuv_in + rgba_in + -(-per_out * num // den)
 
 
-def default_window_frames(w: int, h: int, num: int, den: int, scale: int, device: int = 0) -> int:
-    """The largest window whose frames -- input, RGBA input, RGBA output, up-scaled output and YUV output -- use at most a quarter
-    of the device's free memory (nus_device_memory_info), and at least den + 1.  (The estimators' flows and workspaces come on top;
-    the other three quarters are theirs.)"""
+def default_window_frames(w: int, h: int, num: int, den: int, scale: int, device: int = 0, scale_domain: str = "rgb") -> int:
+    """The largest window whose frames -- input, RGBA input, RGBA output, up-scaled output and YUV output, or what the planar
+    route holds instead (window_bytes_per_frame) -- use at most a quarter of the device's free memory (nus_device_memory_info),
+    and at least den + 1.  (The estimators' flows and workspaces come on top; the other three quarters are theirs.)"""
     free, total = ctypes.c_uint64(0), ctypes.c_uint64(0)
     if C.lib().nus_device_memory_info(int(device), ctypes.byref(free), ctypes.byref(total)) != C.OK:
         raise RuntimeError(C.last_error())
-    return max(den + 1, int(free.value // 4 // window_bytes_per_frame(w, h, num, den, scale)))
+    return max(den + 1, int(free.value // 4 // window_bytes_per_frame(w, h, num, den, scale, scale_domain)))
 
 
 def check_convert_args(fps_in, fps_out, multiplier, method, scale, bidirectional, *,
-                       flow_bidirectional: bool = False) -> tuple[Fraction, int, int]:
-    """The usage rules of `convert_y4m` that need no file and no device: (fps_out, num, den); ValueError otherwise."""
+                       flow_bidirectional: bool = False, scale_domain: str = "rgb", algorithm: str = "lanczos3", width=None,
+                       height=None) -> tuple[Fraction, int, int]:
+    """The usage rules of `convert_y4m` that need no file and no device: (fps_out, num, den); ValueError otherwise.  With
+    scale_domain "yuv" and scale > 1 the planes themselves are resampled: `algorithm` must be one of YUV_DOMAIN_ALGORITHMS, and
+    `width` and `height` (where given: the clip's) even."""
     from .retime import retime_ratio
 
     if (fps_out is None) == (multiplier is None):
@@ -88,6 +99,15 @@ def check_convert_args(fps_in, fps_out, multiplier, method, scale, bidirectional
         raise ValueError("flow_bidirectional needs method optical_flow")
     if isinstance(scale, bool) or not isinstance(scale, int) or not 1 <= scale <= 4:
         raise ValueError(f"scale must be an integer from 1 to 4, got {scale!r}")
+    if scale_domain not in SCALE_DOMAINS:
+        raise ValueError(f"scale_domain must be 'rgb' or 'yuv', got {scale_domain!r}")
+    if scale_domain == "yuv" and scale > 1:
+        if not isinstance(algorithm, str) or algorithm.lower() not in YUV_DOMAIN_ALGORITHMS:
+            raise ValueError(f"scale_domain 'yuv' resamples the Y, U and V planes with lanczos3, bicubic or triangle, not with "
+                             f"{algorithm!r}: nearest, bilinear and the FSR algorithms need scale_domain 'rgb'")
+        if (width is not None and int(width) % 2) or (height is not None and int(height) % 2):
+            raise ValueError(f"scale_domain 'yuv' needs an even width and height (the chroma planes must be exactly half the luma "
+                             f"planes), got {width}x{height}: odd sizes need scale_domain 'rgb'")
     return fps_out, num, den
 
 
@@ -158,7 +178,7 @@ class _Route:
 def convert_y4m(in_path, out_path, *, fps_out=None, multiplier=None, method: str = "optical_flow", scale: int = 1,
                 algorithm: str = "lanczos3", window_frames=None, matrix=None, device: int = 0, scene_detect: bool = False,
                 flow_warps: int = 0, flow_median: int = 0, flow_project: int = 0, bidirectional: bool = False,
-                flow_bidirectional: bool = False) -> dict:
+                flow_bidirectional: bool = False, scale_domain: str = "rgb") -> dict:
     """IN.y4m at its rate -> OUT.y4m at `fps_out` (an int or a Fraction) or at `multiplier` times the input's rate, every output
     frame `scale` times as large with `algorithm` when scale > 1.  method "optical_flow" (Horn-Schunck, the estimator's defaults,
     with flow_warps / flow_median / flow_project; `flow_bidirectional`: both flows of every pair and the select warp), "block_matching" (the Medium preset; `bidirectional`: its forward-backward
@@ -166,6 +186,10 @@ def convert_y4m(in_path, out_path, *, fps_out=None, multiplier=None, method: str
     input's height); the range and the chroma siting are the input's, the chroma is up-sampled bilinearly.  window_frames: input
     frames on the device at a time (None: from the device's free memory), at least den + 1 of the reduced ratio.  The output
     header carries W * scale, H * scale, F = fps_out reduced and the input's I, A, C and XCOLORRANGE tags.
+    scale_domain "rgb" (default): every output frame is up-scaled as RGBA8 and converted to I420 at the target size.  "yuv" (with
+    scale > 1; lanczos3, bicubic or triangle; even sizes): the output frames are converted to I420 at the SOURCE size and their Y, U
+    and V planes up-scaled themselves (yuv.YuvResizer, chroma at the input's siting); at the ratio 1/1 (e.g. multiplier=1) nothing is
+    converted at all -- upload, plane up-scale, download -- and `method` is not consulted.
     Returns {"frames_in", "frames_out", "windows", "width", "height", "fps"}.  ValueError for what is refused."""
     import torch
 
@@ -174,21 +198,27 @@ def convert_y4m(in_path, out_path, *, fps_out=None, multiplier=None, method: str
 
     with Y4MReader(in_path) as rd:
         fps_out, num, den = check_convert_args(rd.fps, fps_out, multiplier, method, scale, bidirectional,
-                                                flow_bidirectional=flow_bidirectional)
+                                                flow_bidirectional=flow_bidirectional, scale_domain=scale_domain, algorithm=algorithm,
+                                                width=rd.width, height=rd.height)
         w, h = rd.width, rd.height
+        planar = scale_domain == "yuv" and scale > 1
+        direct = planar and num == den  # up-scaling only: no colour conversion, no estimator
         ow, oh = w * scale, h * scale
         if matrix is None:
             matrix = default_matrix(h)
         fmt = yuv.YuvFormat(matrix=matrix, range=rd.range, siting=rd.siting, chroma="bilinear")
         if window_frames is None:
-            window_frames = default_window_frames(w, h, num, den, scale, device)
+            window_frames = default_window_frames(w, h, num, den, scale, device, scale_domain)
         window_frames = int(window_frames)
         if window_frames < den + 1:
             raise ValueError(f"a window needs at least den + 1 = {den + 1} frames for the ratio {num}/{den}, got {window_frames}")
         step = (window_frames - 1) // den * den
-        route = _Route(method, device, scene_detect, flow_warps, flow_median, flow_project, bidirectional, flow_bidirectional)
-        up = None
-        if scale > 1:
+        route = None if direct else _Route(method, device, scene_detect, flow_warps, flow_median, flow_project, bidirectional,
+                                           flow_bidirectional)
+        up = planes = None
+        if planar:
+            planes = yuv.YuvResizer(w, h, ow, oh, algorithm=algorithm, siting=rd.siting, mode="fma", device=device)
+        elif scale > 1:
             from .upscaler import PyWgpuUpscaler
 
             up = PyWgpuUpscaler("quality", algorithm, device=device)
@@ -215,6 +245,21 @@ def convert_y4m(in_path, out_path, *, fps_out=None, multiplier=None, method: str
                 d_yuv = torch.empty((n, yb_in), dtype=torch.uint8, device=dev)
                 for k, f in enumerate(win):
                     transfer.upload(d_yuv[k].data_ptr(), f, s)
+                if direct:
+                    d_res = torch.empty((kept, yb_out), dtype=torch.uint8, device=dev)
+                    planes.resize_device(d_yuv.data_ptr(), d_res.data_ptr(), kept, stream=s)
+                    res = transfer.to_numpy(d_res)
+                    for j in range(kept):
+                        wr.write(res[j])
+                    del d_yuv, d_res
+                    frames_out += kept
+                    windows += 1
+                    if final:
+                        break
+                    more = rd.read_frames(step)
+                    frames_in += len(more)
+                    frames = frames[step:] + more
+                    continue
                 d_in = torch.empty((n, fb), dtype=torch.uint8, device=dev)
                 yuv.to_rgba_device(d_yuv.data_ptr(), w, h, d_in.data_ptr(), fmt, n, stream=s)
                 d_out = torch.empty((n_out, fb), dtype=torch.uint8, device=dev)
@@ -224,7 +269,12 @@ def convert_y4m(in_path, out_path, *, fps_out=None, multiplier=None, method: str
                     d_big = torch.empty((kept, ow * oh * 4), dtype=torch.uint8, device=dev)
                     up.upscale_device(d_out.data_ptr(), d_big.data_ptr(), kept, s)
                 d_res = torch.empty((kept, yb_out), dtype=torch.uint8, device=dev)
-                yuv.to_yuv_device(d_big.data_ptr(), ow, oh, d_res.data_ptr(), fmt, kept, stream=s)
+                if planes is not None:  # to I420 at the source size, then the planes themselves: no target-size RGBA
+                    d_big = torch.empty((kept, yb_in), dtype=torch.uint8, device=dev)
+                    yuv.to_yuv_device(d_out.data_ptr(), w, h, d_big.data_ptr(), fmt, kept, stream=s)
+                    planes.resize_device(d_big.data_ptr(), d_res.data_ptr(), kept, stream=s)
+                else:
+                    yuv.to_yuv_device(d_big.data_ptr(), ow, oh, d_res.data_ptr(), fmt, kept, stream=s)
                 res = transfer.to_numpy(d_res)  # (ordered after the stream's work; returns when the bytes are on the host)
                 for j in range(kept):
                     wr.write(res[j])

@@ -112,3 +112,67 @@ def to_yuv(rgba_bytes, w: int, h: int, fmt: YuvFormat | None = None, rgba_format
     del keep, o
     _check(st)
     return bytes(out)
+
+
+_MODE = {"fma": C.LANCZOS_FMA, "exact": C.LANCZOS_EXACT}
+
+
+def _algorithm(value) -> int:
+    from .upscaler import _ALGORITHM
+
+    return _enum("algorithm", _ALGORITHM, value)
+
+
+class YuvResizer:
+    """Up-scales I420 frames plane by plane (nus_yuv_resizer of include/nuscaler_hip.h, where the contract is written): Y, U and V
+    are resampled as single-channel images with `algorithm` "lanczos3" | "bicubic" | "triangle", chroma at the position `siting`
+    ("center" | "left") gives it; `mode` "fma" | "exact".  All four dimensions even, no axis scaled down; equal sizes copy.
+    ValueError for bad arguments, RuntimeError for what the library does not support (odd sizes, down-scaling, other algorithms)
+    and for device errors."""
+
+    def __init__(self, iw: int, ih: int, ow: int, oh: int, algorithm="lanczos3", siting="center", mode="fma", device: int = 0):
+        alg, sit, md = _algorithm(algorithm), _enum("siting", _SITING, siting), _enum("mode", _MODE, mode)
+        self._lib = C.lib()
+        self._h = self._lib.nus_yuv_resizer_create()
+        if not self._h:
+            raise MemoryError("nus_yuv_resizer_create failed")
+        _check(self._lib.nus_yuv_resizer_set_device(self._h, int(device)))
+        _check(self._lib.nus_yuv_resizer_initialize(self._h, int(iw), int(ih), int(ow), int(oh), alg, sit, md))
+        self.iw, self.ih, self.ow, self.oh = int(iw), int(ih), int(ow), int(oh)
+        self.in_frame_bytes = self.iw * self.ih * 3 // 2
+        self.out_frame_bytes = self.ow * self.oh * 3 // 2
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._lib.nus_yuv_resizer_destroy(h)
+
+    def resize_device(self, d_in: int, d_out: int, n_frames: int = 1, in_frame_stride: int = 0, out_frame_stride: int = 0,
+                      stream: int = 0) -> None:
+        """Enqueue the up-scale of `n_frames` device frames on `stream` (nus_yuv420_resize_device); strides in bytes, 0 = tight.
+        The handle's first device call uploads its tables."""
+        _check(self._lib.nus_yuv420_resize_device(self._h, d_in or None, int(in_frame_stride), d_out or None, int(out_frame_stride),
+                                                  int(n_frames), stream or None))
+
+    def resize(self, frame_bytes) -> bytes:
+        """One host I420 frame -> the up-scaled frame (nus_yuv420_resize)."""
+        addr, n, keep = _as_buffer(frame_bytes)
+        out = bytearray(self.out_frame_bytes)
+        o = (ctypes.c_ubyte * len(out)).from_buffer(out)
+        st = self._lib.nus_yuv420_resize(self._h, addr, n, ctypes.addressof(o), len(out))
+        del keep, o
+        _check(st)
+        return bytes(out)
+
+    def export_axis(self, plane: int, axis: int):
+        """(left int32 [out_n], ntaps uint32 [out_n], weights float32 [out_n, RESIZE_MAX_TAPS]) of plane 0 luma / 1 chroma, axis
+        0 x / 1 y (nus_yuv_resizer_export_axis)."""
+        import numpy as np
+
+        if plane not in (0, 1) or axis not in (0, 1):
+            raise ValueError(f"plane and axis must be 0 or 1, got {plane!r}, {axis!r}")
+        n = ((self.ow, self.oh)[axis]) // (2 if plane else 1)
+        left, ntaps = np.zeros(n, np.int32), np.zeros(n, np.uint32)
+        w = np.zeros((n, C.RESIZE_MAX_TAPS), np.float32)
+        _check(self._lib.nus_yuv_resizer_export_axis(self._h, int(plane), int(axis), left.ctypes.data, ntaps.ctypes.data, w.ctypes.data))
+        return left, ntaps, w
