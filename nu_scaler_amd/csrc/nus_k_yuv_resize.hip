@@ -12,7 +12,11 @@
 //                    UNION-long weight vector that is zero outside its own window (the extra terms are exact +-0: same bits);
 //                    the four bytes leave as one dword store.  No byte access anywhere.
 //                    Needs: both widths multiples of 4, every plane of the launch dword aligned on either side, windows of at
-//                    most 8 taps, unions of at most 12.
+//                    most 8 taps, unions of at most 12.  What the public entry points can ask for is less: over every x axis
+//                    the row form takes for input widths 4 .. 1100 and output widths in .. 4 in, at either sample position, no
+//                    window has more than 7 taps and no union more than 10 columns (Lanczos-3; Catmull-Rom 5 and 8, Triangle 3
+//                    and 6; all reached at ratio 1; tests/test_yuv_resize_host.py holds the bound).  So in that range the UNION
+//                    = 12 instances are compiled and never launched; they stay until a follow-up removes them on that bound.
 //   k_plane_px<EXACT>            one output byte per thread, 64-bit addressing, byte accesses, any tap count: the same operations
 //                    in the same order, so the same bytes.  Odd chroma widths, odd plane addresses, offset bases, odd strides.
 //   k_frame_copy<T>              equal sizes: the frame is copied, as imageops::resize does.

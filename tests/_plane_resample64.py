@@ -72,6 +72,38 @@ def axis(in_n, out_n, filt, phi):
     return left, ntaps, w
 
 
+def windows(in_n, out_n, filt, phi):
+    """(left int64 [k, max out_n], ntaps int64 [k, max out_n], valid bool [k, max out_n]) of the axes in_n -> out_n[0..k), all at
+    once: the window expressions of `axis` in the same float32 order (a window needs no weight, so no libm either).  Slots at
+    o >= out_n[i] are not valid and hold 0."""
+    out_n = np.atleast_1d(np.asarray(out_n, np.int64))
+    phi = F(phi)
+    ratio = (F(in_n) / out_n.astype(F))[:, None]
+    src_support = _SUPPORT[filt] * np.maximum(ratio, F(1.0))
+    o = np.arange(int(out_n.max()), dtype=np.int64)[None, :]
+    centre = (o.astype(F) + phi) * ratio
+    if phi != F(0.5):
+        centre = centre + F(F(0.5) - phi)
+    assert centre.dtype == F and src_support.dtype == F
+    lo = np.clip(np.floor(centre - src_support).astype(np.int64), 0, in_n - 1)
+    hi = np.minimum(np.maximum(np.ceil(centre + src_support).astype(np.int64), lo + 1), in_n)
+    valid = o < out_n[:, None]
+    return np.where(valid, lo, 0), np.where(valid, hi - lo, 0), valid
+
+
+def row_geometry(left, ntaps, out_n, run=4, segment=256):
+    """(ncols_max, union) of an x axis in the row kernel, by the two loops of YuvResizer::initialize: the widest dword-aligned input
+    footprint of a segment of 256 outputs, and the widest union of the windows of a lane's run of 4 outputs."""
+    assert out_n % run == 0
+    left, end = np.asarray(left, np.int64)[:out_n], np.asarray(left, np.int64)[:out_n] + np.asarray(ntaps, np.int64)[:out_n]
+    ncols = 0
+    for x0 in range(0, out_n, segment):
+        xl = min(x0 + segment, out_n) - 1
+        ncols = max(ncols, (int(end[xl]) - (int(left[x0]) & ~3) + 3) & ~3)
+    union = int((end.reshape(-1, run).max(axis=1) - left[::run]).max())
+    return ncols, union
+
+
 def _oracle_axis(oracle_mod, in_n, out_n, filt):
     left, ntaps, w = oracle_mod.resize_axis(in_n, out_n, filt)
     return left.astype(np.int64), ntaps.astype(np.int64), np.asarray(w, np.float32)

@@ -8,7 +8,7 @@ class to be multiples of 4 and every plane of the class on a dword; everything e
   16x8 -> 32x16      row kernel for luma and chroma; every window is cut by a border; two luma row blocks
   22x10 -> 66x30     x3; luma 22 wide and chroma 11x5 -> 33x15 with V on an odd address: per-sample kernel for both classes
   20x10 -> 60x30     x3; row kernel for luma (20 -> 60) beside the per-sample kernel for chroma (10 -> 30; V at byte 250)
-  64x36 -> 96x54     x3/2: 7- and 8-tap windows; row kernel for both classes
+  64x36 -> 96x54     x3/2: windows of up to 7 taps (no up-scale has more: test_yuv_resize_host.py); row kernel for both classes
   262x6 -> 1048x12   x4 by x2; per-sample (262 is no multiple of 4), 17 / 9 workgroups along a row
   264x6 -> 1056x12   the same in the row kernel: luma rows span 5 segments (two workgroups), chroma rows 3, the last one partial
   32x18 -> 64x18 / 32x36 / 32x18   one axis unchanged (a 7-tap window at ratio 1), and the copy

@@ -253,6 +253,80 @@ def test_restatement_reproduces_the_oracles_windows(oracle_mod, filt, alg, _):
     assert abs(got - c) < 1e-6
 
 
+SCAN_IN = range(4, 1101, 4)  # every row-form-eligible input width of an x axis, and below every output width in [in, 4 in]
+SCAN_API_IN = tuple(range(4, 1101, 48)) + (1100,)  # the part of it that goes through the library: 24 input widths ...
+
+
+def _scan_api_out(in_n):  # ... each with the ten ratios closest to 1 and every eleventh output width above them
+    return sorted(set(range(in_n, min(in_n + 40, 4 * in_n + 1), 4)) | set(range(in_n, 4 * in_n + 1, 44)))
+
+
+@pytest.mark.parametrize("filt,alg,_", FILTERS)
+def test_no_row_form_axis_needs_the_12_wide_union(nsc, filt, alg, _):
+    """Which k_plane_rows instance can a public call reach?  Every x axis that the row form takes (both widths multiples of 4) for
+    input widths 4 .. 1100 and output widths in .. 4 in, both sample positions: the widest tap window and the widest union of the
+    windows of a lane's four outputs (row_geometry: the loop of YuvResizer::initialize).  114 125 axes per filter and position
+    come from _plane_resample64.windows, the float32 restatement of the window expressions; 1 133 of them (SCAN_API_IN x
+    _scan_api_out) are also built by the library, as the chroma x axis of a 2 in x 2 -> 2 out x 2 handle under either siting, and
+    must give the restatement's windows exactly.  Found: Lanczos-3 7 taps and union 10, Catmull-Rom 5 and 8, Triangle 3 and 6,
+    the same at 0.5 and 0.25, all reached at ratio 1 (8 -> 8, 12 -> 12).  So launch_plane_resize's `union_taps <= 10` always
+    holds in this range and k_plane_rows<*, 12> is never launched."""
+    expected = {0: (7, 10), 1: (5, 8), 2: (3, 6)}[filt]
+    axes = checked = 0
+    for phi, siting in ((0.5, "center"), (0.25, "left")):
+        taps = union = 0
+        for in_n in SCAN_IN:
+            outs = np.arange(in_n, 4 * in_n + 1, 4)
+            for c in range(0, len(outs), 48):  # (blocks that stay in the cache)
+                lo, n, valid = P.windows(in_n, outs[c:c + 48], filt, phi)
+                end = lo + n
+                un = (end.reshape(len(end), -1, 4).max(axis=2) - lo[:, ::4])[valid[:, ::4]]
+                assert (n[valid] >= 1).all() and (un >= 1).all()
+                taps, union = max(taps, int(n.max())), max(union, int(un.max()))
+            axes += len(outs)
+            if in_n in SCAN_API_IN:
+                for out_n in _scan_api_out(in_n):
+                    left, ntaps, _w = nsc.yuv.YuvResizer(2 * in_n, 2, 2 * out_n, 2, alg, siting).export_axis(1, 0)
+                    lo, n, _v = P.windows(in_n, [out_n], filt, phi)
+                    np.testing.assert_array_equal(left, lo[0], err_msg=f"{alg} {in_n}->{out_n} {siting}")
+                    np.testing.assert_array_equal(ntaps, n[0], err_msg=f"{alg} {in_n}->{out_n} {siting}")
+                    u = P.row_geometry(left, ntaps, out_n)[1]
+                    assert u == int(((lo[0] + n[0]).reshape(-1, 4).max(axis=1) - lo[0, ::4]).max())
+                    assert u <= expected[1]
+                    checked += 1
+        print(f"{alg} phi {phi}: most taps {taps}, widest union {union}")
+        assert taps <= 7 and union <= 10, (alg, phi, taps, union)  # the bound that makes the 12-wide instance unreachable
+        assert (taps, union) == expected, (alg, phi, taps, union)  # and what the scan recorded (DESIGN.md 8.8)
+    assert axes == 2 * 114125 and checked == 2 * 1133, (axes, checked)
+
+
+def test_the_launch_cases_of_the_gpu_tests_are_what_they_say(nsc):
+    """tests/test_gpu_yuv_resize_launch.py asserts, before it runs a case, the numbers that make the case one: they need no device,
+    so they are held here as well -- the rows per block of the long batches, the footprints and unions of the wide segments, the
+    pool frames around the grid-z split, and that each filter's seeded sweep holds at least 4 shapes of every class and form."""
+    import test_gpu_yuv_resize_launch as L
+
+    assert [(L._rpb(32, 40, n), L._rpb(16, 20, 2 * n)) for n in (5, 1000, 2000, 3400)] == [(8, 8), (9, 9), (19, 19), (32, 32)]
+    assert L._row_blocks(40, 9) == [9, 9, 9, 9, 4] and L._row_blocks(20, 19) == [19, 1] and L._row_blocks(20, 32) == [20]
+    assert L._rpb(3840, 2160, 31) == 32 and L._rpb(1920, 1080, 62) == 32  # the measured workload: 31 frames, 1080p -> 4K
+    for shape, luma, chroma in L.WIDE:
+        L._assert_wide_case(nsc, shape, luma, chroma)
+    for alg in ("bicubic", "triangle"):
+        L._assert_wide_case(nsc, (520, 8, 520, 16), (">256", None), (">256", None), alg)
+    assert L._geometry(nsc, (1016, 8, 1024, 16), "lanczos3", "left") == ((264, 10), (260, 10))
+    assert L._geometry(nsc, (504, 8, 512, 16), "lanczos3", "center") == ((256, 10), (252, 10))
+    widest = max(max(g[0] for g in L._geometry(nsc, s, "lanczos3", "left")) for s in L.T.FIRST + L.T.REST if s[:2] != s[2:])
+    assert widest == 72  # what tests/test_gpu_yuv_resize.py reaches: one sweep of the V pass everywhere
+    L._pool(8, 4, 32769, 1, L.SPLIT_RESIZE)
+    L._pool(4, 2, 65537, 1, L.SPLIT_COPY)
+    assert len(set(L.SWEEP_SEEDS.values())) == 3
+    for alg in L.SWEEP_SEEDS:
+        shapes = L.sweep_shapes(alg)
+        forms = L.sweep_forms(shapes)
+        print(alg, forms)
+        assert len(shapes) == 20 and len(set(shapes)) == 20 and min(forms.values()) >= 4, (alg, forms)
+
+
 def test_plane_witness_on_a_ramp(oracle_mod):
     """The float64 witness with the triangle filter (linear interpolation on an up-scale) maps a horizontal ramp onto itself away
     from the borders, at the position the siting gives: under phi = 0.25 output o of a x2 axis reads (o + 0.25) / 2 - 0.25."""
