@@ -1021,8 +1021,8 @@ int nus_scene_apply_cuts_retime_device(const void *d_frames, size_t frame_stride
 
 /* ---- YUV 4:2:0 frames: 8-bit planar I420 <-> RGBA8 ------------------------------------------------------------------------
  * BUILD-DEFINED: the reference has no YUV; its frames are RGBA (or BGRA capture surfaces) from end to end.  Decoded video is planar
- * YUV 4:2:0; these entry points are the road between such frames and the RGBA8 frames every other entry point takes.  One layout:
- * I420, 8 bits.  No NV12, no 4:2:2 / 4:4:4, no 10-bit, no interlace.
+ * YUV 4:2:0; these entry points are the road between such frames and the RGBA8 frames every other entry point takes.  Two layouts,
+ * 8 bits: I420 (here) and NV12 ("NV12 frames" below).  No NV21, no 4:2:2 / 4:4:4, no P010 / 10-bit, no interlace.
  * Frame layout.  An I420 frame of w x h is a Y plane of w*h bytes, then a U plane and a V plane of cw*ch bytes each, cw = (w+1)/2,
  * ch = (h+1)/2, rows tight: w*h + 2*cw*ch bytes (nus_yuv420_frame_bytes).  Frames of a batch are yuv_frame_stride bytes apart (0 =
  * tight, else at least one frame; no alignment rule), RGBA frames rgba_frame_stride bytes apart (0 = tight, else a multiple of 4 of
@@ -1130,6 +1130,53 @@ int nus_yuv_resizer_export_axis(const nus_yuv_resizer *h, int plane, int axis, i
 int nus_yuv420_resize_device(nus_yuv_resizer *h, const void *d_in, size_t in_frame_stride, void *d_out, size_t out_frame_stride,
                              uint32_t n_frames, void *stream);
 int nus_yuv420_resize(nus_yuv_resizer *h, const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap);   /* one host frame */
+
+/* ---- NV12 frames: conversions, the repack from and to I420, and the planar up-scaler ------------------------------------------
+ * BUILD-DEFINED: the reference has no YUV.  NV12 is what hardware decoders and `-pix_fmt nv12` hand over: a Y plane and ONE plane
+ * of interleaved U,V byte pairs, usually with a row pitch wider than the picture.  The arithmetic is the I420 contract's above:
+ * an NV12 result is by definition the I420 result with the chroma bytes in another place, every byte of it.
+ * Layout.  With cw = (w+1)/2 and ch = (h+1)/2:
+ *   tight (layout == NULL, or pitch 0, which requires uv_offset 0): Y rows w bytes apart; the UV plane starts at w*h, its rows
+ *     2*cw bytes apart; cell (cx, cy) is U at byte 2cx and V at byte 2cx+1 of row cy; frame bytes = nus_yuv420_frame_bytes(w, h).
+ *   pitched (pitch != 0): pitch >= 2*cw; the rows of both planes are `pitch` apart; uv_offset is 0 (meaning pitch*h) or at least
+ *     pitch*h; frame bytes = the effective uv_offset + pitch*ch.
+ * Frames of a batch are nv12_frame_stride bytes apart (0 = the frame bytes, else at least that).  There is no alignment rule on
+ * the NV12 side; the RGBA side is as above.  Row padding, the gap between the planes and the gaps between frames are never
+ * written.  Dimension limits and error conventions are those of the I420 entry points: NUS_ERR_INVALID_ARGUMENT (sizes of the host
+ * entry points: NUS_ERR_SIZE_MISMATCH) before any HIP call, with a text that begins with the entry point's name; a bad layout is
+ * an invalid argument.  The *_device entry points only enqueue on `stream`.
+ * Conversions.  All 16 (matrix, range, siting, chroma_filter) forms and the four RGBA formats: nus_rgba8_to_nv12* writes what
+ * nus_rgba8_to_yuv420* writes with U and V interleaved; nus_nv12_to_rgba8* writes what nus_yuv420_to_rgba8* writes for the
+ * de-interleaved frame.  nus_yuv420_to_nv12_device / nus_nv12_to_yuv420_device move bytes only (I420 frames tight, i420_frame_stride
+ * apart, 0 = tight).  The host entry points take one tight frame, as nus_yuv420_to_rgba8 does.
+ * Up-scaling.  nus_nv12_resize[_device] use the nus_yuv_resizer handle, its initialize and its four axis tables as they are (U and
+ * V share theirs): the output is nus_yuv420_resize_device's output rearranged, bit for bit, in both modes.  Frames are TIGHT NV12 on
+ * both sides; pitched surfaces go through the conversions or the repack.  Equal sizes copy.
+ * Not here: NV21, P010 / 10-bit, 4:2:2 / 4:4:4, a pitched resize, NV12 in the `video` command (Y4M has no tag for it), the native
+ * command-line tool. */
+typedef struct nus_nv12_layout {
+    size_t pitch;     /* bytes between rows, of the Y plane and of the UV plane alike; 0 = tight */
+    size_t uv_offset; /* bytes from the frame's base to its UV plane; 0 = directly behind the Y rows */
+} nus_nv12_layout;
+/* Host only.  Bytes of one NV12 frame; 0 (and nus_last_error) for bad dimensions or a bad layout. */
+size_t nus_nv12_frame_bytes(uint32_t w, uint32_t h, const nus_nv12_layout *layout);
+int nus_nv12_to_rgba8_device(const void *d_nv12, const nus_nv12_layout *layout, size_t nv12_frame_stride, uint32_t w, uint32_t h,
+                             const nus_yuv_format *fmt, int rgba_format, void *d_rgba, size_t rgba_frame_stride, uint32_t n_frames,
+                             void *stream);
+int nus_rgba8_to_nv12_device(const void *d_rgba, size_t rgba_frame_stride, uint32_t w, uint32_t h, const nus_yuv_format *fmt,
+                             int rgba_format, void *d_nv12, const nus_nv12_layout *layout, size_t nv12_frame_stride, uint32_t n_frames,
+                             void *stream);
+int nus_nv12_to_rgba8(int device, const uint8_t *nv12, size_t nv12_len, uint32_t w, uint32_t h, const nus_yuv_format *fmt,
+                      int rgba_format, uint8_t *rgba, size_t rgba_cap);
+int nus_rgba8_to_nv12(int device, const uint8_t *rgba, size_t rgba_len, uint32_t w, uint32_t h, const nus_yuv_format *fmt,
+                      int rgba_format, uint8_t *nv12, size_t nv12_cap);
+int nus_yuv420_to_nv12_device(const void *d_i420, size_t i420_frame_stride, uint32_t w, uint32_t h, void *d_nv12,
+                              const nus_nv12_layout *layout, size_t nv12_frame_stride, uint32_t n_frames, void *stream);
+int nus_nv12_to_yuv420_device(const void *d_nv12, const nus_nv12_layout *layout, size_t nv12_frame_stride, uint32_t w, uint32_t h,
+                              void *d_i420, size_t i420_frame_stride, uint32_t n_frames, void *stream);
+int nus_nv12_resize_device(nus_yuv_resizer *h, const void *d_in, size_t in_frame_stride, void *d_out, size_t out_frame_stride,
+                           uint32_t n_frames, void *stream);
+int nus_nv12_resize(nus_yuv_resizer *h, const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap);   /* one tight host frame */
 
 #ifdef __cplusplus
 }

@@ -220,6 +220,15 @@ SIGNATURES = [
     ("nus_yuv_resizer_export_axis", _i, [_vp, _i, _i, _vp, _vp, _vp]),
     ("nus_yuv420_resize_device", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _vp]),
     ("nus_yuv420_resize", _i, [_vp, _vp, _sz, _vp, _sz]),
+    ("nus_nv12_frame_bytes", _sz, [_u32, _u32, _vp]),
+    ("nus_nv12_to_rgba8_device", _i, [_vp, _vp, _sz, _u32, _u32, _vp, _i, _vp, _sz, _u32, _vp]),
+    ("nus_rgba8_to_nv12_device", _i, [_vp, _sz, _u32, _u32, _vp, _i, _vp, _vp, _sz, _u32, _vp]),
+    ("nus_nv12_to_rgba8", _i, [_i, _vp, _sz, _u32, _u32, _vp, _i, _vp, _sz]),
+    ("nus_rgba8_to_nv12", _i, [_i, _vp, _sz, _u32, _u32, _vp, _i, _vp, _sz]),
+    ("nus_yuv420_to_nv12_device", _i, [_vp, _sz, _u32, _u32, _vp, _vp, _sz, _u32, _vp]),
+    ("nus_nv12_to_yuv420_device", _i, [_vp, _vp, _sz, _u32, _u32, _vp, _sz, _u32, _vp]),
+    ("nus_nv12_resize_device", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _vp]),
+    ("nus_nv12_resize", _i, [_vp, _vp, _sz, _vp, _sz]),
 ]
 
 

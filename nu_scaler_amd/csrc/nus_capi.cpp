@@ -1185,6 +1185,66 @@ int nus_rgba8_to_yuv420(int device, const uint8_t *rgba, size_t rgba_len, uint32
     });
 }
 
+static_assert(sizeof(nus_nv12_layout) == sizeof(nus::Nv12Layout) && sizeof(nus_nv12_layout) == 2 * sizeof(size_t), "nus_nv12_layout is the host module's Nv12Layout");
+
+size_t nus_nv12_frame_bytes(uint32_t w, uint32_t h, const nus_nv12_layout *layout)
+{
+    try {
+        return nus::nv12_frame_bytes(w, h, reinterpret_cast<const nus::Nv12Layout *>(layout));
+    } catch (...) {
+        nus::set_thread_error("nus_nv12_frame_bytes: unexpected exception");
+        return 0;
+    }
+}
+int nus_nv12_to_rgba8_device(const void *d_nv12, const nus_nv12_layout *layout, size_t nv12_frame_stride, uint32_t w, uint32_t h,
+                             const nus_yuv_format *fmt, int rgba_format, void *d_rgba, size_t rgba_frame_stride, uint32_t n_frames, void *stream)
+{
+    return guarded<int>("nus_nv12_to_rgba8_device", [&]() -> int {
+        return nus::nv12_to_rgba8_device(d_nv12, reinterpret_cast<const nus::Nv12Layout *>(layout), nv12_frame_stride, w, h,
+                                         reinterpret_cast<const nus::YuvFormat *>(fmt), rgba_format, d_rgba, rgba_frame_stride, n_frames,
+                                         static_cast<hipStream_t>(stream));
+    });
+}
+int nus_rgba8_to_nv12_device(const void *d_rgba, size_t rgba_frame_stride, uint32_t w, uint32_t h, const nus_yuv_format *fmt, int rgba_format,
+                             void *d_nv12, const nus_nv12_layout *layout, size_t nv12_frame_stride, uint32_t n_frames, void *stream)
+{
+    return guarded<int>("nus_rgba8_to_nv12_device", [&]() -> int {
+        return nus::rgba8_to_nv12_device(d_rgba, rgba_frame_stride, w, h, reinterpret_cast<const nus::YuvFormat *>(fmt), rgba_format, d_nv12,
+                                         reinterpret_cast<const nus::Nv12Layout *>(layout), nv12_frame_stride, n_frames,
+                                         static_cast<hipStream_t>(stream));
+    });
+}
+int nus_nv12_to_rgba8(int device, const uint8_t *nv12, size_t nv12_len, uint32_t w, uint32_t h, const nus_yuv_format *fmt, int rgba_format,
+                      uint8_t *rgba, size_t rgba_cap)
+{
+    return guarded<int>("nus_nv12_to_rgba8", [&]() -> int {
+        return nus::nv12_to_rgba8(device, nv12, nv12_len, w, h, reinterpret_cast<const nus::YuvFormat *>(fmt), rgba_format, rgba, rgba_cap);
+    });
+}
+int nus_rgba8_to_nv12(int device, const uint8_t *rgba, size_t rgba_len, uint32_t w, uint32_t h, const nus_yuv_format *fmt, int rgba_format,
+                      uint8_t *nv12, size_t nv12_cap)
+{
+    return guarded<int>("nus_rgba8_to_nv12", [&]() -> int {
+        return nus::rgba8_to_nv12(device, rgba, rgba_len, w, h, reinterpret_cast<const nus::YuvFormat *>(fmt), rgba_format, nv12, nv12_cap);
+    });
+}
+int nus_yuv420_to_nv12_device(const void *d_i420, size_t i420_frame_stride, uint32_t w, uint32_t h, void *d_nv12, const nus_nv12_layout *layout,
+                              size_t nv12_frame_stride, uint32_t n_frames, void *stream)
+{
+    return guarded<int>("nus_yuv420_to_nv12_device", [&]() -> int {
+        return nus::yuv420_to_nv12_device(d_i420, i420_frame_stride, w, h, d_nv12, reinterpret_cast<const nus::Nv12Layout *>(layout),
+                                          nv12_frame_stride, n_frames, static_cast<hipStream_t>(stream));
+    });
+}
+int nus_nv12_to_yuv420_device(const void *d_nv12, const nus_nv12_layout *layout, size_t nv12_frame_stride, uint32_t w, uint32_t h, void *d_i420,
+                              size_t i420_frame_stride, uint32_t n_frames, void *stream)
+{
+    return guarded<int>("nus_nv12_to_yuv420_device", [&]() -> int {
+        return nus::nv12_to_yuv420_device(d_nv12, reinterpret_cast<const nus::Nv12Layout *>(layout), nv12_frame_stride, w, h, d_i420,
+                                          i420_frame_stride, n_frames, static_cast<hipStream_t>(stream));
+    });
+}
+
 static_assert(NUS_RESIZE_MAX_TAPS == nus::kResizeMaxTaps, "nus_yuv_resizer_export_axis lays its weights out as the tables do");
 
 namespace {
@@ -1235,6 +1295,20 @@ int nus_yuv420_resize_device(nus_yuv_resizer *h, const void *d_in, size_t in_fra
 int nus_yuv420_resize(nus_yuv_resizer *h, const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap)
 {
     return guarded<int>("nus_yuv420_resize", [&]() -> int { return h ? h->impl.resize(in, in_len, out, out_cap) : null_resizer("nus_yuv420_resize"); });
+}
+
+int nus_nv12_resize_device(nus_yuv_resizer *h, const void *d_in, size_t in_frame_stride, void *d_out, size_t out_frame_stride, uint32_t n_frames,
+                           void *stream)
+{
+    return guarded<int>("nus_nv12_resize_device", [&]() -> int {
+        return h ? h->impl.resize_nv12_device(d_in, in_frame_stride, d_out, out_frame_stride, n_frames, static_cast<hipStream_t>(stream))
+                 : null_resizer("nus_nv12_resize_device");
+    });
+}
+
+int nus_nv12_resize(nus_yuv_resizer *h, const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap)
+{
+    return guarded<int>("nus_nv12_resize", [&]() -> int { return h ? h->impl.resize_nv12(in, in_len, out, out_cap) : null_resizer("nus_nv12_resize"); });
 }
 
 } // extern "C"

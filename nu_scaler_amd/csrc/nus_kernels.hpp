@@ -482,6 +482,33 @@ struct YuvLaunch {
 hipError_t launch_yuv_to_rgba(const YuvLaunch &L);
 hipError_t launch_rgba_to_yuv(const YuvLaunch &L);
 
+// The same conversions on NV12 frames (nus_k_nv12.hip; "NV12 frames" in include/nuscaler_hip.h): `c.yuv` is the NV12 base and
+// c.yuv_frame_stride its frame stride.  Frame i: Y rows y_pitch apart from the base, the rows of U,V byte pairs uv_pitch apart from
+// base + uv_offset (tight: w, 2 cw and w h; pitched: the layout's pitch twice and its uv_offset) -- all three as resolved by the
+// host, never 0.  Row padding, the gap between the planes and the gaps between frames are not written.  Every byte is the I420
+// launch's byte.
+struct Nv12Launch {
+    YuvLaunch c;
+    size_t y_pitch = 0, uv_pitch = 0, uv_offset = 0;
+};
+// The form is chosen per launch: the aligned kernels (8 x 2 pixels per thread and one 8-byte load of four pairs per chroma row
+// towards RGBA; 16 x 2 and one 16-byte store of eight pairs towards NV12) where the width fills the run and the base, both
+// pitches, uv_offset and the stride are multiples of 8 / 16 (the RGBA side as in YuvLaunch), else one pixel / one cell per thread.
+hipError_t launch_nv12_to_rgba(const Nv12Launch &L);
+hipError_t launch_rgba_to_nv12(const Nv12Launch &L);
+// I420 <-> NV12: bytes only.  `i420` frames are tight planes, i420_frame_stride apart; the NV12 side as in Nv12Launch.  A thread
+// moves 16 luma bytes, or 8 U + 8 V bytes as one 16-byte access on the pair side, where the width is a multiple of 16 and every
+// base, pitch, offset and stride is; else one byte / one cell per thread.
+struct Nv12RepackLaunch {
+    uint8_t *i420 = nullptr, *nv12 = nullptr; // the side a launch reads is only read
+    size_t i420_frame_stride = 0, nv12_frame_stride = 0;
+    size_t y_pitch = 0, uv_pitch = 0, uv_offset = 0;
+    uint32_t w = 0, h = 0, n_frames = 1;
+    hipStream_t stream = nullptr;
+};
+hipError_t launch_i420_to_nv12(const Nv12RepackLaunch &L);
+hipError_t launch_nv12_to_i420(const Nv12RepackLaunch &L);
+
 // Separable resampling of the 8-bit planes of I420 frame batches (nus_k_yuv_resize.hip; nus_yuv_resizer of include/nuscaler_hip.h,
 // where the contract is written).  One launch resamples one CLASS of planes: the luma plane of every frame (planes_per_frame 1)
 // or both chroma planes (2), which share their tables.  Plane p of frame i starts at base + i * frame_stride + plane_offset +
@@ -514,6 +541,18 @@ constexpr uint32_t kPlaneMaxUnion = 12;
 // the class starts on a dword on either side, no window has more than 8 taps and the geometry fits; else one output per thread.
 bool plane_rows_form(const PlaneResizeLaunch &L);
 hipError_t launch_plane_resize(const PlaneResizeLaunch &L);
+// The chroma class of tight NV12 frames (nus_k_nv12_resize.hip): ONE plane of U,V byte pairs per frame (planes_per_frame 1, the
+// plane steps unused), iw x ih cells in and ow x oh out, rows of 2 iw / 2 ow bytes; both channels take the same tables.  The same
+// operations in the same order as launch_plane_resize on the two de-interleaved planes, so the same bytes.  ncols_max / union_taps
+// here: the widest dword-aligned input footprint of a wave's segment (128 output pairs) in BYTES, and the widest union of the
+// windows of a lane's run of two pairs in cells (YuvResizer::initialize).
+constexpr uint32_t kPairRun = 2;                 // adjacent output pairs a lane of the row kernel owns: one dword
+constexpr uint32_t kPairSegment = 64 * kPairRun; // output pairs of one wave
+constexpr uint32_t kPairMaxUnion = 8;            // a run of two needs at most taps + 1 columns, and no up-scale has more than 7 taps
+// The row kernel where both row lengths are multiples of 4 bytes, the pair plane starts on a dword on either side, no window has
+// more than 8 taps and the geometry fits; else one output byte per thread.
+bool pair_rows_form(const PlaneResizeLaunch &L);
+hipError_t launch_pair_resize(const PlaneResizeLaunch &L);
 // n_frames frames of frame_bytes each, the strides apart: a copy kernel (dwords where everything is dword aligned, else bytes)
 hipError_t launch_frame_copy(const uint8_t *in, size_t in_frame_stride, uint8_t *out, size_t out_frame_stride, size_t frame_bytes,
                              uint32_t n_frames, hipStream_t stream);

@@ -1,5 +1,6 @@
-// nus_yuv.cpp -- host side of the YUV 4:2:0 conversions (nus_yuv* in include/nuscaler_hip.h): the coefficient tables, the argument
-// checks, which run before any HIP call, the enqueue of the device entry points, and the per-device buffers of the host ones.
+// nus_yuv.cpp -- host side of the YUV 4:2:0 conversions (nus_yuv* and nus_nv12* in include/nuscaler_hip.h): the coefficient tables,
+// the NV12 layout rule, the argument checks, which run before any HIP call, the enqueue of the device entry points, and the
+// per-device buffers of the host ones.
 #include "nus_yuv.hpp"
 
 #include <cmath>
@@ -161,6 +162,175 @@ int rgba8_to_yuv420(int device, const uint8_t *rgba, size_t rgba_len, uint32_t w
     if ((r = upload(s.a.get(), rgba, rgba_bytes, s.stream)) != kOk) return r;
     if ((r = rgba8_to_yuv420_device(s.a.get(), 0, w, h, f, rgba_format, s.b.get(), 0, 1, s.stream)) != kOk) return r;
     return download(yuv, s.b.get(), yuv_bytes, s.stream);
+}
+
+// ---- NV12 frames ------------------------------------------------------------------------------------------------------------------
+
+int resolve_nv12(const char *who, uint32_t w, uint32_t h, const Nv12Layout *layout, Nv12Frame *out)
+{
+    const size_t cw = ((size_t)w + 1) / 2, ch = ((size_t)h + 1) / 2;
+    if (!layout || layout->pitch == 0) {
+        if (layout && layout->uv_offset != 0)
+            return fail(kInvalidArgument, fmt("%s: a layout with pitch 0 (tight) must have uv_offset 0, got %zu", who, layout->uv_offset));
+        out->y_pitch = w, out->uv_pitch = 2 * cw, out->uv_offset = (size_t)w * h, out->bytes = frame_bytes_unchecked(w, h);
+        return kOk;
+    }
+    const size_t pitch = layout->pitch;
+    if (pitch < 2 * cw) return fail(kInvalidArgument, fmt("%s: pitch must be 0 or at least %zu, got %zu", who, 2 * cw, pitch));
+    if (pitch > ((size_t)1 << 40)) return fail(kInvalidArgument, fmt("%s: pitch %zu is too large", who, pitch));
+    const size_t y_bytes = pitch * h;
+    if (layout->uv_offset != 0 && layout->uv_offset < y_bytes)
+        return fail(kInvalidArgument, fmt("%s: uv_offset must be 0 or at least %zu, got %zu", who, y_bytes, layout->uv_offset));
+    if (layout->uv_offset > ((size_t)1 << 62)) return fail(kInvalidArgument, fmt("%s: uv_offset %zu is too large", who, layout->uv_offset));
+    out->y_pitch = out->uv_pitch = pitch;
+    out->uv_offset = layout->uv_offset ? layout->uv_offset : y_bytes;
+    out->bytes = out->uv_offset + pitch * ch;
+    return kOk;
+}
+
+size_t nv12_frame_bytes(uint32_t w, uint32_t h, const Nv12Layout *layout)
+{
+    const char *who = "nus_nv12_frame_bytes";
+    Nv12Frame f;
+    if (check_dims_yuv(who, w, h) != kOk || resolve_nv12(who, w, h, layout, &f) != kOk) return 0;
+    return f.bytes;
+}
+
+namespace {
+
+// every check of an NV12 <-> RGBA device entry point; fills the launch
+int prepare_nv12(const char *who, const void *d_nv12, const Nv12Layout *layout, size_t nv12_frame_stride, const void *d_rgba,
+                 size_t rgba_frame_stride, uint32_t w, uint32_t h, const YuvFormat *f, int rgba_format, uint32_t n_frames, hipStream_t stream,
+                 Nv12Launch *L)
+{
+    if (!d_nv12 || !d_rgba || !f) return fail(kInvalidArgument, fmt("%s: null pointer", who));
+    int st = check_dims_yuv(who, w, h);
+    if (st != kOk || (st = check_formats(who, f, rgba_format)) != kOk) return st;
+    if (n_frames == 0) return fail(kInvalidArgument, fmt("%s: n_frames must be at least 1", who));
+    Nv12Frame fr;
+    if ((st = resolve_nv12(who, w, h, layout, &fr)) != kOk) return st;
+    const size_t rgba_bytes = (size_t)w * h * 4;
+    if (rgba_frame_stride != 0 && (rgba_frame_stride < rgba_bytes || (rgba_frame_stride % 4) != 0))
+        return fail(kInvalidArgument, fmt("%s: rgba_frame_stride must be 0 or a multiple of 4 of at least %zu, got %zu", who, rgba_bytes, rgba_frame_stride));
+    if (nv12_frame_stride != 0 && nv12_frame_stride < fr.bytes)
+        return fail(kInvalidArgument, fmt("%s: nv12_frame_stride must be 0 or at least %zu, got %zu", who, fr.bytes, nv12_frame_stride));
+    if (misaligned(d_rgba, 4)) return fail(kInvalidArgument, fmt("%s: the RGBA frames must be 4-byte aligned", who));
+    YuvLaunch &C = L->c;
+    C.yuv = static_cast<uint8_t *>(const_cast<void *>(d_nv12)), C.rgba = static_cast<uint8_t *>(const_cast<void *>(d_rgba));
+    C.yuv_frame_stride = nv12_frame_stride ? nv12_frame_stride : fr.bytes;
+    C.rgba_frame_stride = rgba_frame_stride ? rgba_frame_stride : rgba_bytes;
+    C.w = w, C.h = h, C.n_frames = n_frames, C.siting = f->siting, C.chroma_filter = f->chroma_filter;
+    yuv_coefficients(f->matrix, f->range, C.to_yuv, C.to_rgb, &C.y_offset);
+    C.sel = input_selector(rgba_format), C.stream = stream;
+    L->y_pitch = fr.y_pitch, L->uv_pitch = fr.uv_pitch, L->uv_offset = fr.uv_offset;
+    return kOk;
+}
+
+// every check of a repack entry point; fills the launch
+int prepare_repack(const char *who, const void *d_i420, size_t i420_frame_stride, const void *d_nv12, const Nv12Layout *layout,
+                   size_t nv12_frame_stride, uint32_t w, uint32_t h, uint32_t n_frames, hipStream_t stream, Nv12RepackLaunch *L)
+{
+    if (!d_i420 || !d_nv12) return fail(kInvalidArgument, fmt("%s: null pointer", who));
+    int st = check_dims_yuv(who, w, h);
+    if (st != kOk) return st;
+    if (n_frames == 0) return fail(kInvalidArgument, fmt("%s: n_frames must be at least 1", who));
+    Nv12Frame fr;
+    if ((st = resolve_nv12(who, w, h, layout, &fr)) != kOk) return st;
+    const size_t i420_bytes = frame_bytes_unchecked(w, h);
+    if (i420_frame_stride != 0 && i420_frame_stride < i420_bytes)
+        return fail(kInvalidArgument, fmt("%s: i420_frame_stride must be 0 or at least %zu, got %zu", who, i420_bytes, i420_frame_stride));
+    if (nv12_frame_stride != 0 && nv12_frame_stride < fr.bytes)
+        return fail(kInvalidArgument, fmt("%s: nv12_frame_stride must be 0 or at least %zu, got %zu", who, fr.bytes, nv12_frame_stride));
+    L->i420 = static_cast<uint8_t *>(const_cast<void *>(d_i420)), L->nv12 = static_cast<uint8_t *>(const_cast<void *>(d_nv12));
+    L->i420_frame_stride = i420_frame_stride ? i420_frame_stride : i420_bytes;
+    L->nv12_frame_stride = nv12_frame_stride ? nv12_frame_stride : fr.bytes;
+    L->y_pitch = fr.y_pitch, L->uv_pitch = fr.uv_pitch, L->uv_offset = fr.uv_offset;
+    L->w = w, L->h = h, L->n_frames = n_frames, L->stream = stream;
+    return kOk;
+}
+
+} // namespace
+
+int nv12_to_rgba8_device(const void *d_nv12, const Nv12Layout *layout, size_t nv12_frame_stride, uint32_t w, uint32_t h, const YuvFormat *f,
+                         int rgba_format, void *d_rgba, size_t rgba_frame_stride, uint32_t n_frames, hipStream_t stream)
+{
+    Nv12Launch L;
+    const int st = prepare_nv12("nus_nv12_to_rgba8_device", d_nv12, layout, nv12_frame_stride, d_rgba, rgba_frame_stride, w, h, f, rgba_format,
+                                n_frames, stream, &L);
+    if (st != kOk) return st;
+    if (device_count() <= 0) return fail(kNoDevice, "nus_nv12_to_rgba8_device: no HIP device available");
+    const hipError_t e = launch_nv12_to_rgba(L);
+    return e != hipSuccess ? fail_hip(e, "nv12-to-rgba launch") : kOk;
+}
+
+int rgba8_to_nv12_device(const void *d_rgba, size_t rgba_frame_stride, uint32_t w, uint32_t h, const YuvFormat *f, int rgba_format,
+                         void *d_nv12, const Nv12Layout *layout, size_t nv12_frame_stride, uint32_t n_frames, hipStream_t stream)
+{
+    Nv12Launch L;
+    const int st = prepare_nv12("nus_rgba8_to_nv12_device", d_nv12, layout, nv12_frame_stride, d_rgba, rgba_frame_stride, w, h, f, rgba_format,
+                                n_frames, stream, &L);
+    if (st != kOk) return st;
+    if (device_count() <= 0) return fail(kNoDevice, "nus_rgba8_to_nv12_device: no HIP device available");
+    const hipError_t e = launch_rgba_to_nv12(L);
+    return e != hipSuccess ? fail_hip(e, "rgba-to-nv12 launch") : kOk;
+}
+
+int nv12_to_rgba8(int device, const uint8_t *nv12, size_t nv12_len, uint32_t w, uint32_t h, const YuvFormat *f, int rgba_format,
+                  uint8_t *rgba, size_t rgba_cap)
+{
+    const char *who = "nus_nv12_to_rgba8";
+    if (!nv12 || !rgba || !f) return fail(kInvalidArgument, fmt("%s: null pointer", who));
+    int r = check_dims_yuv(who, w, h);
+    if (r != kOk || (r = check_formats(who, f, rgba_format)) != kOk) return r;
+    const size_t nv12_bytes = frame_bytes_unchecked(w, h), rgba_bytes = (size_t)w * h * 4;
+    if ((r = check_host(who, nv12_len, nv12_bytes, "nv12_len", rgba_cap, rgba_bytes, "rgba_cap", w, h)) != kOk) return r;
+    if ((r = check_device(who, device)) != kOk) return r;
+    PairScratch &s = scratch_of(device);
+    std::lock_guard<std::mutex> lock(s.m);
+    if ((r = s.prepare(device, rgba_bytes, 0, 0)) != kOk) return r;
+    if ((r = upload(s.a.get(), nv12, nv12_bytes, s.stream)) != kOk) return r;
+    if ((r = nv12_to_rgba8_device(s.a.get(), nullptr, 0, w, h, f, rgba_format, s.b.get(), 0, 1, s.stream)) != kOk) return r;
+    return download(rgba, s.b.get(), rgba_bytes, s.stream);
+}
+
+int rgba8_to_nv12(int device, const uint8_t *rgba, size_t rgba_len, uint32_t w, uint32_t h, const YuvFormat *f, int rgba_format,
+                  uint8_t *nv12, size_t nv12_cap)
+{
+    const char *who = "nus_rgba8_to_nv12";
+    if (!nv12 || !rgba || !f) return fail(kInvalidArgument, fmt("%s: null pointer", who));
+    int r = check_dims_yuv(who, w, h);
+    if (r != kOk || (r = check_formats(who, f, rgba_format)) != kOk) return r;
+    const size_t nv12_bytes = frame_bytes_unchecked(w, h), rgba_bytes = (size_t)w * h * 4;
+    if ((r = check_host(who, rgba_len, rgba_bytes, "rgba_len", nv12_cap, nv12_bytes, "nv12_cap", w, h)) != kOk) return r;
+    if ((r = check_device(who, device)) != kOk) return r;
+    PairScratch &s = scratch_of(device);
+    std::lock_guard<std::mutex> lock(s.m);
+    if ((r = s.prepare(device, rgba_bytes, 0, 0)) != kOk) return r;
+    if ((r = upload(s.a.get(), rgba, rgba_bytes, s.stream)) != kOk) return r;
+    if ((r = rgba8_to_nv12_device(s.a.get(), 0, w, h, f, rgba_format, s.b.get(), nullptr, 0, 1, s.stream)) != kOk) return r;
+    return download(nv12, s.b.get(), nv12_bytes, s.stream);
+}
+
+int yuv420_to_nv12_device(const void *d_i420, size_t i420_frame_stride, uint32_t w, uint32_t h, void *d_nv12, const Nv12Layout *layout,
+                          size_t nv12_frame_stride, uint32_t n_frames, hipStream_t stream)
+{
+    Nv12RepackLaunch L;
+    const int st = prepare_repack("nus_yuv420_to_nv12_device", d_i420, i420_frame_stride, d_nv12, layout, nv12_frame_stride, w, h, n_frames, stream, &L);
+    if (st != kOk) return st;
+    if (device_count() <= 0) return fail(kNoDevice, "nus_yuv420_to_nv12_device: no HIP device available");
+    const hipError_t e = launch_i420_to_nv12(L);
+    return e != hipSuccess ? fail_hip(e, "i420-to-nv12 launch") : kOk;
+}
+
+int nv12_to_yuv420_device(const void *d_nv12, const Nv12Layout *layout, size_t nv12_frame_stride, uint32_t w, uint32_t h, void *d_i420,
+                          size_t i420_frame_stride, uint32_t n_frames, hipStream_t stream)
+{
+    Nv12RepackLaunch L;
+    const int st = prepare_repack("nus_nv12_to_yuv420_device", d_i420, i420_frame_stride, d_nv12, layout, nv12_frame_stride, w, h, n_frames, stream, &L);
+    if (st != kOk) return st;
+    if (device_count() <= 0) return fail(kNoDevice, "nus_nv12_to_yuv420_device: no HIP device available");
+    const hipError_t e = launch_nv12_to_i420(L);
+    return e != hipSuccess ? fail_hip(e, "nv12-to-i420 launch") : kOk;
 }
 
 } // namespace nus

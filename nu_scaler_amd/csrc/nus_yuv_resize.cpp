@@ -1,5 +1,5 @@
-// nus_yuv_resize.cpp -- host side of the planar up-scaler of I420 frames (nus_yuv_resizer* / nus_yuv420_resize* in
-// include/nuscaler_hip.h): the dimension rule, the four axis tables, the argument checks, which run before any HIP call, the
+// nus_yuv_resize.cpp -- host side of the planar up-scaler of I420 and tight NV12 frames (nus_yuv_resizer* / nus_yuv420_resize* /
+// nus_nv12_resize* in include/nuscaler_hip.h): the dimension rule, the four axis tables, the argument checks, which run before any HIP call, the
 // tables' upload on the handle's first device call, the two launches per batch, and the host entry point's buffers.
 #include "nus_yuv_resize.hpp"
 
@@ -97,6 +97,18 @@ int YuvResizer::initialize(uint32_t iw, uint32_t ih, uint32_t ow, uint32_t oh, i
                     A.union_taps = std::max(A.union_taps, (uint32_t)(end - A.left[x]));
                 }
             }
+            // the same for the plane of U,V pairs of an NV12 frame: a segment is kPairSegment output cells, a run two of them
+            if (p == 1 && a == 0 && (A.out_n % kPairRun) == 0 && (A.in_n % 2) == 0 && A.max_taps <= 8) {
+                for (uint32_t x0 = 0; x0 < A.out_n; x0 += kPairSegment) {
+                    const uint32_t xl = std::min(x0 + kPairSegment, A.out_n) - 1;
+                    const int32_t c0 = (2 * A.left[x0]) & ~3, cmax = 2 * (A.left[xl] + (int32_t)A.ntaps[xl]);
+                    A.pair_ncols_max = std::max(A.pair_ncols_max, (uint32_t)((cmax - c0 + 3) & ~3));
+                }
+                for (uint32_t x = 0; x < A.out_n; x += kPairRun) {
+                    const int32_t end = std::max(A.left[x] + (int32_t)A.ntaps[x], A.left[x + 1] + (int32_t)A.ntaps[x + 1]);
+                    A.pair_union = std::max(A.pair_union, (uint32_t)(end - A.left[x]));
+                }
+            }
             A.d_offset = words;
             words += (size_t)A.out_n * (2 + kResizeMaxTaps);
         }
@@ -159,7 +171,7 @@ int YuvResizer::ensure_tables(const char *who)
 }
 
 int YuvResizer::enqueue(const char *who, const uint8_t *d_in, size_t in_stride, uint8_t *d_out, size_t out_stride, uint32_t n_frames,
-                        hipStream_t stream)
+                        hipStream_t stream, bool nv12)
 {
     if (iw_ == ow_ && ih_ == oh_) { // imageops::resize returns a copy when the dimensions are unchanged
         const hipError_t e = launch_frame_copy(d_in, in_stride, d_out, out_stride, in_bytes_, n_frames, stream);
@@ -169,7 +181,7 @@ int YuvResizer::enqueue(const char *who, const uint8_t *d_in, size_t in_stride, 
         const Axis &X = axis_[p][0], &Y = axis_[p][1];
         PlaneResizeLaunch L;
         L.in = d_in, L.out = d_out, L.in_frame_stride = in_stride, L.out_frame_stride = out_stride;
-        L.n_frames = n_frames, L.planes_per_frame = p == 0 ? 1 : 2;
+        L.n_frames = n_frames, L.planes_per_frame = (p == 0 || nv12) ? 1 : 2;
         L.iw = X.in_n, L.ih = Y.in_n, L.ow = X.out_n, L.oh = Y.out_n;
         if (p == 1) {
             L.in_plane_offset = (size_t)iw_ * ih_, L.in_plane_step = (size_t)L.iw * L.ih;
@@ -181,6 +193,13 @@ int YuvResizer::enqueue(const char *who, const uint8_t *d_in, size_t in_stride, 
         L.table_stride = kResizeMaxTaps, L.max_taps = (uint32_t)std::max(X.max_taps, Y.max_taps);
         L.ncols_max = X.ncols_max, L.union_taps = X.union_taps;
         L.exact = exact_, L.stream = stream;
+        if (p == 1 && nv12) { // one plane of U,V pairs where I420 has two planes: same tables, the pair kernels' geometry
+            L.in_plane_step = L.out_plane_step = 0;
+            L.ncols_max = X.pair_ncols_max, L.union_taps = X.pair_union;
+            const hipError_t e = launch_pair_resize(L);
+            if (e != hipSuccess) return fail_hip(e, "pair-plane resize launch");
+            continue;
+        }
         const hipError_t e = launch_plane_resize(L);
         if (e != hipSuccess) return fail_hip(e, p == 0 ? "luma resize launch" : "chroma resize launch");
     }
@@ -188,10 +207,9 @@ int YuvResizer::enqueue(const char *who, const uint8_t *d_in, size_t in_stride, 
     return kOk;
 }
 
-int YuvResizer::resize_device(const void *d_in, size_t in_frame_stride, void *d_out, size_t out_frame_stride, uint32_t n_frames,
-                              hipStream_t stream)
+int YuvResizer::device_call(const char *who, bool nv12, const void *d_in, size_t in_frame_stride, void *d_out, size_t out_frame_stride,
+                            uint32_t n_frames, hipStream_t stream)
 {
-    static const char *const who = "nus_yuv420_resize_device";
     std::lock_guard<std::mutex> lk(mu_);
     if (!d_in || !d_out) return fail(kInvalidArgument, fmt("%s: null pointer", who));
     if (!ready_) return fail(kNotInitialized, fmt("%s: the resizer is not initialized", who));
@@ -203,12 +221,11 @@ int YuvResizer::resize_device(const void *d_in, size_t in_frame_stride, void *d_
     const int rc = ensure_tables(who);
     if (rc != kOk) return rc;
     return enqueue(who, static_cast<const uint8_t *>(d_in), in_frame_stride ? in_frame_stride : in_bytes_, static_cast<uint8_t *>(d_out),
-                   out_frame_stride ? out_frame_stride : out_bytes_, n_frames, stream);
+                   out_frame_stride ? out_frame_stride : out_bytes_, n_frames, stream, nv12);
 }
 
-int YuvResizer::resize(const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap)
+int YuvResizer::host_call(const char *who, bool nv12, const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap)
 {
-    static const char *const who = "nus_yuv420_resize";
     std::lock_guard<std::mutex> lk(mu_);
     if (!in || !out) return fail(kInvalidArgument, fmt("%s: null pointer", who));
     if (!ready_) return fail(kNotInitialized, fmt("%s: the resizer is not initialized", who));
@@ -221,9 +238,31 @@ int YuvResizer::resize(const uint8_t *in, size_t in_len, uint8_t *out, size_t ou
     if (!stream_) NUS_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
     if ((rc = pass(d_in_.reserve(in_bytes_, stream_))) != kOk || (rc = pass(d_out_.reserve(out_bytes_, stream_))) != kOk) return rc;
     if ((rc = pass(upload(d_in_.get(), in, in_bytes_, stream_))) != kOk) return rc;
-    if ((rc = enqueue(who, static_cast<const uint8_t *>(d_in_.get()), in_bytes_, static_cast<uint8_t *>(d_out_.get()), out_bytes_, 1, stream_)) != kOk)
+    if ((rc = enqueue(who, static_cast<const uint8_t *>(d_in_.get()), in_bytes_, static_cast<uint8_t *>(d_out_.get()), out_bytes_, 1, stream_, nv12)) != kOk)
         return rc;
     return pass(download(out, d_out_.get(), out_bytes_, stream_));
+}
+
+int YuvResizer::resize_device(const void *d_in, size_t in_frame_stride, void *d_out, size_t out_frame_stride, uint32_t n_frames,
+                              hipStream_t stream)
+{
+    return device_call("nus_yuv420_resize_device", false, d_in, in_frame_stride, d_out, out_frame_stride, n_frames, stream);
+}
+
+int YuvResizer::resize(const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap)
+{
+    return host_call("nus_yuv420_resize", false, in, in_len, out, out_cap);
+}
+
+int YuvResizer::resize_nv12_device(const void *d_in, size_t in_frame_stride, void *d_out, size_t out_frame_stride, uint32_t n_frames,
+                                   hipStream_t stream)
+{
+    return device_call("nus_nv12_resize_device", true, d_in, in_frame_stride, d_out, out_frame_stride, n_frames, stream);
+}
+
+int YuvResizer::resize_nv12(const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap)
+{
+    return host_call("nus_nv12_resize", true, in, in_len, out, out_cap);
 }
 
 } // namespace nus
